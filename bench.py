@@ -13,8 +13,11 @@ each), weak scaling; the cohort is resident in HBM before the timed region.
     python bench.py --gpus N             # starts N ranks itself (torch.distributed.run, 127.0.0.1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W      # the driver's form
+    python bench.py --full               # + the extra legs (stream, kronvec, LUAD cohorts, CPU baselines, configs[4] batch)
+    python bench.py --dump-outputs DIR   # + what the last timed step returned: DIR/value.npy, DIR/grad.npy (float64)
 
-Rank 0 prints ONE JSON line.  `value` counts 5 000-patient cohort evaluations per second
+A plain run sets up, warms up, times exactly --steps steps and prints the line; every other measurement and check runs
+only under --full.  Rank 0 prints ONE JSON line.  `value` counts 5 000-patient cohort evaluations per second
 over all ranks (N GPUs evaluate an N x 5 000 patient cohort per step).  `roofline` is the
 dominant kernel OF THE TIMED REGION (k_wsolve, forward instantiation), timed with HIP events
 on the engine's stream inside that region; every figure in the line can be recomputed from
@@ -64,18 +67,25 @@ def parse():
     ap.add_argument("--workload", default="full-k", choices=["full-k", "luad", "luad28"],
                     help="full-k: BASELINE configs[2]; luad: the LUAD-reduced cohort of configs[0] (small-k regime); luad28: the "
                          "28-event LUAD cohort the reference's examples/analysis.py fits (heterogeneous, k up to 21)")
-    ap.add_argument("--min-seconds", type=float, default=5.0,
-                    help="the timed region is repeated in whole multiples of --steps until it has lasted this long (steps_run in "
-                         "the line; value and ms_per_step stay per step)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="if > 0, the timed region is repeated in whole multiples of --steps until it has lasted this long (steps_run "
+                         "in the line; value and ms_per_step stay per step); default 0: exactly --steps timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: stream bandwidth, kronvec, LUAD cohorts, CPU baselines with the "
+                         "cross-check of the timed cohort, the configs[4]-shaped batch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (objective value, gradient) as DIR/<name>.npy, float64")
     ap.add_argument("--cpu-sample", type=int, default=-1,
-                    help="patients timed on the reference-structure CPU baseline (-1: two per core)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the kronvec / stream / small-cohort legs")
+                    help="patients timed on the reference-structure CPU baseline (-1: two per core; with --full)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the kronvec / stream / small-cohort legs")
     ap.add_argument("--kronvec-batch", type=int, default=64)
     ap.add_argument("--config", type=int, default=2, choices=[2, 3, 4],
                     help="BASELINE.json configs[]: 2 = n 20, 5 000 patients per GPU (default, weak scaling); 3 = n 20, 50 000 "
                          "patients over the GPUs (6 250 per GPU at --gpus 8); 4 = n 25, 10 000 patients over the GPUs, fp32")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.config == 3:
         a.n, a.patients, a.dtype = 20, max(1, 50000 // a.gpus), "f64"
     elif a.config == 4:
@@ -332,9 +342,9 @@ def main():
         step()
         note("warmup step done")
     eng.reset_counters()
-    # The timed region: EXACTLY a.steps steps between two fences - repeated (whole multiples of a.steps, every rank the same
-    # count) until it has lasted --min-seconds, so that a driver sampling the GPU from outside sees it busy for seconds, not
-    # for the 0.25 s of five steps.  Every figure of the line stays per step.
+    # The timed region: EXACTLY a.steps steps between two fences.  With --min-seconds > 0 it is repeated (whole multiples of
+    # a.steps, every rank the same count) until it has lasted that long, so that a sampler watching the GPU from outside sees it
+    # busy for seconds.  Every figure of the line stays per step.
     reps = 1
     if a.min_seconds > 0:
         fence()
@@ -364,6 +374,12 @@ def main():
         dt = float(t.item())
     cnt = eng.counters()
     note(f"timed region done: {dt:.3f} s for {a.steps} steps")
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (the all-reduced result: the same on every rank)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "value.npy"), np.asarray(val, dtype=np.float64))
+        np.save(os.path.join(a.dump_outputs, "grad.npy"), np.asarray(grad, dtype=np.float64))
+        note(f"outputs written to {a.dump_outputs}")
 
     if rank == 0:
         ms_per_step = dt / a.steps * 1e3
@@ -390,7 +406,7 @@ def main():
 
         # ---- measured stream bandwidth of this box (next to the nominal 8 TB/s)
         stream = {}
-        if not a.no_extras:
+        if a.full and not a.no_extras:
             stream = {"copy_GBps": eng.bench_stream(1 << 30, 10, "copy"), "triad_GBps": eng.bench_stream(1 << 30, 10, "triad"),
                       "what": "16 B/lane copy b=a / triad a=b+s*c over 1 GiB arrays, HIP events, bytes moved / time"}
             note("stream leg done")
@@ -502,7 +518,7 @@ def main():
             out["eval_traffic"] = {"bytes_per_step": tot, "over_floor": tot / (4.0 * live_bytes) if live_bytes else None,
                                    "source": traffic_source}
 
-        if not a.no_extras and a.workload == "full-k":
+        if a.full and not a.no_extras and a.workload == "full-k":
             # ---- metric 2: batched kronvec Q_off p on `kb` resident 2^k vectors (working set > Infinity
             # Cache), HIP events on the engine's stream around 20 launches; B_kv = 2 * 2^k * s per vector
             st = dat[0, :2 * n + 1]
@@ -560,7 +576,7 @@ def main():
             except Exception as exc:
                 out["real_cohort"] = {"error": repr(exc)}
             note("real-cohort leg done")
-        if world == 1 and not a.no_cpu and a.workload == "full-k":
+        if a.full and world == 1 and not a.no_cpu and a.workload == "full-k":
             out["cpu_baseline"] = cpu_baseline(n, a.patients, a.cpu_sample)
             note("cpu baseline (reference structure) done")
             opt, ref = cpu_baseline_optimised(n, a.patients)
@@ -578,7 +594,7 @@ def main():
                 out["check"] = {"against": "oracle/metmhn_fast.c on the host (fp64), first rows of the bench cohort", "errors": errs,
                                 "tolerance": 1e-6 if a.dtype == "f64" else 1e-2}
             note("optimised CPU baseline + cross-check done")
-        if world == 1 and not a.no_extras and a.workload == "full-k" and a.config == 2 and a.n == 20:
+        if a.full and world == 1 and not a.no_extras and a.workload == "full-k" and a.config == 2 and a.n == 20:
             # ---- BASELINE configs[4] shape (n = k = 25, fp32, 128 MiB vectors) on a bounded sample: one resident batch of
             # 768 patients (three per CU), in a child process after this one's engines are gone - a reported figure beside the
             # headline, not part of `value`
