@@ -174,6 +174,32 @@ int mmhn_comm_destroy(mmhn_handle h);
 int mmhn_simulate(mmhn_handle h, const double* log_theta, const double* pt_d_ef, const double* mt_d_ef,
                   int64_t n_sim, uint64_t seed, int8_t* dat_out, int8_t* orders_out);
 
+/* ---- likeliest event orders -------------------------------------------------
+ * mmhn_likeliest_orders: MetMHN.likeliest_order (metmhn/model.py:213-293) of every row of a reference-format `dat`
+ * [n_pat][2 n_mut + 3] in one call, exact (max-product Viterbi / Pareto-front DP over each row's 2^k sub-states).
+ *   status per row of dat[:, -1] (type) and dat[:, -2] (diagnosis order): 0 "absent", 1 "present", 2 "isMetastasis",
+ *   3 "isPaired" with first observation 0 "unknown", 1 "PT", any other value "Met" (as mmhn_set_cohort reads it).
+ *   log_theta [N][N], obs1 / obs2 [N] (N = n_mut + 1), fp64 engines only.
+ *   front_cap: candidates kept per sub-state of a paired row (0: MMHN_ORD_DEFAULT_FRONT_CAP, at most 65536).
+ *   orders [n_pat][2 N - 1] event codes (2i PT, 2i+1 MT, 2 n_mut seeding) padded with -1; prob [n_pat];
+ *   status [n_pat]: MMHN_ORD_OK, MMHN_ORD_OVERFLOW (a front outgrew front_cap: no result, recompute elsewhere),
+ *   MMHN_ORD_INVALID (orders[i][0] holds the MMHN_ORD_* reason), MMHN_ORD_TOO_LARGE (the row's lattice does not fit the
+ *   workspace limit on its own).  prob is NaN and the order all -1 wherever status != 0.
+ * Rows are cut into batches that fit mmhn_set_workspace_limit; the call leaves a loaded cohort as it was.
+ */
+enum { MMHN_ORD_OK = 0, MMHN_ORD_OVERFLOW = 1, MMHN_ORD_INVALID = 2, MMHN_ORD_TOO_LARGE = 3 };
+enum { MMHN_ORD_BAD_STATUS = 1,       /* type not in 0..3 */
+       MMHN_ORD_UNREACHABLE = 2,      /* paired row without the seeding whose tumours differ */
+       MMHN_ORD_NO_SEEDING = 3,       /* paired row without the seeding */
+       MMHN_ORD_MT_PT_PART = 4,       /* "isMetastasis" row with primary-tumour events */
+       MMHN_ORD_MT_NO_SEEDING = 5,    /* "isMetastasis" row without the seeding */
+       MMHN_ORD_ABSENT_MET = 6,       /* "absent" row with metastasis events or the seeding */
+       MMHN_ORD_PRESENT_MET = 7 };    /* "present" row whose metastasis part is not the seeding alone */
+enum { MMHN_ORD_DEFAULT_FRONT_CAP = 64 };
+int mmhn_likeliest_orders(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2,
+                          const int8_t* dat, int64_t n_pat, int n_cols, int front_cap, int8_t* orders, double* prob,
+                          int32_t* status);
+
 /* ---- measurement -------------------------------------------------------------------
  * mmhn_bench_kronvec: `batch` resident copies of a 2^k vector, `iters` back-to-back
  * launches of mmhn_kronvec_batched's launch (diag = 0: y = Q_off p into a NaN-filled y, every tile of every vector,
@@ -204,9 +230,9 @@ typedef struct {
   int32_t comm_rank;  /* this engine's rank in it (ncclCommUserRank), -1: none */
 } mmhn_counters;
 /* ABI version of this header: bumped whenever an exported signature or structure changes (4: mmhn_bench_kronvec has its
- * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank).  A client built against another header must refuse to run:
+ * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists).  A client built against another header must refuse to run:
  * mmhn_abi_version() != MMHN_ABI_VERSION (metmhn_amd/_lib.py checks it on load). */
-#define MMHN_ABI_VERSION 5
+#define MMHN_ABI_VERSION 6
 int mmhn_abi_version(void);
 int mmhn_bench_kronvec(mmhn_handle h, const double* log_theta, const int8_t* state, int64_t batch,
                        int iters, int transpose, int jacobi, double* ms_per_launch, int64_t* tiles);

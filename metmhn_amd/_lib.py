@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("MMHN_LIB", os.path.join(_HERE, "libmetmhn_amd.so"))  
 f64p = C.POINTER(C.c_double)
 i8p = C.POINTER(C.c_int8)
 i64p = C.POINTER(C.c_int64)
+i32p = C.POINTER(C.c_int32)
 
 
 KERNEL_CLASSES = ("other_solve", "psolve_fwd", "psolve_adj", "pclass", "csolve_fwd", "csolve_adj")      # MMHN_K_* of include/metmhn_amd.h
@@ -75,9 +76,10 @@ SIGNATURES = {
     "mmhn_get_counters": [C.c_void_p, C.POINTER(Counters)],
     "mmhn_reset_counters": [C.c_void_p],
     "mmhn_debug_lane_moves": [C.c_void_p, C.c_int, C.POINTER(C.c_int)],
+    "mmhn_likeliest_orders": [C.c_void_p, f64p, f64p, f64p, i8p, C.c_int64, C.c_int, C.c_int, i8p, f64p, i32p],
 }
 OTHER_SYMBOLS = ("mmhn_destroy", "mmhn_last_error", "mmhn_abi_version")
-ABI_VERSION = 5          # MMHN_ABI_VERSION of include/metmhn_amd.h these prototypes were written against
+ABI_VERSION = 6          # MMHN_ABI_VERSION of include/metmhn_amd.h these prototypes were written against
 
 
 def needs_build() -> bool:

@@ -8,6 +8,7 @@
 //   classmarg.h  class marginals: k_class_marg, k_eq_flows, k_pclass          (likelihood.py:25-201)
 //   gradrows.h   gradient rows, bit marginals: k_grad_rows, k_bit_marg        (likelihood.py:163-228, vanilla.py:328-393)
 //   assemble.h   per-patient assembly, cohort reduction                       (likelihood.py:441-731)
+//   orders.h     likeliest event orders of a cohort: k_orders                 (model.py:213-1389)
 // Tile solves (k_tsolve, k_csolve) live in tsolve.h, the window-layout kernels in wsolve.h / wclass.h, the small-space
 // kernels in small.h, the Gillespie sampler in sampler.h.
 #pragma once
@@ -19,3 +20,4 @@
 #include "classmarg.h"
 #include "gradrows.h"
 #include "assemble.h"
+#include "orders.h"

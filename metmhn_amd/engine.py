@@ -315,6 +315,24 @@ class Engine:
                                           od.ctypes.data_as(_lib.i8p) if orders else None))
         return (dat, od) if orders else dat
 
+    # ---- likeliest event orders
+    def likeliest_orders(self, log_theta, obs1, obs2, dat, front_cap=0):
+        """MetMHN.likeliest_order of every row of a reference-format `dat` [n_pat, 2n+3] in one call
+        (mmhn_likeliest_orders): int8 orders [n_pat, 2N-1] padded with -1, float64 prob [n_pat], int32 status [n_pat]
+        (0 ok, 1 front overflow, 2 invalid row - reason code in orders[i, 0] -, 3 lattice larger than the workspace)."""
+        lt, ltp = _f(log_theta); a, ap = _f(obs1); b, bp = _f(obs2)
+        d = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
+        if d.ndim != 2:
+            raise ValueError("dat must be a 2-D array [n_pat, 2 n_mut + 3]")
+        n_pat = d.shape[0]
+        orders = np.full((n_pat, 2 * self.N - 1), -1, dtype=np.int8)
+        prob = np.zeros(n_pat)
+        status = np.zeros(n_pat, dtype=np.int32)
+        _lib.check(self.lib.mmhn_likeliest_orders(self.h, ltp, ap, bp, d.ctypes.data_as(i8p), n_pat, int(d.shape[1]),
+                                                  int(front_cap), orders.ctypes.data_as(i8p), prob.ctypes.data_as(f64p),
+                                                  status.ctypes.data_as(_lib.i32p)))
+        return orders, prob, status
+
     # ---- measurement
     def bench_kronvec(self, log_theta, state, batch, iters, transpose=False, jacobi=False, tiles=False):
         """ms per launch of mmhn_kronvec_batched's launch (or the fused Jacobi step); tiles=True also returns

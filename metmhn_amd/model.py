@@ -39,6 +39,21 @@ from .state import MetState, State
 _FIRST_OBS = ("PT", "Met", "unknown", "sync")
 _STATUS_ERR = "met_status must be one of 'isMetastasis', 'absent', 'present', 'isPaired'"
 _FIRST_ERR = "first_obs must be one of 'PT', 'Met', 'unknown', 'sync'"
+# a reference-format dat row -> likeliest_order's arguments (examples/post_training_analyses.ipynb): type dat[:, -1];
+# first observation of a paired row dat[:, -2], 0 "unknown", 1 "PT" and any other value "Met" as the objective reads it
+# (regularized_optimization.py:101-119)
+_ROW_STATUS = {0: "absent", 1: "present", 2: "isMetastasis", 3: "isPaired"}
+_ROW_FIRST = {0: "unknown", 1: "PT"}
+# the reason codes of mmhn_likeliest_orders (MMHN_ORD_* of include/metmhn_amd.h) -> likeliest_order's messages
+_ROW_ERRORS = {
+    1: _STATUS_ERR,
+    2: "This state is not reachable by mhn.",
+    3: "a paired sample needs the seeding event",
+    4: "PT part of the state was not empty, but met_status is 'isMetastasis'.",
+    5: "Seeding was not observed, but met_status is 'isMetastasis'.",
+    6: "Met part of the state was not empty, but met_status is 'absent'.",
+    7: "Met part of the state was not empty, but met_status is 'present', not 'isPaired'.",
+}
 
 
 def _subset_sums(weights) -> np.ndarray:
@@ -95,6 +110,7 @@ class MetMHN:
         # the primary tumour does not feel the seeding (model.py:207-208)
         self._pt_log_theta = self.log_theta.copy()
         self._pt_log_theta[:-1, -1] = 0.0
+        self.orders_fallback_rows = 0       # rows the last likeliest_orders call recomputed on the host
 
     # ------------------------------------------------------------------ diagonals
     def _get_diag_unpaired(self, state: State, seeding: bool = True) -> np.ndarray:
@@ -135,6 +151,50 @@ class MetMHN:
                 warnings.warn("Synchronous development is deprecated.", DeprecationWarning)
             return self._likeliest_order_paired(state, first_obs)
         raise ValueError(_STATUS_ERR)
+
+    def likeliest_orders(self, dat, backend: str = "device", front_cap: int = 0) -> list:
+        """The likeliest order of every row of a reference-format `dat` [n_pat, 2n+3]: a list of (order, probability),
+        order a tuple of event codes, equal to likeliest_order row by row.  The type column dat[:, -1] gives the status
+        (0 "absent", 1 "present", 2 "isMetastasis", 3 "isPaired"), the diagnosis order dat[:, -2] a paired row's first
+        observation (0 "unknown", 1 "PT", 2 - or any other value, as the objective reads it - "Met").
+
+        backend="device": every row in one call of the HIP library (mmhn_likeliest_orders); a row whose Pareto front
+        outgrew `front_cap` candidates (0: the library's default) or whose lattice does not fit the workspace is
+        recomputed here with likeliest_order - how many did is left in `self.orders_fallback_rows`.
+        backend="host": likeliest_order row by row.  An invalid row raises likeliest_order's ValueError, with its index."""
+        dat = np.asarray(dat)
+        if dat.ndim != 2 or dat.shape[1] != 2 * self.n + 3:
+            raise ValueError(f"dat must have shape [n_pat, {2 * self.n + 3}]")
+        if backend == "host":
+            self.orders_fallback_rows = 0
+            return [self._row_order(dat, i) for i in range(dat.shape[0])]
+        if backend != "device":
+            raise ValueError("backend must be 'device' or 'host'")
+        from .jx import engine
+        orders, prob, status = engine(self.n).likeliest_orders(self.log_theta, self.obs1, self.obs2, dat, front_cap)
+        bad = np.flatnonzero(status == 2)
+        if bad.size:
+            i = int(bad[0])
+            raise ValueError(f"row {i}: {_ROW_ERRORS[int(orders[i, 0])]}")
+        out, fallback = [], 0
+        for i in range(dat.shape[0]):
+            if status[i] == 0:
+                out.append((tuple(int(e) for e in orders[i] if e >= 0), float(prob[i])))
+            else:
+                out.append(self._row_order(dat, i))
+                fallback += 1
+        self.orders_fallback_rows = fallback
+        return out
+
+    def _row_order(self, dat, i: int):
+        row = dat[i]
+        status = _ROW_STATUS.get(int(row[-1]), f"type {int(row[-1])}")
+        first = _ROW_FIRST.get(int(row[-2]), "Met") if status == "isPaired" else None
+        try:
+            order, p = self.likeliest_order(MetState.from_seq(row[:2 * self.n + 1]), status, first)
+        except ValueError as e:
+            raise ValueError(f"row {i}: {e}") from e
+        return tuple(int(e) for e in order), float(p)
 
     def likelihood(self, order, met_status: str, first_obs: str = None) -> float:
         """model.py:295-376: probability of exactly this order of events being what is observed."""
