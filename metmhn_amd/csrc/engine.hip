@@ -495,6 +495,7 @@ struct Engine : EngineBase {
   DevArr<int> d_lvl;
   bool use_jacobi = false;      // MMHN_SOLVER=jacobi: the reference's k+1 sweeps instead of substitution
   bool poison = false;          // MMHN_POISON=1: NaN-fill the solution buffers of per-patient batches before each evaluation
+                                // and the result buffers of every api_* path (poison_fill)
   hipStream_t side[3] = {};               // side streams: [0], [1] of the small-space path, [2] of the staged own-problem patients
   hipEvent_t ev_fork[3] = {}, ev_join[3] = {};
   bool small_path = true;       // MMHN_SMALL=0: keep the staged kernels for single-tumour spaces that fit one tile
@@ -821,6 +822,11 @@ struct Engine : EngineBase {
   }
   void zero(T* p, long long count) {
     if (count > 0) HIPCHECK(hipMemsetAsync(p, 0, (size_t)count * sizeof(T), stream));
+  }
+  // MMHN_POISON=1 (tests): the result buffers of the api_* paths start as NaNs, filled as soon as they are allocated and
+  // before the path's own clearing, so an element that no launch (or memset) writes shows in the output
+  void poison_fill(T* p, long long count) {
+    if (poison && count > 0) HIPCHECK(hipMemsetAsync(p, 0xFF, (size_t)count * sizeof(T), stream));
   }
   // timed launch helper shared by the two solvers
   template <typename F>
@@ -1844,6 +1850,7 @@ struct Engine : EngineBase {
     const size_t V = (size_t)1 << d.k;
     up(m.a, p, V);
     m.b.alloc(V);
+    poison_fill(m.b.p, (long long)V);
     if (d.k > TB) {
       std::vector<int2> live;
       for (int tl = 0; tl < m.ntiles; ++tl) if (!dead_tile(m.d, (uint32_t)tl)) live.push_back(make_int2(0, tl));
@@ -1947,6 +1954,7 @@ struct Engine : EngineBase {
     up(a, p, tot);
     up(r, rhs, tot);
     b.alloc(tot); c.alloc(tot);
+    poison_fill(c.p, (long long)tot);
     launch_diag(kb.dd.p, kb.map.p, kb.ntiles, nullptr, c.p, nullptr, KD_LIDG);
     HIPCHECK(hipMemsetAsync(b.p, 0xFF, tot * sizeof(T), stream));
     kv_launch(kb, tr, a.p, b.p, c.p, r.p);
@@ -1957,6 +1965,7 @@ struct Engine : EngineBase {
     const size_t V = (size_t)1 << d.k;
     if (p) up(m.a, p, V);
     m.b.alloc(V);
+    poison_fill(m.b.p, (long long)V);
     launch_diag(m.dd.p, m.map.p, m.ntiles, m.a.p, m.b.p, nullptr, what, pbit);
     down(outp, m.b.p, V);
   }
@@ -2089,6 +2098,7 @@ struct Engine : EngineBase {
     up(m.a, y, V);
     up(m.b, x, V);
     m.e.alloc(64);
+    poison_fill(m.e.p, 64);
     zero(m.e.p, 64);
     hipLaunchKernelGGL((k_bit_marg<T>), dim3(m.ntiles), dim3(BLOCK), 0, stream, m.dd.p, m.map.p, d_par.p, m.a.p,
                        m.b.p, m.e.p);
@@ -2137,6 +2147,8 @@ struct Engine : EngineBase {
     up(m.a, x, V);
     if (dvec) up(m.e, dvec, V);
     m.b.alloc(V); m.c.alloc(V);
+    poison_fill(m.b.p, (long long)V);
+    poison_fill(m.c.p, (long long)V);
     launch_diag(m.dd.p, m.map.p, m.ntiles, nullptr, m.c.p, m.e.p, KD_LIDG);
     solve(tr, m.plist((long long)V), m.b.p, m.c.p, m.a.p, 0, nullptr);
     down(y, m.b.p, V);
@@ -2148,6 +2160,8 @@ struct Engine : EngineBase {
     up(m.b, x, V);   // q (left vector)
     m.c.alloc((size_t)a_size(m.d));
     m.e.alloc((size_t)3 * N * N);
+    poison_fill(m.c.p, a_size(m.d));
+    poison_fill(m.e.p, 3ll * N * N);
     zero(m.e.p, 3ll * N * N);
     zero(m.c.p, a_size(m.d));
     hipLaunchKernelGGL((k_class_marg<T>), dim3(m.ntiles), dim3(CMB), 2 * sizeof(T) << TB, stream, m.dd.p, m.map.p,
@@ -2172,6 +2186,7 @@ struct Engine : EngineBase {
     up(m.a, y, V);
     up(m.b, x, V);
     m.e.alloc((size_t)N * N);
+    poison_fill(m.e.p, (long long)N * N);
     zero(m.e.p, (long long)N * N);
     {
       std::vector<int2> gc = grad_chunks(std::vector<Desc>{m.d}, GK_S);
@@ -2194,6 +2209,7 @@ struct Engine : EngineBase {
     up(m.a, y, V);
     up(m.b, x, V);
     m.e.alloc(64);
+    poison_fill(m.e.p, 64);
     zero(m.e.p, 64);
     hipLaunchKernelGGL((k_bit_marg<T>), dim3(m.ntiles), dim3(BLOCK), 0, stream, m.dd.p, m.map.p, d_par.p, m.a.p,
                        m.b.p, m.e.p);

@@ -42,6 +42,14 @@ def _s(a):
     return a, a.ctypes.data_as(i8p)
 
 
+def _vec(a, V, name):
+    """float64 copy of a vector of length V (a restricted state vector, V = 2^k)."""
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+    if a.shape != (V,):
+        raise ValueError(f"{name} must have shape ({V},), got {a.shape}")
+    return a, a.ctypes.data_as(f64p)
+
+
 class Engine:
     """Owns a mmhn_handle.  `n_mut` mutations -> N = n_mut + 1 events incl. seeding."""
 
@@ -157,18 +165,49 @@ class Engine:
                                                gp.ctypes.data_as(f64p), gm.ctypes.data_as(f64p)))
         return lp, g, gp, gm
 
+    # ---- argument checks of the single-vector primitives: everything the C side reads through a raw pointer has the
+    # length it will read (make_joint / make_single read the whole state, build_params N x N / N entries, up() and down()
+    # 2^k elements)
+    def _state(self, state, joint=True):
+        """int8 state of length 2n+1 (joint) or n+1 (single tumour) holding only 0 / 1, its pointer and k."""
+        st = np.asarray(state)
+        L = 2 * self.n + 1 if joint else self.N
+        if st.ndim != 1 or st.shape[0] != L:
+            raise ValueError(f"state must have shape ({L},), got {st.shape}")
+        if not np.isin(st, (0, 1)).all():
+            raise ValueError("state must hold only 0 and 1")
+        st, sp = _s(st)
+        return st, sp, int(st.sum())
+
+    def _theta(self, log_theta):
+        lt, ltp = _f(log_theta)
+        if lt.shape != (self.N, self.N):
+            raise ValueError(f"log_theta must have shape ({self.N}, {self.N}), got {lt.shape}")
+        return lt, ltp
+
+    def _rates(self, log_d, name="log_d"):
+        d, dp_ = _f(log_d)
+        if d.shape != (self.N,):
+            raise ValueError(f"{name} must have shape ({self.N},), got {d.shape}")
+        return d, dp_
+
+    def _event(self, i):
+        if isinstance(i, (bool, np.bool_)) or not isinstance(i, (int, np.integer)) or not 0 <= int(i) <= self.n:
+            raise ValueError(f"i must be an event index in 0..{self.n}, got {i!r}")
+        return int(i)
+
     # ---- joint primitives
     def kronvec(self, log_theta, p, state, diag=True, transpose=False):
-        lt, ltp = _f(log_theta); pv, pp = _f(p); st, sp = _s(state)
+        lt, ltp = self._theta(log_theta); st, sp, k = self._state(state); pv, pp = _vec(p, 2 ** k, "p")
         y = np.zeros_like(pv)
         _lib.check(self.lib.mmhn_kronvec(self.h, ltp, sp, pp, y.ctypes.data_as(f64p), int(diag), int(transpose)))
         return y
 
     def kronvec_batched(self, log_theta, p, state, diag=True, transpose=False):
         """kronvec for a batch p[b][2^k] of vectors of one restricted space: one launch, y[b][2^k]."""
-        lt, ltp = _f(log_theta); st, sp = _s(state)
+        lt, ltp = self._theta(log_theta); st, sp, k = self._state(state)
         pv = np.ascontiguousarray(p, dtype=np.float64)
-        if pv.ndim != 2 or pv.shape[1] != 2 ** int(st.sum()):
+        if pv.ndim != 2 or pv.shape[1] != 2 ** k:
             raise ValueError("p must have shape [batch, 2^k]")
         y = np.zeros_like(pv)
         _lib.check(self.lib.mmhn_kronvec_batched(self.h, ltp, sp, int(pv.shape[0]), pv.ctypes.data_as(f64p),
@@ -177,10 +216,10 @@ class Engine:
 
     def jacobi_step_batched(self, log_theta, log_d_p, log_d_m, p, rhs, state, transpose=False):
         """One sweep of R_i_inv_vec's iteration for a batch: lidg * (Q_off p + rhs), shapes [batch, 2^k]."""
-        lt, ltp = _f(log_theta); a, ap = _f(log_d_p); b, bp = _f(log_d_m); st, sp = _s(state)
+        keep, (ltp, ap, bp) = self._params(log_theta, log_d_p, log_d_m); st, sp, k = self._state(state)
         pv = np.ascontiguousarray(p, dtype=np.float64)
         rv = np.ascontiguousarray(rhs, dtype=np.float64)
-        if pv.ndim != 2 or pv.shape != rv.shape or pv.shape[1] != 2 ** int(st.sum()):
+        if pv.ndim != 2 or pv.shape != rv.shape or pv.shape[1] != 2 ** k:
             raise ValueError("p and rhs must have shape [batch, 2^k]")
         y = np.zeros_like(pv)
         _lib.check(self.lib.mmhn_jacobi_step_batched(self.h, ltp, ap, bp, sp, int(pv.shape[0]), pv.ctypes.data_as(f64p),
@@ -188,20 +227,20 @@ class Engine:
         return y
 
     def kron_diag(self, log_theta, state):
-        lt, ltp = _f(log_theta); st, sp = _s(state)
-        y = np.zeros(2 ** int(st.sum()))
+        lt, ltp = self._theta(log_theta); st, sp, k = self._state(state)
+        y = np.zeros(2 ** k)
         _lib.check(self.lib.mmhn_kron_diag(self.h, ltp, sp, y.ctypes.data_as(f64p)))
         return y
 
     def diag_scal(self, log_d, state, p, which):
-        d, dp_ = _f(log_d); pv, pp = _f(p); st, sp = _s(state)
+        d, dp_ = self._rates(log_d); st, sp, k = self._state(state); pv, pp = _vec(p, 2 ** k, "p")
         y = np.zeros_like(pv)
         _lib.check(self.lib.mmhn_diag_scal(self.h, dp_, sp, pp, y.ctypes.data_as(f64p), int(which)))
         return y
 
     def obs_indices(self, state, pt_first):
-        st, sp = _s(state)
-        n = (st.shape[0] - 1) // 2
+        st, sp, k = self._state(state)
+        n = self.n
         free = int(st[1:2 * n:2].sum()) if pt_first else int(st[0:2 * n:2].sum())
         idx = np.zeros(2 ** free, dtype=np.int64)
         cnt = C.c_int64()
@@ -210,82 +249,91 @@ class Engine:
 
     def resolvent(self, log_theta, log_d_p, log_d_m, x, state, transpose=False):
         keep, (a, b, c) = self._params(log_theta, log_d_p, log_d_m)
-        xv, xp = _f(x); st, sp = _s(state)
+        st, sp, k = self._state(state); xv, xp = _vec(x, 2 ** k, "x")
         y = np.zeros_like(xv)
         _lib.check(self.lib.mmhn_resolvent(self.h, a, b, c, sp, xp, y.ctypes.data_as(f64p), int(transpose)))
         return y
 
     def x_partial_Q_y(self, log_theta, x, y, state):
-        lt, ltp = _f(log_theta); xv, xp = _f(x); yv, yp = _f(y); st, sp = _s(state)
+        lt, ltp = self._theta(log_theta); st, sp, k = self._state(state)
+        xv, xp = _vec(x, 2 ** k, "x"); yv, yp = _vec(y, 2 ** k, "y")
         G = np.zeros((self.N, self.N))
         _lib.check(self.lib.mmhn_x_partial_Q_y(self.h, ltp, sp, xp, yp, G.ctypes.data_as(f64p)))
         return G
 
     def x_partial_D_y(self, log_d_p, log_d_m, state, x, y):
-        a, ap = _f(log_d_p); b, bp = _f(log_d_m); xv, xp = _f(x); yv, yp = _f(y); st, sp = _s(state)
+        a, ap = self._rates(log_d_p, "log_d_p"); b, bp = self._rates(log_d_m, "log_d_m"); st, sp, k = self._state(state)
+        xv, xp = _vec(x, 2 ** k, "x"); yv, yp = _vec(y, 2 ** k, "y")
         ddp, ddm = np.zeros(self.N), np.zeros(self.N)
         _lib.check(self.lib.mmhn_x_partial_D_y(self.h, ap, bp, sp, xp, yp, ddp.ctypes.data_as(f64p),
                                                ddm.ctypes.data_as(f64p)))
         return ddp, ddm
 
     def partial_diag_scal(self, log_d, state, p, i, which):
-        d, dp_ = _f(log_d); pv, pp = _f(p); st, sp = _s(state)
+        d, dp_ = self._rates(log_d); st, sp, k = self._state(state); pv, pp = _vec(p, 2 ** k, "p")
+        i = self._event(i)
         y = np.zeros_like(pv)
-        _lib.check(self.lib.mmhn_partial_diag_scal(self.h, dp_, sp, pp, int(i), int(which), y.ctypes.data_as(f64p)))
+        _lib.check(self.lib.mmhn_partial_diag_scal(self.h, dp_, sp, pp, i, int(which), y.ctypes.data_as(f64p)))
         return y
 
     # ---- single-tumour primitives
     def v_kronvec(self, log_theta, p, state, diag=True, transpose=False):
-        lt, ltp = _f(log_theta); pv, pp = _f(p); st, sp = _s(state)
+        lt, ltp = self._theta(log_theta); st, sp, k = self._state(state, False); pv, pp = _vec(p, 2 ** k, "p")
         y = np.zeros_like(pv)
         _lib.check(self.lib.mmhn_v_kronvec(self.h, ltp, sp, pp, y.ctypes.data_as(f64p), int(diag), int(transpose)))
         return y
 
     def v_resolvent(self, log_theta, x, state, d_rates=None, transpose=False):
-        lt, ltp = _f(log_theta); xv, xp = _f(x); st, sp = _s(state)
+        lt, ltp = self._theta(log_theta); st, sp, k = self._state(state, False); xv, xp = _vec(x, 2 ** k, "x")
         y = np.zeros_like(xv)
-        if d_rates is None or np.isscalar(d_rates):
+        if d_rates is None or np.ndim(d_rates) == 0:
             if d_rates is not None and float(d_rates) != 1.0:
                 d_rates = np.full_like(xv, float(d_rates))
             else:
                 d_rates = None
         dr = None
         if d_rates is not None:
-            dkeep, dr = _f(d_rates)
+            dkeep, dr = _vec(d_rates, 2 ** k, "d_rates")
         _lib.check(self.lib.mmhn_v_resolvent(self.h, ltp, sp, dr, xp, y.ctypes.data_as(f64p), int(transpose)))
         return y
 
     def v_x_partial_Q_y(self, log_theta, x, y, state):
-        lt, ltp = _f(log_theta); xv, xp = _f(x); yv, yp = _f(y); st, sp = _s(state)
+        lt, ltp = self._theta(log_theta); st, sp, k = self._state(state, False)
+        xv, xp = _vec(x, 2 ** k, "x"); yv, yp = _vec(y, 2 ** k, "y")
         G, dd = np.zeros((self.N, self.N)), np.zeros(self.N)
         _lib.check(self.lib.mmhn_v_x_partial_Q_y(self.h, ltp, sp, xp, yp, G.ctypes.data_as(f64p),
                                                  dd.ctypes.data_as(f64p)))
         return G, dd
 
     def v_kron_diag(self, log_theta, state, diag=None):
-        lt, ltp = _f(log_theta); st, sp = _s(state)
-        out = np.zeros(2 ** int(st.sum()))
+        lt, ltp = self._theta(log_theta); st, sp, k = self._state(state, False)
+        out = np.zeros(2 ** k)
         dg = None
         if diag is not None:
-            dkeep, dg = _f(diag)
+            dkeep, dg = _vec(diag, 2 ** k, "diag")
         _lib.check(self.lib.mmhn_v_kron_diag(self.h, ltp, sp, dg, out.ctypes.data_as(f64p)))
         return out
 
     def v_scal_d_pt(self, log_d_p, log_d_m, state, vec):
-        a, ap = _f(log_d_p); b, bp = _f(log_d_m); v, vp = _f(vec); st, sp = _s(state)
+        a, ap = self._rates(log_d_p, "log_d_p"); b, bp = self._rates(log_d_m, "log_d_m")
+        st, sp, k = self._state(state, False); v, vp = _vec(vec, 2 ** k, "vec")
         op, om = np.zeros_like(v), np.zeros_like(v)
         _lib.check(self.lib.mmhn_v_scal_d_pt(self.h, ap, bp, sp, vp, op.ctypes.data_as(f64p), om.ctypes.data_as(f64p)))
         return op, om
 
     def v_d_scal_d_pt(self, log_d_p, log_d_m, state, vec, i):
-        a, ap = _f(log_d_p); b, bp = _f(log_d_m); v, vp = _f(vec); st, sp = _s(state)
+        a, ap = self._rates(log_d_p, "log_d_p"); b, bp = self._rates(log_d_m, "log_d_m")
+        st, sp, k = self._state(state, False); v, vp = _vec(vec, 2 ** k, "vec")
+        i = self._event(i)
         op, om = np.zeros_like(v), np.zeros_like(v)
-        _lib.check(self.lib.mmhn_v_d_scal_d_pt(self.h, ap, bp, sp, vp, int(i), op.ctypes.data_as(f64p),
+        _lib.check(self.lib.mmhn_v_d_scal_d_pt(self.h, ap, bp, sp, vp, i, op.ctypes.data_as(f64p),
                                                om.ctypes.data_as(f64p)))
         return op, om
 
     def v_x_partial_D_y(self, log_d_p, log_d_m, state, x, y):
-        a, ap = _f(log_d_p); b, bp = _f(log_d_m); xv, xp = _f(x); yv, yp = _f(y); st, sp = _s(state)
+        a, ap = self._rates(log_d_p, "log_d_p"); b, bp = self._rates(log_d_m, "log_d_m")
+        st, sp, k = self._state(state, False)
+        xv, xp = _vec(x, 2 ** k, "x"); yv, yp = _vec(y, 2 ** k, "y")
         ddp, ddm = np.zeros(self.N), np.zeros(self.N)
         _lib.check(self.lib.mmhn_v_x_partial_D_y(self.h, ap, bp, sp, xp, yp, ddp.ctypes.data_as(f64p),
                                                  ddm.ctypes.data_as(f64p)))

@@ -17,6 +17,9 @@ exp(log_theta[i, j]) is the multiplicative effect of event j on event i):
 States in which PT != MT while seed = 0 are unreachable and carry zero rates.
 The restricted space of an observation `state` keeps the 2^k states that are
 subsets of the observed ones; transitions that leave it only feed the diagonal.
+
+joint_Q, joint_D, single_Q and single_D take an optional dtype (np.longdouble for a
+high-precision reference, a complex type for complex-step derivatives in the parameters).
 """
 from __future__ import annotations
 
@@ -37,14 +40,14 @@ def _slots(state):
     return out
 
 
-def joint_Q(log_theta, state):
+def joint_Q(log_theta, state, dtype=np.float64):
     """Dense restricted generator Q[to, from] (columns sum to <= 0)."""
-    th = np.exp(np.asarray(log_theta, dtype=np.float64))
+    th = np.exp(np.asarray(log_theta, dtype=dtype))
     n = th.shape[0] - 1
     slots = _slots(state)
     k = len(slots)
     bit = {s: b for b, s in enumerate(slots)}
-    Q = np.zeros((2 ** k, 2 ** k))
+    Q = np.zeros((2 ** k, 2 ** k), dtype=th.dtype)
     for x in range(2 ** k):
         pt = {e for b, (e, t) in enumerate(slots) if t == 0 and x >> b & 1}
         mt = {e for b, (e, t) in enumerate(slots) if t == 1 and x >> b & 1}
@@ -78,14 +81,14 @@ def joint_Q(log_theta, state):
     return Q
 
 
-def joint_D(log_d_p, log_d_m, state):
+def joint_D(log_d_p, log_d_m, state, dtype=np.float64):
     """Observation-rate diagonals D_p, D_m on the restricted joint space."""
-    dp = np.exp(np.asarray(log_d_p, dtype=np.float64))
-    dm = np.exp(np.asarray(log_d_m, dtype=np.float64))
+    dp = np.exp(np.asarray(log_d_p, dtype=dtype))
+    dm = np.exp(np.asarray(log_d_m, dtype=dtype))
     slots = _slots(state)
     k = len(slots)
-    Dp = np.ones(2 ** k)
-    Dm = np.ones(2 ** k)
+    Dp = np.ones(2 ** k, dtype=dp.dtype)
+    Dm = np.ones(2 ** k, dtype=dm.dtype)
     for x in range(2 ** k):
         seeded = False
         for b, (e, t) in enumerate(slots):
@@ -104,12 +107,13 @@ def joint_D(log_d_p, log_d_m, state):
     return Dp, Dm
 
 
-def single_Q(theta, state):
+def single_Q(theta, state, dtype=None):
     """Dense generator of a single-tumour MHN (theta NOT logarithmic) restricted to `state` (len n+1)."""
+    theta = np.asarray(theta, dtype=dtype)
     ev = [j for j in range(len(state)) if state[j]]
     k = len(ev)
     N = theta.shape[0]
-    Q = np.zeros((2 ** k, 2 ** k))
+    Q = np.zeros((2 ** k, 2 ** k), dtype=np.result_type(theta, np.float64))
     for x in range(2 ** k):
         S = [ev[b] for b in range(k) if x >> b & 1]
         for i in range(N):
@@ -122,10 +126,12 @@ def single_Q(theta, state):
     return Q
 
 
-def _single_D(d, state):
+def single_D(d, state, dtype=None):
+    """Product of the rates d (NOT logarithmic) of the events present in each state of the restricted space."""
+    d = np.asarray(d, dtype=dtype)
     ev = [j for j in range(len(state)) if state[j]]
     k = len(ev)
-    D = np.ones(2 ** k)
+    D = np.ones(2 ** k, dtype=np.result_type(d, np.float64))
     for x in range(2 ** k):
         for b in range(k):
             if x >> b & 1:
@@ -149,7 +155,7 @@ def patient_lp(log_theta, log_d_p, log_d_m, row):
         if typ == 0 and st.sum() == 0:
             return -np.log(1.0 + np.trace(th))
         Q = single_Q(th_pt, st)
-        D = _single_D(dp, st)
+        D = single_D(dp, st)
         e0 = np.zeros(Q.shape[0])
         e0[0] = 1.0
         return np.log(D[-1] * np.linalg.solve(np.diag(D) - Q, e0)[-1])
@@ -158,8 +164,8 @@ def patient_lp(log_theta, log_d_p, log_d_m, row):
         Q = single_Q(th, st)
         k = int(st.sum())
         D = np.empty(2 ** k)
-        Dp_ = _single_D(np.append(dp[:n], 1.0), st)
-        Dm_ = _single_D(dm, st)
+        Dp_ = single_D(np.append(dp[:n], 1.0), st)
+        Dm_ = single_D(dm, st)
         half = 2 ** (k - 1)
         D[:half] = Dp_[:half]
         D[half:] = Dm_[half:]
@@ -182,7 +188,7 @@ def patient_lp(log_theta, log_d_p, log_d_m, row):
         idx = [x for x in range(2 ** k) if (x & maskP) == maskP and x & seedb]
         met = np.append(st[1::2], 1)
         QM = single_Q(th, met)
-        DM = _single_D(dm, met)
+        DM = single_D(dm, met)
         v = np.zeros(QM.shape[0])
         v[len(v) // 2:] = (Dp * pi)[idx]
         tot += DM[-1] * np.linalg.solve(np.diag(DM) - QM, v)[-1]
@@ -190,7 +196,7 @@ def patient_lp(log_theta, log_d_p, log_d_m, row):
         idx = [x for x in range(2 ** k) if (x & maskM) == maskM and x & seedb]
         prim = st[0::2]
         QP = single_Q(th_pt, prim)
-        DP = _single_D(dp, prim)
+        DP = single_D(dp, prim)
         v = np.zeros(QP.shape[0])
         v[len(v) // 2:] = (Dm * pi)[idx]
         tot += DP[-1] * np.linalg.solve(np.diag(DP) - QP, v)[-1]
