@@ -153,7 +153,6 @@ struct Batch {
   std::vector<WDesc> wd;         // sorted by shape; the state vectors of consecutive entries lie back to back
   DevArr<WDesc> d_wd;
   int wnx = -1;                  // external bits of every window problem of the batch, -1: they differ
-  bool wsplit = false;           // this batch runs the window route with two workgroups per patient (MMHN_WSPLIT)
   std::vector<WChain> wchains;   // runs of same-shape entries, one workgroup each (wsolve.h)
   DevArr<WChain> d_wchains;
   long long offT = 0;            // the RT_T problems' vectors start here (the tile solver skips their dead tiles: kept zero)
@@ -500,7 +499,6 @@ struct Engine : EngineBase {
   hipEvent_t ev_fork[3] = {}, ev_join[3] = {};
   bool small_path = true;       // MMHN_SMALL=0: keep the staged kernels for single-tumour spaces that fit one tile
   int prep_split_max = 2048;    // MMHN_PREP_SPLIT: problems up to which k_prep / k_pclass run a workgroup per table / class pass
-  bool pair_small = true;       // MMHN_PAIR_SMALL=0: the two marginal problems of a paired row one after the other
   int psolve_min = 384;         // multi-tile joint problems (outside the window route) in a batch from which they take one workgroup
                                 // per patient (k_psolve2) instead of the cooperative tile launch (MMHN_PSOLVE_MIN)
   int wsolve_min = 128;         // window-shaped joint problems in a batch from which they take the window route (MMHN_WSOLVE_MIN;
@@ -521,11 +519,7 @@ struct Engine : EngineBase {
   int cur_lane = 0;                 // lane of the launches being issued (1: a side stream)
   unsigned* h_abort = nullptr;
   unsigned* h_abort_dev = nullptr;
-  int wsolve_chain = 1;         // MMHN_WSOLVE_CHAIN=0: every window problem its own chain (the pipeline drains between patients)
   int wsolve_wgs = 0;           // MMHN_WSOLVE_WGS: workgroups of the window solve (default: one per CU)
-  bool wsplit = false;          // MMHN_WSPLIT=1: two workgroups per patient on the window route (wsolve.h: SPLIT; measured, off)
-  DevArr<unsigned> wprog;       // ... the progress words of its pairs
-  unsigned wsplit_epoch = 0;
   int wsolve_mode = 1;          // joint solves of per-patient batches in the window layout (wsolve.h); MMHN_WSOLVE=0: the tile
                                 // kernels (k_psolve2) for every problem, 2: window solves converted back to index order
   DevArr<T> piM, qM;            // matrix / window path: solutions in their own layout
@@ -578,13 +572,10 @@ struct Engine : EngineBase {
       if (const char* pm = std::getenv("MMHN_COOP_FAULT")) coop_fault = std::atoi(pm) != 0;
       if (const char* po = std::getenv("MMHN_POISON")) poison = std::atoi(po) != 0;
       if (const char* sp = std::getenv("MMHN_SMALL")) small_path = std::atoi(sp) != 0;
-      if (const char* sp = std::getenv("MMHN_PAIR_SMALL")) pair_small = std::atoi(sp) != 0;
       if (const char* sp = std::getenv("MMHN_ZEROCOPY")) zero_copy = std::atoi(sp) != 0;
       if (const char* sp = std::getenv("MMHN_PREP_SPLIT")) prep_split_max = std::atoi(sp);
       if (const char* ms = std::getenv("MMHN_WSOLVE")) wsolve_mode = std::atoi(ms);
       if (const char* ms = std::getenv("MMHN_WSOLVE_WGS")) wsolve_wgs = std::atoi(ms);
-      if (const char* ms = std::getenv("MMHN_WSPLIT")) wsplit = std::atoi(ms) != 0;
-      if (const char* ms = std::getenv("MMHN_WSOLVE_CHAIN")) wsolve_chain = std::atoi(ms);
       hipDeviceProp_t prop;
       HIPCHECK(hipGetDeviceProperties(&prop, device));
       n_cu = std::max(1, prop.multiProcessorCount);
@@ -593,8 +584,6 @@ struct Engine : EngineBase {
     HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wsolve<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wsolve_lds<T>()));
     HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wsolve<T, false, WCfg<T>::NXT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wsolve_lds<T>()));
     HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wsolve<T, true, WCfg<T>::NXT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wsolve_lds<T>()));
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wsolve<T, false, WCfg<T>::NXT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wsolve_lds<T>()));
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wsolve<T, true, WCfg<T>::NXT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wsolve_lds<T>()));
     HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wclass<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wclass_lds<T>()));
     // kernels may need more than the default dynamic LDS window
     const int lds = 150 * 1024;
@@ -864,8 +853,6 @@ struct Engine : EngineBase {
   size_t psolve2_lds(int maxk) const {
     return DESC_PAD + ((size_t)(1 << TB) + (size_t)((1 << TB) / TSB) + 3 * (size_t)maxk * 64 + (size_t)maxk * maxk + maxk) * sizeof(T) + 400 * sizeof(uint32_t) + (size_t)TSB * sizeof(uint16_t);
   }
-  // groups of chains under MMHN_WSPLIT (a multiple of eight: the pair of a block is the block eight further on)
-  int wsplit_groups() const { return std::max(8, (wsolve_wgs > 0 ? wsolve_wgs : n_cu) / 16 * 8); }
   // the joint solves of a batch, every problem on its route (Batch::route)
   void psolve(bool tr, const Batch& b, T* y, int rhs_mode) {
     const int nJ = (int)b.dJ.size();
@@ -880,25 +867,10 @@ struct Engine : EngineBase {
         const int nch = (int)b.wchains.size();
         const dim3 g((unsigned)std::min(nch, wsolve_wgs > 0 ? wsolve_wgs : n_cu)), bk(WROWS);
         const size_t lds = wsolve_lds<T>();
-#define WS_ARGS g, bk, lds, stream, b.d_dJ.p, b.d_wd.p, b.d_wchains.p, nch, yw, tabJ.p, links.p, qS.p, (unsigned*)nullptr, 0u, (unsigned*)nullptr, (unsigned*)nullptr
+#define WS_ARGS g, bk, lds, stream, b.d_dJ.p, b.d_wd.p, b.d_wchains.p, nch, yw, tabJ.p, links.p, qS.p
         // (a batch whose chains all have the same number of external bits - every k = 20 cohort: 5, k = 25: 9 - runs the instantiation
         // that knows it at compile time)
-        if (b.wsplit) {
-          // two workgroups per patient: pairs (b, b + 8) walk the chains dealt to wsplit_groups() groups
-          const int npairs = std::min((nch + 7) / 8 * 8, wsplit_groups());
-          if (wprog.n < (size_t)npairs) { wprog.alloc((size_t)wsplit_groups() + 64); wsplit_epoch = 0; }
-          if (wsplit_epoch == 0 || wsplit_epoch >= 2047u) {
-            HIPCHECK(hipMemsetAsync(wprog.p, 0, wprog.n * sizeof(unsigned), stream));
-            wsplit_epoch = 0;
-          }
-          ++wsplit_epoch;
-          coop_used = true;
-          const dim3 g2((unsigned)(2 * npairs));
-#define WS2_ARGS g2, bk, lds, stream, b.d_dJ.p, b.d_wd.p, b.d_wchains.p, nch, yw, tabJ.p, links.p, qS.p, wprog.p, wsplit_epoch << 20, &coop_ctl.p->abort, h_abort_dev
-          if (tr) hipLaunchKernelGGL((k_wsolve<T, true, WCfg<T>::NXT, true>), WS2_ARGS);
-          else hipLaunchKernelGGL((k_wsolve<T, false, WCfg<T>::NXT, true>), WS2_ARGS);
-#undef WS2_ARGS
-        } else if (b.wnx == WCfg<T>::NXT) { if (tr) hipLaunchKernelGGL((k_wsolve<T, true, WCfg<T>::NXT>), WS_ARGS); else hipLaunchKernelGGL((k_wsolve<T, false, WCfg<T>::NXT>), WS_ARGS); }
+        if (b.wnx == WCfg<T>::NXT) { if (tr) hipLaunchKernelGGL((k_wsolve<T, true, WCfg<T>::NXT>), WS_ARGS); else hipLaunchKernelGGL((k_wsolve<T, false, WCfg<T>::NXT>), WS_ARGS); }
         else if (tr) hipLaunchKernelGGL((k_wsolve<T, true>), WS_ARGS);
         else hipLaunchKernelGGL((k_wsolve<T, false>), WS_ARGS);
 #undef WS_ARGS
@@ -913,11 +885,7 @@ struct Engine : EngineBase {
       const int mk = std::max(b.maxkP, 1);
       const long long spare = (80 * 1024 - 64) - (long long)psolve2_lds(mk);
       const int dl_cap = (int)std::max<long long>(0, std::min<long long>(PS_DL2, spare / (long long)sizeof(T)));
-#ifdef MMHN_ABL_PACK
-      const size_t lds = std::max<size_t>(psolve2_lds(mk) + (size_t)dl_cap * sizeof(T), 100 * 1024);   // one workgroup per CU
-#else
       const size_t lds = psolve2_lds(mk) + (size_t)dl_cap * sizeof(T);
-#endif
       const double bytes = (double)b.ptiles.size() * (double)(1 << TB) * sizeof(T);
       const bool dlok = b.max_dl <= dl_cap;       // every patient's dP / dM tile slices fit the dl area: branch-free instantiation
       const int nold = (int)b.olist.size();
@@ -1217,15 +1185,14 @@ struct Engine : EngineBase {
         const int nW = (int)b.wd.size();
         b.wnx = b.wd[0].nXc + b.wd[0].nXr;
         for (const WDesc& w : b.wd) if (w.nXc + w.nXr != b.wnx) b.wnx = -1;
-        b.wsplit = wsplit && b.wnx == WCfg<T>::NXT && WCfg<T>::NXT >= 4;
-        const int groups = b.wsplit ? wsplit_groups() : std::max(1, wsolve_wgs > 0 ? wsolve_wgs : n_cu);
+        const int groups = std::max(1, wsolve_wgs > 0 ? wsolve_wgs : n_cu);
         const int per = (nW + groups - 1) / groups;
         for (int i0 = 0; i0 < nW;) {
           const WDesc& w = b.wd[i0];
           const int k = b.dJ[w.prob].k;
           // a chain keeps two patients' tables alive at once: it needs 2^nX > 6 passes per patient; its span must stay
           // below 2 GB (32-bit buffer offsets)
-          const int maxlen = (w.nXc + w.nXr >= 3 && wsolve_chain) ? (int)std::min<long long>(per, (1ll << 31) / ((long long)sizeof(T) << k) - 1) : 1;
+          const int maxlen = w.nXc + w.nXr >= 3 ? (int)std::min<long long>(per, (1ll << 31) / ((long long)sizeof(T) << k) - 1) : 1;
           int len = 1;
           while (len < maxlen && i0 + len < nW && b.wd[i0 + len].kR == w.kR && b.wd[i0 + len].kC == w.kC && (i0 + len) % per != 0) ++len;
           b.wchains.push_back(WChain{i0, len});
@@ -1341,14 +1308,14 @@ struct Engine : EngineBase {
           if (pr.kind == 2) g.kind2 = true;
           continue;
         }
-        const bool side_by_side = pair_small && pr.j >= 0 && pr.s[0] >= 0 && pr.s[1] >= 0 && c < 2;
+        const bool side_by_side = pr.j >= 0 && pr.s[0] >= 0 && pr.s[1] >= 0 && c < 2;
         b.sp_list[side_by_side ? 2 : pr.j >= 0 ? 1 : 0][c].push_back((int)pi_);
       }
       // paired rows of the 1024-thread class: when they are few and of at most 10 bits they ride in the merged 256-thread
       // launch (its LDS sized for them) - on a small cohort their own launch is a side stream, a fork and a join
       // (~20 us of queue latency) for a handful of patients
       b.mk1p = spatient_class_maxk(1);
-      if (pair_small && !b.sp_list[1][2].empty() && b.sp_list[1][2].size() <= 16) {
+      if (!b.sp_list[1][2].empty() && b.sp_list[1][2].size() <= 16) {
         int mk = 0;
         for (int pi_ : b.sp_list[1][2])
           for (int part = 0; part < 2; ++part) if (b.pats[pi_].s[part] >= 0) mk = std::max(mk, b.dS[b.pats[pi_].s[part]].k);

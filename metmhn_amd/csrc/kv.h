@@ -269,9 +269,6 @@ __global__ __launch_bounds__(64) void k_hx(const Desc* __restrict__ descs, const
 #ifndef MMHN_KV_LU
 #define MMHN_KV_LU 2            // lane-bit moves unrolled (3: 98 VGPRs, one wave per SIMD less)
 #endif
-#ifndef MMHN_KV_DIRECT
-#define MMHN_KV_DIRECT 1         // y leaves as 8-byte write-through stores straight from the accumulators (0: through LDS as 16-byte stores)
-#endif
 #ifndef MMHN_KV_WPS
 #define MMHN_KV_WPS 4          // waves per SIMD k_kv's registers are sized for (4: two 512-thread workgroups per CU, 128 VGPRs)
 #endif
@@ -545,31 +542,18 @@ __global__ __launch_bounds__(KSB, MMHN_KV_WPS) void k_kv(const Desc* __restrict_
         acc[j] = a;
       }
     }
-    // y is not read again by this launch: it leaves through LDS as 16-byte write-through stores that do not stay in
-    // the XCD's L2, which keeps the p tiles that later tiles read as neighbours
     if (JAC) {
 #pragma unroll
       for (int j = 0; j < NJ; ++j) acc[j] = jl[j] * (acc[j] + jr[j]);
     }
-#if MMHN_KV_DIRECT
-    // (variant: 8-byte write-through stores straight from the accumulators, no trip through LDS)
+    // y is not read again by this launch: it leaves straight from the accumulators, in fp64 as 8-byte write-through
+    // stores that do not stay in the XCD's L2, which keeps the p tiles that later tiles read as neighbours
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       T* dst = y + base + xhi + ((((uint32_t)(wave * NJ + j)) << 6) | (uint32_t)lane);
       if (sizeof(T) == 8) asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" ::"v"(dst), "v"(acc[j]) : "memory");
       else *dst = acc[j];
     }
-#else
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) tile[((uint32_t)(wave * NJ + j) << 6) | (uint32_t)lane] = acc[j];
-    __syncthreads();
-    for (uint32_t e = (uint32_t)tid * PER; e < nelem; e += KSB * PER) {
-      const f32x4 val = *reinterpret_cast<const f32x4*>(&tile[e]);
-      T* dst = y + base + xhi + e;
-      asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(dst), "v"(val) : "memory");
-    }
-#endif
     if (it + 1 < tpw) __syncthreads();                       // the tile (and hx) are rewritten by the next trip
   }
 }

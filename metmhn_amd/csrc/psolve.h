@@ -22,13 +22,6 @@ namespace mmhn {
 #ifndef MMHN_Q_TPA
 #define MMHN_Q_TPA 2          // neighbour tiles in flight per thread in k_psolve2's step A
 #endif
-#ifndef MMHN_Q_EARLY
-#define MMHN_Q_EARLY 0        // 1: first trip of neighbour-tile loads requested before the per-tile set-up barriers (measured: the
-                              // values spill across the set-up at 64 VGPRs - 68 B scratch, 27.8 instead of 22.3 ms; one tile ahead: 23.2 ms)
-#endif
-#ifndef MMHN_Q_CLATE
-#define MMHN_Q_CLATE -1
-#endif
 #ifndef MMHN_Q_LANES
 #define MMHN_Q_LANES 2        // lanes that share one group of k_psolve2's in-tile solve (1, 2 or 4)
 #endif
@@ -87,13 +80,8 @@ __device__ __forceinline__ T cluster_bcast(T v, int src) {
 // 27 %, LDS 39 % busy with 52 % of its cycles conflicts), not by HBM.
 // Same arithmetic as k_psolve term by term (rate_b(s) = Ltab[b][s & 63] * Utab[b][s >> 6], s the source state).
 // ------------------------------------------------------------------------------------
-#ifdef MMHN_ABL_PACK   // timing-only ablation (wrong results): the work of MMHN_ABL_PACK tiles per phase, one workgroup per CU
-#define PS2_WPE 4
-#else
-#define PS2_WPE TSB_WPE
-#endif
 template <typename T, bool TR, bool DLOK>
-__global__ __launch_bounds__(TSB, PS2_WPE) void k_psolve2(const Desc* __restrict__ descs,
+__global__ __launch_bounds__(TSB, TSB_WPE) void k_psolve2(const Desc* __restrict__ descs,
                                                     const int* __restrict__ pt_off,
                                                     const uint32_t* __restrict__ ptiles,
                                                     const Params<T>* __restrict__ par, T* y, int rhs_mode,
@@ -213,9 +201,7 @@ __global__ __launch_bounds__(TSB, PS2_WPE) void k_psolve2(const Desc* __restrict
     const uint32_t nlo = ((uint32_t)tid & LOM) << GL, nhi = (uint32_t)tid >> (6 - GL);
     // ---- per tile: slices of the diagonal tables (land in LDS behind the next barrier), tile-bit factors
     // (up to 2^10 + 2^4 entries: thread tid takes entry tid and, for the few beyond the workgroup size, tid + TSB)
-    // ---- single-bit moves above the tile (step A): scalar bit list of the tile index.  With MMHN_Q_EARLY the first
-    // MMHN_Q_TPA neighbour tiles that come from HBM are requested here - they were solved at least two tiles ago, their
-    // stores were waited for at the previous tile's barrier - and fly through the set-up barriers below
+    // ---- single-bit moves above the tile (step A): scalar bit list of the tile index
     uint32_t mb = (TR ? ~H : H) & ((1u << (k - t)) - 1u) & ~(1u << (seedb - t));
     const uint32_t dprev = H ^ Hprev;
     const bool prev_in_lds = Hprev != 0xffffffffu && (dprev & (dprev - 1)) == 0 && (dprev & mb);
@@ -228,21 +214,12 @@ __global__ __launch_bounds__(TSB, PS2_WPE) void k_psolve2(const Desc* __restrict
         bq[q] = on ? t + __ffs(mb) - 1 : -1;
         mb &= mb - 1;
         if (on) {
-#ifdef MMHN_ABL_FAKE_NBR      // timing-only ablation (wrong results): neighbour reads served by L2 instead of HBM
-          const T* yn = y + base + ((uint32_t)tid << GL);
-#else
           const T* yn = y + base + (xhi ^ (1u << bq[q])) + ((uint32_t)tid << GL);
-#endif
           nv[q][0] = *reinterpret_cast<const lvec_t*>(yn);
           nv[q][1] = *reinterpret_cast<const lvec_t*>(yn + (1u << HB));
         }
       }
     };
-#if MMHN_Q_EARLY
-    int bq0[TPA];
-    lvec_t nv0[TPA][2];
-    nbr_fetch(bq0, nv0);
-#endif
     T dval = 0, dval2 = 0;
     const int ndl = dl_ok ? (1 << nPin) + (1 << nMin) : 0;
     auto dl_fetch = [&](int e) {
@@ -268,9 +245,6 @@ __global__ __launch_bounds__(TSB, PS2_WPE) void k_psolve2(const Desc* __restrict
     if (tid + TSB < ndl) dl[tid + TSB] = dval2;
     const uint32_t hP = pxt[384], hM = pxt[385];
     // ---- right-hand side (natural states).  Forward: e_0 lies in the seed = 0 part, so zero here.
-#ifdef MMHN_ABL_PACK
-    for (int rep = 0; rep < MMHN_ABL_PACK; ++rep) {
-#endif
     T acc[NJ];
 #pragma unroll
     for (int jq = 0; jq < NJ; ++jq) acc[jq] = T(0);
@@ -319,9 +293,6 @@ __global__ __launch_bounds__(TSB, PS2_WPE) void k_psolve2(const Desc* __restrict
         add_move(t + __ffs(dprev) - 1, nf);
       }
       // the others stream from HBM, TPA neighbour tiles in flight per thread
-#if MMHN_Q_EARLY
-      nbr_take(bq0, nv0);
-#endif
       while (mb) {
         int bq[TPA];
         lvec_t nv[TPA][2];
@@ -355,9 +326,6 @@ __global__ __launch_bounds__(TSB, PS2_WPE) void k_psolve2(const Desc* __restrict
     }
     STAMP(2);
     __syncthreads();
-#ifdef MMHN_ABL_PACK
-    }
-#endif
     STAMP(3);
     // ---- step B: levels over the popcount of the base state.  HP lanes of one DPP quad share a group (HP = 1, 2, 4;
     // a level has at most C(BB, BB/2) groups, a quarter of the workgroup): each lane takes every HP-th base-bit move,
@@ -372,15 +340,8 @@ __global__ __launch_bounds__(TSB, PS2_WPE) void k_psolve2(const Desc* __restrict
       for (int s = 0; s <= BB; ++s) {
         const int level = TR ? BB - s : s;
         const uint32_t goff = BP.v[level], gcnt = BP.v[level + 1] - goff;
-#ifdef MMHN_ABL_PACK
-        for (uint32_t item = gi; item < gcnt * MMHN_ABL_PACK; item += (uint32_t)(TSB >> LHP)) {
-          uint32_t gsel = item;
-          while (gsel >= gcnt) gsel -= gcnt;
-          const uint32_t ub = pml[goff + gsel];
-#else
         if (gi < gcnt) {
           const uint32_t ub = pml[goff + gi];
-#endif
           const uint32_t ulo = (ub & LOM) << GL, uhi = ub >> (6 - GL);
           // this lane's share of the group's right-hand side
           T z[NJ];
@@ -410,7 +371,7 @@ __global__ __launch_bounds__(TSB, PS2_WPE) void k_psolve2(const Desc* __restrict
               cmine[o] = Ltab[cbit * 64 + ulo + (jq == 3 ? 1u : 0u)] * Utab[cbit * 64 + uhi + (jq == 1 ? 32u : 0u)];
             }
           };
-          constexpr bool CLATE = MMHN_Q_CLATE < 0 ? HP == 1 : MMHN_Q_CLATE != 0;   // coefficients after the move loop (registers)
+          constexpr bool CLATE = HP == 1;                          // coefficients after the move loop (registers)
           if (!CLATE) coefs();
 #pragma unroll
           for (int o = 0; o < OWN; ++o)
@@ -496,20 +457,9 @@ __global__ __launch_bounds__(TSB, PS2_WPE) void k_psolve2(const Desc* __restrict
     }
     STAMP(4);
     // ---- step C: the thread's natural group leaves as 2^GL adjacent states per store
-#ifdef MMHN_ABL_NO_STORE       // timing-only ablation (wrong results): every tile is stored over the patient's first tile
-    const uint32_t xst = 0;
-#else
-    const uint32_t xst = xhi;
-#endif
-#ifdef MMHN_ABL_PACK
-    for (int rep = 0; rep < MMHN_ABL_PACK; ++rep)
-#endif
     {
       const group_t gq = *reinterpret_cast<const group_t*>(yt + ((uint32_t)tid << G));
-      T* yo = y + base + xst + ((uint32_t)tid << GL);
-#ifdef MMHN_ABL_PACK
-      asm volatile("" ::: "memory");
-#endif
+      T* yo = y + base + xhi + ((uint32_t)tid << GL);
 #pragma unroll
       for (int jh = 0; jh < 2; ++jh) {
         lvec_t ov;

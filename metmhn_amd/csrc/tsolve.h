@@ -49,9 +49,6 @@ struct CoopCtl {
 #ifndef MMHN_CS_WPE
 #define MMHN_CS_WPE MMHN_TS_WPE
 #endif
-#ifndef MMHN_TS_APIPE
-#define MMHN_TS_APIPE 0          // 1: step A as a software pipeline over the moves (next neighbour tile requested before the current terms)
-#endif
 #ifndef MMHN_TS_TRIP
 #define MMHN_TS_TRIP 3           // in-tile moves of a state whose LDS loads are issued together (step B)
 #endif
@@ -199,53 +196,6 @@ __device__ __forceinline__ void tsolve_tile(unsigned char* smem, const Desc* __r
   STAMP(2);
   wait();                                                      // (k_csolve: the tiles read below are complete and visible)
   STAMP(3);
-#if MMHN_TS_APIPE
-  // software pipeline over the moves: the neighbour tile of move i + 1 is requested before the terms of move i are formed
-  {
-    uint32_t p_mv = 0; int p_b = 0, p_kind = 0; bool p_seed = false;
-    T p_nv[NJ];
-    auto consume = [&]() {
-      const uint32_t ml = p_mv & tmask;
-      const T Lb = Ltab[p_b * 64 + lane];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int r = wave + NW * j;
-        const uint32_t xl = ((uint32_t)r << 6) | (uint32_t)lane;
-        const uint32_t x = xhi | xl;
-        const bool ss = seed_set(d, x);
-        bool cond = xl < nelem && (TR ? (xl & ml) == 0 : (xl & ml) == ml);
-        if (p_kind == 1) cond = cond && !ss && eq_noseed(d, x);
-        else if (p_seed) cond = cond && eq_noseed(d, x);
-        else cond = cond && ss;
-        const T term = Lb * Utab[p_b * 64 + (r & 63)] * p_nv[j];
-        acc[j] += cond ? term : T(0);
-      }
-    };
-    for (int b = (t > 0 ? t - 1 : 0); b < k; ++b) {
-      const int c = d.cls[b];
-      const bool is_seed = joint && c == CS;
-      const bool is_pair = joint && ((d.pairP >> b) & 1u);
-      for (int kind = 0; kind < 2; ++kind) {
-        if (kind == 1 && !is_pair) continue;
-        const uint32_t mv = kind == 0 ? (1u << b) : (3u << b);
-        const uint32_t mh = mv >> t;
-        if (mh == 0) continue;
-        if (TR ? (H & mh) != 0 : (H & mh) != mh) continue;
-        T c_nv[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const uint32_t xl = ((uint32_t)(wave + NW * j) << 6) | (uint32_t)lane;
-          c_nv[j] = xl < nelem ? y[base + ((xhi | xl) ^ mv)] : T(0);
-        }
-        if (p_mv) consume();
-        p_mv = mv; p_b = b; p_kind = kind; p_seed = is_seed;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) p_nv[j] = c_nv[j];
-      }
-    }
-    if (p_mv) consume();
-  }
-#else
   for (int b = (t > 0 ? t - 1 : 0); b < k; ++b) {
     const int c = d.cls[b];
     const bool is_seed = joint && c == CS;
@@ -280,7 +230,6 @@ __device__ __forceinline__ void tsolve_tile(unsigned char* smem, const Desc* __r
       }
     }
   }
-#endif
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const uint32_t xl = ((uint32_t)(wave + NW * j) << 6) | (uint32_t)lane;
@@ -442,23 +391,11 @@ __global__ __launch_bounds__(TSB, WPE) void k_csolve(const Desc* __restrict__ de
           }
           __builtin_amdgcn_s_sleep(MMHN_CS_SLEEP);
         }
-#ifndef MMHN_CS_NOACQ   // (timing-only ablation: wrong results)
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");     // ONE acquire after the match: drops this CU's stale lines
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // ... and is complete before the barrier lets the loads go
-#endif
       }
       __syncthreads();
     };
-#ifdef MMHN_CS_PLAIN    // variant: plain stores + ONE agent-scope release (L2 write-back) instead of write-through stores
-    tsolve_tile<T, TR, LIDGV, false>(smem, descs, ci.prob, ci.H, y, lidg, rhs, rhs_mode, scal, perm, maxk, tab, links, qS, wait);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(flags + it, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-#else
     tsolve_tile<T, TR, LIDGV, true>(smem, descs, ci.prob, ci.H, y, lidg, rhs, rhs_mode, scal, perm, maxk, tab, links, qS, wait);
     // publish: every storing wave drains its write-through stores, the workgroup meets, one lane raises the flag
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -466,7 +403,6 @@ __global__ __launch_bounds__(TSB, WPE) void k_csolve(const Desc* __restrict__ de
     // (fault != 0 - MMHN_COOP_FAULT=1, tests only: the first item never raises its flag, so that its dependants run into the
     // bound of their spin and the abort path is exercised)
     if (tid == 0 && !(fault && it == 0u)) __hip_atomic_store(flags + it, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
   }
 }
 

@@ -36,34 +36,9 @@
 
 namespace mmhn {
 
-#ifndef MMHN_W_NTFAR
-#define MMHN_W_NTFAR -1   // >= 0: external blocks of bit >= this value are loaded with the nt policy
-#endif
-// Round-5 switches, all measured and left off: none of them moves a launch by more than the noise - the
-// launch moves its 3.84 units of a patient's seeded half at the rate HBM delivers, whatever the order inside a step
-#ifndef MMHN_W_WPERM
-#define MMHN_W_WPERM 0  // 1: the wave index of the rows comes from a permutation of the hardware wave id that gives each SIMD (hardware
-                        // waves s, s + 4, s + 8, s + 12) the same number of ring moves (8 of the 32 of a step)
-#endif
-#ifndef MMHN_W_PRIO
-#define MMHN_W_PRIO 0   // 1: issue priority of a wave = its wave-level (the wave with the most ring moves is the one a barrier waits for)
-#endif
-#ifndef MMHN_W_STAG
-#define MMHN_W_STAG 0   // 1: the second external request of a step goes out half-way down the lane moves
-#endif
-// Timing-only ablations (WRONG results): MMHN_WABL_NOLOAD / _NOSTORE (no external block read / nothing written),
-// _NOTAB (no table read in a step), _NOPERM (the two lane exchanges of the LDS crossbar as DPP moves), _NORING (no ring reads),
-// _NOBAR (no barrier in the step loop)
-#ifndef MMHN_W_CW
-#define MMHN_W_CW 0     // 1: the rates of the four wave-bit moves kept in registers with the lane-bit rates (round 4: +4 ms with the
-                        // spills of the time; re-measured in round 5 with 9 - 16 registers free)
-#endif
-
 __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_s_waitcnt(0xc07f);              // lgkmcnt(0): LDS only, vector memory stays in flight
-#ifndef MMHN_WABL_NOBAR
   __builtin_amdgcn_s_barrier();
-#endif
 }
 
 template <typename T> __device__ __forceinline__ T fma_m(T a, T b, T c);
@@ -200,22 +175,11 @@ constexpr size_t wsolve_lds() { return WLds<T>::bytes; }
 // ------------------------------------------------------------------------------------
 // NXT >= 0: the number of external bits of every chain of the launch, as a compile-time constant (the step loop then has no
 // scalar branches on it); NXT < 0: read per chain
-// SPLIT (NXT >= 4): TWO workgroups per patient (review item 2 of round 4 in its cheapest form).  Blocks b and
-// b + 8 - the same XCD under the round-robin placement of workgroups - are a pair that walks the same chains: role 0 ("A") takes the
-// half of every patient's passes it does not need the partner for (forward: top bit of the external index clear; transposed: set),
-// role 1 ("B") the other half, whose move along the top bit reads what A wrote.  A lane of B at pass g needs the SAME lane of A at
-// pass g, i.e. A's iteration of the same number: A drains its stores at the end of every iteration of the pass loop and its last wave
-// raises the pair's progress word (write-through stores, relaxed agent-scope flag: the protocol of k_csolve, tsolve.h); every wave of B
-// polls that word in front of an iteration (bounded; `abort_w` / `h_abort` as in k_csolve), one agent-scope acquire, plain loads.
-// Every workgroup sets the patient's tables up; the transposed solve's seed = 0 lattice is B's.
-constexpr unsigned WSPLIT_SPIN_LIMIT = 1u << 22;
-template <typename T, bool TR, int NXT = -1, bool SPLIT = false>
+template <typename T, bool TR, int NXT = -1>
 __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs, const WDesc* __restrict__ wds,
                                                   const WChain* __restrict__ chains, int nchains,
                                                   T* y, const T* __restrict__ tab,
-                                                  const JLink<T>* __restrict__ links, const T* __restrict__ qS,
-                                                  unsigned* wprog, unsigned wbase, unsigned* abort_w, unsigned* h_abort) {
-  static_assert(!SPLIT || NXT >= 4, "two workgroups per patient: a compile-time number of external bits, 2^(NXT - 1) > 6 passes per half");
+                                                  const JLink<T>* __restrict__ links, const T* __restrict__ qS) {
   using C = WCfg<T>;
   using L = WLds<T>;
   constexpr int RB = C::RB, HB = C::HB, NC = 1 << RB, H = 1 << HB, WB = RB + HB, WIN = 1 << WB;
@@ -236,27 +200,12 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
   T* const thc = lds + L::thc;
   T* const e0 = lds + L::e0;
   WPInfo<T>* const pinfo = reinterpret_cast<WPInfo<T>*>(lds + L::end);
-#if MMHN_W_WPERM
-  // hardware wave -> wave index of its rows (nibble h of the constant, from the top)
-  const int wv = __builtin_amdgcn_readfirstlane((int)((0x0123FEDC5647A9B8ull >> (60 - 4 * ((int)threadIdx.x >> 6))) & 15ull));
-  const int tid = (wv << 6) | ((int)threadIdx.x & 63);
-#else
   const int tid = threadIdx.x;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-#endif
   const int lam = TR ? WWB - __popc(wv) : __popc(wv);          // wave-level: blocks this wave runs behind
-#if MMHN_W_PRIO
-  if (lam >= 3) __builtin_amdgcn_s_setprio(3);
-  else if (lam == 2) __builtin_amdgcn_s_setprio(2);
-  else if (lam == 1) __builtin_amdgcn_s_setprio(1);
-#endif
   // (thread-derived values are re-derived from an opaque copy of the thread id inside every step / pass: hipcc would
   // otherwise hoist a dozen loop-invariant LDS addresses out of the step loop and spill them)
-#if MMHN_W_WPERM
-  auto opaque_tid = [&]() -> uint32_t { uint32_t t = (uint32_t)threadIdx.x & 63u; asm volatile("" : "+v"(t)); return t | ((uint32_t)wv << 6); };
-#else
   auto opaque_tid = [&]() -> uint32_t { uint32_t t = (uint32_t)threadIdx.x; asm volatile("" : "+v"(t)); return t; };
-#endif
   // a column set that does not contain bit b, with bit b squeezed out
   auto squeeze = [](uint32_t v, int b) -> uint32_t { return ((v >> (b + 1)) << b) | (v & ((1u << b) - 1u)); };
   auto deskew = [&]() { for (int s = lam; s < WWB; ++s) lds_barrier(); };
@@ -265,35 +214,7 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
   // (formed once: inside the chain loop the addresses of wrho's tables were kept over the step loop and spilled)
   const uint32_t voff = wrho((uint32_t)tid >> 6, (uint32_t)tid & 63u) * (uint32_t)sizeof(VecT);
   STAMP_DECL;
-  // SPLIT: pair and role of this workgroup; cum = iterations of the pass loop the pair has behind it in this launch
-  const int role = SPLIT ? (int)((blockIdx.x >> 3) & 1u) : 0;
-  const int cstart = SPLIT ? (int)(((blockIdx.x >> 4) << 3) | (blockIdx.x & 7u)) : (int)blockIdx.x;
-  const int cstep = SPLIT ? (int)(gridDim.x >> 1) : (int)gridDim.x;
-  unsigned* const prog = SPLIT ? wprog + cstart : nullptr;
-  unsigned cum = 0;
-  // B: wait until A has `need` iterations behind it (every wave by itself: no barrier; one acquire)
-  auto wait_partner = [&](unsigned need) {
-    const unsigned want = wbase + need;
-    unsigned spins = 0;
-    for (;;) {
-      const unsigned v = __hip_atomic_load(prog, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if ((int)(v - want) >= 0) break;
-      if ((++spins & 15u) == 0u) {
-        if (__hip_atomic_load(abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-        if (spins > WSPLIT_SPIN_LIMIT) {
-          __hip_atomic_store(abort_w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(h_abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          break;
-        }
-      }
-      __builtin_amdgcn_s_sleep(8);
-    }
-#ifndef MMHN_WSPLIT_NOACQ   // (experiment, timing only)
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  };
-  for (int ci = cstart; ci < nchains; ci += cstep) {
+  for (int ci = (int)blockIdx.x, cstep = (int)gridDim.x; ci < nchains; ci += cstep) {
     STAMP_START;
     const int first = sgpr(chains[ci].start), npat = sgpr(chains[ci].count);
     if (npat == 0) continue;                                   // (a filler entry of the host's chain deal)
@@ -313,11 +234,9 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
     const long long half = 1ll << (k - 1);
     const long long ybase = sgpr64(d0.off);                    // patient j of the chain: y + ybase + (j << k)
     const uint32_t NXS = 1u << nX, mXc = (1u << nXc) - 1u;
-    const int nXw = SPLIT ? nX - 1 : nX;                       // log2 of the passes of a patient THIS workgroup makes
-    const uint32_t NXW = 1u << nXw;
     const uint32_t Sxfull = (1u << nXr) - 1u, Txfull = mXc;
     const uint32_t PATB = (uint32_t)(sizeof(T) << k), HALFB = PATB >> 1;   // bytes of a patient's vector / of its seeded half
-    const int NPASS = npat * (int)NXW + WLB;
+    const int NPASS = npat * (int)NXS + WLB;
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(sgpr64((long long)reinterpret_cast<char*>(y + ybase))), 0,
                                                         (int)sgpr((uint32_t)npat * PATB), 0x00020000);
     // ---- a patient enters: its tables (buffer j & 1), forward: its seed = 0 lattice (only PT == MT states carry values).
@@ -464,20 +383,10 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
     };
     auto st_row = [&](uint32_t off, uint32_t soff, const VecT& v) {
       const Raw r = __builtin_bit_cast(Raw, v);
-#ifdef MMHN_WSPLIT_PLAIN   // (experiment: plain stores - only valid while both workgroups of a pair sit on one XCD)
-      constexpr int WT = 0;
-#else
-      constexpr int WT = SPLIT ? 16 : 0;                        // (16: sc1, write-through)
-#endif
-      __builtin_amdgcn_raw_buffer_store_b128(r.q[0], rsrc, (int)off, (int)soff, WT);
-      __builtin_amdgcn_raw_buffer_store_b128(r.q[1], rsrc, (int)off + 16, (int)soff, WT);
+      __builtin_amdgcn_raw_buffer_store_b128(r.q[0], rsrc, (int)off, (int)soff, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(r.q[1], rsrc, (int)off + 16, (int)soff, 0);
     };
     auto lds_vec = [&](const T* p) -> VecT {                   // NC consecutive elements, 16-byte aligned
-#ifdef MMHN_WABL_NOTAB
-      VecT cv;
-      for (int c = 0; c < NC; ++c) cv[c] = T(0.25);
-      return cv;
-#endif
       Raw r;
       r.q[0] = *reinterpret_cast<const u32x4*>(p);
       r.q[1] = *reinterpret_cast<const u32x4*>(p + QE);
@@ -500,17 +409,14 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
     auto opq = [](uint32_t v) -> uint32_t { asm volatile("" : "+v"(v)); return v; };
     uint32_t Sigma = 0, soff = opq(OOB), tbo = L::tab0;
     T cL[WLB], dRv = T(1);
-#if MMHN_W_CW
-    T cW[WWB];                                                 // rates of the four wave-bit moves (same row constants as cL)
-#endif
     uint32_t hitT = opq(0xffffffffu), hitE = 0;
     uint32_t rowkey = opq(0xffffffffu);                        // (patient, external row setting) the row constants were formed for
     auto begin_pass = [&](int sig) {
       const uint32_t tt = opaque_tid(), ln = tt & 63u;
       const int V = sig - (TR ? WLB - __popc(ln) : __popc(ln));
-      const bool act = (unsigned)V < (unsigned)npat * NXW;
+      const bool act = (unsigned)V < (unsigned)npat * NXS;
       const uint32_t Vc = act ? (uint32_t)V : 0u;
-      const uint32_t j = Vc >> nXw, g = (Vc & (NXW - 1u)) | (SPLIT ? (uint32_t)role << nXw : 0u);
+      const uint32_t j = Vc >> nX, g = Vc & (NXS - 1u);
       Sigma = TR ? NXS - 1u - g : g;
       const uint32_t Sx = Sigma >> nXc;
       tbo = L::tab0 + (j & 1u) * L::TABSZ;
@@ -528,11 +434,6 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
         const T r = tb[oLr + i * 64 + ln] * tb[oUr + i * 16 + wv] * tb[oEr + i * ES + Sx];
         cL[i] = has ? r : T(0);
       }
-#if MMHN_W_CW
-#pragma unroll
-      for (int j = 0; j < WWB; ++j)
-        cW[j] = tb[oLr + (WLB + j) * 64 + ln] * tb[oUr + (WLB + j) * 16 + wv] * tb[oEr + (WLB + j) * ES + Sx];
-#endif
       dRv = tab[pi_.droff + (tt | (Sx << WTB))];
       if (!TR) {
         // forward right-hand side: seeding enters row S at the one column whose paired events are those of S
@@ -567,9 +468,6 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
       // external moves: the thread's own earlier blocks.  A move that does not exist is requested beyond the end of
       // the buffer (zeros come back, nothing is touched): no per-move control flow.
       auto ext_off = [&](int j) -> uint32_t {
-#ifdef MMHN_WABL_NOLOAD   // timing-only ablation (wrong results): no external block is read
-        return OOB;
-#endif
         const bool has = TR ? !((Sgo >> j) & 1u) : ((Sgo >> j) & 1u);
         return (has && soff != OOB) ? (soff ^ (1u << (j + BSH))) : OOB;
       };
@@ -588,11 +486,7 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
           }
         } else {
           const int i = WTB + (j - nXc);
-#ifdef MMHN_WABL_NOTAB
-          const T r = T(0.125);
-#else
           const T r = tb[oLr + i * 64 + ln] * tb[oUr + i * 16 + wv] * tb[oEr + i * ES + Sx];
-#endif
 #pragma unroll
           for (int c = 0; c < NC; ++c) acc[c] = fma_m(r, nv[c], acc[c]);
         }
@@ -601,49 +495,22 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
       // window, the likeliest cache hit - takes the slot at the end of the step that is requested and waited for in one go
       // (forward 13.5 -> 13.1 ms per 5 000 patients; no gain in fp32 at k = 25, whose slots are all requested a phase ahead)
       auto sb = [&](int sl) -> int { return C::REV ? nX - 1 - sl : sl; };
-      // (MMHN_W_NTFAR = j0: the blocks of the external bits >= j0 - written 2^j0 window passes ago, far beyond what the XCD's L2
-      // holds for this workgroup - are loaded non-temporally, so that they do not displace the near ones; measured, section 6)
-      auto ld_ext = [&](int j) -> VecT {
-        const uint32_t off = ext_off(j);
-#if MMHN_W_NTFAR >= 0
-        if (j >= MMHN_W_NTFAR) {
-          Raw r;
-          r.q[0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)off, (int)boff, 2);
-          r.q[1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)off + 16, (int)boff, 2);
-          return __builtin_bit_cast(VecT, r);
-        }
-#endif
-        return ld_row(off, boff);
-      };
+      auto ld_ext = [&](int j) -> VecT { return ld_row(ext_off(j), boff); };
       VecT ev0, ev1;
       if (nX > 0) ev0 = ld_ext(sb(0));
-#if !MMHN_W_STAG
       if (nX > 1) ev1 = ld_ext(sb(1));
-#endif
       __builtin_amdgcn_sched_barrier(0);
       // lane moves: the neighbour lane's window slot (its previous window pass = this lane's pass)
       {
         const VecT old = Wd[beta];
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-#if MMHN_W_STAG
-          if (c == NC / 2) {
-            __builtin_amdgcn_sched_barrier(0);
-            if (nX > 1) ev1 = ld_ext(sb(1));
-            __builtin_amdgcn_sched_barrier(0);
-          }
-#endif
           acc[c] = fma_m(cL[0], lane_nbr<0, TR>(old[c], (int)ln), acc[c]);
           acc[c] = fma_m(cL[1], lane_nbr<1, TR>(old[c], (int)ln), acc[c]);
           acc[c] = fma_m(cL[2], lane_nbr<2, TR>(old[c], (int)ln), acc[c]);
           acc[c] = fma_m(cL[3], lane_nbr<3, TR>(old[c], (int)ln), acc[c]);
-#ifdef MMHN_WABL_NOPERM
-          acc[c] = fma_m(cL[4], lane_nbr<3, TR>(old[c], (int)ln), acc[c]);
-          acc[c] = fma_m(cL[5], lane_nbr<2, TR>(old[c], (int)ln), acc[c]);
-#else
           acc[c] = fma_m(cL[4], lane_nbr<4, TR>(old[c], (int)ln), acc[c]);
           acc[c] = fma_m(cL[5], lane_nbr<5, TR>(old[c], (int)ln), acc[c]);
-#endif
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -665,24 +532,14 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
         const T* rs = ring + (uint32_t)(gpar ^ 1) * (NC * WROWS);
 #pragma unroll
         for (int j = 0; j < WWB; ++j) {
-#ifdef MMHN_WABL_NORING
-          const bool has = false;
-#else
           const bool has = TR ? !((wv >> j) & 1) : ((wv >> j) & 1);
-#endif
           if (has) {                                           // wave-uniform
             const uint32_t row = tt ^ (64u << j);
             Raw r;
             r.q[0] = *reinterpret_cast<const u32x4*>(rs + row * QE);
             r.q[1] = *reinterpret_cast<const u32x4*>(rs + WROWS * QE + row * QE);
             const VecT nv = __builtin_bit_cast(VecT, r);
-#if MMHN_W_CW
-            const T cw = cW[j];
-#elif defined(MMHN_WABL_NOTAB)
-            const T cw = T(0.125);
-#else
             const T cw = tb[oLr + (WLB + j) * 64 + ln] * tb[oUr + (WLB + j) * 16 + wv] * tb[oEr + (WLB + j) * ES + Sx];
-#endif
 #pragma unroll
             for (int c = 0; c < NC; ++c) acc[c] = fma_m(cw, nv[c], acc[c]);
           }
@@ -783,9 +640,6 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
         for (int r = 0; r < RB; ++r) fxr[r] = tb[oFx + r * XS + Tx];
       }
       auto blk_rate = [&](int r, int wset, int wsq) -> T {     // rate of column bit r at window setting wset (bit r clear)
-#ifdef MMHN_WABL_NOTAB
-        return T(0.125);
-#endif
         if constexpr (C::FACT) return tb[L::oFw + r * WIN + wset] * fxr[r];
         else return tb[L::oRh + r * SZLO + Tx * LOS + wsq];
       };
@@ -825,23 +679,17 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
         *reinterpret_cast<u32x4*>(ws + tt * QE) = r.q[0];
         *reinterpret_cast<u32x4*>(ws + WROWS * QE + tt * QE) = r.q[1];
       }
-#ifdef MMHN_WABL_NOSTORE  // timing-only ablation (wrong results): nothing is written
-      st_row(OOB, boff, Y);
-#else
       st_row(soff, boff, Y);
-#endif
       STAMP(4);
     };
     // ---- the pipeline: wave-level lam delays the wave by lam steps, lane-level m delays a lane by m window passes;
     // a patient enters every 2^nX passes (the waves meet for its tables: four steps of slack) and, transposed, is
     // completed by its seed = 0 lattice six passes after the next one entered
     for (int sig = 0; sig < NPASS; ++sig) {
-      const uint32_t ph = (uint32_t)sig & (NXW - 1u);
-      const int jj = sig >> nXw;
+      const uint32_t ph = (uint32_t)sig & (NXS - 1u);
+      const int jj = sig >> nX;
       if (ph == 0 && jj >= 1 && jj < npat) { deskew(); enter(jj); reskew(); }
-      // SPLIT: B needs A's iteration of the same number (A's word counts the iterations it has drained)
-      if constexpr (SPLIT) { if (role == 1) wait_partner(cum + (unsigned)sig + 1u); }
-      if (TR && ph == (uint32_t)WLB && jj >= 1 && !(SPLIT && role == 0)) { deskew(); leave(jj - 1); reskew(); }
+      if (TR && ph == (uint32_t)WLB && jj >= 1) { deskew(); leave(jj - 1); reskew(); }
  STAMP(7);
       begin_pass(sig);
       STAMP(6);
@@ -859,24 +707,9 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
         step(IC<7 % H>{}, g0 ^ 1); lds_barrier(); STAMP(5);
       }
       static_assert(H == 2 || H == 4 || H == 8, "window of 2, 4 or 8 blocks");
-      if constexpr (SPLIT) {
-        // A: this wave's stores up to here are complete; the wave that runs furthest behind (every other one passed this point
-        // before it) raises the pair's word
-        if (role == 0) {
-#ifndef MMHN_WSPLIT_NODRAIN  // (experiment, timing only)
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-          if (lam == WWB && (threadIdx.x & 63u) == 0u)
-            __hip_atomic_store(prog, wbase + cum + (unsigned)sig + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-    }
-    if constexpr (SPLIT) {
-      if (role == 1) wait_partner(cum + (unsigned)NPASS);      // (the transposed solve's last lattice reads A's half too)
-      cum += (unsigned)NPASS;
     }
     deskew();
-    if (TR && !(SPLIT && role == 0)) leave(npat - 1);
+    if (TR) leave(npat - 1);
     __syncthreads();
     STAMP(7);
   }
