@@ -173,6 +173,21 @@ int mmhn_comm_destroy(mmhn_handle h);
  */
 int mmhn_simulate(mmhn_handle h, const double* log_theta, const double* pt_d_ef, const double* mt_d_ef,
                   int64_t n_sim, uint64_t seed, int8_t* dat_out, int8_t* orders_out);
+/* mmhn_simulate_summary: the same trajectories, counted on the device instead of written out (metmhn/simulations.py:150-240
+ * `preseeding_probs`, Utilityfunctions.py:116-155 `marg_frequs` without the per-sample arrays).  Simulates the sample
+ * indices [first, first + n_sim) - sample i is the i-th row mmhn_simulate returns under the same seed - in launches of
+ * MMHN_SIM_CHUNK samples (default 2^26), so n_sim is bounded by time, not memory.  first >= 0, n_sim >= 0 and
+ * first + n_sim < 2^63.  counts int64 [4 + 5 n_mut] (overwritten; seeding = event n_mut):
+ *   [0] n_sim  [1] seeded  [2] seeded, PT observed first  [3] seeded, MT observed first  (dat_out's order 1 / 2)
+ *   [4 + 0 n_mut + m] pre     seeded, mutation m occurred before the seeding (the PT set when it seeded)
+ *   [4 + 1 n_mut + m] pt      seeded, final PT bit of m
+ *   [4 + 2 n_mut + m] mt      seeded, final MT bit of m
+ *   [4 + 3 n_mut + m] shared  seeded, final PT and MT bits of m
+ *   [4 + 4 n_mut + m] pt_nm   unseeded, final PT bit of m
+ * Integer counts: the result does not depend on the chunking or the launch geometry.
+ */
+int mmhn_simulate_summary(mmhn_handle h, const double* log_theta, const double* pt_d_ef, const double* mt_d_ef,
+                          int64_t first, int64_t n_sim, uint64_t seed, int64_t* counts);
 
 /* ---- likeliest event orders -------------------------------------------------
  * mmhn_likeliest_orders: MetMHN.likeliest_order (metmhn/model.py:213-293) of every row of a reference-format `dat`
@@ -230,9 +245,9 @@ typedef struct {
   int32_t comm_rank;  /* this engine's rank in it (ncclCommUserRank), -1: none */
 } mmhn_counters;
 /* ABI version of this header: bumped whenever an exported signature or structure changes (4: mmhn_bench_kronvec has its
- * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists).  A client built against another header must refuse to run:
+ * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists).  A client built against another header must refuse to run:
  * mmhn_abi_version() != MMHN_ABI_VERSION (metmhn_amd/_lib.py checks it on load). */
-#define MMHN_ABI_VERSION 6
+#define MMHN_ABI_VERSION 7
 int mmhn_abi_version(void);
 int mmhn_bench_kronvec(mmhn_handle h, const double* log_theta, const int8_t* state, int64_t batch,
                        int iters, int transpose, int jacobi, double* ms_per_launch, int64_t* tiles);

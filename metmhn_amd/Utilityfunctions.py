@@ -3,6 +3,8 @@ examples/analysis.py that sit directly around score / learn_mhn.  Host-side NumP
 names and argument meaning as the reference; the likelihood work goes to the GPU engine through
 metmhn_amd.regularized_optimization.
 
+`marg_frequs` tabulates a cohort for comparison with `simulations.simulate_summary(...).marg_frequs`.
+
 Not mirrored (plots, Gillespie sampling, state-space helpers): out of scope, see DESIGN.md.
 """
 from __future__ import annotations
@@ -129,6 +131,34 @@ def load_cohort(events_csv: str, annot_csv: str, muts: list[str] | None = None):
     dat = cleaned.to_numpy(dtype=np.int8, na_value=-99)
     events = [c.split(".")[1] for c in muts[::2]] + ["Seeding"]
     return dat, events
+
+
+def marg_frequs(dat, events: list):
+    """Marginal frequencies of every event per stratum of a cohort `dat` [n_pat, 2n+3] (Utilityfunctions.py:116-155):
+    coupled rows (type 3) split into PT-private / MT-private / shared, NM (type 0) and EM-PT (type 1) PT bits,
+    EM-MT (type 2) MT bits; the seeding column from the seeding flag.  DataFrame [n+1 events x 6], rounded to two
+    decimals, columns labelled with the stratum sizes.  The reference reads the sizes by position from np.unique
+    and is right only when all four types occur; a cohort without one of them raises ValueError here."""
+    import pandas as pd
+    dat = np.asarray(dat)
+    n_mut = (dat.shape[1] - 3) // 2
+    types = dat[:, -1]
+    if set(np.unique(types).tolist()) != {0, 1, 2, 3}:
+        raise ValueError(f"marg_frequs needs rows of all four types 0-3, got types {sorted(set(np.unique(types).tolist()))}")
+    sizes = [int(np.count_nonzero(types == t)) for t in range(4)]
+    coupled = dat[types == 3].astype(np.int64)
+    code = np.hstack((coupled[:, 0:2 * n_mut:2] + 2 * coupled[:, 1:2 * n_mut:2], coupled[:, 2 * n_mut:2 * n_mut + 1]))
+    counts = np.zeros((6, n_mut + 1))
+    for j in range(1, 4):                                   # 1 PT-private, 2 MT-private, 3 shared
+        counts[j - 1] = np.count_nonzero(code == j, axis=0) / sizes[3]
+    col = lambda t, c: np.sum(dat[types == t][:, c], axis=0)
+    counts[3] = col(0, np.arange(0, 2 * n_mut + 1, 2)) / sizes[0]
+    counts[4] = col(1, np.arange(0, 2 * n_mut + 1, 2)) / sizes[1]
+    counts[5] = np.append(col(2, np.arange(1, 2 * n_mut, 2)), col(2, 2 * n_mut)) / sizes[2]
+    labels = [[f"Coupled ({sizes[3]})"] * 3 + [f"NM ({sizes[0]})", f"EM-PT ({sizes[1]})", f"EM-MT ({sizes[2]})"],
+              ["PT-Private", "MT-Private", "Shared"] + ["Present"] * 3]
+    inds = pd.MultiIndex.from_tuples(list(zip(*labels)))
+    return pd.DataFrame(np.around(counts, 2), columns=events, index=inds).T
 
 
 def save_params(path: str, theta, d_p, d_m, events: list[str]):

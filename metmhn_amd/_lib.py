@@ -73,13 +73,14 @@ SIGNATURES = {
     "mmhn_bench_stream": [C.c_void_p, C.c_size_t, C.c_int, C.c_int, f64p],
     "mmhn_bench_kronvec": [C.c_void_p, f64p, i8p, C.c_int64, C.c_int, C.c_int, C.c_int, f64p, i64p],
     "mmhn_simulate": [C.c_void_p, f64p, f64p, f64p, C.c_int64, C.c_uint64, i8p, i8p],
+    "mmhn_simulate_summary": [C.c_void_p, f64p, f64p, f64p, C.c_int64, C.c_int64, C.c_uint64, i64p],
     "mmhn_get_counters": [C.c_void_p, C.POINTER(Counters)],
     "mmhn_reset_counters": [C.c_void_p],
     "mmhn_debug_lane_moves": [C.c_void_p, C.c_int, C.POINTER(C.c_int)],
     "mmhn_likeliest_orders": [C.c_void_p, f64p, f64p, f64p, i8p, C.c_int64, C.c_int, C.c_int, i8p, f64p, i32p],
 }
 OTHER_SYMBOLS = ("mmhn_destroy", "mmhn_last_error", "mmhn_abi_version")
-ABI_VERSION = 6          # MMHN_ABI_VERSION of include/metmhn_amd.h these prototypes were written against
+ABI_VERSION = 7          # MMHN_ABI_VERSION of include/metmhn_amd.h these prototypes were written against
 
 
 def needs_build() -> bool:

@@ -296,6 +296,7 @@ struct EngineBase {
   int dtype = 0;
   int device = 0;
   hipStream_t stream = nullptr;
+  long long sim_chunk = 1ll << 26;   // MMHN_SIM_CHUNK: samples per launch of mmhn_simulate_summary
 };
 
 // Every ABI entry runs with the engine's GPU current and puts the caller's device back on exit, so engines on
@@ -576,6 +577,7 @@ struct Engine : EngineBase {
       if (const char* sp = std::getenv("MMHN_PREP_SPLIT")) prep_split_max = std::atoi(sp);
       if (const char* ms = std::getenv("MMHN_WSOLVE")) wsolve_mode = std::atoi(ms);
       if (const char* ms = std::getenv("MMHN_WSOLVE_WGS")) wsolve_wgs = std::atoi(ms);
+      if (const char* sc = std::getenv("MMHN_SIM_CHUNK")) sim_chunk = std::max(1ll, std::atoll(sc));
       hipDeviceProp_t prop;
       HIPCHECK(hipGetDeviceProperties(&prop, device));
       n_cu = std::max(1, prop.multiProcessorCount);
@@ -2712,6 +2714,44 @@ int mmhn_simulate(mmhn_handle h, const double* lt, const double* pt_d_ef, const 
     HIPCHECK(hipStreamSynchronize(st));
     HIPCHECK(hipMemcpy(dat_out, d_dat.p, (size_t)n_sim * W, hipMemcpyDeviceToHost));
     if (orders_out) HIPCHECK(hipMemcpy(orders_out, d_ord.p, (size_t)n_sim * L, hipMemcpyDeviceToHost));
+  }
+  API_END
+}
+
+int mmhn_simulate_summary(mmhn_handle h, const double* lt, const double* pt_d_ef, const double* mt_d_ef, int64_t first,
+                          int64_t n_sim, uint64_t seed, int64_t* counts) {
+  API_BEGIN
+  GUARD(h);
+  REQUIRE(h && lt && pt_d_ef && mt_d_ef && counts, "null pointer");
+  REQUIRE(first >= 0, "first must be non-negative");
+  REQUIRE(n_sim >= 0, "n_sim must be non-negative");
+  REQUIRE(n_sim <= INT64_MAX - first, "first + n_sim overflows 64 bits");
+  const int N = h->n + 1;
+  REQUIRE(N < SIM_MAXN, "too many events for the sampler (n_mut <= 30: event and diagnosis flags share one 32-bit set)");
+  const int C = SIM_HEAD + 5 * h->n;
+  std::fill(counts, counts + C, (int64_t)0);
+  if (n_sim > 0) {
+    DevArr<double> d_lt, d_dp, d_dm;
+    DevArr<unsigned long long> d_cnt;
+    d_lt.alloc((size_t)N * N); d_dp.alloc(N); d_dm.alloc(N); d_cnt.alloc(C);
+    HIPCHECK(hipMemcpy(d_lt.p, lt, sizeof(double) * N * N, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(d_dp.p, pt_d_ef, sizeof(double) * N, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(d_dm.p, mt_d_ef, sizeof(double) * N, hipMemcpyHostToDevice));
+    hipStream_t st = h->impl->stream;
+    HIPCHECK(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long) * C, st));
+    int n_cu = 1;
+    HIPCHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->impl->device));
+    // a grid-stride loop over the chunk: enough workgroups to fill the chip (7 resident per CU), few global atomics
+    const long long max_grid = 8ll * std::max(1, n_cu);
+    for (int64_t done = 0; done < n_sim; done += h->impl->sim_chunk) {
+      const long long cnt = (long long)std::min<int64_t>(h->impl->sim_chunk, n_sim - done);
+      const unsigned grid = (unsigned)std::min<long long>((cnt + SIM_BLOCK - 1) / SIM_BLOCK, max_grid);
+      hipLaunchKernelGGL(k_gillespie_summary, dim3(grid), dim3(SIM_BLOCK), 0, st, d_lt.p, d_dp.p, d_dm.p, N,
+                         (long long)(first + done), cnt, seed, d_cnt.p);
+      HIPCHECK(hipGetLastError());
+    }
+    HIPCHECK(hipMemcpyAsync(counts, d_cnt.p, sizeof(int64_t) * C, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
   }
   API_END
 }

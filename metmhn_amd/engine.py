@@ -363,6 +363,19 @@ class Engine:
                                           od.ctypes.data_as(_lib.i8p) if orders else None))
         return (dat, od) if orders else dat
 
+    def simulate_summary(self, log_theta, pt_d_ef, mt_d_ef, n_sim, seed=0, first=0):
+        """Counts of the Gillespie samples [first, first + n_sim) without the samples (mmhn_simulate_summary): int64
+        [4 + 5n] = n_sim, seeded, PT first, MT first, then per mutation pre, pt, mt, shared (seeded) and pt_nm
+        (unseeded); include/metmhn_amd.h has the layout."""
+        lt, ltp = self._theta(log_theta); a, ap = self._rates(pt_d_ef, "pt_d_ef"); b, bp = self._rates(mt_d_ef, "mt_d_ef")
+        n_sim, first = int(n_sim), int(first)
+        if n_sim < 0 or first < 0:
+            raise ValueError(f"n_sim and first must be non-negative, got n_sim={n_sim}, first={first}")
+        counts = np.zeros(4 + 5 * self.n, dtype=np.int64)
+        _lib.check(self.lib.mmhn_simulate_summary(self.h, ltp, ap, bp, first, n_sim, int(seed) & (2 ** 64 - 1),
+                                                  counts.ctypes.data_as(i64p)))
+        return counts
+
     # ---- likeliest event orders
     def likeliest_orders(self, log_theta, obs1, obs2, dat, front_cap=0):
         """MetMHN.likeliest_order of every row of a reference-format `dat` [n_pat, 2n+3] in one call

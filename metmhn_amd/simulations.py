@@ -1,5 +1,7 @@
 """Gillespie sampling of the joint PT/MT process on the GPU - the reference's `metmhn/simulations.py` call
-surface (`simulate_dat`, `simulate_orders`, :87-147) over `mmhn_simulate` (csrc/sampler.h).
+surface (`simulate_dat`, `simulate_orders`, :87-147) over `mmhn_simulate` (csrc/sampler.h), its reductions of
+trajectories on the host (`extract_bse`, `preseeding_probs`, :150-240), and the same reductions counted on the
+device without the samples (`simulate_summary`, `simulate_preseeding_probs` over `mmhn_simulate_summary`).
 
 `original_key` takes the place of the `jax.random.PRNGKey`: an int, or anything array-like whose integers are
 folded into the 64-bit Philox key.  Streams differ from jax.random's; distributions do not."""
@@ -40,3 +42,117 @@ def simulate_orders(log_theta, pt_d_ef, mt_d_ef, n_sim: int, original_key=0) -> 
     """int8 [n_sim, 2N+2]: event sequences padded with -99, events numbered as simulations.py:100-107."""
     lt = np.asarray(log_theta, dtype=np.float64)
     return _engine(lt.shape[0] - 1).simulate(lt, pt_d_ef, mt_d_ef, n_sim, _seed(original_key), orders=True)[1]
+
+
+# ---- reductions of the samples (simulations.py:150-240, Utilityfunctions.py:116-155)
+
+def extract_bse(traject, n: int, seeding_num: int):
+    """Pre-seeding events and all events of trajectories as simulate_orders returns them (simulations.py:150-221).
+
+    traject: int [2n+2] or [T, 2n+2], events numbered as simulate_orders numbers them, padded with -99.
+    Returns int8 (bsc [.., n], tc [.., 2n+2]): bsc[e] = 1 if event e happened before the seeding (the seeding
+    itself included), tc the events of the trajectory, pre-seeding events in both tumours (e and e + n + 1).
+    Trajectories without the seeding give zeros.  Indices past the end of bsc / tc are dropped, as jax drops
+    out-of-bounds scatters (a post-seeding event e >= n never clears bsc)."""
+    t = np.asarray(traject)
+    one = t.ndim == 1
+    t = np.atleast_2d(t).astype(np.int64)
+    T, L = t.shape
+    bsc = np.zeros((T, n), dtype=np.int8)
+    tc = np.zeros((T, 2 * n + 2), dtype=np.int8)
+    rows = np.arange(T)
+    live = np.any(t == seeding_num, axis=1)           # lax.cond: trajectories without the seeding stay zero
+    pre = np.ones(T, dtype=bool)                       # psf: the seeding itself still counts as pre-seeding
+
+    def put(arr, r, idx, v):
+        ok = (idx >= 0) & (idx < arr.shape[1])
+        arr[r[ok], idx[ok]] = v
+
+    for i in range(L):
+        e = t[:, i]
+        live &= e != -99                               # the while loop ends at the first padding value
+        pre_now, post_now = live & pre, live & ~pre
+        put(bsc, rows[pre_now], e[pre_now], 1)
+        put(tc, rows[pre_now], e[pre_now], 1)
+        put(tc, rows[pre_now], e[pre_now] + n + 1, 1)
+        put(bsc, rows[post_now], e[post_now], 0)
+        put(tc, rows[post_now], e[post_now], 1)
+        pre &= ~(live & (e == seeding_num))
+    return (bsc[0], tc[0]) if one else (bsc, tc)
+
+
+def preseeding_probs(dat, n: int, seeding_num: int):
+    """(P(t_mut < t_seed | PT(mut) = 1, seeded), P(t_mut < t_seed | MT(mut) = 1, seeded)) from trajectories
+    [T, 2n+2] as simulate_orders returns them (simulations.py:224-240); float64 [seeding_num] each, NaN where no
+    seeded trajectory has the mutation (0 / 0)."""
+    bsc, tc = extract_bse(np.atleast_2d(np.asarray(dat)), n, seeding_num)
+    num = bsc[:, :-1].sum(axis=0, dtype=np.int64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        pt_cond = num / tc[:, :seeding_num].sum(axis=0, dtype=np.int64)
+        mt_cond = num / tc[:, seeding_num + 2:-2].sum(axis=0, dtype=np.int64)
+    return pt_cond, mt_cond
+
+
+class SimSummary:
+    """Counts of Gillespie samples (mmhn_simulate_summary).  Totals n_sim, n_seeded, n_pt_first, n_mt_first; per
+    mutation (int64 [n_mut]) over the seeded samples pre (occurred before the seeding), pt, mt, shared (final PT /
+    MT / both bits) and over the unseeded ones pt_nm (final PT bit).  counts: the raw int64 vector."""
+
+    def __init__(self, counts, n_mut: int):
+        self.counts = np.asarray(counts, dtype=np.int64)
+        self.n_mut = n = int(n_mut)
+        self.n_sim, self.n_seeded, self.n_pt_first, self.n_mt_first = (int(v) for v in self.counts[:4])
+        self.pre, self.pt, self.mt, self.shared, self.pt_nm = (self.counts[4 + k * n:4 + (k + 1) * n] for k in range(5))
+
+    def __repr__(self):
+        return (f"SimSummary(n_mut={self.n_mut}, n_sim={self.n_sim}, n_seeded={self.n_seeded}, "
+                f"n_pt_first={self.n_pt_first}, n_mt_first={self.n_mt_first})")
+
+    def preseeding_probs(self):
+        """preseeding_probs of the same samples: (pre / pt, pre / mt) in float64, NaN where the denominator is 0."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.pre / self.pt, self.pre / self.mt
+
+    def marg_frequs(self, events, decimals: int = 2):
+        """The model-implied counterpart of Utilityfunctions.marg_frequs: the seeded samples stand for the coupled,
+        EM-PT and EM-MT rows, the unseeded ones for the NM rows; same layout, labels and rounding."""
+        import pandas as pd
+        s, u = self.n_seeded, self.n_sim - self.n_seeded
+        seed_col = lambda c: np.append(c, 0)
+        num = np.vstack((np.append(self.pt - self.shared, s), seed_col(self.mt - self.shared), seed_col(self.shared),
+                         seed_col(self.pt_nm), np.append(self.pt, s), np.append(self.mt, s)))
+        size = np.array([s, s, s, u, s, s], dtype=np.int64).reshape(-1, 1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tab = num / size
+        labels = [[f"Coupled ({s})"] * 3 + [f"NM ({u})", f"EM-PT ({s})", f"EM-MT ({s})"],
+                  ["PT-Private", "MT-Private", "Shared"] + ["Present"] * 3]
+        inds = pd.MultiIndex.from_tuples(list(zip(*labels)))
+        return pd.DataFrame(np.around(tab, decimals), columns=events, index=inds).T
+
+
+def _check_params(log_theta, pt_d_ef, mt_d_ef):
+    lt = np.asarray(log_theta, dtype=np.float64)
+    if lt.ndim != 2 or lt.shape[0] != lt.shape[1] or lt.shape[0] < 2:
+        raise ValueError(f"log_theta must have shape (N, N) with N >= 2, got {lt.shape}")
+    N = lt.shape[0]
+    for name, d in (("pt_d_ef", pt_d_ef), ("mt_d_ef", mt_d_ef)):
+        if np.shape(d) != (N,):
+            raise ValueError(f"{name} must have shape ({N},), got {np.shape(d)}")
+    return lt
+
+
+def simulate_summary(log_theta, pt_d_ef, mt_d_ef, n_sim: int, original_key=0, first: int = 0) -> SimSummary:
+    """Counts of the samples [first, first + n_sim) on the GPU without materialising them (mmhn_simulate_summary).
+    With first = 0 these are exactly the samples simulate_dat / simulate_orders(..., n_sim, original_key) return;
+    n_sim is bounded by time, not memory, and `first` extends a run or splits it into parts with the same samples."""
+    lt = _check_params(log_theta, pt_d_ef, mt_d_ef)
+    if int(n_sim) < 0 or int(first) < 0:
+        raise ValueError(f"n_sim and first must be non-negative, got n_sim={n_sim}, first={first}")
+    n_mut = lt.shape[0] - 1
+    counts = _engine(n_mut).simulate_summary(lt, pt_d_ef, mt_d_ef, int(n_sim), _seed(original_key), first=int(first))
+    return SimSummary(counts, n_mut)
+
+
+def simulate_preseeding_probs(log_theta, pt_d_ef, mt_d_ef, n_sim: int, original_key=0):
+    """simulate_summary(...).preseeding_probs(): the pre-seeding probabilities of n_sim samples, counted on the GPU."""
+    return simulate_summary(log_theta, pt_d_ef, mt_d_ef, n_sim, original_key).preseeding_probs()
