@@ -113,6 +113,7 @@ struct Batch {
   std::vector<Desc> dJ, dS;
   std::vector<int2> mapJ, mapS;
   long long vecJ = 0, vecS = 0, asize = 0, tabJ = 0, tabS = 0;
+  long long aclr = 0;            // class-marginal arrays cleared per evaluation: [0, aclr); the rest is written whole (k_wclass, eq flows)
   int id = 0;
   int maxkJ = 0, maxkS = 0;
   int maxkcJ = 0;                // most bits of one class (PT / MT) over the joint problems
@@ -479,10 +480,14 @@ struct Engine : EngineBase {
   // workspace (sized for the largest batch)
   DevArr<T> pi, lidgJ, qJ, rhsJ, rhsS, pS, lidgS, qS, seedS, GS, dots, bmJ, bmS, tabJ, tabS;
   // accumulators of the joint gradient that must be zero on entry - rows of the three G matrices, observation-rate rows,
-  // class marginals - share one allocation, laid out per batch and cleared by ONE memset at the start of the batch
+  // class marginals - share one allocation, laid out per batch and cleared by ONE memset at the start of the batch.  The
+  // arrays of the window-layout problems lie at the end of it, outside that memset: k_wclass writes every entry of their
+  // class tables that a consumer reads, the eq-block flows every entry of their eq blocks.
   DevArr<T> zarena;
   struct View { T* p = nullptr; } GJ, DJ, Abuf;
   static long long zarena_elems(long long nJ, long long asize, int N) { return up4(3 * nJ * N * N) + up4(3 * nJ * N) + up4(asize); }
+  // elements of a batch's zarena that the memset clears
+  static long long zclear_elems(const Batch& b, int N) { return zarena_elems((long long)b.dJ.size(), b.aclr, N); }
   static long long up4(long long v) { return (v + 3) / 4 * 4; }
   int pi_owner = -1, qJ_owner = -1;   // batch whose (pruned) layout the zero-initialised buffers hold
   DevArr<double> lp, out, sums, abi_sums, redbuf;
@@ -1365,6 +1370,15 @@ struct Engine : EngineBase {
       // the window layout stays in place: every consumer of the joint vectors reads it there (k_gather_marg / the small-space
       // kernels, k_eq_flows, k_wclass); MMHN_WSOLVE=2 converts to index order after each solve instead (k_wconvert)
       b.wdirect = b.wpath && wsolve_mode != 2;
+      {
+        // class-marginal arrays: the problems whose tables are added into first, then the window-layout ones
+        long long ao = 0;
+        for (int pj = 0; pj < nJ; ++pj) if (!(b.wdirect && b.route[pj] == RT_W)) { b.dJ[pj].aoff = ao; ao += a_size(b.dJ[pj]); }
+        b.aclr = up4(ao);
+        ao = b.aclr;
+        for (int pj = 0; pj < nJ; ++pj) if (b.wdirect && b.route[pj] == RT_W) { b.dJ[pj].aoff = ao; ao += a_size(b.dJ[pj]); }
+        b.asize = ao;
+      }
       for (Desc& dj : b.dJ) dj.wl = -1;
       if (b.wdirect) for (size_t i = 0; i < b.wd.size(); ++i) b.dJ[b.wd[i].prob].wl = (int)i;
       up(b.d_dJ, b.dJ); up(b.d_dS, b.dS); up(b.d_mapJ, b.mapJ); up(b.d_mapS, b.mapS);
@@ -1465,7 +1479,7 @@ struct Engine : EngineBase {
       const Batch& b0 = batches.front();
       // (a large batch clears its ~GB of work arrays with the runtime's fill, which is faster at that size: +1.0 ms
       // per evaluation on the 5 000-patient bench cohort when this kernel did it)
-      long long nz = grad && !b0.dJ.empty() ? zarena_elems((long long)b0.dJ.size(), b0.asize, N) * (long long)sizeof(T) / 16 : 0;
+      long long nz = grad && !b0.dJ.empty() ? zclear_elems(b0, N) * (long long)sizeof(T) / 16 : 0;
       const bool fill_here = nz <= (32ll << 20) / 16;
       if (!fill_here) nz = 0;
       const int nw = (int)(NPSET * sizeof(Params<T>) / sizeof(uint4));
@@ -1528,7 +1542,10 @@ struct Engine : EngineBase {
       GJ.p = zarena.p;
       DJ.p = GJ.p + up4(3 * gjs);
       Abuf.p = DJ.p + up4(3ll * nJ * N);
-      if (grad && nJ && !(head_done && &b == &batches.front())) zero(zarena.p, zarena_elems(nJ, b.asize, N));
+      if (grad && nJ && !(head_done && &b == &batches.front())) zero(zarena.p, zclear_elems(b, N));
+      // (MMHN_POISON=1, tests: the arrays outside the memset start as NaNs - an entry that a consumer reads and no launch
+      // wrote shows in the gradient)
+      if (grad && nJ && poison) poison_fill(Abuf.p + b.aclr, b.asize - b.aclr);
       prep(b.d_dJ.p, nJ, tabJ.p, true, b.maxkcJ);                    // (first: the head of the critical chain)
       // staged patients that are their own problem: a side stream of their own from here to the assembly (a timed
       // evaluation keeps them on the main stream - events are recorded there)

@@ -9,10 +9,16 @@
 //   phase R (row class):    thread = row.  Per block the rows' q values go through LDS (every thread-bit neighbour of a
 //                           row is another row of the same block), the sums over the columns stay in registers for the
 //                           whole patient and every table entry is written once - no atomics, no cross-lane reduction.
-//                           Neighbours along the row bits beyond the tenth are other blocks: one extra read of q each.
-//   phase C (column class): thread = 16-byte piece of columns x some rows of a chunk of RCH rows x all columns staged in
-//                           LDS (every column neighbour is in the chunk); sums over the rows in registers, one small
-//                           reduction over the threads that share a piece at the end.
+//                           Neighbours along the external row bits that phase C does not cover are other blocks:
+//                           one extra read of q each.
+//   phase C (column class): thread = 16-byte piece of columns x some rows of a chunk of RCH storage rows x the 2^m
+//                           settings of the lowest m external row bits x all columns staged in LDS (every column
+//                           neighbour and every neighbour along those m row bits is in the chunk); column sums over the
+//                           rows in registers, one small reduction over the threads that share a piece at the end; the
+//                           sums along the m external row bits are reduced per row over the threads that share it
+//                           (DPP segment sums, across waves through LDS) and written once each.
+//   m is the most of the external row bits for which a chunk still reads runs of at least one 128-byte line (fp64 at
+//   k = 20: every external row bit of every shape).
 #pragma once
 #include "kernels.h"
 
@@ -21,8 +27,33 @@ namespace mmhn {
 template <typename T>
 struct WClass {
   static constexpr int CHE = 32768 / (int)sizeof(T);          // elements of one staged array (a block, or a chunk of rows)
-  static constexpr size_t lds = 4 * (size_t)CHE * sizeof(T) + 64;
+  static constexpr int LGCHE = sizeof(T) == 8 ? 12 : 13;
+  static constexpr int LGMINR = 2;                             // a run of a chunk: at least 4 storage rows (128 bytes)
+  // most external row bits phase C covers (its chunks hold 2^(kC + m) <= CHE / 4 elements per storage row, kC >= RB + HB)
+  static constexpr int MX = WCfg<T>::KR - WTB < LGCHE - LGMINR - WCfg<T>::RB - WCfg<T>::HB ? WCfg<T>::KR - WTB
+                                                                                           : LGCHE - LGMINR - WCfg<T>::RB - WCfg<T>::HB;
+  // partial sums of those: m * (CHE >> kC) rows x max(1, 2^kC / QE / 64) waves, at most MX * (CHE >> (RB + HB))
+  static constexpr int XP = MX * (CHE >> (WCfg<T>::RB + WCfg<T>::HB));
+  static constexpr size_t lds = (4 * (size_t)CHE + 2 * (size_t)XP) * sizeof(T) + WROWS * sizeof(uint16_t) + 64;
+  static_assert((1 << LGCHE) == CHE, "");
 };
+// external row bits whose neighbours phase C of k_wclass sums (the rest: phase R's extra reads of q)
+template <typename T>
+__host__ __device__ inline int wclass_mbits(int kC, int nXr) {
+  const int m = WClass<T>::LGCHE - WClass<T>::LGMINR - kC;
+  return m < 0 ? 0 : m < nXr ? m : nXr;
+}
+// sum over aligned groups of 2^lg lanes (lg <= 6, wave-uniform): the total lands in the last lane of each group
+template <typename T>
+__device__ __forceinline__ T seg_sum(T v, int lg) {
+  if (lg > 0) v = dpp_stage<0>(v);
+  if (lg > 1) v = dpp_stage<1>(v);
+  if (lg > 2) v = dpp_stage<2>(v);
+  if (lg > 3) v = dpp_stage<3>(v);
+  if (lg > 4) v = dpp_stage<4>(v);
+  if (lg > 5) v = dpp_stage<5>(v);
+  return v;
+}
 template <typename T>
 constexpr size_t wclass_lds() { return WClass<T>::lds; }
 
@@ -40,6 +71,10 @@ __global__ __launch_bounds__(WROWS) void k_wclass(const Desc* __restrict__ descs
   T* const lds = reinterpret_cast<T*>(smem);                 // four staged arrays of CHE elements
   const int tid = threadIdx.x;
   const uint32_t rho = wrho((uint32_t)tid >> 6, (uint32_t)tid & 63u);
+  // row index of storage row rho (wrho_inv, a chain of dependent table reads, out of the hot loop; read after the first
+  // barrier of the problem loop)
+  uint16_t* const rinv = reinterpret_cast<uint16_t*>(lds + 4 * (size_t)CHE + 2 * (size_t)WClass<T>::XP);
+  rinv[rho] = (uint16_t)tid;
   for (int it = blockIdx.x; it < nw; it += gridDim.x) {
     const WDesc& wd = wds[it];
     const Desc& d = descs[wd.prob];
@@ -52,6 +87,7 @@ __global__ __launch_bounds__(WROWS) void k_wclass(const Desc* __restrict__ descs
     T* outR = A + d.aoff + (majP ? 0 : class_block_size(kP));
     T* outC = A + d.aoff + (majP ? class_block_size(kP) : 0);
     const int NBc = (1 << nXc) << HB;                         // blocks of one external row setting
+    const int mX = wclass_mbits<T>(kC, nXr);                  // external row bits of phase C
     auto ldv = [&](const T* src, uint32_t Sigma, uint32_t beta, uint32_t row) -> VecT {
       const QT* a = reinterpret_cast<const QT*>(src + wpos<T>(Sigma, beta, row, 0));
       const QT lo = a[0], hi = a[1];
@@ -102,7 +138,7 @@ __global__ __launch_bounds__(WROWS) void k_wclass(const Desc* __restrict__ descs
         }
 #pragma unroll
         for (int i = 0; i < WNXR; ++i) {
-          if (i < nXr && !((Sx >> i) & 1u)) {                  // (uniform)
+          if (i >= mX && i < nXr && !((Sx >> i) & 1u)) {      // (uniform)
             const VecT qx = ldv(qs, Sigma | (1u << (nXc + i)), beta, rho);
             acc[1 + WTB + i] += dot(pv, qx);
           }
@@ -115,39 +151,64 @@ __global__ __launch_bounds__(WROWS) void k_wclass(const Desc* __restrict__ descs
         if (!((tid >> i) & 1)) outR[((long long)(1 + i) << kR) + S] = acc[1 + i];
 #pragma unroll
       for (int i = 0; i < WNXR; ++i)
-        if (i < nXr && !((Sx >> i) & 1u)) outR[((long long)(1 + WTB + i) << kR) + S] = acc[1 + WTB + i];
+        if (i >= mX && i < nXr && !((Sx >> i) & 1u)) outR[((long long)(1 + WTB + i) << kR) + S] = acc[1 + WTB + i];
     }
     // =============================== phase C: thread = piece of QE columns, rows of a chunk dealt over the threads
     {
-      const int NPc = (1 << kC) / QE;                          // pieces of a row
-      const int RCH = CHE >> kC;                               // rows of a chunk
-      const int nch = WROWS / RCH;
-      const int cp = tid & (NPc - 1);                          // (NPc divides 1024)
-      const int r0 = tid / NPc, rstep = WROWS / NPc;           // rows r0, r0 + rstep, ... of a chunk: CHE / QE / 1024 = 2 items
+      // a chunk: storage rows ch * RCH .. + RCH of the 2^mX row settings Sx = sxl | sxh << mX, every column; in LDS row
+      // (sxl << lgR | r) x column T
+      constexpr int XP = WClass<T>::XP, JU = sizeof(T) == 8 ? 2 : 1;
+      static_assert(CHE == 2 * WROWS * QE, "a thread takes two rows of a chunk");
+      const int lgR = WClass<T>::LGCHE - kC - mX;              // log2 of the storage rows of a chunk
+      const int RCH = 1 << lgR, RCX = RCH << mX;               // storage rows, rows in LDS (= CHE >> kC)
+      const int lgnch = WTB - lgR, nch = 1 << lgnch;
+      const int lgP = kC - LGQ, NPc = 1 << lgP;                // pieces of a row (NPc divides 1024)
+      const int cp = tid & (NPc - 1);
+      const int r0 = tid >> lgP, rstep = WROWS >> lgP;         // rows r0, r0 + rstep of a chunk
+      const int lgRX = lgR + mX, nW = lgP > 6 ? 1 << (lgP - 6) : 1;   // a row's sums: nW partials (one per wave)
+      T* const xpart = lds + 4 * (size_t)CHE;                  // [2][XP]: [bit][row][wave] partials of the external row sums
       T ac[QE][1 + KC];
 #pragma unroll
       for (int e = 0; e < QE; ++e)
 #pragma unroll
         for (int s = 0; s <= KC; ++s) ac[e][s] = T(0);
-      // piece g of a chunk (both arrays): run = block (Tx, beta), inside the run row-major
-      const int rl = RCH * NQ;                                 // pieces of a run
-      auto piece_src = [&](int g, uint32_t Sx, int ch) -> long long {
-        const int run = g / rl, rr = g % rl;
-        const uint32_t Sigma = ((uint32_t)run >> HB) | (Sx << nXc), beta = (uint32_t)run & (uint32_t)(H - 1);
+      // piece g of a chunk (both arrays): run = block (sxl, Tx, beta), inside the run row-major
+      const int lgrl = lgR + 1;                                // log2 of the pieces of a run (RCH rows x NQ pieces)
+      auto piece_src = [&](int g, uint32_t sxh, int ch) -> long long {
+        const int run = g >> lgrl, rr = g & ((1 << lgrl) - 1);
+        const uint32_t Sigma = ((uint32_t)run >> HB) | (sxh << (nXc + mX)), beta = (uint32_t)run & (uint32_t)(H - 1);
         return wpos<T>(Sigma, beta, (uint32_t)(ch * RCH + (rr >> 1)), (uint32_t)((rr & 1) * QE));
       };
       auto piece_dst = [&](int g) -> int {
-        const int run = g / rl, rr = g % rl;
-        return ((rr >> 1) << kC) + (run << RB) + (rr & 1) * QE;
+        const int run = g >> lgrl, rr = g & ((1 << lgrl) - 1);
+        const int sxl = run >> (kC - RB), cb = run & ((1 << (kC - RB)) - 1);
+        return (((sxl << lgR) | (rr >> 1)) << kC) + (cb << RB) + (rr & 1) * QE;
       };
-      const int ntot = nch << nXr;                             // chunks of the patient
+      // table index of LDS row r of chunk cidx (without the slot)
+      auto row_S = [&](int cidx, int r) -> long long {
+        const uint32_t Sx = (uint32_t)(r >> lgR) | ((uint32_t)(cidx >> lgnch) << mX);
+        return (long long)rinv[((cidx & (nch - 1)) << lgR) | (r & (RCH - 1))] | ((long long)Sx << WTB);
+      };
+      // the external row sums of chunk cidx: add the partials of a row in a fixed order, write the tables
+      auto xfinish = [&](int cidx) {
+        const T* xp = xpart + (cidx & 1) * XP;
+        for (int i = tid; i < (mX << lgRX); i += WROWS) {
+          const int l = i >> lgRX, r = i & (RCX - 1);
+          if (!((r >> (lgR + l)) & 1)) {
+            T v = xp[(size_t)i * nW];
+            for (int w = 1; w < nW; ++w) v += xp[(size_t)i * nW + w];
+            outR[((long long)(1 + WTB + l) << kR) + row_S(cidx, r)] = v;
+          }
+        }
+      };
+      const int ntot = nch << (nXr - mX);                      // chunks of the patient
       QT rp[2], rq[2];
       auto fetch = [&](int cidx) {
-        const uint32_t Sx = (uint32_t)(cidx / nch);
-        const int ch = cidx % nch;
+        const uint32_t sxh = (uint32_t)(cidx >> lgnch);
+        const int ch = cidx & (nch - 1);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          const long long src = piece_src(tid + WROWS * j, Sx, ch);
+          const long long src = piece_src(tid + WROWS * j, sxh, ch);
           rp[j] = *reinterpret_cast<const QT*>(ps + src);
           rq[j] = *reinterpret_cast<const QT*>(qs + src);
         }
@@ -165,7 +226,10 @@ __global__ __launch_bounds__(WROWS) void k_wclass(const Desc* __restrict__ descs
         }
         if (cidx + 1 < ntot) fetch(cidx + 1);
         __syncthreads();
-        for (int r = r0; r < RCH; r += rstep) {
+        if (mX > 0 && cidx > 0) xfinish(cidx - 1);             // (its partials were written before this barrier)
+#pragma unroll JU
+        for (int j = 0; j < 2; ++j) {                          // (fp32 rolled: unrolled, it spills)
+          const int r = r0 + j * rstep;
           const T* prow = pc + ((size_t)r << kC);
           const T* qrow = qc + ((size_t)r << kC);
           const QT pv = *reinterpret_cast<const QT*>(prow + cp * QE);
@@ -186,10 +250,23 @@ __global__ __launch_bounds__(WROWS) void k_wclass(const Desc* __restrict__ descs
               for (int e = 0; e < QE; ++e) ac[e][1 + b] += pv[e] * nq[e];
             }
           }
+          // external row bits l < mX: the row's neighbour S | l is LDS row r | RCH << l (a row that has bit l computes a
+          // sum that is dropped); every lane takes part in the segment sums
+#pragma unroll 1
+          for (int l = 0; l < mX; ++l) {                       // (uniform; rolled: the accumulators above fill the registers)
+            const QT nq = *reinterpret_cast<const QT*>(qc + ((size_t)(r | (RCH << l)) << kC) + cp * QE);
+            T s = pv[0] * nq[0];
+#pragma unroll
+            for (int e = 1; e < QE; ++e) s += pv[e] * nq[e];
+            s = seg_sum(s, lgP < 6 ? lgP : 6);                 // (the last lane of a row's segment holds its sum)
+            if ((cp & 63) == ((NPc - 1) & 63))
+              xpart[(cidx & 1) * XP + (size_t)((l << lgRX) + r) * nW + (cp >> 6)] = s;
+          }
         }
       }
       // ---- sum over the threads that share a piece, write the tables
       __syncthreads();
+      if (mX > 0) xfinish(ntot - 1);
       T* red = lds;
 #pragma unroll
       for (int s = 0; s <= KC; ++s) {
