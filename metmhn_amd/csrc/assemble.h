@@ -1,4 +1,5 @@
-// Per-patient assembly and the deterministic cohort reduction.  Reference: likelihood.py:441-512, 623-731;
+// Per-patient assembly, the deterministic cohort reduction, and the small kernels at the two ends of an evaluation
+// (parameter upload, packing of the cohort sums).  Reference: likelihood.py:441-512, 623-731;
 // regularized_optimization.py:256-266.
 #pragma once
 #include "common.h"
@@ -117,6 +118,88 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_parts(const double* __restrict
 #pragma unroll 8
   for (int c = 0; c < nchunk; ++c) acc += part[((long long)c * 2 + cls) * stride + e];
   sums[cls * stride + e] += acc;
+}
+
+// sums[2][stride] (EM, NM rows of k_reduce_parts) -> the buffer layout of mmhn_cohort_sums (include/metmhn_amd.h)
+__global__ void k_pack_sums(const double* __restrict__ sums, int N, double n_em, double n_pat, double* __restrict__ o) {
+  const int st = 1 + N * N + 2 * N, NN = N * N;
+  const double* em = sums;
+  const double* nm = sums + st;
+  const int total = 4 + 2 * NN + 3 * N;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+    double v;
+    if (e == 0) v = em[0];
+    else if (e == 1) v = nm[0];
+    else if (e == 2) v = n_em;
+    else if (e == 3) v = n_pat;
+    else {
+      int q = e - 4;
+      if (q < NN) v = em[1 + q];
+      else if ((q -= NN) < NN) v = nm[1 + q];
+      else if ((q -= NN) < N) v = em[1 + NN + q];
+      else if ((q -= N) < N) v = nm[1 + NN + q];
+      else v = em[1 + NN + N + (q - N)];
+    }
+    o[e] = v;
+  }
+}
+
+// sums[2][stride] -> the pre-combined buffer of mmhn_cohort_wsums: [w s_EM + s_NM, w G_EM + G_NM, w p_EM + p_NM, w m_EM]
+// (regularized_optimization.py:256-266 without the division by n_full): 1 + N^2 + 2 N doubles, the all-reduce
+// payload of SURVEY 8e - the weight w only needs the GLOBAL counts, which every rank knows when the cohort is set
+__global__ void k_pack_wsums(const double* __restrict__ sums, int N, double w, double* __restrict__ o, double flag) {
+  const int st = 1 + N * N + 2 * N, NN = N * N;
+  if (blockIdx.x == 0 && threadIdx.x == 0) o[st] = flag;              // (mmhn_set_reduce_flag: rides in the same all-reduce)
+  const double* em = sums;
+  const double* nm = sums + st;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < st; e += gridDim.x * blockDim.x)
+    o[e] = e < 1 + NN + N ? w * em[e] + nm[e] : w * em[e];          // (d_d_m has no NM part, :266)
+}
+
+// host <-> device traffic of an evaluation without the copy engine: the parameters are read from, and the result is
+// written to, pinned host memory by kernels of the evaluation's own queue.  (A hipMemcpyAsync in front of the first
+// launch costs the hand-over between the copy engine and the compute queue - on a 0.4 ms evaluation of a small cohort
+// ~60 us passed between the 27 KB upload and the first kernel - and the download the same at the other end.)
+__global__ void k_copy_words(const uint4* __restrict__ src, uint4* __restrict__ dst, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = src[i];
+}
+// ... and the head of an evaluation in ONE launch: the parameter upload, the cleared cohort sums and the cleared gradient
+// work arrays of the first batch (three launches otherwise, each a few us of queue latency on a short evaluation)
+__global__ void k_begin_eval(const uint4* __restrict__ src, uint4* __restrict__ dst, int n, double* __restrict__ sums, int nsums,
+                             uint4* __restrict__ z, long long nz) {
+  const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, step = (long long)gridDim.x * blockDim.x;
+  if (i0 < n) dst[i0] = src[i0];
+  if (i0 < nsums) sums[i0] = 0.0;
+  for (long long i = i0; i < nz; i += step) z[i] = uint4{0u, 0u, 0u, 0u};
+}
+
+// k_reduce_parts of the LAST batch and the packing in one launch: thread e adds the chunk sums of both classes in chunk
+// order (as k_reduce_parts does), keeps sums[] current and writes its entries of the packed buffer
+// (mode 1: k_pack_sums layout, a = n_em, b = n_pat; mode 2: k_pack_wsums, a = w)
+__global__ __launch_bounds__(BLOCK) void k_reduce_parts_pack(const double* __restrict__ part, int stride, int nelem, int nchunk,
+                                                             double* sums, int mode, int N, double a, double b,
+                                                             double* __restrict__ o) {
+  const int e = blockIdx.x * BLOCK + threadIdx.x;
+  if (e == 0 && mode == 2) o[stride] = b;                             // (mode 2: b = the reduce flag, behind the buffer)
+  if (e >= stride) return;
+  double em = sums[e], nm = sums[stride + e];
+  if (e < nelem) {
+    double acc0 = 0, acc1 = 0;
+#pragma unroll 8
+    for (int c = 0; c < nchunk; ++c) {
+      acc0 += part[((long long)c * 2 + 0) * stride + e];
+      acc1 += part[((long long)c * 2 + 1) * stride + e];
+    }
+    em += acc0; nm += acc1;
+    sums[e] = em; sums[stride + e] = nm;
+  }
+  const int NN = N * N;
+  if (mode == 2) { o[e] = e < 1 + NN + N ? a * em + nm : a * em; return; }
+  if (e == 0) { o[0] = em; o[1] = nm; o[2] = a; o[3] = b; }
+  else if (e < 1 + NN) { o[4 + (e - 1)] = em; o[4 + NN + (e - 1)] = nm; }
+  else if (e < 1 + NN + N) { o[4 + 2 * NN + (e - 1 - NN)] = em; o[4 + 2 * NN + N + (e - 1 - NN)] = nm; }
+  else o[4 + 2 * NN + 2 * N + (e - 1 - NN - N)] = em;
 }
 
 }  // namespace mmhn

@@ -229,7 +229,7 @@ __device__ __forceinline__ uint32_t low_bits(uint32_t m, int n) {
   return r;
 }
 
-// the outer loop of a class pass (host: Engine::pclass_items mirrors it): o runs over the settings of the other class's bits
+// the outer loop of a class pass (host: plan.h build_pclass_items mirrors it): o runs over the settings of the other class's bits
 // above the tile
 __host__ __device__ inline int pclass_outer_bits(int kc, int kf) {
   const int a = kc < PCA ? kc : PCA;

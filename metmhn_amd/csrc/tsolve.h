@@ -201,7 +201,7 @@ __device__ __forceinline__ void tsolve_tile(unsigned char* smem, const Desc* __r
     const bool is_seed = joint && c == CS;
     const bool is_pair = joint && ((d.pairP >> b) & 1u);
     // candidate moves of bit b: single bit (async / seeding) and, for a paired P bit, both bits
-    // (the host's dependency lists follow exactly these conditions: Engine::tile_deps)
+    // (the host's dependency lists follow exactly these conditions: plan.h: tile_deps)
     for (int kind = 0; kind < 2; ++kind) {
       if (kind == 1 && !is_pair) continue;
       const uint32_t mv = kind == 0 ? (1u << b) : (3u << b);

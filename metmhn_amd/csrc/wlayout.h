@@ -74,7 +74,7 @@ template <> struct WCfg<float> {
   static constexpr bool FACT = true, REV = false, ON = MMHN_WF32 != 0;
 };
 
-// static description of one joint problem on the window path (host-built, set_cohort)
+// static description of one joint problem on the window path (host-built, plan.h: route_joint_problems)
 struct WDesc {
   int prob;                  // index into the batch's joint descriptors
   int kR, kC, majP;          // row-class bits, column-class bits, 1: the row class is P

@@ -1,7 +1,7 @@
 """Every single-vector primitive against a high-precision reference, across the tile boundary.
 
 The 15 entry points of the reference's module surface (jx.kronvec, jx.likelihood, jx.vanilla -> Engine.kronvec ...
-Engine.v_x_partial_D_y -> the api_* paths of csrc/engine.hip) are swept over k = 0 .. 18, past the 12 tile bits
+Engine.v_x_partial_D_y -> the api_* paths of csrc/prims.h) are swept over k = 0 .. 18, past the 12 tile bits
 (MMHN_TB), on unseeded joint states and on joint states with one tumour plus seeding, on fp64 and fp32 engines, under
 both solvers, and with MMHN_POISON=1 on half of the cases: a poisoned engine NaN-fills every result buffer as soon as it
 is allocated, so an element that no launch or memset writes shows in the output.
