@@ -215,6 +215,26 @@ int mmhn_likeliest_orders(mmhn_handle h, const double* log_theta, const double* 
                           const int8_t* dat, int64_t n_pat, int n_cols, int front_cap, int8_t* orders, double* prob,
                           int32_t* status);
 
+/* ---- pre-seeding posteriors of a cohort ------------------------------------------------------
+ * mmhn_order_posteriors: for every row of a reference-format `dat` (read as mmhn_likeliest_orders reads it) the sum over
+ * ALL admissible orders where mmhn_likeliest_orders takes the maximum - exact sum-product over the row's 2^k sub-states,
+ * forward and backward.  No reference counterpart (the reference derives such statements from likeliest orders and
+ * simulation).  fp64 engines only.
+ *   log_evidence [n_pat]        log of the summed order likelihoods = the row's log-probability under the model
+ *   pre [n_pat][n_mut]          P(mutation m occurred before the seeding | the row); 0 for mutations the row does not carry
+ *                               (paired rows: not in both tumours)
+ *   seed_pos [n_pat][n_mut + 1] P(j mutations preceded the seeding | the row); sums to 1
+ *   status [n_pat]: low half MMHN_ORD_OK, MMHN_ORD_INVALID (the MMHN_ORD_* reason is in the HIGH half: status >> 16) or
+ *   MMHN_ORD_TOO_LARGE (the row's lattice - 2^k x 64 + 2^(k-1) x 24 B paired, 2^k x 16 B one tumour - does not fit the
+ *   workspace limit on its own); never MMHN_ORD_OVERFLOW.  Every output of a row is NaN where its status != 0; pre and
+ *   seed_pos are also NaN for rows of type 0 ("absent": no seeding in the observation), whose log_evidence is valid.
+ * No atomics: two calls return the same bits, whatever the batching.  Rows are cut into batches that fit
+ * mmhn_set_workspace_limit (allocated once per call); the call leaves a loaded cohort as it was.
+ */
+int mmhn_order_posteriors(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2,
+                          const int8_t* dat, int64_t n_pat, int n_cols, double* log_evidence, double* pre,
+                          double* seed_pos, int32_t* status);
+
 /* ---- measurement -------------------------------------------------------------------
  * mmhn_bench_kronvec: `batch` resident copies of a 2^k vector, `iters` back-to-back
  * launches of mmhn_kronvec_batched's launch (diag = 0: y = Q_off p into a NaN-filled y, every tile of every vector,
@@ -245,9 +265,9 @@ typedef struct {
   int32_t comm_rank;  /* this engine's rank in it (ncclCommUserRank), -1: none */
 } mmhn_counters;
 /* ABI version of this header: bumped whenever an exported signature or structure changes (4: mmhn_bench_kronvec has its
- * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists).  A client built against another header must refuse to run:
+ * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists).  A client built against another header must refuse to run:
  * mmhn_abi_version() != MMHN_ABI_VERSION (metmhn_amd/_lib.py checks it on load). */
-#define MMHN_ABI_VERSION 7
+#define MMHN_ABI_VERSION 8
 int mmhn_abi_version(void);
 int mmhn_bench_kronvec(mmhn_handle h, const double* log_theta, const int8_t* state, int64_t batch,
                        int iters, int transpose, int jacobi, double* ms_per_launch, int64_t* tiles);

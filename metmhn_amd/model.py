@@ -97,6 +97,23 @@ def _pareto(vecs: list) -> list:
     return keep
 
 
+class OrderPosterior(SimpleNamespace):
+    """One observation summed over its admissible orders: log_evidence, pre [n], seed_pos [n+1]."""
+
+    def __init__(self, log_evidence, pre, seed_pos):
+        super().__init__(log_evidence=log_evidence, pre=pre, seed_pos=seed_pos)
+
+
+class OrderPosteriors(OrderPosterior):
+    """The same for every row of a cohort: log_evidence [n_pat], pre [n_pat, n], seed_pos [n_pat, n+1]."""
+
+    def cohort_preseeding(self) -> np.ndarray:
+        """Mean of `pre` over the rows that carry the seeding: the cohort's pre-seeding probabilities given the data
+        (simulations.SimSummary.preseeding_probs is the same quantity of the model alone)."""
+        seeded = ~np.isnan(self.pre).any(axis=1)
+        return self.pre[seeded].mean(axis=0)
+
+
 class MetMHN:
     """The metastasis MHN with its two observation-rate vectors (model.py:175-211)."""
 
@@ -111,6 +128,7 @@ class MetMHN:
         self._pt_log_theta = self.log_theta.copy()
         self._pt_log_theta[:-1, -1] = 0.0
         self.orders_fallback_rows = 0       # rows the last likeliest_orders call recomputed on the host
+        self.posteriors_fallback_rows = 0   # ... and the last order_posteriors call
 
     # ------------------------------------------------------------------ diagonals
     def _get_diag_unpaired(self, state: State, seeding: bool = True) -> np.ndarray:
@@ -124,8 +142,9 @@ class MetMHN:
                           dtype=np.float64)
 
     # ------------------------------------------------------------------ public entry points
-    def likeliest_order(self, state, met_status: str, first_obs: str = None):
-        """model.py:213-293: (order, probability)."""
+    def _route(self, state, met_status: str, first_obs: str):
+        """The checks of model.py:213-293: which chain a (state, status) pair runs on - "mt" / "pt" with its one-tumour
+        state, "paired" with the MetState."""
         if isinstance(state, np.ndarray):
             state = MetState.from_seq(state)
         if met_status == "isMetastasis":
@@ -133,24 +152,33 @@ class MetMHN:
                 raise ValueError("PT part of the state was not empty, but met_status is 'isMetastasis'.")
             if not state.Seeding:
                 raise ValueError("Seeding was not observed, but met_status is 'isMetastasis'.")
-            return self._likeliest_order_unpaired_mt(state.MT)
+            return "mt", state.MT
         if met_status == "absent":
             if len(state.MT) > 0 or state.MT_events:
                 raise ValueError("Met part of the state was not empty, but met_status is 'absent'.")
             if state.Seeding:
                 raise ValueError("Seeding was observed, but met_status is 'absent'.")
-            return self._likeliest_order_unpaired_pt(state.PT_S)
+            return "pt", state.PT_S
         if met_status == "present":
             if tuple(state.MT) != (self.n,):
                 raise ValueError("Met part of the state was not empty, but met_status is 'present', not 'isPaired'.")
-            return self._likeliest_order_unpaired_pt(state.PT_S)
+            return "pt", state.PT_S
         if met_status == "isPaired":
             if first_obs not in _FIRST_OBS:
                 raise ValueError(_FIRST_ERR)
             if first_obs == "sync":
                 warnings.warn("Synchronous development is deprecated.", DeprecationWarning)
-            return self._likeliest_order_paired(state, first_obs)
+            return "paired", state
         raise ValueError(_STATUS_ERR)
+
+    def likeliest_order(self, state, met_status: str, first_obs: str = None):
+        """model.py:213-293: (order, probability)."""
+        chain, st = self._route(state, met_status, first_obs)
+        if chain == "mt":
+            return self._likeliest_order_unpaired_mt(st)
+        if chain == "pt":
+            return self._likeliest_order_unpaired_pt(st)
+        return self._likeliest_order_paired(st, first_obs)
 
     def likeliest_orders(self, dat, backend: str = "device", front_cap: int = 0) -> list:
         """The likeliest order of every row of a reference-format `dat` [n_pat, 2n+3]: a list of (order, probability),
@@ -195,6 +223,59 @@ class MetMHN:
         except ValueError as e:
             raise ValueError(f"row {i}: {e}") from e
         return tuple(int(e) for e in order), float(p)
+
+    def order_posterior(self, state, met_status: str, first_obs: str = None) -> "OrderPosterior":
+        """The sum over every admissible order where likeliest_order takes the maximum (same arguments, checks and
+        errors): `log_evidence` = log of the summed order likelihoods, `pre[m]` = P(mutation m occurred before the seeding
+        | the observation), `seed_pos[j]` = P(j mutations preceded the seeding | the observation).  Exact: a forward and a
+        backward sum-product pass over the lattice of sub-states likeliest_order walks.  "absent" has no seeding to place:
+        pre and seed_pos are NaN."""
+        chain, st = self._route(state, met_status, first_obs)
+        if chain == "mt":
+            return self._posterior_single(self._single_tables(self.log_theta, st, self.obs2))
+        if chain == "pt":
+            return self._posterior_single(self._single_tables(self._pt_log_theta, st, self.obs1))
+        return self._posterior_paired(st, first_obs)
+
+    def order_posteriors(self, dat, backend: str = "device") -> "OrderPosteriors":
+        """order_posterior of every row of a reference-format `dat` [n_pat, 2n+3], rows read as likeliest_orders reads
+        them: arrays log_evidence [n_pat], pre [n_pat, n], seed_pos [n_pat, n+1].
+
+        backend="device": every row in one call of the HIP library (mmhn_order_posteriors); a row whose lattice does not
+        fit the workspace is recomputed here with order_posterior - how many were is left in
+        `self.posteriors_fallback_rows`.  backend="host": order_posterior row by row.  An invalid row raises
+        likeliest_order's ValueError, with its index."""
+        dat = np.asarray(dat)
+        if dat.ndim != 2 or dat.shape[1] != 2 * self.n + 3:
+            raise ValueError(f"dat must have shape [n_pat, {2 * self.n + 3}]")
+        if backend not in ("device", "host"):
+            raise ValueError("backend must be 'device' or 'host'")
+        P = dat.shape[0]
+        if backend == "host":
+            le, pre, sp = np.zeros(P), np.zeros((P, self.n)), np.zeros((P, self.n + 1))
+            redo = range(P)
+        else:
+            from .jx import engine
+            le, pre, sp, status = engine(self.n).order_posteriors(self.log_theta, self.obs1, self.obs2, dat)
+            bad = np.flatnonzero((status & 0xFFFF) == 2)
+            if bad.size:
+                i = int(bad[0])
+                raise ValueError(f"row {i}: {_ROW_ERRORS[int(status[i]) >> 16]}")
+            redo = [int(i) for i in np.flatnonzero(status != 0)]
+        for i in redo:
+            r = self._row_posterior(dat, i)
+            le[i], pre[i], sp[i] = r.log_evidence, r.pre, r.seed_pos
+        self.posteriors_fallback_rows = 0 if backend == "host" else len(redo)
+        return OrderPosteriors(le, pre, sp)
+
+    def _row_posterior(self, dat, i: int):
+        row = dat[i]
+        status = _ROW_STATUS.get(int(row[-1]), f"type {int(row[-1])}")
+        first = _ROW_FIRST.get(int(row[-2]), "Met") if status == "isPaired" else None
+        try:
+            return self.order_posterior(MetState.from_seq(row[:2 * self.n + 1]), status, first)
+        except ValueError as e:
+            raise ValueError(f"row {i}: {e}") from e
 
     def likelihood(self, order, met_status: str, first_obs: str = None) -> float:
         """model.py:295-376: probability of exactly this order of events being what is observed."""
@@ -267,6 +348,40 @@ class MetMHN:
             rev.append(T.ev[last[x]])
             x ^= 1 << last[x]
         return np.array(rev[::-1], dtype=np.int64), float(best[-1] * T.final)
+
+    def _posterior_single(self, T) -> "OrderPosterior":
+        """_single_viterbi's recurrence with the maximum replaced by the sum, and its transpose over the seeded half."""
+        n, k, V = self.n, T.k, 1 << T.k
+        F = [0.0] * V
+        F[0] = 1.0 / T.den[0]
+        for x in range(1, V):
+            s = 0.0
+            for b in range(k):
+                if x >> b & 1:
+                    s += F[x ^ 1 << b] * T.num[b][x]
+            F[x] = s / T.den[x]
+        Z = F[-1] * T.final
+        pre, pos = np.full(n, np.nan), np.full(n + 1, np.nan)
+        if k == 0 or T.ev[-1] != n:                  # "absent": no seeding in the observation
+            return OrderPosterior(float(np.log(Z)), pre, pos)
+        top, full = 1 << (k - 1), V - 1
+        B = {full: T.final}
+        for x in range(full - 1, top - 1, -1):
+            s = 0.0
+            for b in range(k - 1):
+                if not x >> b & 1:
+                    y = x | 1 << b
+                    s += B[y] * T.num[b][y] / T.den[y]
+            B[x] = s
+        pre[:], pos[:] = 0.0, 0.0
+        for x in range(top):                         # the orders that seed at x
+            y = x | top
+            w = F[x] * T.num[k - 1][y] / T.den[y] * B[y]
+            pos[bin(x).count("1")] += w
+            for b in range(k - 1):
+                if x >> b & 1:
+                    pre[T.ev[b]] += w
+        return OrderPosterior(float(np.log(Z)), pre / Z, pos / Z)
 
     def _likelihood_unpaired_mt(self, order) -> float:
         """model.py:1391-1426: a metastasis seen once (obs2), the chain feeling the seeding."""
@@ -388,6 +503,64 @@ class MetMHN:
             x, v = self._advance(T, x, v, b)
             i += 1
         return self._total(T, v)
+
+    def _posterior_paired(self, state: MetState, first_obs: str) -> "OrderPosterior":
+        """_likeliest_order_paired's walk with the Pareto step replaced by the sum (_advance, _settle and _total are
+        linear in the prefix vector), then the transposed walk over the seeded half: B[x] is the weight the rest of the
+        order gives the (unsettled) vector at x, so the orders that seed at x have the mass B[x | top] . A(x, top) F[x]."""
+        if not state.reachable:
+            raise ValueError("This state is not reachable by mhn.")
+        T = self._paired_tables(state, first_obs)
+        n, k = self.n, T.k
+        top, full = 1 << (k - 1), (1 << k) - 1
+        F = {0: (1.0 / T.den[0], 0.0, 0.0)}
+        for y in range(1, 1 << k):
+            if not y & top:
+                lo = y & T.joint
+                if y != lo | lo << 1:
+                    continue                                    # tumours differ before the seeding
+                moves = [(y ^ 3 << b, b) for b in range(k - 1) if lo >> b & 1]
+            else:
+                moves = [(y ^ 1 << b, b) for b in range(k) if y >> b & 1 and y ^ 1 << b in F]
+            a = bp = bm = 0.0
+            for x, b in moves:
+                v = self._advance(T, x, F[x], b)[1]
+                a, bp, bm = a + v[0], bp + v[1], bm + v[2]
+            F[y] = (a, bp, bm)
+        Z = self._total(T, F[full])
+
+        def settle_t(x, ga, gp, gm):                            # _settle transposed (x seeded)
+            if T.pt_first and x & T.pt_mask == T.pt_mask:
+                ga = ga + gp * (T.o1[x] / T.den_mt[x])
+            if T.mt_first and x & T.mt_mask == T.mt_mask:
+                ga = ga + gm * (T.o2[x] / T.den_pt[x])
+            return ga, gp, gm
+
+        t = (T.o1[full] + T.o2[full], 0.0, 0.0) if T.sync else (0.0, T.o2[full], T.o1[full])
+        B = {full: settle_t(full, *t)}
+        for x in range(full - 1, top - 1, -1):
+            ga = gp = gm = 0.0
+            for b in range(k - 1):
+                if not x >> b & 1:
+                    y = x | 1 << b
+                    num, g = T.num[b][y], B[y]
+                    ga += g[0] * num / T.den[y]
+                    if T.pt_first and T.kind[b] == 1:
+                        gp += g[1] * num / T.den_mt[y]
+                    if T.mt_first and T.kind[b] == 0:
+                        gm += g[2] * num / T.den_pt[y]
+            B[x] = settle_t(x, ga, gp, gm)
+        pre, pos = np.zeros(n), np.zeros(n + 1)
+        for x in F:
+            if x & top:
+                continue
+            y = x | top
+            w = B[y][0] * (F[x][0] * T.num[k - 1][y] / T.den[y])
+            pos[bin(x).count("1") // 2] += w
+            for b in range(k - 1):
+                if T.joint >> b & 1 and x >> b & 1:
+                    pre[T.slots[b] // 2] += w
+        return OrderPosterior(float(np.log(Z)), pre / Z, pos / Z)
 
     def _likeliest_order_paired(self, state: MetState, first_obs: str):
         """model.py:503-1389 (_likeliest_order_pt_mt / _mt_pt / _unknown / _sync)."""
