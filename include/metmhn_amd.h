@@ -235,6 +235,31 @@ int mmhn_order_posteriors(mmhn_handle h, const double* log_theta, const double* 
                           const int8_t* dat, int64_t n_pat, int n_cols, double* log_evidence, double* pre,
                           double* seed_pos, int32_t* status);
 
+/* ---- pairwise precedence posteriors of a cohort ---------------------------------------------
+ * mmhn_order_precedences: for every row of a reference-format `dat` (read as mmhn_likeliest_orders reads it), over the
+ * same admissible orders as mmhn_order_posteriors: which of two events came first.  Event codes as in the orders of
+ * mmhn_likeliest_orders (2i event i in the primary tumour, 2i+1 in the metastasis, 2 n_mut the seeding; a one-tumour row
+ * carries the codes its likeliest order is written in).  No reference counterpart.  fp64 engines only.
+ *   log_evidence [n_pat]                        as mmhn_order_posteriors
+ *   prec [n_pat][2 n_mut + 1][2 n_mut + 1]      prec[c][d] = P(code c happened strictly earlier than code d | the row).
+ *                                               The two codes of an event that occurred before the seeding of a paired
+ *                                               row happen at the same moment: neither precedes the other, so
+ *                                               prec[c][d] + prec[d][c] = 1 - pre for them and 1 for every other pair.
+ *                                               NaN where c or d is not in the row, 0 on the diagonal of those that are.
+ *   status [n_pat]: as mmhn_order_posteriors - low half MMHN_ORD_OK, MMHN_ORD_INVALID (reason in the HIGH half) or
+ *   MMHN_ORD_TOO_LARGE (the row does not fit the workspace limit on its own); every output of a row is NaN where its
+ *   status != 0.  Workspace of a row of k slots, in doubles: the lattice of mmhn_order_posteriors (8 x 2^k + 3 x 2^(k-1)
+ *   paired, 2 x 2^k one tumour) + the chunk partials of the reduction, k x sum over its levels of (c_l + 1) 2^(m_l - c_l)
+ *   with m_0 = k - 2 paired / k - 1 one tumour, m_(l+1) = m_l - c_l, c_l = min(m_l, 10) past the first level and
+ *   c_0 = min(m_0, max(6, min(10, m_0 - 2))) below 15 slots, min(m_0, max(6, min(10, m_0 - 4))) from there up: under 3 %
+ *   on top of the lattice.
+ * No atomics: two calls return the same bits, whatever the batching.  Rows are cut into batches that fit
+ * mmhn_set_workspace_limit (allocated once per call); the call leaves a loaded cohort as it was.
+ */
+int mmhn_order_precedences(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2,
+                           const int8_t* dat, int64_t n_pat, int n_cols, double* log_evidence, double* prec,
+                           int32_t* status);
+
 /* ---- measurement -------------------------------------------------------------------
  * mmhn_bench_kronvec: `batch` resident copies of a 2^k vector, `iters` back-to-back
  * launches of mmhn_kronvec_batched's launch (diag = 0: y = Q_off p into a NaN-filled y, every tile of every vector,
@@ -265,7 +290,7 @@ typedef struct {
   int32_t comm_rank;  /* this engine's rank in it (ncclCommUserRank), -1: none */
 } mmhn_counters;
 /* ABI version of this header: bumped whenever an exported signature or structure changes (4: mmhn_bench_kronvec has its
- * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists).  A client built against another header must refuse to run:
+ * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences was added within version 8, a purely additive change).  A client built against another header must refuse to run:
  * mmhn_abi_version() != MMHN_ABI_VERSION (metmhn_amd/_lib.py checks it on load). */
 #define MMHN_ABI_VERSION 8
 int mmhn_abi_version(void);

@@ -2,7 +2,7 @@
 // C ABI of include/metmhn_amd.h.  One engine = one GPU, one HIP stream.
 // The rest of the host side lives in headers of this one translation unit: plan.h (the cohort planner, host-only:
 // batches, routes, work lists, offsets), host.h (errors, device arrays, MMHN_* knob readers), comm.h (RCCL),
-// prims.h / orders_host.h / orderpost_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
+// prims.h / orders_host.h / orderpost_host.h / orderprec_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
 //
 // Pipeline of one evaluation (reference call graph: regularized_optimization.py:163-267 ->
 // likelihood.py:_g_coupled_*, _grad_prim_obs, _grad_met_obs), run batch by batch with every
@@ -1015,6 +1015,7 @@ struct Engine : EngineBase {
 #include "prims.h"
 #include "orders_host.h"
 #include "orderpost_host.h"
+#include "orderprec_host.h"
 #include "sampler_host.h"
 #include "bench.h"
 
@@ -1479,6 +1480,20 @@ int mmhn_order_posteriors(mmhn_handle h, const double* log_theta, const double* 
   REQUIRE(h->dtype == MMHN_F64, "order posteriors need an fp64 engine (MMHN_F64)");
   order_posteriors(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, log_evidence, pre,
                    seed_pos, status);
+  API_END
+}
+
+// ---- pairwise precedence posteriors of a cohort: which of two events came first, over the same orders
+int mmhn_order_precedences(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, const int8_t* dat,
+                           int64_t n_pat, int n_cols, double* log_evidence, double* prec, int32_t* status) {
+  API_BEGIN
+  GUARD(h);
+  REQUIRE(log_theta && obs1 && obs2 && log_evidence && prec && status, "null pointer");
+  REQUIRE(dat || n_pat == 0, "null dat");
+  REQUIRE(n_pat >= 0 && n_pat < ((int64_t)1 << 31), "n_pat out of range");
+  REQUIRE(h->dtype == MMHN_F64, "order precedences need an fp64 engine (MMHN_F64)");
+  order_precedences(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, log_evidence, prec,
+                    status);
   API_END
 }
 

@@ -1,0 +1,421 @@
+// Pairwise event-precedence posteriors of a cohort: the device form of metmhn_amd/model.py MetMHN.order_precedence, next to
+// orderpost.h (k_order_post), whose tables, forward vectors F, backward vectors B and level walk it shares.
+//
+// Every admissible order of a row is a path of moves x -> y over the row's lattice of 2^k sub-states (slot b = bit b).
+//   mass of a move   m(x, b) = B[y] . A(x, b) F[x]   (a scalar product of 3-vectors on the seeded half of a paired row, a
+//                    product of scalars elsewhere): the summed likelihood of the orders that make this move
+//   output           P[c][d] = (1 / Z) sum of m(x, b) over the moves that add slot d from a state x that holds slot c
+//                    = P(c happened strictly earlier than d | the row); a joint move (before the seeding of a paired row)
+//                    adds both of its slots, so neither of the two precedes the other
+// One tumour: the whole lattice, B as G[x] = B[x] / den[x] in den's place once the forward pass is done.  Both tumours: B
+// over the seeded half as k_order_post forms it, then the scalar B of the unseeded states whose tumours agree (joint moves
+// and the seeding edge; at most 2^((k-1)/2) states, LDS: the host side turns a row of more than 10 joint events away).
+// The move masses are recomputed from F, B and the tables - a k x 2^(k-1) edge array would not fit.
+//
+// The reduction.  For a target slot d the moves that add d are indexed by the other slots: idx of m bits (m = k - 1 for
+// one tumour, k - 2 on the seeded half, where the seeding is always held).  The k - 1 sums "over the x that hold c" are the
+// sums over the idx with one bit set.  The vector of masses is folded along one index bit at a time: the upper half's sum
+// is that bit's answer, lower + upper goes on to the next bit.  A wave folds a chunk of 2^c consecutive idx (c = the chunk
+// bits of the level walk): bits 9..6 in registers (lane l holds idx l + 64 i), bits 5..0 with one xor-shuffle each - in
+// step j a lane whose highest set bit is j keeps its value and from then on collects that bit's answer, every other lane
+// adds its partner - and writes the chunk's c bit sums and its total.  The totals of the chunks are a vector over the
+// high bits and are folded the same way (a second level; a third from m = 21 on), the bit sums of the chunks are added by
+// one wave per sum, lanes striding the chunks.  Every value is written once, every sum has a fixed shape, no atomics: a
+// row's result does not depend on the batch, the launch geometry (a function of k alone) or the run.
+//
+// Workspace of a row in doubles: opost_doubles (paired 8 x 2^k + 3 x 2^(k-1), one tumour 2 x 2^k) + the chunk partials
+// k x sum over the levels of (c_l + 1) 2^(m_l - c_l), m_0 = m, c_0 = c, m_(l+1) = m_l - c_l, c_l = min(m_l, 10) - that is
+// k (c + 1) 2^(m - c) + k (m - c + 1) up to m = 20, under 3 % of the lattice.  Output: the compact k x k matrix in slot
+// order (row c, column d, diagonal 0); the host side scatters it to the event codes.  fp64 only.
+#pragma once
+#include "orderpost.h"
+
+namespace mmhn {
+
+// index bits of the vector of moves that add one slot
+inline int oprec_bits(const ORow& r) {
+  const int m = r.mode == ORD_PAIRED ? r.k - 2 : r.k - 1;
+  return m > 0 ? m : 0;
+}
+
+// opo_chunk_bits for a launch of kb threads (host and device)
+__host__ __device__ inline int oprec_chunk_bits(int kk, int kb) {
+  int lg = 0;
+  while ((64 << lg) < kb) ++lg;
+  int c = kk - lg;
+  c = c < 6 ? 6 : c;
+  c = c > OPO_CB ? OPO_CB : c;
+  return c < kk ? c : (kk > 0 ? kk : 0);
+}
+
+// chunk partials of nt vectors of 2^m values whose first level has chunks of c bits, in doubles
+__host__ __device__ inline long long oprec_part_doubles(int nt, int m, int c) {
+  long long s = 0;
+  for (;;) {
+    s += (long long)nt * (c + 1) << (m - c);
+    if (m == c) return s;
+    m -= c;
+    c = m < OPO_CB ? m : OPO_CB;
+  }
+}
+
+// workspace of a row in doubles (kb: threads of the row's launch)
+inline long long oprec_doubles(const ORow& r, int kb) {
+  const int m = oprec_bits(r);
+  return opost_doubles(r) + oprec_part_doubles(r.k, m, oprec_chunk_bits(m, kb));
+}
+
+// idx with a zero inserted at bit d
+__device__ __forceinline__ uint32_t opr_ins0(uint32_t idx, int d) { return ((idx >> d) << (d + 1)) | (idx & ((1u << d) - 1u)); }
+
+// The fold of one chunk by one wave.  In: v[i] = the value of chunk index lane + 64 i (0 past the chunk).  Out: t = the
+// chunk's total on lane 0 and the sum over the indices with bit j set on lane 2^j (j < 6); hi[j] = the sum over the
+// indices with bit 6 + j set, on every lane.
+__device__ __forceinline__ void opr_fold(double (&v)[1 << (OPO_CB - 6)], double& t, double (&hi)[OPO_CB - 6]) {
+#pragma unroll
+  for (int j = OPO_CB - 7; j >= 0; --j) {
+    const int h = 1 << j;
+    double u = v[h];
+#pragma unroll
+    for (int i = 1; i < h; ++i) u += v[h + i];
+#pragma unroll
+    for (int i = 0; i < h; ++i) v[i] += v[h + i];
+    hi[j] = opo_wave_sum(u);
+  }
+  t = v[0];
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (int j = 5; j >= 0; --j) {
+    const double u = __shfl_xor(t, 1 << j, 64);
+    if ((lane >> j) != 1u) t += u;              // the lanes [2^j, 2^(j+1)) hold the upper half: bit j's answer from here on
+  }
+}
+
+// Bit sums of nt vectors of 2^m values val(t, idx): out(t, j, s) with s = the sum over the idx with bit j set (j < m)
+// and out(t, m, s) with the total.  c0: chunk bits of the first level; part: oprec_part_doubles(nt, m, c0) doubles.
+// Every thread of the workgroup; starts from values the caller has fenced with a barrier, ends with a barrier.
+template <int KB, class Val, class Out>
+__device__ __forceinline__ void opr_bit_sums(int nt, int m, int c0, double* part, Val val, Out out) {
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  int ml = m, cl = c0, lo = 0, pc = 0;
+  long long pnh = 0;
+  double* pl = part;
+  const double* prev = nullptr;                 // the level below: its chunks' totals are this level's values
+  for (;;) {
+    const long long nh = 1ll << (ml - cl);
+    for (long long task = wave; task < nt * nh; task += KB / 64) {
+      const int t = (int)(task / nh);
+      const long long h = task - t * nh;
+      double v[1 << (OPO_CB - 6)], tot, hi[OPO_CB - 6];
+#pragma unroll
+      for (int i = 0; i < (1 << (OPO_CB - 6)); ++i) {
+        const uint32_t p = lane + 64u * i;
+        v[i] = 0.0;
+        if (p < (1u << cl)) {
+          const long long idx = (h << cl) | p;
+          v[i] = prev ? prev[(t * pnh + idx) * (pc + 1) + pc] : val(t, (uint32_t)idx);
+        }
+      }
+      opr_fold(v, tot, hi);
+      double* o = pl + (t * nh + h) * (cl + 1);
+#pragma unroll
+      for (int j = 0; j < 6; ++j)
+        if (lane == (1u << j) && j < cl) o[j] = tot;
+      if (lane == 0) {
+        for (int j = 6; j < cl; ++j) o[j] = hi[j - 6];
+        o[cl] = tot;
+      }
+    }
+    __syncthreads();
+    // this level's bit sums over its chunks: one wave per sum, lanes stride the chunks
+    for (int task = wave; task < nt * cl; task += KB / 64) {
+      const int t = task / cl, j = task - t * cl;
+      double s = 0.0;
+      for (long long h = lane; h < nh; h += 64) s += pl[(t * nh + h) * (cl + 1) + j];
+      s = opo_wave_sum(s);
+      if (lane == 0) out(t, lo + j, s);
+    }
+    if (nh == 1) {
+      for (int t = threadIdx.x; t < nt; t += KB) out(t, m, pl[t * (cl + 1) + cl]);
+      break;
+    }
+    prev = pl; pc = cl; pnh = nh;
+    pl += nt * nh * (cl + 1);
+    lo += cl; ml -= cl;
+    cl = ml < OPO_CB ? ml : OPO_CB;
+  }
+  __syncthreads();
+}
+
+// rows[blockIdx.x]; lt [N][N], obs1 / obs2 [N]; diagJ already in tab[toff ..] of the paired rows (k_diag, KD_DQ).
+// Row fields: toff tables (opost_doubles), coff chunk partials, foff the row's k x k block of out_prec.  out_le [row]
+template <int KB>
+__global__ __launch_bounds__(KB) void k_order_prec(const ORow* __restrict__ rows, const double* __restrict__ g_lt,
+                                                   const double* __restrict__ g_o1, const double* __restrict__ g_o2, int N,
+                                                   double* tab, double* out_le, double* out_prec) {
+  __shared__ double lt[ORD_MAXN * ORD_MAXN];
+  __shared__ double o1w[ORD_MAXN], o2w[ORD_MAXN];
+  __shared__ ORow r;
+  __shared__ OpoLevels L;
+  __shared__ double Rs[32][32];                // Rs[d][c]: summed masses of the moves that add d from a state holding c
+  __shared__ double Rj[OPO_CB + 1][OPO_CB + 1]; // paired, before the seeding: Rj[t][q] target joint event t (kj: the
+                                               // seeding), held joint event q
+  __shared__ double bu[1 << OPO_CB];           // paired: B of the unseeded state of the joint events e
+  __shared__ double pj[(OPO_CB + 1) * (OPO_CB + 1)];   // chunk partials of the sums before the seeding (one chunk each)
+  __shared__ int8_t jslot[32];                 // paired: slot of the i-th joint event
+  __shared__ int8_t jev[32];                   // paired: joint event of a slot, -1 none
+  __shared__ double zsh;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < N * N; i += KB) lt[i] = g_lt[i];
+  for (int i = tid; i < N; i += KB) { o1w[i] = g_o1[i]; o2w[i] = g_o2[i]; }
+  if (tid == 0) r = rows[blockIdx.x];
+  __syncthreads();
+  const int n = N - 1, k = r.k;
+  const uint32_t V = 1u << k, full = V - 1u;
+  double* den = tab + r.toff;
+  double* part = tab + r.coff;
+  double* P = out_prec + r.foff;
+
+  if (r.mode != ORD_PAIRED) {
+    // ---------------------------------------------------------------- one tumour: _single_tables, every slot alike
+    const bool pt = r.mode == ORD_PT;
+    const double* after = pt ? o1w : o2w;
+    double* F = den + V;
+    const bool sd = r.seeded_top && k > 0;
+    opo_levels_init<KB>(L, opo_chunk_bits<KB>(k));
+    const int c = L.c;
+    for (uint32_t x = tid; x < V; x += KB) {
+      const bool sx = r.seeded_top && ((x >> (k - 1)) & 1u);
+      const double ob = exp(sx ? ord_obs_sum(after, r, x) : ord_obs_sum(o1w, r, x));
+      den[x] = ob - ord_single_diag(lt, N, r, full, x, N, pt);
+    }
+    __syncthreads();
+    if (tid == 0) F[0] = 1.0 / den[0];
+    __syncthreads();
+    for (int lev = 1; lev <= k; ++lev) {
+      opo_level<KB>(L, 0u, V >> c, lev, [&](uint32_t x) {
+        double s = 0.0;
+        for (uint32_t m = x; m; m &= m - 1) {
+          const int b = __builtin_ctz(m);
+          s += F[x ^ (1u << b)] * ord_num(lt, N, r, r.ev[b], x, pt);
+        }
+        F[x] = s / den[x];
+      });
+      __syncthreads();
+    }
+    const double fin = exp(sd ? ord_obs_sum(after, r, full) : ord_obs_sum(o1w, r, full));
+    const double Z = F[full] * fin;
+    if (tid == 0) out_le[r.row] = log(Z);
+    if (k == 0) return;
+    // backward over the whole lattice, G[x] = B[x] / den[x] in den's place (den[x] is read for the last time by the
+    // thread that writes G[x])
+    double* G = den;
+    if (tid == 0) G[full] = fin / den[full];
+    __syncthreads();
+    for (int lev = k - 1; lev >= 0; --lev) {
+      opo_level<KB>(L, 0u, V >> c, lev, [&](uint32_t x) {
+        double s = 0.0;
+        for (uint32_t m = full & ~x; m; m &= m - 1) {
+          const int b = __builtin_ctz(m);
+          const uint32_t y = x | (1u << b);
+          s += G[y] * ord_num(lt, N, r, r.ev[b], y, pt);
+        }
+        G[x] = s / den[x];
+      });
+      __syncthreads();
+    }
+    const int m = k - 1;
+    opr_bit_sums<KB>(k, m, oprec_chunk_bits(m, KB), part,
+        [&](int d, uint32_t idx) {
+          const uint32_t x = opr_ins0(idx, d), y = x | (1u << d);
+          return F[x] * ord_num(lt, N, r, r.ev[d], y, pt) * G[y];
+        },
+        [&](int d, int j, double s) { if (j < m) Rs[d][j < d ? j : j + 1] = s; });
+    for (int i = tid; i < k * k; i += KB) {
+      const int cc = i / k, d = i - cc * k;
+      P[i] = cc == d ? 0.0 : fmin(Rs[d][cc] / Z, 1.0);     // a probability: the quotient of two roundings may pass 1
+    }
+    return;
+  }
+
+  // ---------------------------------------------------------------- both tumours: _paired_tables (as k_order_post)
+  double* o1 = den + V;
+  double* o2 = o1 + V;
+  double* dmt = o2 + V;
+  double* dpt = dmt + V;
+  double* F = dpt + V;
+  double* B = F + 3ll * V;                      // B[3 (x ^ top)] of the seeded x
+  const uint32_t top = 1u << (k - 1);
+  const uint32_t in_mt = r.mt_mask | top;
+  const int c = opo_chunk_bits<KB>(k - 1);
+  opo_levels_init<KB>(L, c);
+  if (tid == 0) {
+    int kj = 0;
+    for (int b = 0; b < 32; ++b) jev[b] = -1;
+    for (uint32_t m = r.joint; m; m &= m - 1) {
+      const int b = __builtin_ctz(m);
+      jslot[kj] = (int8_t)b; jev[b] = jev[b + 1] = (int8_t)kj; ++kj;
+    }
+  }
+  for (uint32_t x = tid; x < V; x += KB) {
+    double s1 = 0.0, s2 = 0.0;
+    for (uint32_t m = x; m; m &= m - 1) {
+      const int j = __builtin_ctz(m);
+      if (r.kind[j] != ORD_K_MT) s1 += o1w[r.ev[j]];
+      if (r.kind[j] != ORD_K_PT) s2 += o2w[r.ev[j]];
+    }
+    const double e1 = exp(s1), e2 = exp(s2);
+    o1[x] = e1; o2[x] = e2;
+    den[x] = (e1 + ((x & top) ? e2 : 0.0)) - den[x];
+    if (r.pt_first) dmt[x] = e2 - ord_single_diag(lt, N, r, in_mt, x, N, false);
+    if (r.mt_first) dpt[x] = e1 - ord_single_diag(lt, N, r, r.pt_mask, x, n, false);
+  }
+  const OrdTab t{o1, o2, dmt, dpt};
+  const int kj = __builtin_popcount(r.joint);
+  const uint32_t EJ = 1u << kj;
+  // state of the compact index e over the joint events: both slots of every event in e
+  auto joint_state = [&](uint32_t e) {
+    uint32_t x = 0;
+    for (uint32_t m = e; m; m &= m - 1) x |= 3u << jslot[__builtin_ctz(m)];
+    return x;
+  };
+  __syncthreads();
+  if (tid == 0) { F[0] = 1.0 / den[0]; F[1] = 0.0; F[2] = 0.0; }
+  __syncthreads();
+  // before the seeding: the states whose tumours agree, joint moves only
+  for (int lev = 1; lev <= kj; ++lev) {
+    for (uint32_t e = tid; e < EJ; e += KB) {
+      if (__builtin_popcount(e) != lev) continue;
+      const uint32_t y = joint_state(e);
+      double a = 0.0;
+      for (uint32_t m = e; m; m &= m - 1) {
+        const int b = jslot[__builtin_ctz(m)];
+        a += F[3ll * (y ^ (3u << b))] * ord_num(lt, N, r, r.ev[b], y & r.pt_mask, false) / den[y];
+      }
+      F[3ll * y] = a; F[3ll * y + 1] = 0.0; F[3ll * y + 2] = 0.0;
+    }
+    __syncthreads();
+  }
+  // seeded half, level by level: every move
+  for (int lev = 1; lev <= k; ++lev) {
+    opo_level<KB>(L, top >> c, V >> c, lev, [&](uint32_t y) {
+      double a = 0.0, bp = 0.0, bm = 0.0;
+      for (uint32_t m = y; m; m &= m - 1) {
+        const int b = __builtin_ctz(m);
+        const uint32_t x = y ^ (1u << b);
+        if (b == k - 1) {                       // the seeding itself, from a state whose tumours agree
+          const uint32_t lo = x & r.joint;
+          if (x != (lo | lo << 1)) continue;
+          a += F[3ll * x] * ord_num(lt, N, r, r.ev[b], y & in_mt, false) / den[y];
+          continue;
+        }
+        const bool pt_ev = r.kind[b] == ORD_K_PT;
+        const double num = ord_num(lt, N, r, r.ev[b], y & (pt_ev ? r.pt_mask : in_mt), false);
+        double fa = F[3ll * x], fp = F[3ll * x + 1], fm = F[3ll * x + 2];
+        ord_settle(r, t, x, fa, fp, fm);                                   // _advance
+        if (r.pt_first && !pt_ev) bp += fp * num / dmt[y];
+        if (r.mt_first && pt_ev) bm += fm * num / dpt[y];
+        a += fa * num / den[y];
+      }
+      F[3ll * y] = a; F[3ll * y + 1] = bp; F[3ll * y + 2] = bm;
+    });
+    __syncthreads();
+  }
+  // _settle's two coefficients at a seeded x (transposed: they carry the b's weights back to a)
+  auto settle_t = [&](uint32_t x, double& ga, double gp, double gm) {
+    if (r.pt_first && (x & r.pt_mask) == r.pt_mask) ga = ga + gp * (o1[x] / dmt[x]);
+    if (r.mt_first && (x & r.mt_mask) == r.mt_mask) ga = ga + gm * (o2[x] / dpt[x]);
+  };
+  if (tid == 0) {
+    double a = F[3ll * full], bp = F[3ll * full + 1], bm = F[3ll * full + 2];
+    ord_settle(r, t, full, a, bp, bm);
+    zsh = bp * o2[full] + bm * o1[full];                                   // _total
+    double ga = 0.0;
+    settle_t(full, ga, o2[full], o1[full]);
+    double* bf = B + 3ll * (full ^ top);
+    bf[0] = ga; bf[1] = o2[full]; bf[2] = o1[full];
+  }
+  __syncthreads();
+  const double Z = zsh;
+  for (int lev = k - 1; lev >= 1; --lev) {
+    opo_level<KB>(L, top >> c, V >> c, lev, [&](uint32_t x) {
+      double ga = 0.0, gp = 0.0, gm = 0.0;
+      for (uint32_t m = full & ~x; m; m &= m - 1) {
+        const int b = __builtin_ctz(m);
+        const uint32_t y = x | (1u << b);
+        const bool pt_ev = r.kind[b] == ORD_K_PT;
+        const double num = ord_num(lt, N, r, r.ev[b], y & (pt_ev ? r.pt_mask : in_mt), false);
+        const double* by = B + 3ll * (y ^ top);
+        ga += by[0] * num / den[y];
+        if (r.pt_first && !pt_ev) gp += by[1] * num / dmt[y];
+        if (r.mt_first && pt_ev) gm += by[2] * num / dpt[y];
+      }
+      settle_t(x, ga, gp, gm);
+      double* bx = B + 3ll * (x ^ top);
+      bx[0] = ga; bx[1] = gp; bx[2] = gm;
+    });
+    __syncthreads();
+  }
+  // the seeding edge of the unseeded state x: the factor that takes F[x]_a to its mass
+  auto seed_edge = [&](uint32_t x) {
+    const uint32_t y = x | top;
+    return ord_num(lt, N, r, r.ev[k - 1], y & in_mt, false) / den[y] * B[3ll * x];
+  };
+  // the same for the joint move of event q from the unseeded state of the joint events e
+  auto joint_edge = [&](uint32_t e, int q) {
+    const uint32_t y = joint_state(e | (1u << q));
+    return ord_num(lt, N, r, r.ev[jslot[q]], y & r.pt_mask, false) / den[y] * bu[e | (1u << q)];
+  };
+  // backward over the unseeded states whose tumours agree: joint moves in ascending event, then the seeding edge
+  for (int lev = kj; lev >= 0; --lev) {
+    for (uint32_t e = tid; e < EJ; e += KB) {
+      if (__builtin_popcount(e) != lev) continue;
+      double s = 0.0;
+      for (uint32_t m = (EJ - 1u) & ~e; m; m &= m - 1) s += joint_edge(e, __builtin_ctz(m));
+      bu[e] = s + seed_edge(joint_state(e));
+    }
+    __syncthreads();
+  }
+  if (tid == 0) out_le[r.row] = log(Z);
+  // after the seeding: target slot d < k - 1, the moves from the seeded x without d
+  const int m = k >= 2 ? k - 2 : 0;
+  opr_bit_sums<KB>(k - 1, m, oprec_chunk_bits(m, KB), part,
+      [&](int d, uint32_t idx) {
+        const uint32_t x = opr_ins0(idx, d) | top, y = x | (1u << d);
+        const bool pt_ev = r.kind[d] == ORD_K_PT;
+        const double num = ord_num(lt, N, r, r.ev[d], y & (pt_ev ? r.pt_mask : in_mt), false);
+        double fa = F[3ll * x], fp = F[3ll * x + 1], fm = F[3ll * x + 2];
+        ord_settle(r, t, x, fa, fp, fm);                                     // _advance
+        const double* by = B + 3ll * (y ^ top);
+        double w = by[0] * (fa * num / den[y]);
+        if (r.pt_first && !pt_ev) w += by[1] * (fp * num / dmt[y]);
+        if (r.mt_first && pt_ev) w += by[2] * (fm * num / dpt[y]);
+        return w;
+      },
+      [&](int d, int j, double s) { Rs[d][j < m ? (j < d ? j : j + 1) : k - 1] = s; });   // every seeded x holds the seeding
+  // before the seeding: the joint move of event q from the states without it, then the seeding from every such state
+  opr_bit_sums<KB>(kj, kj > 0 ? kj - 1 : 0, kj > 0 ? kj - 1 : 0, pj,
+      [&](int q, uint32_t idx) {
+        const uint32_t e = opr_ins0(idx, q);
+        return F[3ll * joint_state(e)] * joint_edge(e, q);
+      },
+      [&](int q, int j, double s) { if (j < kj - 1) Rj[q][j < q ? j : j + 1] = s; });
+  opr_bit_sums<KB>(1, kj, kj, pj,
+      [&](int, uint32_t e) {
+        const uint32_t x = joint_state(e);
+        return F[3ll * x] * seed_edge(x);
+      },
+      [&](int, int j, double s) { if (j < kj) Rj[kj][j] = s; });
+  for (int i = tid; i < k * k; i += KB) {
+    const int cc = i / k, d = i - cc * k;
+    double s = 0.0;
+    if (cc != d) {
+      if (d < k - 1) s = Rs[d][cc];
+      const int q = jev[cc], td = d == k - 1 ? kj : jev[d];
+      if (q >= 0 && td >= 0 && td != q) s += Rj[td][q];
+    }
+    P[i] = fmin(s / Z, 1.0);
+  }
+}
+
+}  // namespace mmhn

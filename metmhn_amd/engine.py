@@ -413,6 +413,24 @@ class Engine:
                                                   sp.ctypes.data_as(f64p), status.ctypes.data_as(_lib.i32p)))
         return le, pre, sp, status
 
+    def order_precedences(self, log_theta, obs1, obs2, dat):
+        """MetMHN.order_precedence of every row of a reference-format `dat` [n_pat, 2n+3] in one call
+        (mmhn_order_precedences): float64 log_evidence [n_pat], prec [n_pat, 2n+1, 2n+1] over the event codes (NaN where
+        a code is not in the row), int32 status [n_pat] (low half 0 ok, 2 invalid row - reason code in status >> 16 -,
+        3 lattice larger than the workspace; NaN outputs wherever it is not 0)."""
+        keep, (ltp, ap, bp) = self._params(log_theta, obs1, obs2)
+        d = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
+        if d.ndim != 2:
+            raise ValueError("dat must be a 2-D array [n_pat, 2 n_mut + 3]")
+        n_pat, L = d.shape[0], 2 * self.n + 1
+        le = np.zeros(n_pat)
+        prec = np.empty((n_pat, L, L))
+        status = np.zeros(n_pat, dtype=np.int32)
+        _lib.check(self.lib.mmhn_order_precedences(self.h, ltp, ap, bp, d.ctypes.data_as(i8p), n_pat, int(d.shape[1]),
+                                                   le.ctypes.data_as(f64p), prec.ctypes.data_as(f64p),
+                                                   status.ctypes.data_as(_lib.i32p)))
+        return le, prec, status
+
     # ---- measurement
     def bench_kronvec(self, log_theta, state, batch, iters, transpose=False, jacobi=False, tiles=False):
         """ms per launch of mmhn_kronvec_batched's launch (or the fused Jacobi step); tiles=True also returns

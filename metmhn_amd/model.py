@@ -114,6 +114,25 @@ class OrderPosteriors(OrderPosterior):
         return self.pre[seeded].mean(axis=0)
 
 
+class OrderPrecedence(SimpleNamespace):
+    """One observation summed over its admissible orders: log_evidence and prec [2n+1, 2n+1] over the event codes,
+    prec[c, d] = P(c happened strictly earlier than d | the observation); NaN where a code is not in the observation."""
+
+    def __init__(self, log_evidence, prec):
+        super().__init__(log_evidence=log_evidence, prec=prec)
+
+
+class OrderPrecedences(OrderPrecedence):
+    """The same for every row of a cohort: log_evidence [n_pat], prec [n_pat, 2n+1, 2n+1]."""
+
+    def cohort_mean(self) -> np.ndarray:
+        """Entry by entry the mean of `prec` over the rows that carry both codes; NaN where no row does."""
+        have = ~np.isnan(self.prec)
+        rows = have.sum(axis=0)
+        total = np.where(have, self.prec, 0.0).sum(axis=0)
+        return np.where(rows > 0, total / np.maximum(rows, 1), np.nan)
+
+
 class MetMHN:
     """The metastasis MHN with its two observation-rate vectors (model.py:175-211)."""
 
@@ -129,6 +148,7 @@ class MetMHN:
         self._pt_log_theta[:-1, -1] = 0.0
         self.orders_fallback_rows = 0       # rows the last likeliest_orders call recomputed on the host
         self.posteriors_fallback_rows = 0   # ... and the last order_posteriors call
+        self.precedences_fallback_rows = 0  # ... and the last order_precedences call
 
     # ------------------------------------------------------------------ diagonals
     def _get_diag_unpaired(self, state: State, seeding: bool = True) -> np.ndarray:
@@ -277,6 +297,63 @@ class MetMHN:
         except ValueError as e:
             raise ValueError(f"row {i}: {e}") from e
 
+    def order_precedence(self, state, met_status: str, first_obs: str = None) -> "OrderPrecedence":
+        """Which of two events came first, summed over every admissible order (same arguments, checks and errors as
+        order_posterior): `prec[c, d]` = P(code c happened strictly earlier than code d | the observation) over the event
+        codes of likeliest_order (2i PT, 2i+1 MT, 2n seeding).  The two codes of an event that occurred before the
+        seeding happen at the same moment: neither precedes the other.  Entries of codes the observation does not carry
+        are NaN, the diagonal of those it carries is 0.  Exact: every order is a path of moves x -> y over the lattice
+        likeliest_order walks, a move has the mass B[y] . A(x, b) F[x] (forward prefix vector, backward weight), and
+        prec[c, d] is the summed mass of the moves that add d from a state that holds c, over the evidence."""
+        chain, st = self._route(state, met_status, first_obs)
+        if chain == "mt":
+            T = self._single_tables(self.log_theta, st, self.obs2)
+            return self._precedence_single(T, [2 * self.n if e == self.n else 2 * e + 1 for e in T.ev])
+        if chain == "pt":
+            T = self._single_tables(self._pt_log_theta, st, self.obs1)
+            return self._precedence_single(T, [2 * e for e in T.ev])
+        return self._precedence_paired(st, first_obs)
+
+    def order_precedences(self, dat, backend: str = "device") -> "OrderPrecedences":
+        """order_precedence of every row of a reference-format `dat` [n_pat, 2n+3], rows read as order_posteriors reads
+        them: arrays log_evidence [n_pat], prec [n_pat, 2n+1, 2n+1].
+
+        backend="device": every row in one call of the HIP library (mmhn_order_precedences); a row whose lattice does not
+        fit the workspace is recomputed here with order_precedence - how many were is left in
+        `self.precedences_fallback_rows`.  backend="host": order_precedence row by row.  An invalid row raises
+        likeliest_order's ValueError, with its index."""
+        dat = np.asarray(dat)
+        if dat.ndim != 2 or dat.shape[1] != 2 * self.n + 3:
+            raise ValueError(f"dat must have shape [n_pat, {2 * self.n + 3}]")
+        if backend not in ("device", "host"):
+            raise ValueError("backend must be 'device' or 'host'")
+        P, L = dat.shape[0], 2 * self.n + 1
+        if backend == "host":
+            le, prec = np.zeros(P), np.zeros((P, L, L))
+            redo = range(P)
+        else:
+            from .jx import engine
+            le, prec, status = engine(self.n).order_precedences(self.log_theta, self.obs1, self.obs2, dat)
+            bad = np.flatnonzero((status & 0xFFFF) == 2)
+            if bad.size:
+                i = int(bad[0])
+                raise ValueError(f"row {i}: {_ROW_ERRORS[int(status[i]) >> 16]}")
+            redo = [int(i) for i in np.flatnonzero(status != 0)]
+        for i in redo:
+            r = self._row_precedence(dat, i)
+            le[i], prec[i] = r.log_evidence, r.prec
+        self.precedences_fallback_rows = 0 if backend == "host" else len(redo)
+        return OrderPrecedences(le, prec)
+
+    def _row_precedence(self, dat, i: int):
+        row = dat[i]
+        status = _ROW_STATUS.get(int(row[-1]), f"type {int(row[-1])}")
+        first = _ROW_FIRST.get(int(row[-2]), "Met") if status == "isPaired" else None
+        try:
+            return self.order_precedence(MetState.from_seq(row[:2 * self.n + 1]), status, first)
+        except ValueError as e:
+            raise ValueError(f"row {i}: {e}") from e
+
     def likelihood(self, order, met_status: str, first_obs: str = None) -> float:
         """model.py:295-376: probability of exactly this order of events being what is observed."""
         order = tuple(int(e) for e in order)
@@ -382,6 +459,45 @@ class MetMHN:
                 if x >> b & 1:
                     pre[T.ev[b]] += w
         return OrderPosterior(float(np.log(Z)), pre / Z, pos / Z)
+
+    def _precedence_matrix(self, codes, P, Z) -> np.ndarray:
+        """The slot matrix P (summed move masses) over the evidence, at the positions of the slots' event codes."""
+        prec = np.full((2 * self.n + 1, 2 * self.n + 1), np.nan)
+        if len(codes):
+            prec[np.ix_(codes, codes)] = np.minimum(P / Z, 1.0)     # the quotient of two roundings may pass 1
+        return prec
+
+    def _precedence_single(self, T, codes) -> "OrderPrecedence":
+        """_posterior_single's forward pass, the backward pass over the whole lattice (G[x] = B[x] / den[x]), and per
+        target slot d the masses F[x] num_d[y] G[y] of the moves x -> y = x | d, summed over the x that hold c."""
+        k, V = T.k, 1 << T.k
+        F = np.zeros(V)
+        F[0] = 1.0 / T.den[0]
+        for x in range(1, V):
+            s = 0.0
+            for b in range(k):
+                if x >> b & 1:
+                    s += F[x ^ 1 << b] * T.num[b][x]
+            F[x] = s / T.den[x]
+        Z = F[-1] * T.final
+        G = np.zeros(V)
+        G[-1] = T.final / T.den[-1]
+        for x in range(V - 2, -1, -1):
+            s = 0.0
+            for b in range(k):
+                if not x >> b & 1:
+                    y = x | 1 << b
+                    s += G[y] * T.num[b][y]
+            G[x] = s / T.den[x]
+        P = np.zeros((k, k))
+        idx = np.arange(V)
+        for d in range(k):
+            xs = idx[(idx >> d & 1) == 0]
+            w = F[xs] * T.num[d][xs | 1 << d] * G[xs | 1 << d]
+            for c in range(k):
+                if c != d:
+                    P[c, d] = w[(xs >> c & 1) == 1].sum()
+        return OrderPrecedence(float(np.log(Z)), self._precedence_matrix(codes, P, Z))
 
     def _likelihood_unpaired_mt(self, order) -> float:
         """model.py:1391-1426: a metastasis seen once (obs2), the chain feeling the seeding."""
@@ -504,10 +620,10 @@ class MetMHN:
             i += 1
         return self._total(T, v)
 
-    def _posterior_paired(self, state: MetState, first_obs: str) -> "OrderPosterior":
-        """_likeliest_order_paired's walk with the Pareto step replaced by the sum (_advance, _settle and _total are
-        linear in the prefix vector), then the transposed walk over the seeded half: B[x] is the weight the rest of the
-        order gives the (unsettled) vector at x, so the orders that seed at x have the mass B[x | top] . A(x, top) F[x]."""
+    def _paired_passes(self, state: MetState, first_obs: str):
+        """The two sum-product passes of a paired row: tables T, forward prefix vectors F (unsettled, every state the
+        chain can be in), evidence Z, backward weights B over the seeded half (B[x] is the weight the rest of the order
+        gives the unsettled vector at x)."""
         if not state.reachable:
             raise ValueError("This state is not reachable by mhn.")
         T = self._paired_tables(state, first_obs)
@@ -550,6 +666,15 @@ class MetMHN:
                     if T.mt_first and T.kind[b] == 0:
                         gm += g[2] * num / T.den_pt[y]
             B[x] = settle_t(x, ga, gp, gm)
+        return T, F, Z, B
+
+    def _posterior_paired(self, state: MetState, first_obs: str) -> "OrderPosterior":
+        """_likeliest_order_paired's walk with the Pareto step replaced by the sum (_advance, _settle and _total are
+        linear in the prefix vector), then the transposed walk over the seeded half: B[x] is the weight the rest of the
+        order gives the (unsettled) vector at x, so the orders that seed at x have the mass B[x | top] . A(x, top) F[x]."""
+        T, F, Z, B = self._paired_passes(state, first_obs)
+        n, k = self.n, T.k
+        top = 1 << (k - 1)
         pre, pos = np.zeros(n), np.zeros(n + 1)
         for x in F:
             if x & top:
@@ -561,6 +686,47 @@ class MetMHN:
                 if T.joint >> b & 1 and x >> b & 1:
                     pre[T.slots[b] // 2] += w
         return OrderPosterior(float(np.log(Z)), pre / Z, pos / Z)
+
+    def _precedence_paired(self, state: MetState, first_obs: str) -> "OrderPrecedence":
+        """_posterior_paired's passes, the backward pass continued over the unseeded states whose tumours agree (a scalar:
+        joint moves and the seeding edge), and the mass of EVERY move added to P[c, d] for the slots c its state holds and
+        the slot(s) d it adds - a joint move adds both of its slots, so neither precedes the other."""
+        T, F, Z, B = self._paired_passes(state, first_obs)
+        k = T.k
+        top = 1 << (k - 1)
+        bits = lambda x: [c for c in range(k) if x >> c & 1]
+        P = np.zeros((k, k))
+        Bu = {}
+        for x in sorted((x for x in F if not x & top), reverse=True):
+            y = x | top
+            s = 0.0
+            for b in range(k - 1):
+                if T.joint >> b & 1 and not x >> b & 1:
+                    s += T.num[b][x | 3 << b] / T.den[x | 3 << b] * Bu[x | 3 << b]
+            Bu[x] = s + T.num[k - 1][y] / T.den[y] * B[y][0]
+        for x in F:
+            held = bits(x)
+            if x & top:
+                for d in range(k - 1):
+                    if not x >> d & 1:
+                        y, v = self._advance(T, x, F[x], d)
+                        g = B[y]
+                        w = g[0] * v[0] + g[1] * v[1] + g[2] * v[2]
+                        for c in held:
+                            P[c, d] += w
+                continue
+            y = x | top
+            w = B[y][0] * (F[x][0] * T.num[k - 1][y] / T.den[y])
+            for c in held:
+                P[c, k - 1] += w
+            for b in range(k - 1):
+                if T.joint >> b & 1 and not x >> b & 1:
+                    y = x | 3 << b
+                    w = F[x][0] * T.num[b][y] / T.den[y] * Bu[y]
+                    for c in held:
+                        P[c, b] += w
+                        P[c, b + 1] += w
+        return OrderPrecedence(float(np.log(Z)), self._precedence_matrix(T.slots, P, Z))
 
     def _likeliest_order_paired(self, state: MetState, first_obs: str):
         """model.py:503-1389 (_likeliest_order_pt_mt / _mt_pt / _unknown / _sync)."""
