@@ -5,9 +5,11 @@
 // two bit sets (events 0..N-2 mutations, N-1 seeding, N diagnosis) and the event rates are recomputed from the
 // log-parameters in LDS every step exactly as the reference does (exp of a sum of logs, `tumor_dynamics`
 // :28-44); the next event is drawn by inverting the cumulative rates with one uniform per step.
-// Random numbers: Philox4x32-10 keyed by the caller's seed, counter = (trajectory, step): reproducible for a
-// given (seed, n_sim), independent of the launch geometry.  The stream differs from jax.random's threefry, the
-// distribution does not (tests/test_montecarlo.py).
+// Random numbers: Philox4x32-10, key = (seed low word, seed high word), counter = (trajectory low word, trajectory
+// high word, step, 0); the step's uniform is the top 27 bits of output word 0 and the top 26 of word 1 as a 53-bit
+// fraction.  A trajectory depends on (seed, its index) only, not on n_sim or the launch geometry.  The stream differs
+// from jax.random's threefry, the distribution does not (tests/test_montecarlo.py); tests/test_sampler_replay.py
+// replays this stream and gillespie_step in NumPy (oracle/sampler_replay.py) and compares every trajectory exactly.
 // k_gillespie writes every trajectory (mmhn_simulate); k_gillespie_summary draws the same ones through the same step
 // function and only counts them (mmhn_simulate_summary, the layout is above the kernel).
 #pragma once

@@ -1,6 +1,7 @@
 """The property the reference pins in tests/test_likelihood.py:10-132: the analytic probability of a datapoint
 equals its frequency among Gillespie-simulated patients (there: 1e5 jax.random samples, 2 significant digits;
-here: own NumPy sampler oracle/gillespie.py following simulations.py, 4e5 samples, 4.5 binomial sigmas)."""
+here: own NumPy sampler oracle/gillespie.py following simulations.py, 4e5 samples, 4.5 binomial sigmas).
+The device sampler's exact, trajectory-by-trajectory check is tests/test_sampler_replay.py."""
 import numpy as np
 import pytest
 

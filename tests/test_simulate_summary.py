@@ -3,7 +3,8 @@
 Its counts are pinned to the materialised sampler: with the same key it must describe exactly the samples
 simulate_dat / simulate_orders return, counted on the host with the reference's reductions (extract_bse /
 preseeding_probs / marg_frequs, themselves pinned to the reference by tests/test_preseeding.py).  Then chunking,
-ranges, invariants, and a two-sample check against the NumPy sampler oracle/gillespie.py."""
+ranges, invariants, and a two-sample check against the NumPy sampler oracle/gillespie.py.
+The exact check of both kernels against an independent replay of the stream is tests/test_sampler_replay.py."""
 import numpy as np
 import pandas as pd
 import pytest
