@@ -260,6 +260,30 @@ int mmhn_order_precedences(mmhn_handle h, const double* log_theta, const double*
                            const int8_t* dat, int64_t n_pat, int n_cols, double* log_evidence, double* prec,
                            int32_t* status);
 
+/* ---- posterior event positions of a cohort --------------------------------------------------
+ * mmhn_order_positions: for every row of a reference-format `dat` (read as mmhn_likeliest_orders reads it), over the same
+ * admissible orders as mmhn_order_posteriors: at which position of its lineage every event happened.  An order has two
+ * lineages: the metastasis' (the order without its even codes other than the seeding: the events before the seeding, the
+ * seeding, the metastasis' own events) and the primary tumour's (the order without its odd codes).  No reference
+ * counterpart (the reference reads positions off the likeliest order).  fp64 engines only.
+ *   log_evidence [n_pat]                        as mmhn_order_posteriors
+ *   pos_pt [n_pat][n_mut + 1][n_mut + 1]        pos_pt[e][j] = P(event e - n_mut: the seeding - is the j-th (0-based) entry
+ *                                               of the primary tumour's lineage | the row)
+ *   pos_mt [n_pat][n_mut + 1][n_mut + 1]        the same for the metastasis' lineage
+ *                                               A row of type 2 has the metastasis' lineage only, rows of type 0 and 1 the
+ *                                               primary tumour's (type 0 without the seeding).  NaN for an event the row
+ *                                               does not carry in that lineage and throughout a lineage the row does not
+ *                                               have; for a carried event 0 at the positions past the lineage's length.
+ *                                               The seeding's row equals seed_pos of mmhn_order_posteriors.
+ *   status [n_pat]: as mmhn_order_precedences, with the same workspace per row or less (the same rows fit); every output
+ *   of a row is NaN where its status != 0.
+ * No atomics: two calls return the same bits, whatever the batching.  Rows are cut into batches that fit
+ * mmhn_set_workspace_limit (allocated once per call); the call leaves a loaded cohort as it was.
+ */
+int mmhn_order_positions(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2,
+                         const int8_t* dat, int64_t n_pat, int n_cols, double* log_evidence, double* pos_pt,
+                         double* pos_mt, int32_t* status);
+
 /* ---- measurement -------------------------------------------------------------------
  * mmhn_bench_kronvec: `batch` resident copies of a 2^k vector, `iters` back-to-back
  * launches of mmhn_kronvec_batched's launch (diag = 0: y = Q_off p into a NaN-filled y, every tile of every vector,
@@ -290,7 +314,7 @@ typedef struct {
   int32_t comm_rank;  /* this engine's rank in it (ncclCommUserRank), -1: none */
 } mmhn_counters;
 /* ABI version of this header: bumped whenever an exported signature or structure changes (4: mmhn_bench_kronvec has its
- * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences was added within version 8, a purely additive change).  A client built against another header must refuse to run:
+ * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences and mmhn_order_positions were added within version 8, purely additive changes).  A client built against another header must refuse to run:
  * mmhn_abi_version() != MMHN_ABI_VERSION (metmhn_amd/_lib.py checks it on load). */
 #define MMHN_ABI_VERSION 8
 int mmhn_abi_version(void);

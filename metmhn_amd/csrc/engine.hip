@@ -1016,6 +1016,7 @@ struct Engine : EngineBase {
 #include "orders_host.h"
 #include "orderpost_host.h"
 #include "orderprec_host.h"
+#include "orderpos_host.h"
 #include "sampler_host.h"
 #include "bench.h"
 
@@ -1494,6 +1495,20 @@ int mmhn_order_precedences(mmhn_handle h, const double* log_theta, const double*
   REQUIRE(h->dtype == MMHN_F64, "order precedences need an fp64 engine (MMHN_F64)");
   order_precedences(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, log_evidence, prec,
                     status);
+  API_END
+}
+
+// ---- posterior event positions of a cohort: where in its lineage every event happened, over the same orders
+int mmhn_order_positions(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, const int8_t* dat,
+                         int64_t n_pat, int n_cols, double* log_evidence, double* pos_pt, double* pos_mt, int32_t* status) {
+  API_BEGIN
+  GUARD(h);
+  REQUIRE(log_theta && obs1 && obs2 && log_evidence && pos_pt && pos_mt && status, "null pointer");
+  REQUIRE(dat || n_pat == 0, "null dat");
+  REQUIRE(n_pat >= 0 && n_pat < ((int64_t)1 << 31), "n_pat out of range");
+  REQUIRE(h->dtype == MMHN_F64, "order positions need an fp64 engine (MMHN_F64)");
+  order_positions(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, log_evidence, pos_pt,
+                  pos_mt, status);
   API_END
 }
 

@@ -147,122 +147,176 @@ __device__ __forceinline__ void opr_bit_sums(int nt, int m, int c0, double* part
   __syncthreads();
 }
 
-// rows[blockIdx.x]; lt [N][N], obs1 / obs2 [N]; diagJ already in tab[toff ..] of the paired rows (k_diag, KD_DQ).
-// Row fields: toff tables (opost_doubles), coff chunk partials, foff the row's k x k block of out_prec.  out_le [row]
+// ---- what k_order_prec and k_order_pos (orderpos.h) share: the row in LDS, the tables, the forward pass, the backward
+// pass over every state the chain can be in, the masses of the moves
+
+// LDS of a row
+struct OprRow {
+  double lt[ORD_MAXN * ORD_MAXN];
+  double o1w[ORD_MAXN], o2w[ORD_MAXN];
+  ORow r;
+  OpoLevels L;
+  double bu[1 << OPO_CB];                      // paired: B of the unseeded state of the joint events e
+  int8_t jslot[32];                            // paired: slot of the i-th joint event
+  int8_t jev[32];                              // paired: joint event of a slot, -1 none
+  double zsh;
+};
+
+// a value every lane of the wave holds, moved to scalar registers (the offsets of a row come from LDS, in vector ones)
+__device__ __forceinline__ long long opr_uniform(long long v) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// the parameters and rows[blockIdx.x] into LDS (every thread of the workgroup; ends with a barrier)
 template <int KB>
-__global__ __launch_bounds__(KB) void k_order_prec(const ORow* __restrict__ rows, const double* __restrict__ g_lt,
-                                                   const double* __restrict__ g_o1, const double* __restrict__ g_o2, int N,
-                                                   double* tab, double* out_le, double* out_prec) {
-  __shared__ double lt[ORD_MAXN * ORD_MAXN];
-  __shared__ double o1w[ORD_MAXN], o2w[ORD_MAXN];
-  __shared__ ORow r;
-  __shared__ OpoLevels L;
-  __shared__ double Rs[32][32];                // Rs[d][c]: summed masses of the moves that add d from a state holding c
-  __shared__ double Rj[OPO_CB + 1][OPO_CB + 1]; // paired, before the seeding: Rj[t][q] target joint event t (kj: the
-                                               // seeding), held joint event q
-  __shared__ double bu[1 << OPO_CB];           // paired: B of the unseeded state of the joint events e
-  __shared__ double pj[(OPO_CB + 1) * (OPO_CB + 1)];   // chunk partials of the sums before the seeding (one chunk each)
-  __shared__ int8_t jslot[32];                 // paired: slot of the i-th joint event
-  __shared__ int8_t jev[32];                   // paired: joint event of a slot, -1 none
-  __shared__ double zsh;
+__device__ __forceinline__ void opr_load(OprRow& S, const ORow* __restrict__ rows, const double* __restrict__ g_lt,
+                                         const double* __restrict__ g_o1, const double* __restrict__ g_o2, int N) {
   const int tid = threadIdx.x;
-  for (int i = tid; i < N * N; i += KB) lt[i] = g_lt[i];
-  for (int i = tid; i < N; i += KB) { o1w[i] = g_o1[i]; o2w[i] = g_o2[i]; }
-  if (tid == 0) r = rows[blockIdx.x];
+  for (int i = tid; i < N * N; i += KB) S.lt[i] = g_lt[i];
+  for (int i = tid; i < N; i += KB) { S.o1w[i] = g_o1[i]; S.o2w[i] = g_o2[i]; }
+  if (tid == 0) S.r = rows[blockIdx.x];
   __syncthreads();
-  const int n = N - 1, k = r.k;
+}
+
+// One tumour (_single_tables, every slot alike): den, the forward pass into F and - unless the row is empty - the
+// backward pass over the whole lattice, G[x] = B[x] / den[x] in den's place.  Returns Z; ends with a barrier.
+template <int KB>
+__device__ __forceinline__ double opr_single_passes(OprRow& S, int N, double* den, double* F) {
+  const ORow& r = S.r;
+  const double* lt = S.lt;
+  const int tid = threadIdx.x, k = r.k;
   const uint32_t V = 1u << k, full = V - 1u;
-  double* den = tab + r.toff;
-  double* part = tab + r.coff;
-  double* P = out_prec + r.foff;
-
-  if (r.mode != ORD_PAIRED) {
-    // ---------------------------------------------------------------- one tumour: _single_tables, every slot alike
-    const bool pt = r.mode == ORD_PT;
-    const double* after = pt ? o1w : o2w;
-    double* F = den + V;
-    const bool sd = r.seeded_top && k > 0;
-    opo_levels_init<KB>(L, opo_chunk_bits<KB>(k));
-    const int c = L.c;
-    for (uint32_t x = tid; x < V; x += KB) {
-      const bool sx = r.seeded_top && ((x >> (k - 1)) & 1u);
-      const double ob = exp(sx ? ord_obs_sum(after, r, x) : ord_obs_sum(o1w, r, x));
-      den[x] = ob - ord_single_diag(lt, N, r, full, x, N, pt);
-    }
-    __syncthreads();
-    if (tid == 0) F[0] = 1.0 / den[0];
-    __syncthreads();
-    for (int lev = 1; lev <= k; ++lev) {
-      opo_level<KB>(L, 0u, V >> c, lev, [&](uint32_t x) {
-        double s = 0.0;
-        for (uint32_t m = x; m; m &= m - 1) {
-          const int b = __builtin_ctz(m);
-          s += F[x ^ (1u << b)] * ord_num(lt, N, r, r.ev[b], x, pt);
-        }
-        F[x] = s / den[x];
-      });
-      __syncthreads();
-    }
-    const double fin = exp(sd ? ord_obs_sum(after, r, full) : ord_obs_sum(o1w, r, full));
-    const double Z = F[full] * fin;
-    if (tid == 0) out_le[r.row] = log(Z);
-    if (k == 0) return;
-    // backward over the whole lattice, G[x] = B[x] / den[x] in den's place (den[x] is read for the last time by the
-    // thread that writes G[x])
-    double* G = den;
-    if (tid == 0) G[full] = fin / den[full];
-    __syncthreads();
-    for (int lev = k - 1; lev >= 0; --lev) {
-      opo_level<KB>(L, 0u, V >> c, lev, [&](uint32_t x) {
-        double s = 0.0;
-        for (uint32_t m = full & ~x; m; m &= m - 1) {
-          const int b = __builtin_ctz(m);
-          const uint32_t y = x | (1u << b);
-          s += G[y] * ord_num(lt, N, r, r.ev[b], y, pt);
-        }
-        G[x] = s / den[x];
-      });
-      __syncthreads();
-    }
-    const int m = k - 1;
-    opr_bit_sums<KB>(k, m, oprec_chunk_bits(m, KB), part,
-        [&](int d, uint32_t idx) {
-          const uint32_t x = opr_ins0(idx, d), y = x | (1u << d);
-          return F[x] * ord_num(lt, N, r, r.ev[d], y, pt) * G[y];
-        },
-        [&](int d, int j, double s) { if (j < m) Rs[d][j < d ? j : j + 1] = s; });
-    for (int i = tid; i < k * k; i += KB) {
-      const int cc = i / k, d = i - cc * k;
-      P[i] = cc == d ? 0.0 : fmin(Rs[d][cc] / Z, 1.0);     // a probability: the quotient of two roundings may pass 1
-    }
-    return;
+  const bool pt = r.mode == ORD_PT;
+  const double* after = pt ? S.o1w : S.o2w;
+  const bool sd = r.seeded_top && k > 0;
+  opo_levels_init<KB>(S.L, opo_chunk_bits<KB>(k));
+  const int c = S.L.c;
+  for (uint32_t x = tid; x < V; x += KB) {
+    const bool sx = r.seeded_top && ((x >> (k - 1)) & 1u);
+    const double ob = exp(sx ? ord_obs_sum(after, r, x) : ord_obs_sum(S.o1w, r, x));
+    den[x] = ob - ord_single_diag(lt, N, r, full, x, N, pt);
   }
+  __syncthreads();
+  if (tid == 0) F[0] = 1.0 / den[0];
+  __syncthreads();
+  for (int lev = 1; lev <= k; ++lev) {
+    opo_level<KB>(S.L, 0u, V >> c, lev, [&](uint32_t x) {
+      double s = 0.0;
+      for (uint32_t m = x; m; m &= m - 1) {
+        const int b = __builtin_ctz(m);
+        s += F[x ^ (1u << b)] * ord_num(lt, N, r, r.ev[b], x, pt);
+      }
+      F[x] = s / den[x];
+    });
+    __syncthreads();
+  }
+  const double fin = exp(sd ? ord_obs_sum(after, r, full) : ord_obs_sum(S.o1w, r, full));
+  const double Z = F[full] * fin;
+  if (k == 0) return Z;
+  // (den[x] is read for the last time by the thread that writes G[x])
+  double* G = den;
+  if (tid == 0) G[full] = fin / den[full];
+  __syncthreads();
+  for (int lev = k - 1; lev >= 0; --lev) {
+    opo_level<KB>(S.L, 0u, V >> c, lev, [&](uint32_t x) {
+      double s = 0.0;
+      for (uint32_t m = full & ~x; m; m &= m - 1) {
+        const int b = __builtin_ctz(m);
+        const uint32_t y = x | (1u << b);
+        s += G[y] * ord_num(lt, N, r, r.ev[b], y, pt);
+      }
+      G[x] = s / den[x];
+    });
+    __syncthreads();
+  }
+  return Z;
+}
 
-  // ---------------------------------------------------------------- both tumours: _paired_tables (as k_order_post)
-  double* o1 = den + V;
-  double* o2 = o1 + V;
-  double* dmt = o2 + V;
-  double* dpt = dmt + V;
-  double* F = dpt + V;
-  double* B = F + 3ll * V;                      // B[3 (x ^ top)] of the seeded x
-  const uint32_t top = 1u << (k - 1);
-  const uint32_t in_mt = r.mt_mask | top;
+// mass of the one-tumour move that adds slot d from the state of the other slots idx
+__device__ __forceinline__ double opr_single_mass(const OprRow& S, int N, const double* G, const double* F, int d, uint32_t idx) {
+  const uint32_t x = opr_ins0(idx, d), y = x | (1u << d);
+  return F[x] * ord_num(S.lt, N, S.r, S.r.ev[d], y, S.r.mode == ORD_PT) * G[y];
+}
+
+// the tables of a paired row in its workspace (_paired_tables, as k_order_post lays them out)
+struct OprPaired {
+  double *den, *o1, *o2, *dmt, *dpt, *F, *B;    // B[3 (x ^ top)] of the seeded x
+  uint32_t top, in_mt;
+  int kj;                                       // joint events
+};
+
+__device__ __forceinline__ OprPaired opr_paired_tables(const ORow& r, double* den) {
+  const long long V = 1ll << r.k;
+  OprPaired P;
+  P.den = den; P.o1 = den + V; P.o2 = P.o1 + V; P.dmt = P.o2 + V; P.dpt = P.dmt + V; P.F = P.dpt + V; P.B = P.F + 3 * V;
+  P.top = 1u << (r.k - 1);
+  P.in_mt = r.mt_mask | P.top;
+  P.kj = __builtin_popcount(r.joint);
+  return P;
+}
+
+// state of the compact index e over the joint events: both slots of every event in e
+__device__ __forceinline__ uint32_t opr_joint_state(const OprRow& S, uint32_t e) {
+  uint32_t x = 0;
+  for (uint32_t m = e; m; m &= m - 1) x |= 3u << S.jslot[__builtin_ctz(m)];
+  return x;
+}
+
+// the seeding edge of the unseeded state x: the factor that takes F[x]_a to its mass
+__device__ __forceinline__ double opr_seed_edge(const OprRow& S, int N, const OprPaired& P, uint32_t x) {
+  const uint32_t y = x | P.top;
+  return ord_num(S.lt, N, S.r, S.r.ev[S.r.k - 1], y & P.in_mt, false) / P.den[y] * P.B[3ll * x];
+}
+
+// the same for the joint move of event q from the unseeded state of the joint events e
+__device__ __forceinline__ double opr_joint_edge(const OprRow& S, int N, const OprPaired& P, uint32_t e, int q) {
+  const uint32_t y = opr_joint_state(S, e | (1u << q));
+  return ord_num(S.lt, N, S.r, S.r.ev[S.jslot[q]], y & S.r.pt_mask, false) / P.den[y] * S.bu[e | (1u << q)];
+}
+
+// mass of the move that adds slot d < k - 1 from the seeded state of the other slots idx (k - 2 bits)
+__device__ __forceinline__ double opr_seeded_mass(const OprRow& S, int N, const OprPaired& P, int d, uint32_t idx) {
+  const ORow& r = S.r;
+  const OrdTab t{P.o1, P.o2, P.dmt, P.dpt};
+  const uint32_t x = opr_ins0(idx, d) | P.top, y = x | (1u << d);
+  const bool pt_ev = r.kind[d] == ORD_K_PT;
+  const double num = ord_num(S.lt, N, r, r.ev[d], y & (pt_ev ? r.pt_mask : P.in_mt), false);
+  double fa = P.F[3ll * x], fp = P.F[3ll * x + 1], fm = P.F[3ll * x + 2];
+  ord_settle(r, t, x, fa, fp, fm);                                     // _advance
+  const double* by = P.B + 3ll * (y ^ P.top);
+  double w = by[0] * (fa * num / P.den[y]);
+  if (r.pt_first && !pt_ev) w += by[1] * (fp * num / P.dmt[y]);
+  if (r.mt_first && pt_ev) w += by[2] * (fm * num / P.dpt[y]);
+  return w;
+}
+
+// Both tumours (as k_order_post): the tables, the forward pass, the backward pass over the seeded half and the scalar B
+// of the unseeded states whose tumours agree (S.bu).  diagJ is in den already.  Returns Z; ends with a barrier.
+template <int KB>
+__device__ __forceinline__ double opr_paired_passes(OprRow& S, int N, const OprPaired& P) {
+  const ORow& r = S.r;
+  const double* lt = S.lt;
+  const int tid = threadIdx.x, n = N - 1, k = r.k;
+  const uint32_t V = 1u << k, full = V - 1u;
+  double *den = P.den, *o1 = P.o1, *o2 = P.o2, *dmt = P.dmt, *dpt = P.dpt, *F = P.F, *B = P.B;
+  const uint32_t top = P.top, in_mt = P.in_mt;
   const int c = opo_chunk_bits<KB>(k - 1);
-  opo_levels_init<KB>(L, c);
+  opo_levels_init<KB>(S.L, c);
   if (tid == 0) {
     int kj = 0;
-    for (int b = 0; b < 32; ++b) jev[b] = -1;
+    for (int b = 0; b < 32; ++b) S.jev[b] = -1;
     for (uint32_t m = r.joint; m; m &= m - 1) {
       const int b = __builtin_ctz(m);
-      jslot[kj] = (int8_t)b; jev[b] = jev[b + 1] = (int8_t)kj; ++kj;
+      S.jslot[kj] = (int8_t)b; S.jev[b] = S.jev[b + 1] = (int8_t)kj; ++kj;
     }
   }
   for (uint32_t x = tid; x < V; x += KB) {
     double s1 = 0.0, s2 = 0.0;
     for (uint32_t m = x; m; m &= m - 1) {
       const int j = __builtin_ctz(m);
-      if (r.kind[j] != ORD_K_MT) s1 += o1w[r.ev[j]];
-      if (r.kind[j] != ORD_K_PT) s2 += o2w[r.ev[j]];
+      if (r.kind[j] != ORD_K_MT) s1 += S.o1w[r.ev[j]];
+      if (r.kind[j] != ORD_K_PT) s2 += S.o2w[r.ev[j]];
     }
     const double e1 = exp(s1), e2 = exp(s2);
     o1[x] = e1; o2[x] = e2;
@@ -271,14 +325,8 @@ __global__ __launch_bounds__(KB) void k_order_prec(const ORow* __restrict__ rows
     if (r.mt_first) dpt[x] = e1 - ord_single_diag(lt, N, r, r.pt_mask, x, n, false);
   }
   const OrdTab t{o1, o2, dmt, dpt};
-  const int kj = __builtin_popcount(r.joint);
+  const int kj = P.kj;
   const uint32_t EJ = 1u << kj;
-  // state of the compact index e over the joint events: both slots of every event in e
-  auto joint_state = [&](uint32_t e) {
-    uint32_t x = 0;
-    for (uint32_t m = e; m; m &= m - 1) x |= 3u << jslot[__builtin_ctz(m)];
-    return x;
-  };
   __syncthreads();
   if (tid == 0) { F[0] = 1.0 / den[0]; F[1] = 0.0; F[2] = 0.0; }
   __syncthreads();
@@ -286,10 +334,10 @@ __global__ __launch_bounds__(KB) void k_order_prec(const ORow* __restrict__ rows
   for (int lev = 1; lev <= kj; ++lev) {
     for (uint32_t e = tid; e < EJ; e += KB) {
       if (__builtin_popcount(e) != lev) continue;
-      const uint32_t y = joint_state(e);
+      const uint32_t y = opr_joint_state(S, e);
       double a = 0.0;
       for (uint32_t m = e; m; m &= m - 1) {
-        const int b = jslot[__builtin_ctz(m)];
+        const int b = S.jslot[__builtin_ctz(m)];
         a += F[3ll * (y ^ (3u << b))] * ord_num(lt, N, r, r.ev[b], y & r.pt_mask, false) / den[y];
       }
       F[3ll * y] = a; F[3ll * y + 1] = 0.0; F[3ll * y + 2] = 0.0;
@@ -298,7 +346,7 @@ __global__ __launch_bounds__(KB) void k_order_prec(const ORow* __restrict__ rows
   }
   // seeded half, level by level: every move
   for (int lev = 1; lev <= k; ++lev) {
-    opo_level<KB>(L, top >> c, V >> c, lev, [&](uint32_t y) {
+    opo_level<KB>(S.L, top >> c, V >> c, lev, [&](uint32_t y) {
       double a = 0.0, bp = 0.0, bm = 0.0;
       for (uint32_t m = y; m; m &= m - 1) {
         const int b = __builtin_ctz(m);
@@ -329,16 +377,15 @@ __global__ __launch_bounds__(KB) void k_order_prec(const ORow* __restrict__ rows
   if (tid == 0) {
     double a = F[3ll * full], bp = F[3ll * full + 1], bm = F[3ll * full + 2];
     ord_settle(r, t, full, a, bp, bm);
-    zsh = bp * o2[full] + bm * o1[full];                                   // _total
+    S.zsh = bp * o2[full] + bm * o1[full];                                 // _total
     double ga = 0.0;
     settle_t(full, ga, o2[full], o1[full]);
     double* bf = B + 3ll * (full ^ top);
     bf[0] = ga; bf[1] = o2[full]; bf[2] = o1[full];
   }
   __syncthreads();
-  const double Z = zsh;
   for (int lev = k - 1; lev >= 1; --lev) {
-    opo_level<KB>(L, top >> c, V >> c, lev, [&](uint32_t x) {
+    opo_level<KB>(S.L, top >> c, V >> c, lev, [&](uint32_t x) {
       double ga = 0.0, gp = 0.0, gm = 0.0;
       for (uint32_t m = full & ~x; m; m &= m - 1) {
         const int b = __builtin_ctz(m);
@@ -356,54 +403,74 @@ __global__ __launch_bounds__(KB) void k_order_prec(const ORow* __restrict__ rows
     });
     __syncthreads();
   }
-  // the seeding edge of the unseeded state x: the factor that takes F[x]_a to its mass
-  auto seed_edge = [&](uint32_t x) {
-    const uint32_t y = x | top;
-    return ord_num(lt, N, r, r.ev[k - 1], y & in_mt, false) / den[y] * B[3ll * x];
-  };
-  // the same for the joint move of event q from the unseeded state of the joint events e
-  auto joint_edge = [&](uint32_t e, int q) {
-    const uint32_t y = joint_state(e | (1u << q));
-    return ord_num(lt, N, r, r.ev[jslot[q]], y & r.pt_mask, false) / den[y] * bu[e | (1u << q)];
-  };
   // backward over the unseeded states whose tumours agree: joint moves in ascending event, then the seeding edge
   for (int lev = kj; lev >= 0; --lev) {
     for (uint32_t e = tid; e < EJ; e += KB) {
       if (__builtin_popcount(e) != lev) continue;
       double s = 0.0;
-      for (uint32_t m = (EJ - 1u) & ~e; m; m &= m - 1) s += joint_edge(e, __builtin_ctz(m));
-      bu[e] = s + seed_edge(joint_state(e));
+      for (uint32_t m = (EJ - 1u) & ~e; m; m &= m - 1) s += opr_joint_edge(S, N, P, e, __builtin_ctz(m));
+      S.bu[e] = s + opr_seed_edge(S, N, P, opr_joint_state(S, e));
     }
     __syncthreads();
   }
+  return S.zsh;
+}
+
+// rows[blockIdx.x]; lt [N][N], obs1 / obs2 [N]; diagJ already in tab[toff ..] of the paired rows (k_diag, KD_DQ).
+// Row fields: toff tables (opost_doubles), coff chunk partials, foff the row's k x k block of out_prec.  out_le [row]
+template <int KB>
+__global__ __launch_bounds__(KB) void k_order_prec(const ORow* __restrict__ rows, const double* __restrict__ g_lt,
+                                                   const double* __restrict__ g_o1, const double* __restrict__ g_o2, int N,
+                                                   double* tab, double* out_le, double* out_prec) {
+  __shared__ OprRow S;
+  __shared__ double Rs[32][32];                // Rs[d][c]: summed masses of the moves that add d from a state holding c
+  __shared__ double Rj[OPO_CB + 1][OPO_CB + 1]; // paired, before the seeding: Rj[t][q] target joint event t (kj: the
+                                               // seeding), held joint event q
+  __shared__ double pj[(OPO_CB + 1) * (OPO_CB + 1)];   // chunk partials of the sums before the seeding (one chunk each)
+  const int tid = threadIdx.x;
+  opr_load<KB>(S, rows, g_lt, g_o1, g_o2, N);
+  const ORow& r = S.r;
+  const int k = r.k;
+  double* den = tab + opr_uniform(r.toff);
+  double* part = tab + opr_uniform(r.coff);
+  double* P = out_prec + opr_uniform(r.foff);
+
+  if (r.mode != ORD_PAIRED) {
+    double* F = den + (1ll << k);
+    const double Z = opr_single_passes<KB>(S, N, den, F);
+    if (tid == 0) out_le[r.row] = log(Z);
+    if (k == 0) return;
+    const int m = k - 1;
+    opr_bit_sums<KB>(k, m, oprec_chunk_bits(m, KB), part,
+        [&](int d, uint32_t idx) { return opr_single_mass(S, N, den, F, d, idx); },
+        [&](int d, int j, double s) { if (j < m) Rs[d][j < d ? j : j + 1] = s; });
+    for (int i = tid; i < k * k; i += KB) {
+      const int cc = i / k, d = i - cc * k;
+      P[i] = cc == d ? 0.0 : fmin(Rs[d][cc] / Z, 1.0);     // a probability: the quotient of two roundings may pass 1
+    }
+    return;
+  }
+
+  const OprPaired T = opr_paired_tables(r, den);
+  const double Z = opr_paired_passes<KB>(S, N, T);
+  const int kj = T.kj;
   if (tid == 0) out_le[r.row] = log(Z);
   // after the seeding: target slot d < k - 1, the moves from the seeded x without d
   const int m = k >= 2 ? k - 2 : 0;
   opr_bit_sums<KB>(k - 1, m, oprec_chunk_bits(m, KB), part,
-      [&](int d, uint32_t idx) {
-        const uint32_t x = opr_ins0(idx, d) | top, y = x | (1u << d);
-        const bool pt_ev = r.kind[d] == ORD_K_PT;
-        const double num = ord_num(lt, N, r, r.ev[d], y & (pt_ev ? r.pt_mask : in_mt), false);
-        double fa = F[3ll * x], fp = F[3ll * x + 1], fm = F[3ll * x + 2];
-        ord_settle(r, t, x, fa, fp, fm);                                     // _advance
-        const double* by = B + 3ll * (y ^ top);
-        double w = by[0] * (fa * num / den[y]);
-        if (r.pt_first && !pt_ev) w += by[1] * (fp * num / dmt[y]);
-        if (r.mt_first && pt_ev) w += by[2] * (fm * num / dpt[y]);
-        return w;
-      },
+      [&](int d, uint32_t idx) { return opr_seeded_mass(S, N, T, d, idx); },
       [&](int d, int j, double s) { Rs[d][j < m ? (j < d ? j : j + 1) : k - 1] = s; });   // every seeded x holds the seeding
   // before the seeding: the joint move of event q from the states without it, then the seeding from every such state
   opr_bit_sums<KB>(kj, kj > 0 ? kj - 1 : 0, kj > 0 ? kj - 1 : 0, pj,
       [&](int q, uint32_t idx) {
         const uint32_t e = opr_ins0(idx, q);
-        return F[3ll * joint_state(e)] * joint_edge(e, q);
+        return T.F[3ll * opr_joint_state(S, e)] * opr_joint_edge(S, N, T, e, q);
       },
       [&](int q, int j, double s) { if (j < kj - 1) Rj[q][j < q ? j : j + 1] = s; });
   opr_bit_sums<KB>(1, kj, kj, pj,
       [&](int, uint32_t e) {
-        const uint32_t x = joint_state(e);
-        return F[3ll * x] * seed_edge(x);
+        const uint32_t x = opr_joint_state(S, e);
+        return T.F[3ll * x] * opr_seed_edge(S, N, T, x);
       },
       [&](int, int j, double s) { if (j < kj) Rj[kj][j] = s; });
   for (int i = tid; i < k * k; i += KB) {
@@ -411,7 +478,7 @@ __global__ __launch_bounds__(KB) void k_order_prec(const ORow* __restrict__ rows
     double s = 0.0;
     if (cc != d) {
       if (d < k - 1) s = Rs[d][cc];
-      const int q = jev[cc], td = d == k - 1 ? kj : jev[d];
+      const int q = S.jev[cc], td = d == k - 1 ? kj : S.jev[d];
       if (q >= 0 && td >= 0 && td != q) s += Rj[td][q];
     }
     P[i] = fmin(s / Z, 1.0);

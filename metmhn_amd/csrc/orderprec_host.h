@@ -19,20 +19,21 @@ static long long oprec_bytes(const ORow& r) {
   return oprec_doubles(r, r.k >= ORD_BIG_K ? 1024 : 256) * (long long)sizeof(double);
 }
 
+// k_order_prec / k_order_pos (orderpos.h): both write log_ev and a compact k x k block per row
+using OprKernel = void (*)(const ORow*, const double*, const double*, const double*, int, double*, double*, double*);
+
 // Rows are decoded and checked (status MMHN_ORD_INVALID with the reason in the high half), then cut into batches whose
 // lattices fit the workspace limit; a row that does not fit on its own is MMHN_ORD_TOO_LARGE.  The workspace is
-// allocated once, for the largest batch.  One workgroup per row, so a row's result does not depend on the batch it lands
-// in.  prec [npat][2n+1][2n+1] over the event codes: NaN where a code is not in the row.
-template <typename T>
-void order_precedences(Engine<T>& E, const double* lt, const double* obs1, const double* obs2, const int8_t* dat, long long npat,
-                       int ncols, double* log_ev, double* prec, int32_t* status) {
+// allocated once, for the largest batch.  One workgroup per row (k256 below ORD_BIG_K slots, k1024 from there on), so a
+// row's result does not depend on the batch it lands in.  scatter(row, cohort row, block) takes a finished row's k x k
+// block to the caller's arrays, which the caller has filled with NaN.
+template <typename T, class Scatter>
+void opr_rows(Engine<T>& E, const double* lt, const double* obs1, const double* obs2, const int8_t* dat, long long npat,
+              int ncols, double* log_ev, int32_t* status, OprKernel k256, OprKernel k1024, Scatter scatter) {
   REQUIRE(ncols == 2 * E.n + 3, "dat must have 2 n_mut + 3 columns (states, diagnosis order, type)");
   REQUIRE(E.N <= ORD_MAXN, "too many events for the order kernels (n_mut <= 31)");
   const int n = E.n, N = E.N;
-  const long long L = 2 * n + 1;
-  const double nan = std::nan("");
-  std::fill(log_ev, log_ev + npat, nan);
-  std::fill(prec, prec + npat * L * L, nan);
+  std::fill(log_ev, log_ev + npat, std::nan(""));
   const long long limit = (long long)E.cfg.plan.ws_limit;
   std::vector<ORow> todo;
   for (long long i = 0; i < npat; ++i) {
@@ -40,7 +41,7 @@ void order_precedences(Engine<T>& E, const double* lt, const double* obs1, const
     const int why = ord_decode(dat + i * ncols, ncols, n, r);
     if (why) { status[i] = MMHN_ORD_INVALID | (why << 16); continue; }
     r.row = (int)i;
-    // (more than OPO_CB joint events, 23 slots or more: the unseeded states would not fit k_order_prec's LDS)
+    // (more than OPO_CB joint events, 23 slots or more: the unseeded states would not fit the kernels' LDS)
     if (r.k > MAXK || __builtin_popcount(r.joint) > OPO_CB || oprec_bytes(r) > limit) { status[i] = MMHN_ORD_TOO_LARGE; continue; }
     status[i] = MMHN_ORD_OK;
     todo.push_back(r);
@@ -56,7 +57,7 @@ void order_precedences(Engine<T>& E, const double* lt, const double* obs1, const
     most = std::max(most, used);
   }
   cut.push_back(todo.size());
-  // the parameters: exp(log_theta) for k_diag (PS_THETA), the log-parameters themselves for k_order_prec
+  // the parameters: exp(log_theta) for k_diag (PS_THETA), the log-parameters themselves for the order kernel
   E.build_params(lt, nullptr, nullptr);
   DevArr<double> par, tab, d_le, d_prec;
   DevArr<ORow> d_rows;
@@ -93,7 +94,7 @@ void order_precedences(Engine<T>& E, const double* lt, const double* obs1, const
       }
       r.row = (int)j;
     }
-    REQUIRE((size_t)toff <= tab.n, "order precedences: batch larger than its workspace");
+    REQUIRE((size_t)toff <= tab.n, "order kernels: batch larger than its workspace");
     const size_t R = rows.size();
     d_rows.alloc(R); d_le.alloc(R); d_prec.alloc((size_t)poff + 1);
     HIPCHECK(hipMemcpyAsync(d_rows.p, rows.data(), R * sizeof(ORow), hipMemcpyHostToDevice, E.stream));
@@ -106,12 +107,12 @@ void order_precedences(Engine<T>& E, const double* lt, const double* obs1, const
 #define OPR_ARGS E.stream, d_rows.p + off, par.p, par.p + N * N, par.p + N * N + N, N, tab.p, d_le.p, d_prec.p
     if (!small.empty()) {
       const size_t off = 0;
-      hipLaunchKernelGGL((k_order_prec<256>), dim3(small.size()), dim3(256), 0, OPR_ARGS);
+      hipLaunchKernelGGL(k256, dim3(small.size()), dim3(256), 0, OPR_ARGS);
       HIPCHECK(hipGetLastError());
     }
     if (!big.empty()) {
       const size_t off = small.size();
-      hipLaunchKernelGGL((k_order_prec<1024>), dim3(big.size()), dim3(1024), 0, OPR_ARGS);
+      hipLaunchKernelGGL(k1024, dim3(big.size()), dim3(1024), 0, OPR_ARGS);
       HIPCHECK(hipGetLastError());
     }
 #undef OPR_ARGS
@@ -120,15 +121,24 @@ void order_precedences(Engine<T>& E, const double* lt, const double* obs1, const
     HIPCHECK(hipMemcpyAsync(b_prec.data(), d_prec.p, (size_t)poff * sizeof(double), hipMemcpyDeviceToHost, E.stream));
     HIPCHECK(hipStreamSynchronize(E.stream));
     for (size_t j = 0; j < R; ++j) {
-      const ORow& r = rows[j];
-      const long long i = src[j];
-      log_ev[i] = b_le[j];
-      double* out = prec + i * L * L;
-      const double* in = b_prec.data() + r.foff;
-      for (int a = 0; a < r.k; ++a)
-        for (int b = 0; b < r.k; ++b) out[r.code[a] * L + r.code[b]] = in[a * r.k + b];
+      log_ev[src[j]] = b_le[j];
+      scatter(rows[j], src[j], b_prec.data() + rows[j].foff);
     }
   }
+}
+
+// prec [npat][2n+1][2n+1] over the event codes: NaN where a code is not in the row.
+template <typename T>
+void order_precedences(Engine<T>& E, const double* lt, const double* obs1, const double* obs2, const int8_t* dat, long long npat,
+                       int ncols, double* log_ev, double* prec, int32_t* status) {
+  const long long L = 2 * E.n + 1;
+  std::fill(prec, prec + npat * L * L, std::nan(""));
+  opr_rows(E, lt, obs1, obs2, dat, npat, ncols, log_ev, status, k_order_prec<256>, k_order_prec<1024>,
+           [&](const ORow& r, long long i, const double* in) {
+             double* out = prec + i * L * L;
+             for (int a = 0; a < r.k; ++a)
+               for (int b = 0; b < r.k; ++b) out[r.code[a] * L + r.code[b]] = in[a * r.k + b];
+           });
 }
 
 }  // namespace mmhn

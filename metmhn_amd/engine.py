@@ -431,6 +431,25 @@ class Engine:
                                                    status.ctypes.data_as(_lib.i32p)))
         return le, prec, status
 
+    def order_positions(self, log_theta, obs1, obs2, dat):
+        """MetMHN.order_position of every row of a reference-format `dat` [n_pat, 2n+3] in one call
+        (mmhn_order_positions): float64 log_evidence [n_pat], pos_pt and pos_mt [n_pat, N, N] (event, position; NaN for an
+        event the row does not carry in that lineage), int32 status [n_pat] (low half 0 ok, 2 invalid row - reason code in
+        status >> 16 -, 3 lattice larger than the workspace; NaN outputs wherever it is not 0)."""
+        keep, (ltp, ap, bp) = self._params(log_theta, obs1, obs2)
+        d = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
+        if d.ndim != 2:
+            raise ValueError("dat must be a 2-D array [n_pat, 2 n_mut + 3]")
+        n_pat = d.shape[0]
+        le = np.zeros(n_pat)
+        pos_pt = np.empty((n_pat, self.N, self.N))
+        pos_mt = np.empty((n_pat, self.N, self.N))
+        status = np.zeros(n_pat, dtype=np.int32)
+        _lib.check(self.lib.mmhn_order_positions(self.h, ltp, ap, bp, d.ctypes.data_as(i8p), n_pat, int(d.shape[1]),
+                                                 le.ctypes.data_as(f64p), pos_pt.ctypes.data_as(f64p),
+                                                 pos_mt.ctypes.data_as(f64p), status.ctypes.data_as(_lib.i32p)))
+        return le, pos_pt, pos_mt, status
+
     # ---- measurement
     def bench_kronvec(self, log_theta, state, batch, iters, transpose=False, jacobi=False, tiles=False):
         """ms per launch of mmhn_kronvec_batched's launch (or the fused Jacobi step); tiles=True also returns

@@ -133,6 +133,42 @@ class OrderPrecedences(OrderPrecedence):
         return np.where(rows > 0, total / np.maximum(rows, 1), np.nan)
 
 
+class OrderPosition(SimpleNamespace):
+    """One observation summed over its admissible orders: log_evidence, pos_pt and pos_mt [n+1, n+1] (event - n: the
+    seeding -, position), pos[e, j] = P(e is the j-th (0-based) entry of that lineage | the observation).  The MT lineage
+    of an order is the order without its even codes other than the seeding, the PT lineage the order without its odd
+    codes.  NaN for an event the observation does not carry in the lineage (and throughout a lineage it does not have), 0
+    at the positions past the lineage's length."""
+
+    def __init__(self, log_evidence, pos_pt, pos_mt):
+        super().__init__(log_evidence=log_evidence, pos_pt=pos_pt, pos_mt=pos_mt)
+
+
+class OrderPositions(OrderPosition):
+    """The same for every row of a cohort: log_evidence [n_pat], pos_pt and pos_mt [n_pat, n+1, n+1]."""
+
+    def relative_profile(self, lineage: str = "mt", bins: int = None) -> np.ndarray:
+        """Where in a lineage's history every event happens, over the cohort, on a common relative axis [n+1, bins]
+        (examples/post_training_analyses.ipynb, "Finding relative event positions", with the posterior in the place of
+        the likeliest order): a row whose lineage has L >= 1 entries adds pos[e, j] * L to the bins
+        [bins * j // L, bins * (j + 1) // L) of every event e it carries, for every j < L.  `bins` defaults to
+        lcm(1 ... the longest lineage), which every L divides - give it for lineages of more than a dozen entries, where that
+        number is out of reach.  Rows without the lineage are skipped."""
+        if lineage not in ("mt", "pt"):
+            raise ValueError("lineage must be 'mt' or 'pt'")
+        pos = self.pos_mt if lineage == "mt" else self.pos_pt
+        carried = ~np.isnan(pos[:, :, 0])
+        length = carried.sum(axis=1)
+        if bins is None:
+            bins = int(np.lcm.reduce(np.arange(1, max(int(length.max(initial=1)), 1) + 1)))
+        out = np.zeros((pos.shape[1], bins))
+        for i in np.flatnonzero(length > 0):
+            L = int(length[i])
+            for j in range(L):
+                out[carried[i], bins * j // L:bins * (j + 1) // L] += pos[i, carried[i], j, None] * L
+        return out
+
+
 class MetMHN:
     """The metastasis MHN with its two observation-rate vectors (model.py:175-211)."""
 
@@ -149,6 +185,7 @@ class MetMHN:
         self.orders_fallback_rows = 0       # rows the last likeliest_orders call recomputed on the host
         self.posteriors_fallback_rows = 0   # ... and the last order_posteriors call
         self.precedences_fallback_rows = 0  # ... and the last order_precedences call
+        self.positions_fallback_rows = 0    # ... and the last order_positions call
 
     # ------------------------------------------------------------------ diagonals
     def _get_diag_unpaired(self, state: State, seeding: bool = True) -> np.ndarray:
@@ -354,6 +391,66 @@ class MetMHN:
         except ValueError as e:
             raise ValueError(f"row {i}: {e}") from e
 
+    def order_position(self, state, met_status: str, first_obs: str = None) -> "OrderPosition":
+        """At which position of its lineage every event happened, summed over every admissible order (same arguments,
+        checks and errors as order_precedence): `pos_mt[e, j]` = P(event e - n: the seeding - is the j-th (0-based) entry of
+        the MT lineage | the observation), `pos_pt` the same for the PT lineage.  The MT lineage of an order is the order
+        without its even codes other than the seeding (the events before the seeding, the seeding, the metastasis' own
+        events), the PT lineage the order without its odd codes.  "isMetastasis" has the MT lineage only, "present" and
+        "absent" the PT lineage ("absent" without the seeding).  Rows of events the observation does not carry in a lineage
+        are NaN, a lineage it does not have is NaN throughout; positions past the lineage's length are 0.  Exact: the move
+        that adds slot d from the state x (mass as in order_precedence) puts d's event at the position
+        popcount(x & the slots of d's lineage)."""
+        chain, st = self._route(state, met_status, first_obs)
+        nan = np.full((self.n + 1, self.n + 1), np.nan)
+        if chain == "mt":
+            le, pos = self._position_single(self._single_tables(self.log_theta, st, self.obs2))
+            return OrderPosition(le, nan, pos)
+        if chain == "pt":
+            le, pos = self._position_single(self._single_tables(self._pt_log_theta, st, self.obs1))
+            return OrderPosition(le, pos, nan)
+        return self._position_paired(st, first_obs)
+
+    def order_positions(self, dat, backend: str = "device") -> "OrderPositions":
+        """order_position of every row of a reference-format `dat` [n_pat, 2n+3], rows read as order_posteriors reads
+        them: arrays log_evidence [n_pat], pos_pt and pos_mt [n_pat, n+1, n+1].
+
+        backend="device": every row in one call of the HIP library (mmhn_order_positions); a row whose lattice does not
+        fit the workspace is recomputed here with order_position - how many were is left in
+        `self.positions_fallback_rows`.  backend="host": order_position row by row.  An invalid row raises
+        likeliest_order's ValueError, with its index."""
+        dat = np.asarray(dat)
+        if dat.ndim != 2 or dat.shape[1] != 2 * self.n + 3:
+            raise ValueError(f"dat must have shape [n_pat, {2 * self.n + 3}]")
+        if backend not in ("device", "host"):
+            raise ValueError("backend must be 'device' or 'host'")
+        P, N = dat.shape[0], self.n + 1
+        if backend == "host":
+            le, pos_pt, pos_mt = np.zeros(P), np.zeros((P, N, N)), np.zeros((P, N, N))
+            redo = range(P)
+        else:
+            from .jx import engine
+            le, pos_pt, pos_mt, status = engine(self.n).order_positions(self.log_theta, self.obs1, self.obs2, dat)
+            bad = np.flatnonzero((status & 0xFFFF) == 2)
+            if bad.size:
+                i = int(bad[0])
+                raise ValueError(f"row {i}: {_ROW_ERRORS[int(status[i]) >> 16]}")
+            redo = [int(i) for i in np.flatnonzero(status != 0)]
+        for i in redo:
+            r = self._row_position(dat, i)
+            le[i], pos_pt[i], pos_mt[i] = r.log_evidence, r.pos_pt, r.pos_mt
+        self.positions_fallback_rows = 0 if backend == "host" else len(redo)
+        return OrderPositions(le, pos_pt, pos_mt)
+
+    def _row_position(self, dat, i: int):
+        row = dat[i]
+        status = _ROW_STATUS.get(int(row[-1]), f"type {int(row[-1])}")
+        first = _ROW_FIRST.get(int(row[-2]), "Met") if status == "isPaired" else None
+        try:
+            return self.order_position(MetState.from_seq(row[:2 * self.n + 1]), status, first)
+        except ValueError as e:
+            raise ValueError(f"row {i}: {e}") from e
+
     def likelihood(self, order, met_status: str, first_obs: str = None) -> float:
         """model.py:295-376: probability of exactly this order of events being what is observed."""
         order = tuple(int(e) for e in order)
@@ -467,9 +564,10 @@ class MetMHN:
             prec[np.ix_(codes, codes)] = np.minimum(P / Z, 1.0)     # the quotient of two roundings may pass 1
         return prec
 
-    def _precedence_single(self, T, codes) -> "OrderPrecedence":
-        """_posterior_single's forward pass, the backward pass over the whole lattice (G[x] = B[x] / den[x]), and per
-        target slot d the masses F[x] num_d[y] G[y] of the moves x -> y = x | d, summed over the x that hold c."""
+    @staticmethod
+    def _single_passes(T):
+        """_posterior_single's forward pass F, the evidence Z and the backward pass over the whole lattice as
+        G[x] = B[x] / den[x]: the move x -> y = x | d has the mass F[x] num_d[y] G[y]."""
         k, V = T.k, 1 << T.k
         F = np.zeros(V)
         F[0] = 1.0 / T.den[0]
@@ -489,6 +587,12 @@ class MetMHN:
                     y = x | 1 << b
                     s += G[y] * T.num[b][y]
             G[x] = s / T.den[x]
+        return F, Z, G
+
+    def _precedence_single(self, T, codes) -> "OrderPrecedence":
+        """Per target slot d the masses of the moves x -> y = x | d (_single_passes), summed over the x that hold c."""
+        k, V = T.k, 1 << T.k
+        F, Z, G = self._single_passes(T)
         P = np.zeros((k, k))
         idx = np.arange(V)
         for d in range(k):
@@ -498,6 +602,20 @@ class MetMHN:
                 if c != d:
                     P[c, d] = w[(xs >> c & 1) == 1].sum()
         return OrderPrecedence(float(np.log(Z)), self._precedence_matrix(codes, P, Z))
+
+    def _position_single(self, T):
+        """(log evidence, pos [n+1, n+1]) of a one-tumour chain: the masses of the moves that add slot d, summed by the
+        number of events their state holds."""
+        k, V = T.k, 1 << T.k
+        F, Z, G = self._single_passes(T)
+        pos = np.full((self.n + 1, self.n + 1), np.nan)
+        idx = np.arange(V)
+        held = np.array([bin(x).count("1") for x in range(V)])
+        for d in range(k):
+            xs = idx[(idx >> d & 1) == 0]
+            w = F[xs] * T.num[d][xs | 1 << d] * G[xs | 1 << d]
+            pos[T.ev[d]] = np.minimum(np.bincount(held[xs], weights=w, minlength=self.n + 1) / Z, 1.0)
+        return float(np.log(Z)), pos
 
     def _likelihood_unpaired_mt(self, order) -> float:
         """model.py:1391-1426: a metastasis seen once (obs2), the chain feeling the seeding."""
@@ -687,6 +805,63 @@ class MetMHN:
                     pre[T.slots[b] // 2] += w
         return OrderPosterior(float(np.log(Z)), pre / Z, pos / Z)
 
+    @staticmethod
+    def _unseeded_backward(T, F, B) -> dict:
+        """_paired_passes' backward pass continued over the unseeded states whose tumours agree: a scalar per state (joint
+        moves and the seeding edge), the weight the rest of the order gives F[x]_a."""
+        k = T.k
+        top = 1 << (k - 1)
+        Bu = {}
+        for x in sorted((x for x in F if not x & top), reverse=True):
+            y = x | top
+            s = 0.0
+            for b in range(k - 1):
+                if T.joint >> b & 1 and not x >> b & 1:
+                    s += T.num[b][x | 3 << b] / T.den[x | 3 << b] * Bu[x | 3 << b]
+            Bu[x] = s + T.num[k - 1][y] / T.den[y] * B[y][0]
+        return Bu
+
+    def _position_paired(self, state: MetState, first_obs: str) -> "OrderPosition":
+        """_precedence_paired's move masses, added to the position popcount(x & the slots of the lineage) of the event the
+        move adds; before the seeding both tumours agree and a state of j joint events puts the move's event at j in both
+        lineages."""
+        T, F, Z, B = self._paired_passes(state, first_obs)
+        n, k = self.n, T.k
+        top = 1 << (k - 1)
+        Bu = self._unseeded_backward(T, F, B)
+        ev = [n if s == 2 * n else s // 2 for s in T.slots]
+        count = lambda x: bin(x).count("1")
+        pos_pt, pos_mt = np.full((n + 1, n + 1), np.nan), np.full((n + 1, n + 1), np.nan)
+        for d in range(k):
+            if T.kind[d] != 1:
+                pos_pt[ev[d]] = 0.0
+            if T.kind[d] != 0:
+                pos_mt[ev[d]] = 0.0
+        for x in F:
+            if x & top:
+                for d in range(k - 1):
+                    if not x >> d & 1:
+                        y, v = self._advance(T, x, F[x], d)
+                        g = B[y]
+                        w = g[0] * v[0] + g[1] * v[1] + g[2] * v[2]
+                        if T.kind[d] == 0:
+                            pos_pt[ev[d], count(x & (T.pt_mask | top))] += w
+                        else:
+                            pos_mt[ev[d], count(x & (T.mt_mask | top))] += w
+                continue
+            j = count(x) // 2
+            y = x | top
+            w = B[y][0] * (F[x][0] * T.num[k - 1][y] / T.den[y])
+            pos_pt[n, j] += w
+            pos_mt[n, j] += w
+            for b in range(k - 1):
+                if T.joint >> b & 1 and not x >> b & 1:
+                    y = x | 3 << b
+                    w = F[x][0] * T.num[b][y] / T.den[y] * Bu[y]
+                    pos_pt[ev[b], j] += w
+                    pos_mt[ev[b], j] += w
+        return OrderPosition(float(np.log(Z)), np.minimum(pos_pt / Z, 1.0), np.minimum(pos_mt / Z, 1.0))
+
     def _precedence_paired(self, state: MetState, first_obs: str) -> "OrderPrecedence":
         """_posterior_paired's passes, the backward pass continued over the unseeded states whose tumours agree (a scalar:
         joint moves and the seeding edge), and the mass of EVERY move added to P[c, d] for the slots c its state holds and
@@ -696,14 +871,7 @@ class MetMHN:
         top = 1 << (k - 1)
         bits = lambda x: [c for c in range(k) if x >> c & 1]
         P = np.zeros((k, k))
-        Bu = {}
-        for x in sorted((x for x in F if not x & top), reverse=True):
-            y = x | top
-            s = 0.0
-            for b in range(k - 1):
-                if T.joint >> b & 1 and not x >> b & 1:
-                    s += T.num[b][x | 3 << b] / T.den[x | 3 << b] * Bu[x | 3 << b]
-            Bu[x] = s + T.num[k - 1][y] / T.den[y] * B[y][0]
+        Bu = self._unseeded_backward(T, F, B)
         for x in F:
             held = bits(x)
             if x & top:
