@@ -51,3 +51,35 @@ def mixed_cohort(n: int, n_pat: int, seed: int = 0, p_event: float = 0.3) -> np.
                 bits[0::2] = 0
                 dat[r] = np.concatenate((bits, [1, -99, 2]))
     return dat
+
+
+def pattern_row(n: int, events: str, order: int) -> np.ndarray:
+    """One paired row from a string of events: J = in both tumours, P = PT only, M = MT only, - = in neither.
+    The index bits of its joint space follow the string: two per J (PT bit, then MT bit), one per P / M, seeding last."""
+    assert len(events) <= n
+    r = np.zeros(2 * n + 3, dtype=np.int8)
+    for j, ch in enumerate(events):
+        r[2 * j] = ch in "JP"
+        r[2 * j + 1] = ch in "JM"
+    r[2 * n], r[2 * n + 1], r[2 * n + 2] = 1, order, 3
+    return r
+
+
+# joint spaces around the 2^12 tile boundary: a pair on bits 11 / 12 (seeding on 13, k = 14; behind an MT-only event; with
+# events above it), the seeding on bit 11 (k = 12), on bit 12 (k = 13) and on bit 13, pairs wholly above the tile
+TILE_EDGE_PATTERNS = ("JJJJJPJ", "JJJJJMJ", "JJJJJPJP", "JJJJJPJJ", "JJJJJP", "JJJJJJ", "JJJJJPM", "JJJJJJP", "JJJJJJM",
+                      "JJJJJJJ", "JJJJJJJJ")
+# window shapes of the fp64 engine (10 .. 12 bits in one class, 4 .. 6 in the other, k = 16 .. 18); the last one has the three
+# external bits from which same-shape rows form a chain.  Twelve events each.
+WINDOW_PATTERNS = ("JJJPPPPPPPMM", "JJJPPPPPPPPM", "JJJMMMMMMMMP", "JJJJPPPPPPPP", "JJJMMMMMMMPP", "JJJJPPPPPPMM", "JJJJJPPPPPPP")
+
+
+def tile_edge_cohort(n: int, per_k: int = 8, seed: int = 412) -> np.ndarray:
+    """Paired rows whose joint spaces sit on the tile boundary (TILE_EDGE_PATTERNS at orders 0 / 1 / 2 / -99), for n >= 12
+    the window shapes as well, between per_k rows each of full_k_cohort(n, k = 13 .. 16); shuffled.  n >= 8."""
+    rows = [pattern_row(n, p, o) for p in TILE_EDGE_PATTERNS for o in (0, 1, 2, -99)]
+    if n >= 12:
+        rows += [pattern_row(n, p, o) for p in WINDOW_PATTERNS for o in (0, 1, 2, -99)]
+    dat = np.vstack([np.array(rows, dtype=np.int8)] + [full_k_cohort(n, per_k, k=kk, seed=seed + kk) for kk in (13, 14, 15, 16)])
+    np.random.default_rng(seed).shuffle(dat, axis=0)
+    return dat

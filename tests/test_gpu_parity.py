@@ -1684,3 +1684,75 @@ def test_cache_guard_full_crc_and_in_place_refresh(golden):
     t1 = ro.score(lt, dp, dm, big, 0.3)
     np.testing.assert_allclose(t1, ro.score(lt, dp, dm, big.copy(), 0.3), rtol=1e-13)
     ro.configure()
+
+
+# ---- joint spaces on the tile boundary through every route (the shapes tests/host/plan_check.hip checks the plans of)
+_TILE_EDGE = {}
+TILE_EDGE_RUNS = {
+    "default": {},
+    "coop0": {"MMHN_COOP": "0"},
+    "psolve_min1": {"MMHN_PSOLVE_MIN": "1"},
+    "wsolve_min1": {"MMHN_WSOLVE_MIN": "1"},
+    "wsolve_min1_wgs3": {"MMHN_WSOLVE_MIN": "1", "MMHN_WSOLVE_WGS": "3"},
+    "prep_split0": {"MMHN_PREP_SPLIT": "0"},
+    "pcl_per1": {"MMHN_PCL_PER": "1"},
+}
+
+
+def _tile_edge_case(n):
+    """Cohort, parameters, CPU reference (oracle/metmhn_fast.c; oracle/metmhn_ref.c for rows it does not take) and the
+    default engine's cohort sums - computed once per n."""
+    if n not in _TILE_EDGE:
+        from oracle import cref
+        from metmhn_amd import Engine, synthetic
+        dat = synthetic.tile_edge_cohort(n)
+        lt, dp, dm = synthetic.random_params(n, seed=300 + n)
+        try:
+            ref = cref.fast_patients(lt, dp, dm, dat)
+        except ValueError:
+            ref = cref.patients(lt, dp, dm, dat, with_grad=True)
+        e = Engine(n)
+        e.set_cohort(dat)
+        sums = e.cohort_sums(lt, dp, dm)
+        e.close()
+        _TILE_EDGE[n] = (dat, lt, dp, dm, ref, sums)
+    return _TILE_EDGE[n]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", (8, 12))
+@pytest.mark.parametrize("run", list(TILE_EDGE_RUNS))
+def test_tile_edge_shapes_on_every_route(monkeypatch, run, n):
+    """synthetic.tile_edge_cohort: a pair on index bits 11 / 12 (across the 2^12 tile boundary), the seeding on bit 11, 12
+    and 13, k = 12 and k = 13, pairs wholly above the tile, at orders 0 / 1 / 2 / -99, between random rows of k = 13 .. 16.
+    Per-patient log-probabilities and gradients of a fresh engine with NaN-poisoned buffers against the CPU reference, on the
+    cooperative tile route, level by level (MMHN_COOP=0), one workgroup per patient (MMHN_PSOLVE_MIN=1), the window route
+    (MMHN_WSOLVE_MIN=1; with MMHN_WSOLVE_WGS=3 its chains are dealt to three workgroups), and with the class-marginal work
+    cut differently (MMHN_PREP_SPLIT=0, MMHN_PCL_PER=1: also against the default run's cohort sums).  At n = 8 no class
+    has the ten bits of a window shape, so the window runs of that cohort stay on the tile route; the n = 12 cohort adds
+    window-shaped rows (tests/test_plan_invariants.py asserts that its chains are dealt)."""
+    from metmhn_amd import Engine
+    dat, lt, dp, dm, (lp, g, a, b), sums0 = _tile_edge_case(n)
+    monkeypatch.setenv("MMHN_POISON", "1")
+    for k_, v_ in TILE_EDGE_RUNS[run].items():
+        monkeypatch.setenv(k_, v_)
+    e = Engine(n)
+    e.set_cohort(dat)
+    r = e.patient_grads(lt, dp, dm)
+    sums = e.cohort_sums(lt, dp, dm)
+    e.close()
+
+    def worst(x, y, atol):
+        return float(np.max(np.abs(x - y) / (atol + np.abs(y))))
+    # worst |x - ref| / (atol / rtol + |ref|): to be read against rtol (1e-10; 1e-7 for the gradients; 1e-12 for the sums)
+    print(f"tile edge n={n} {run}: lp {worst(r[0], lp, 0):.2e}, d_theta {worst(r[1], g, 1e-10 / 1e-7):.2e}, "
+          f"d_dp {worst(r[2], a, 1e-10 / 1e-7):.2e}, d_dm {worst(r[3], b, 1e-10 / 1e-7):.2e}, "
+          f"sums against the default run {worst(sums, sums0, 1e-13 / 1e-12):.2e}")
+    for x in r:
+        assert np.isfinite(x).all()
+    np.testing.assert_allclose(r[0], lp, rtol=1e-10, err_msg=run)
+    np.testing.assert_allclose(r[1], g, rtol=1e-7, atol=1e-10, err_msg=run)
+    np.testing.assert_allclose(r[2], a, rtol=1e-7, atol=1e-10, err_msg=run)
+    np.testing.assert_allclose(r[3], b, rtol=1e-7, atol=1e-10, err_msg=run)
+    if run in ("prep_split0", "pcl_per1"):
+        np.testing.assert_allclose(sums, sums0, rtol=1e-12, atol=1e-13, err_msg=run)
