@@ -2,7 +2,8 @@
 // C ABI of include/metmhn_amd.h.  One engine = one GPU, one HIP stream.
 // The rest of the host side lives in headers of this one translation unit: plan.h (the cohort planner, host-only:
 // batches, routes, work lists, offsets), host.h (errors, device arrays, MMHN_* knob readers), comm.h (RCCL),
-// prims.h / orders_host.h / orderpost_host.h / orderprec_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
+// prims.h / orders_host.h / orderpost_host.h (the batching of the three order-posterior entry points, opr_rows) /
+// orderprec_host.h / orderpos_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
 //
 // Pipeline of one evaluation (reference call graph: regularized_optimization.py:163-267 ->
 // likelihood.py:_g_coupled_*, _grad_prim_obs, _grad_met_obs), run batch by batch with every

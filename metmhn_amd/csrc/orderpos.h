@@ -1,5 +1,6 @@
-// Posterior event positions of a cohort: the device form of metmhn_amd/model.py MetMHN.order_position, next to orderprec.h
-// (k_order_prec), whose row set-up, tables, passes and move masses m(x, b) it calls (opr_*: one copy for both kernels).
+// Posterior event positions of a cohort: the device form of metmhn_amd/model.py MetMHN.order_position, on the row set-up,
+// tables and passes of orderpass.h (every order kernel's) and the backward passes over every state and the move masses
+// m(x, b) of orderprec.h (k_order_prec's and this kernel's).
 //
 // An order has two lineages: the metastasis' (the joint events before the seeding, the seeding, the metastasis' own events)
 // and the primary tumour's (the joint events, the seeding, the primary tumour's own events).
@@ -11,7 +12,7 @@
 //
 // The reduction.  For a target slot d the moves that add d are indexed by the other slots (idx of m bits, as in
 // orderprec.h); mask_d without bit d, packed to the index bits, is mk.  A wave owns a chunk of 2^c consecutive idx
-// (c = oprec_chunk_bits): the class popcount(idx & mk) splits into popcount(h & mk_hi) of the chunk's number h
+// (c = opo_chunk_bits): the class popcount(idx & mk) splits into popcount(h & mk_hi) of the chunk's number h
 // (wave-uniform) and popcount(p & mk_lo) of the index p = lane + 64 i in the chunk, which splits again into the lane's part
 // and popcount(i & (mk_lo >> 6)) (wave-uniform per i).  A lane adds its masses into five sums by that last part - no array
 // of masses in registers -, then the wave does one opo_wave_sum tree per class of the chunk and writes c + 1 partials.
@@ -90,6 +91,7 @@ __global__ __launch_bounds__(KB) void k_order_pos(const ORow* __restrict__ rows,
                                                   const double* __restrict__ g_o1, const double* __restrict__ g_o2, int N,
                                                   double* tab, double* out_le, double* out_pos) {
   __shared__ OprRow S;
+  __shared__ double bu[1 << OPO_CB];           // paired: B of the unseeded state of the joint events e
   __shared__ double Rs[32][32];                // Rs[d][j]: summed masses of the moves that put slot d at position j
   __shared__ double Rj[OPO_CB + 1][OPO_CB + 1]; // paired, before the seeding: Rj[t][j] target joint event t (kj: the
                                                // seeding) from a state of j joint events
@@ -108,7 +110,7 @@ __global__ __launch_bounds__(KB) void k_order_pos(const ORow* __restrict__ rows,
     if (tid == 0) out_le[r.row] = log(Z);
     if (k == 0) return;
     const int m = k - 1;
-    opp_class_sums<KB>(k, m, oprec_chunk_bits(m, KB), part,
+    opp_class_sums<KB>(k, m, opo_chunk_bits(m, KB), part,
         [&](int d, uint32_t idx) { return opr_single_mass(S, N, den, F, d, idx); },
         [&](int) { return (1u << m) - 1u; },
         [&](int d, int j, double s) { Rs[d][j] = s; });
@@ -118,12 +120,13 @@ __global__ __launch_bounds__(KB) void k_order_pos(const ORow* __restrict__ rows,
 
   const OprPaired T = opr_paired_tables(r, den);
   const double Z = opr_paired_passes<KB>(S, N, T);
+  opr_unseeded_backward<KB>(S, N, T, bu);
   const int kj = T.kj;
   if (tid == 0) out_le[r.row] = log(Z);
   // after the seeding: target slot d < k - 1, the moves from the seeded x without d; x holds the seeding, an entry of
   // both lineages
   const int m = k >= 2 ? k - 2 : 0;
-  opp_class_sums<KB>(k - 1, m, oprec_chunk_bits(m, KB), part,
+  opp_class_sums<KB>(k - 1, m, opo_chunk_bits(m, KB), part,
       [&](int d, uint32_t idx) { return opr_seeded_mass(S, N, T, d, idx); },
       [&](int d) { return opp_index_mask(r.kind[d] == ORD_K_PT ? r.pt_mask : r.mt_mask, d, m); },
       [&](int d, int j, double s) { Rs[d][j + 1] = s; });
@@ -137,7 +140,7 @@ __global__ __launch_bounds__(KB) void k_order_pos(const ORow* __restrict__ rows,
       for (uint32_t e = lane; e < EJ; e += 64) {
         if (__builtin_popcount(e) != j || (q < kj && ((e >> q) & 1u))) continue;
         const uint32_t x = opr_joint_state(S, e);
-        s += T.F[3ll * x] * (q < kj ? opr_joint_edge(S, N, T, e, q) : opr_seed_edge(S, N, T, x));
+        s += T.F[3ll * x] * (q < kj ? opr_joint_edge(S, N, T, bu, e, q) : opr_seed_edge(S, N, T, x));
       }
       s = opo_wave_sum(s);
       if (lane == 0) Rj[q][j] = s;

@@ -1,5 +1,6 @@
-// Host side of the pre-seeding posteriors of a cohort (orderpost.h: k_order_post): row decoding (orders.h: ord_decode,
-// the one mmhn_likeliest_orders uses), batching, launches.
+// Host side of the three order-posterior entry points of a cohort: row decoding (orders.h: ord_decode, the one
+// mmhn_likeliest_orders uses), limits, batching, launches and the copy back, in one place (opr_rows) - orderprec_host.h and
+// orderpos_host.h call it too -, and the pre-seeding posteriors themselves (orderpost.h: k_order_post).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -14,30 +15,32 @@ namespace mmhn {
 
 // (engine.hip includes this file behind the definition of Engine<T> and orders_host.h, whose ORD_BIG_K it shares)
 
-static long long opost_bytes(const ORow& r) { return opost_doubles(r) * (long long)sizeof(double); }
+// k_order_post / k_order_prec (orderprec.h) / k_order_pos (orderpos.h): each writes log_ev and one block of doubles per row
+using OprKernel = void (*)(const ORow*, const double*, const double*, const double*, int, double*, double*, double*);
 
 // Rows are decoded and checked (status MMHN_ORD_INVALID with the reason in the high half), then cut into batches whose
-// lattices fit the workspace limit - with 76 B per sub-state a cohort is normally one batch; a row that does not fit on
-// its own is MMHN_ORD_TOO_LARGE.  The workspace is allocated once, for the largest batch.  One workgroup per row, so a
-// row's result does not depend on the batch it lands in.
-template <typename T>
-void order_posteriors(Engine<T>& E, const double* lt, const double* obs1, const double* obs2, const int8_t* dat, long long npat,
-                      int ncols, double* log_ev, double* pre, double* seed_pos, int32_t* status) {
+// lattices fit the workspace limit; a row that does not fit on its own is MMHN_ORD_TOO_LARGE.  The workspace is
+// allocated once, for the largest batch.  One workgroup per row (k256 below ORD_BIG_K slots, k1024 from there on), so a
+// row's result does not depend on the batch it lands in.  Per entry point: doubles(row) the row's workspace in doubles,
+// block(row) the doubles of its output block, fits(row) what else the kernel asks of a row, scatter(row, cohort row,
+// block) takes a finished row's block to the caller's arrays, which the caller has filled with NaN.
+template <typename T, class Doubles, class Block, class Fits, class Scatter>
+void opr_rows(Engine<T>& E, const double* lt, const double* obs1, const double* obs2, const int8_t* dat, long long npat,
+              int ncols, double* log_ev, int32_t* status, OprKernel k256, OprKernel k1024, Doubles doubles, Block block,
+              Fits fits, Scatter scatter) {
   REQUIRE(ncols == 2 * E.n + 3, "dat must have 2 n_mut + 3 columns (states, diagnosis order, type)");
   REQUIRE(E.N <= ORD_MAXN, "too many events for the order kernels (n_mut <= 31)");
   const int n = E.n, N = E.N;
-  const double nan = std::nan("");
-  std::fill(log_ev, log_ev + npat, nan);
-  std::fill(pre, pre + npat * n, nan);
-  std::fill(seed_pos, seed_pos + npat * N, nan);
+  std::fill(log_ev, log_ev + npat, std::nan(""));
   const long long limit = (long long)E.cfg.plan.ws_limit;
+  const auto bytes = [&](const ORow& r) { return (long long)doubles(r) * (long long)sizeof(double); };
   std::vector<ORow> todo;
   for (long long i = 0; i < npat; ++i) {
     ORow r;
     const int why = ord_decode(dat + i * ncols, ncols, n, r);
     if (why) { status[i] = MMHN_ORD_INVALID | (why << 16); continue; }
     r.row = (int)i;
-    if (r.k > MAXK || opost_bytes(r) > limit) { status[i] = MMHN_ORD_TOO_LARGE; continue; }
+    if (r.k > MAXK || !fits(r) || bytes(r) > limit) { status[i] = MMHN_ORD_TOO_LARGE; continue; }
     status[i] = MMHN_ORD_OK;
     todo.push_back(r);
   }
@@ -46,15 +49,15 @@ void order_posteriors(Engine<T>& E, const double* lt, const double* obs1, const 
   std::vector<size_t> cut{0};
   long long used = 0, most = 0;
   for (size_t j = 0; j < todo.size(); ++j) {
-    const long long b = opost_bytes(todo[j]);
+    const long long b = bytes(todo[j]);
     if (j > cut.back() && used + b > limit) { cut.push_back(j); used = 0; }
     used += b;
     most = std::max(most, used);
   }
   cut.push_back(todo.size());
-  // the parameters: exp(log_theta) for k_diag (PS_THETA), the log-parameters themselves for k_order_post
+  // the parameters: exp(log_theta) for k_diag (PS_THETA), the log-parameters themselves for the order kernel
   E.build_params(lt, nullptr, nullptr);
-  DevArr<double> par, tab, d_le, d_pre, d_sp;
+  DevArr<double> par, tab, d_le, d_out;
   DevArr<ORow> d_rows;
   DevArr<Desc> dd;
   DevArr<int2> dmap;
@@ -70,14 +73,17 @@ void order_posteriors(Engine<T>& E, const double* lt, const double* obs1, const 
     std::vector<ORow> rows(small);
     rows.insert(rows.end(), big.begin(), big.end());
     std::vector<long long> src(rows.size());
-    long long toff = 0;
+    long long toff = 0, poff = 0;
     std::vector<Desc> descs;
     std::vector<int2> map;
     for (size_t j = 0; j < rows.size(); ++j) {
       ORow& r = rows[j];
       src[j] = r.row;
       r.toff = toff;
-      toff += opost_doubles(r);
+      r.coff = toff + opost_doubles(r);                               // the move-mass kernels' partials; k_order_post has none there
+      r.foff = poff;
+      toff += doubles(r);
+      poff += block(r);
       if (r.mode == ORD_PAIRED) {
         Desc d = make_joint(dat + (long long)r.row * ncols, n);       // the joint diagonal of the row's state (mmhn_kron_diag's)
         d.off = r.toff;
@@ -86,9 +92,9 @@ void order_posteriors(Engine<T>& E, const double* lt, const double* obs1, const 
       }
       r.row = (int)j;
     }
-    REQUIRE((size_t)toff <= tab.n, "order posteriors: batch larger than its workspace");
+    REQUIRE((size_t)toff <= tab.n, "order kernels: batch larger than its workspace");
     const size_t R = rows.size();
-    d_rows.alloc(R); d_le.alloc(R); d_pre.alloc(R * n + 1); d_sp.alloc(R * N);
+    d_rows.alloc(R); d_le.alloc(R); d_out.alloc((size_t)poff + 1);
     HIPCHECK(hipMemcpyAsync(d_rows.p, rows.data(), R * sizeof(ORow), hipMemcpyHostToDevice, E.stream));
     if (!descs.empty()) {
       dd.alloc(descs.size()); dmap.alloc(map.size());
@@ -96,31 +102,45 @@ void order_posteriors(Engine<T>& E, const double* lt, const double* obs1, const 
       HIPCHECK(hipMemcpyAsync(dmap.p, map.data(), map.size() * sizeof(int2), hipMemcpyHostToDevice, E.stream));
       E.launch_diag(dd.p, dmap.p, (int)map.size(), nullptr, tab.p, nullptr, KD_DQ);
     }
-#define OPO_ARGS E.stream, d_rows.p + off, par.p, par.p + N * N, par.p + N * N + N, N, tab.p, d_le.p, d_pre.p, d_sp.p
+#define OPR_ARGS E.stream, d_rows.p + off, par.p, par.p + N * N, par.p + N * N + N, N, tab.p, d_le.p, d_out.p
     if (!small.empty()) {
       const size_t off = 0;
-      hipLaunchKernelGGL((k_order_post<256>), dim3(small.size()), dim3(256), 0, OPO_ARGS);
+      hipLaunchKernelGGL(k256, dim3(small.size()), dim3(256), 0, OPR_ARGS);
       HIPCHECK(hipGetLastError());
     }
     if (!big.empty()) {
       const size_t off = small.size();
-      hipLaunchKernelGGL((k_order_post<1024>), dim3(big.size()), dim3(1024), 0, OPO_ARGS);
+      hipLaunchKernelGGL(k1024, dim3(big.size()), dim3(1024), 0, OPR_ARGS);
       HIPCHECK(hipGetLastError());
     }
-#undef OPO_ARGS
-    std::vector<double> b_le(R), b_pre(R * n + 1), b_sp(R * N);
+#undef OPR_ARGS
+    std::vector<double> b_le(R), b_out((size_t)poff + 1);
     HIPCHECK(hipMemcpyAsync(b_le.data(), d_le.p, R * sizeof(double), hipMemcpyDeviceToHost, E.stream));
-    HIPCHECK(hipMemcpyAsync(b_pre.data(), d_pre.p, R * n * sizeof(double), hipMemcpyDeviceToHost, E.stream));
-    HIPCHECK(hipMemcpyAsync(b_sp.data(), d_sp.p, R * N * sizeof(double), hipMemcpyDeviceToHost, E.stream));
+    HIPCHECK(hipMemcpyAsync(b_out.data(), d_out.p, (size_t)poff * sizeof(double), hipMemcpyDeviceToHost, E.stream));
     HIPCHECK(hipStreamSynchronize(E.stream));
     for (size_t j = 0; j < R; ++j) {
-      const long long i = src[j];
-      log_ev[i] = b_le[j];
-      if (dat[i * ncols + ncols - 1] == 0) continue;                  // "absent": no seeding in the observation, NaN
-      std::memcpy(pre + i * n, b_pre.data() + j * n, sizeof(double) * n);
-      std::memcpy(seed_pos + i * N, b_sp.data() + j * N, sizeof(double) * N);
+      log_ev[src[j]] = b_le[j];
+      scatter(rows[j], src[j], b_out.data() + rows[j].foff);
     }
   }
+}
+
+// pre [npat][n], seed_pos [npat][n+1]: NaN in the "absent" rows, which have no seeding to place.  With 76 B per sub-state a
+// cohort is normally one batch.
+template <typename T>
+void order_posteriors(Engine<T>& E, const double* lt, const double* obs1, const double* obs2, const int8_t* dat, long long npat,
+                      int ncols, double* log_ev, double* pre, double* seed_pos, int32_t* status) {
+  const int n = E.n, N = E.N;
+  std::fill(pre, pre + npat * n, std::nan(""));
+  std::fill(seed_pos, seed_pos + npat * N, std::nan(""));
+  opr_rows(E, lt, obs1, obs2, dat, npat, ncols, log_ev, status, k_order_post<256>, k_order_post<1024>,
+           [](const ORow& r) { return opost_doubles(r); }, [&](const ORow&) { return (long long)n + N; },
+           [](const ORow&) { return true; },
+           [&](const ORow&, long long i, const double* in) {
+             if (dat[i * ncols + ncols - 1] == 0) return;                  // "absent": no seeding in the observation, NaN
+             std::memcpy(pre + i * n, in, sizeof(double) * n);
+             std::memcpy(seed_pos + i * N, in + n, sizeof(double) * N);
+           });
 }
 
 }  // namespace mmhn

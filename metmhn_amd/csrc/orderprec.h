@@ -1,5 +1,5 @@
-// Pairwise event-precedence posteriors of a cohort: the device form of metmhn_amd/model.py MetMHN.order_precedence, next to
-// orderpost.h (k_order_post), whose tables, forward vectors F, backward vectors B and level walk it shares.
+// Pairwise event-precedence posteriors of a cohort: the device form of metmhn_amd/model.py MetMHN.order_precedence, on the
+// tables, forward vectors F, backward vectors B and level walk of orderpass.h, which k_order_post (orderpost.h) calls too.
 //
 // Every admissible order of a row is a path of moves x -> y over the row's lattice of 2^k sub-states (slot b = bit b).
 //   mass of a move   m(x, b) = B[y] . A(x, b) F[x]   (a scalar product of 3-vectors on the seeded half of a paired row, a
@@ -8,7 +8,7 @@
 //                    = P(c happened strictly earlier than d | the row); a joint move (before the seeding of a paired row)
 //                    adds both of its slots, so neither of the two precedes the other
 // One tumour: the whole lattice, B as G[x] = B[x] / den[x] in den's place once the forward pass is done.  Both tumours: B
-// over the seeded half as k_order_post forms it, then the scalar B of the unseeded states whose tumours agree (joint moves
+// over the seeded half as opr_paired_passes forms it, then the scalar B of the unseeded states whose tumours agree (joint moves
 // and the seeding edge; at most 2^((k-1)/2) states, LDS: the host side turns a row of more than 10 joint events away).
 // The move masses are recomputed from F, B and the tables - a k x 2^(k-1) edge array would not fit.
 //
@@ -28,7 +28,7 @@
 // k (c + 1) 2^(m - c) + k (m - c + 1) up to m = 20, under 3 % of the lattice.  Output: the compact k x k matrix in slot
 // order (row c, column d, diagonal 0); the host side scatters it to the event codes.  fp64 only.
 #pragma once
-#include "orderpost.h"
+#include "orderpass.h"
 
 namespace mmhn {
 
@@ -36,16 +36,6 @@ namespace mmhn {
 inline int oprec_bits(const ORow& r) {
   const int m = r.mode == ORD_PAIRED ? r.k - 2 : r.k - 1;
   return m > 0 ? m : 0;
-}
-
-// opo_chunk_bits for a launch of kb threads (host and device)
-__host__ __device__ inline int oprec_chunk_bits(int kk, int kb) {
-  int lg = 0;
-  while ((64 << lg) < kb) ++lg;
-  int c = kk - lg;
-  c = c < 6 ? 6 : c;
-  c = c > OPO_CB ? OPO_CB : c;
-  return c < kk ? c : (kk > 0 ? kk : 0);
 }
 
 // chunk partials of nt vectors of 2^m values whose first level has chunks of c bits, in doubles
@@ -62,7 +52,7 @@ __host__ __device__ inline long long oprec_part_doubles(int nt, int m, int c) {
 // workspace of a row in doubles (kb: threads of the row's launch)
 inline long long oprec_doubles(const ORow& r, int kb) {
   const int m = oprec_bits(r);
-  return opost_doubles(r) + oprec_part_doubles(r.k, m, oprec_chunk_bits(m, kb));
+  return opost_doubles(r) + oprec_part_doubles(r.k, m, opo_chunk_bits(m, kb));
 }
 
 // idx with a zero inserted at bit d
@@ -147,40 +137,11 @@ __device__ __forceinline__ void opr_bit_sums(int nt, int m, int c0, double* part
   __syncthreads();
 }
 
-// ---- what k_order_prec and k_order_pos (orderpos.h) share: the row in LDS, the tables, the forward pass, the backward
-// pass over every state the chain can be in, the masses of the moves
+// ---- what k_order_prec and k_order_pos (orderpos.h) share on top of orderpass.h: the backward pass over every state the
+// chain can be in, the masses of the moves
 
-// LDS of a row
-struct OprRow {
-  double lt[ORD_MAXN * ORD_MAXN];
-  double o1w[ORD_MAXN], o2w[ORD_MAXN];
-  ORow r;
-  OpoLevels L;
-  double bu[1 << OPO_CB];                      // paired: B of the unseeded state of the joint events e
-  int8_t jslot[32];                            // paired: slot of the i-th joint event
-  int8_t jev[32];                              // paired: joint event of a slot, -1 none
-  double zsh;
-};
-
-// a value every lane of the wave holds, moved to scalar registers (the offsets of a row come from LDS, in vector ones)
-__device__ __forceinline__ long long opr_uniform(long long v) {
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-  return (long long)(((unsigned long long)hi << 32) | lo);
-}
-
-// the parameters and rows[blockIdx.x] into LDS (every thread of the workgroup; ends with a barrier)
-template <int KB>
-__device__ __forceinline__ void opr_load(OprRow& S, const ORow* __restrict__ rows, const double* __restrict__ g_lt,
-                                         const double* __restrict__ g_o1, const double* __restrict__ g_o2, int N) {
-  const int tid = threadIdx.x;
-  for (int i = tid; i < N * N; i += KB) S.lt[i] = g_lt[i];
-  for (int i = tid; i < N; i += KB) { S.o1w[i] = g_o1[i]; S.o2w[i] = g_o2[i]; }
-  if (tid == 0) S.r = rows[blockIdx.x];
-  __syncthreads();
-}
-
-// One tumour (_single_tables, every slot alike): den, the forward pass into F and - unless the row is empty - the
-// backward pass over the whole lattice, G[x] = B[x] / den[x] in den's place.  Returns Z; ends with a barrier.
+// One tumour (_single_passes): opr_single_forward over every bit and - unless the row is empty - the backward pass over the
+// whole lattice, G[x] = B[x] / den[x] in den's place.  Returns Z; ends with a barrier.
 template <int KB>
 __device__ __forceinline__ double opr_single_passes(OprRow& S, int N, double* den, double* F) {
   const ORow& r = S.r;
@@ -188,31 +149,9 @@ __device__ __forceinline__ double opr_single_passes(OprRow& S, int N, double* de
   const int tid = threadIdx.x, k = r.k;
   const uint32_t V = 1u << k, full = V - 1u;
   const bool pt = r.mode == ORD_PT;
-  const double* after = pt ? S.o1w : S.o2w;
-  const bool sd = r.seeded_top && k > 0;
-  opo_levels_init<KB>(S.L, opo_chunk_bits<KB>(k));
+  double fin;
+  const double Z = opr_single_forward<KB>(S, N, den, F, k, fin);
   const int c = S.L.c;
-  for (uint32_t x = tid; x < V; x += KB) {
-    const bool sx = r.seeded_top && ((x >> (k - 1)) & 1u);
-    const double ob = exp(sx ? ord_obs_sum(after, r, x) : ord_obs_sum(S.o1w, r, x));
-    den[x] = ob - ord_single_diag(lt, N, r, full, x, N, pt);
-  }
-  __syncthreads();
-  if (tid == 0) F[0] = 1.0 / den[0];
-  __syncthreads();
-  for (int lev = 1; lev <= k; ++lev) {
-    opo_level<KB>(S.L, 0u, V >> c, lev, [&](uint32_t x) {
-      double s = 0.0;
-      for (uint32_t m = x; m; m &= m - 1) {
-        const int b = __builtin_ctz(m);
-        s += F[x ^ (1u << b)] * ord_num(lt, N, r, r.ev[b], x, pt);
-      }
-      F[x] = s / den[x];
-    });
-    __syncthreads();
-  }
-  const double fin = exp(sd ? ord_obs_sum(after, r, full) : ord_obs_sum(S.o1w, r, full));
-  const double Z = F[full] * fin;
   if (k == 0) return Z;
   // (den[x] is read for the last time by the thread that writes G[x])
   double* G = den;
@@ -239,30 +178,6 @@ __device__ __forceinline__ double opr_single_mass(const OprRow& S, int N, const 
   return F[x] * ord_num(S.lt, N, S.r, S.r.ev[d], y, S.r.mode == ORD_PT) * G[y];
 }
 
-// the tables of a paired row in its workspace (_paired_tables, as k_order_post lays them out)
-struct OprPaired {
-  double *den, *o1, *o2, *dmt, *dpt, *F, *B;    // B[3 (x ^ top)] of the seeded x
-  uint32_t top, in_mt;
-  int kj;                                       // joint events
-};
-
-__device__ __forceinline__ OprPaired opr_paired_tables(const ORow& r, double* den) {
-  const long long V = 1ll << r.k;
-  OprPaired P;
-  P.den = den; P.o1 = den + V; P.o2 = P.o1 + V; P.dmt = P.o2 + V; P.dpt = P.dmt + V; P.F = P.dpt + V; P.B = P.F + 3 * V;
-  P.top = 1u << (r.k - 1);
-  P.in_mt = r.mt_mask | P.top;
-  P.kj = __builtin_popcount(r.joint);
-  return P;
-}
-
-// state of the compact index e over the joint events: both slots of every event in e
-__device__ __forceinline__ uint32_t opr_joint_state(const OprRow& S, uint32_t e) {
-  uint32_t x = 0;
-  for (uint32_t m = e; m; m &= m - 1) x |= 3u << S.jslot[__builtin_ctz(m)];
-  return x;
-}
-
 // the seeding edge of the unseeded state x: the factor that takes F[x]_a to its mass
 __device__ __forceinline__ double opr_seed_edge(const OprRow& S, int N, const OprPaired& P, uint32_t x) {
   const uint32_t y = x | P.top;
@@ -270,9 +185,9 @@ __device__ __forceinline__ double opr_seed_edge(const OprRow& S, int N, const Op
 }
 
 // the same for the joint move of event q from the unseeded state of the joint events e
-__device__ __forceinline__ double opr_joint_edge(const OprRow& S, int N, const OprPaired& P, uint32_t e, int q) {
+__device__ __forceinline__ double opr_joint_edge(const OprRow& S, int N, const OprPaired& P, const double* bu, uint32_t e, int q) {
   const uint32_t y = opr_joint_state(S, e | (1u << q));
-  return ord_num(S.lt, N, S.r, S.r.ev[S.jslot[q]], y & S.r.pt_mask, false) / P.den[y] * S.bu[e | (1u << q)];
+  return ord_num(S.lt, N, S.r, S.r.ev[S.jslot[q]], y & S.r.pt_mask, false) / P.den[y] * bu[e | (1u << q)];
 }
 
 // mass of the move that adds slot d < k - 1 from the seeded state of the other slots idx (k - 2 bits)
@@ -291,129 +206,22 @@ __device__ __forceinline__ double opr_seeded_mass(const OprRow& S, int N, const 
   return w;
 }
 
-// Both tumours (as k_order_post): the tables, the forward pass, the backward pass over the seeded half and the scalar B
-// of the unseeded states whose tumours agree (S.bu).  diagJ is in den already.  Returns Z; ends with a barrier.
+// Both tumours, after opr_paired_passes (_unseeded_backward): the scalar B of the unseeded states whose tumours agree, into
+// bu[e] of the state of the joint events e (1 << OPO_CB doubles of LDS) - joint moves in ascending event, then the seeding
+// edge.  Ends with a barrier.
 template <int KB>
-__device__ __forceinline__ double opr_paired_passes(OprRow& S, int N, const OprPaired& P) {
-  const ORow& r = S.r;
-  const double* lt = S.lt;
-  const int tid = threadIdx.x, n = N - 1, k = r.k;
-  const uint32_t V = 1u << k, full = V - 1u;
-  double *den = P.den, *o1 = P.o1, *o2 = P.o2, *dmt = P.dmt, *dpt = P.dpt, *F = P.F, *B = P.B;
-  const uint32_t top = P.top, in_mt = P.in_mt;
-  const int c = opo_chunk_bits<KB>(k - 1);
-  opo_levels_init<KB>(S.L, c);
-  if (tid == 0) {
-    int kj = 0;
-    for (int b = 0; b < 32; ++b) S.jev[b] = -1;
-    for (uint32_t m = r.joint; m; m &= m - 1) {
-      const int b = __builtin_ctz(m);
-      S.jslot[kj] = (int8_t)b; S.jev[b] = S.jev[b + 1] = (int8_t)kj; ++kj;
-    }
-  }
-  for (uint32_t x = tid; x < V; x += KB) {
-    double s1 = 0.0, s2 = 0.0;
-    for (uint32_t m = x; m; m &= m - 1) {
-      const int j = __builtin_ctz(m);
-      if (r.kind[j] != ORD_K_MT) s1 += S.o1w[r.ev[j]];
-      if (r.kind[j] != ORD_K_PT) s2 += S.o2w[r.ev[j]];
-    }
-    const double e1 = exp(s1), e2 = exp(s2);
-    o1[x] = e1; o2[x] = e2;
-    den[x] = (e1 + ((x & top) ? e2 : 0.0)) - den[x];
-    if (r.pt_first) dmt[x] = e2 - ord_single_diag(lt, N, r, in_mt, x, N, false);
-    if (r.mt_first) dpt[x] = e1 - ord_single_diag(lt, N, r, r.pt_mask, x, n, false);
-  }
-  const OrdTab t{o1, o2, dmt, dpt};
-  const int kj = P.kj;
+__device__ __forceinline__ void opr_unseeded_backward(const OprRow& S, int N, const OprPaired& P, double* bu) {
+  const int tid = threadIdx.x, kj = P.kj;
   const uint32_t EJ = 1u << kj;
-  __syncthreads();
-  if (tid == 0) { F[0] = 1.0 / den[0]; F[1] = 0.0; F[2] = 0.0; }
-  __syncthreads();
-  // before the seeding: the states whose tumours agree, joint moves only
-  for (int lev = 1; lev <= kj; ++lev) {
-    for (uint32_t e = tid; e < EJ; e += KB) {
-      if (__builtin_popcount(e) != lev) continue;
-      const uint32_t y = opr_joint_state(S, e);
-      double a = 0.0;
-      for (uint32_t m = e; m; m &= m - 1) {
-        const int b = S.jslot[__builtin_ctz(m)];
-        a += F[3ll * (y ^ (3u << b))] * ord_num(lt, N, r, r.ev[b], y & r.pt_mask, false) / den[y];
-      }
-      F[3ll * y] = a; F[3ll * y + 1] = 0.0; F[3ll * y + 2] = 0.0;
-    }
-    __syncthreads();
-  }
-  // seeded half, level by level: every move
-  for (int lev = 1; lev <= k; ++lev) {
-    opo_level<KB>(S.L, top >> c, V >> c, lev, [&](uint32_t y) {
-      double a = 0.0, bp = 0.0, bm = 0.0;
-      for (uint32_t m = y; m; m &= m - 1) {
-        const int b = __builtin_ctz(m);
-        const uint32_t x = y ^ (1u << b);
-        if (b == k - 1) {                       // the seeding itself, from a state whose tumours agree
-          const uint32_t lo = x & r.joint;
-          if (x != (lo | lo << 1)) continue;
-          a += F[3ll * x] * ord_num(lt, N, r, r.ev[b], y & in_mt, false) / den[y];
-          continue;
-        }
-        const bool pt_ev = r.kind[b] == ORD_K_PT;
-        const double num = ord_num(lt, N, r, r.ev[b], y & (pt_ev ? r.pt_mask : in_mt), false);
-        double fa = F[3ll * x], fp = F[3ll * x + 1], fm = F[3ll * x + 2];
-        ord_settle(r, t, x, fa, fp, fm);                                   // _advance
-        if (r.pt_first && !pt_ev) bp += fp * num / dmt[y];
-        if (r.mt_first && pt_ev) bm += fm * num / dpt[y];
-        a += fa * num / den[y];
-      }
-      F[3ll * y] = a; F[3ll * y + 1] = bp; F[3ll * y + 2] = bm;
-    });
-    __syncthreads();
-  }
-  // _settle's two coefficients at a seeded x (transposed: they carry the b's weights back to a)
-  auto settle_t = [&](uint32_t x, double& ga, double gp, double gm) {
-    if (r.pt_first && (x & r.pt_mask) == r.pt_mask) ga = ga + gp * (o1[x] / dmt[x]);
-    if (r.mt_first && (x & r.mt_mask) == r.mt_mask) ga = ga + gm * (o2[x] / dpt[x]);
-  };
-  if (tid == 0) {
-    double a = F[3ll * full], bp = F[3ll * full + 1], bm = F[3ll * full + 2];
-    ord_settle(r, t, full, a, bp, bm);
-    S.zsh = bp * o2[full] + bm * o1[full];                                 // _total
-    double ga = 0.0;
-    settle_t(full, ga, o2[full], o1[full]);
-    double* bf = B + 3ll * (full ^ top);
-    bf[0] = ga; bf[1] = o2[full]; bf[2] = o1[full];
-  }
-  __syncthreads();
-  for (int lev = k - 1; lev >= 1; --lev) {
-    opo_level<KB>(S.L, top >> c, V >> c, lev, [&](uint32_t x) {
-      double ga = 0.0, gp = 0.0, gm = 0.0;
-      for (uint32_t m = full & ~x; m; m &= m - 1) {
-        const int b = __builtin_ctz(m);
-        const uint32_t y = x | (1u << b);
-        const bool pt_ev = r.kind[b] == ORD_K_PT;
-        const double num = ord_num(lt, N, r, r.ev[b], y & (pt_ev ? r.pt_mask : in_mt), false);
-        const double* by = B + 3ll * (y ^ top);
-        ga += by[0] * num / den[y];
-        if (r.pt_first && !pt_ev) gp += by[1] * num / dmt[y];
-        if (r.mt_first && pt_ev) gm += by[2] * num / dpt[y];
-      }
-      settle_t(x, ga, gp, gm);
-      double* bx = B + 3ll * (x ^ top);
-      bx[0] = ga; bx[1] = gp; bx[2] = gm;
-    });
-    __syncthreads();
-  }
-  // backward over the unseeded states whose tumours agree: joint moves in ascending event, then the seeding edge
   for (int lev = kj; lev >= 0; --lev) {
     for (uint32_t e = tid; e < EJ; e += KB) {
       if (__builtin_popcount(e) != lev) continue;
       double s = 0.0;
-      for (uint32_t m = (EJ - 1u) & ~e; m; m &= m - 1) s += opr_joint_edge(S, N, P, e, __builtin_ctz(m));
-      S.bu[e] = s + opr_seed_edge(S, N, P, opr_joint_state(S, e));
+      for (uint32_t m = (EJ - 1u) & ~e; m; m &= m - 1) s += opr_joint_edge(S, N, P, bu, e, __builtin_ctz(m));
+      bu[e] = s + opr_seed_edge(S, N, P, opr_joint_state(S, e));
     }
     __syncthreads();
   }
-  return S.zsh;
 }
 
 // rows[blockIdx.x]; lt [N][N], obs1 / obs2 [N]; diagJ already in tab[toff ..] of the paired rows (k_diag, KD_DQ).
@@ -423,6 +231,7 @@ __global__ __launch_bounds__(KB) void k_order_prec(const ORow* __restrict__ rows
                                                    const double* __restrict__ g_o1, const double* __restrict__ g_o2, int N,
                                                    double* tab, double* out_le, double* out_prec) {
   __shared__ OprRow S;
+  __shared__ double bu[1 << OPO_CB];           // paired: B of the unseeded state of the joint events e
   __shared__ double Rs[32][32];                // Rs[d][c]: summed masses of the moves that add d from a state holding c
   __shared__ double Rj[OPO_CB + 1][OPO_CB + 1]; // paired, before the seeding: Rj[t][q] target joint event t (kj: the
                                                // seeding), held joint event q
@@ -441,7 +250,7 @@ __global__ __launch_bounds__(KB) void k_order_prec(const ORow* __restrict__ rows
     if (tid == 0) out_le[r.row] = log(Z);
     if (k == 0) return;
     const int m = k - 1;
-    opr_bit_sums<KB>(k, m, oprec_chunk_bits(m, KB), part,
+    opr_bit_sums<KB>(k, m, opo_chunk_bits(m, KB), part,
         [&](int d, uint32_t idx) { return opr_single_mass(S, N, den, F, d, idx); },
         [&](int d, int j, double s) { if (j < m) Rs[d][j < d ? j : j + 1] = s; });
     for (int i = tid; i < k * k; i += KB) {
@@ -453,18 +262,19 @@ __global__ __launch_bounds__(KB) void k_order_prec(const ORow* __restrict__ rows
 
   const OprPaired T = opr_paired_tables(r, den);
   const double Z = opr_paired_passes<KB>(S, N, T);
+  opr_unseeded_backward<KB>(S, N, T, bu);
   const int kj = T.kj;
   if (tid == 0) out_le[r.row] = log(Z);
   // after the seeding: target slot d < k - 1, the moves from the seeded x without d
   const int m = k >= 2 ? k - 2 : 0;
-  opr_bit_sums<KB>(k - 1, m, oprec_chunk_bits(m, KB), part,
+  opr_bit_sums<KB>(k - 1, m, opo_chunk_bits(m, KB), part,
       [&](int d, uint32_t idx) { return opr_seeded_mass(S, N, T, d, idx); },
       [&](int d, int j, double s) { Rs[d][j < m ? (j < d ? j : j + 1) : k - 1] = s; });   // every seeded x holds the seeding
   // before the seeding: the joint move of event q from the states without it, then the seeding from every such state
   opr_bit_sums<KB>(kj, kj > 0 ? kj - 1 : 0, kj > 0 ? kj - 1 : 0, pj,
       [&](int q, uint32_t idx) {
         const uint32_t e = opr_ins0(idx, q);
-        return T.F[3ll * opr_joint_state(S, e)] * opr_joint_edge(S, N, T, e, q);
+        return T.F[3ll * opr_joint_state(S, e)] * opr_joint_edge(S, N, T, bu, e, q);
       },
       [&](int q, int j, double s) { if (j < kj - 1) Rj[q][j < q ? j : j + 1] = s; });
   opr_bit_sums<KB>(1, kj, kj, pj,

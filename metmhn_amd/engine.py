@@ -394,61 +394,42 @@ class Engine:
                                                   status.ctypes.data_as(_lib.i32p)))
         return orders, prob, status
 
-    def order_posteriors(self, log_theta, obs1, obs2, dat):
-        """MetMHN.order_posterior of every row of a reference-format `dat` [n_pat, 2n+3] in one call
-        (mmhn_order_posteriors): float64 log_evidence [n_pat], pre [n_pat, n], seed_pos [n_pat, N], int32 status [n_pat]
-        (low half 0 ok, 2 invalid row - reason code in status >> 16 -, 3 lattice larger than the workspace; NaN outputs
-        wherever it is not 0, and in pre / seed_pos of the "absent" rows)."""
+    def _order_rows(self, fn, log_theta, obs1, obs2, dat, *shapes):
+        """One call of an mmhn_order_* entry point `fn` on a reference-format `dat`: log_evidence [n_pat], one float64 array
+        [n_pat, *shape] per result of the entry point, int32 status [n_pat]."""
         keep, (ltp, ap, bp) = self._params(log_theta, obs1, obs2)
         d = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
         if d.ndim != 2:
             raise ValueError("dat must be a 2-D array [n_pat, 2 n_mut + 3]")
         n_pat = d.shape[0]
-        le = np.zeros(n_pat)
-        pre = np.zeros((n_pat, self.n))
-        sp = np.zeros((n_pat, self.N))
+        out = [np.zeros(n_pat)] + [np.empty((n_pat,) + shape) for shape in shapes]      # (the library fills them with NaN first)
         status = np.zeros(n_pat, dtype=np.int32)
-        _lib.check(self.lib.mmhn_order_posteriors(self.h, ltp, ap, bp, d.ctypes.data_as(i8p), n_pat, int(d.shape[1]),
-                                                  le.ctypes.data_as(f64p), pre.ctypes.data_as(f64p),
-                                                  sp.ctypes.data_as(f64p), status.ctypes.data_as(_lib.i32p)))
-        return le, pre, sp, status
+        _lib.check(fn(self.h, ltp, ap, bp, d.ctypes.data_as(i8p), n_pat, int(d.shape[1]),
+                      *(a.ctypes.data_as(f64p) for a in out), status.ctypes.data_as(_lib.i32p)))
+        return (*out, status)
+
+    def order_posteriors(self, log_theta, obs1, obs2, dat):
+        """MetMHN.order_posterior of every row of a reference-format `dat` [n_pat, 2n+3] in one call
+        (mmhn_order_posteriors): float64 log_evidence [n_pat], pre [n_pat, n], seed_pos [n_pat, N], int32 status [n_pat]
+        (low half 0 ok, 2 invalid row - reason code in status >> 16 -, 3 lattice larger than the workspace; NaN outputs
+        wherever it is not 0, and in pre / seed_pos of the "absent" rows)."""
+        return self._order_rows(self.lib.mmhn_order_posteriors, log_theta, obs1, obs2, dat, (self.n,), (self.N,))
 
     def order_precedences(self, log_theta, obs1, obs2, dat):
         """MetMHN.order_precedence of every row of a reference-format `dat` [n_pat, 2n+3] in one call
         (mmhn_order_precedences): float64 log_evidence [n_pat], prec [n_pat, 2n+1, 2n+1] over the event codes (NaN where
         a code is not in the row), int32 status [n_pat] (low half 0 ok, 2 invalid row - reason code in status >> 16 -,
         3 lattice larger than the workspace; NaN outputs wherever it is not 0)."""
-        keep, (ltp, ap, bp) = self._params(log_theta, obs1, obs2)
-        d = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
-        if d.ndim != 2:
-            raise ValueError("dat must be a 2-D array [n_pat, 2 n_mut + 3]")
-        n_pat, L = d.shape[0], 2 * self.n + 1
-        le = np.zeros(n_pat)
-        prec = np.empty((n_pat, L, L))
-        status = np.zeros(n_pat, dtype=np.int32)
-        _lib.check(self.lib.mmhn_order_precedences(self.h, ltp, ap, bp, d.ctypes.data_as(i8p), n_pat, int(d.shape[1]),
-                                                   le.ctypes.data_as(f64p), prec.ctypes.data_as(f64p),
-                                                   status.ctypes.data_as(_lib.i32p)))
-        return le, prec, status
+        L = 2 * self.n + 1
+        return self._order_rows(self.lib.mmhn_order_precedences, log_theta, obs1, obs2, dat, (L, L))
 
     def order_positions(self, log_theta, obs1, obs2, dat):
         """MetMHN.order_position of every row of a reference-format `dat` [n_pat, 2n+3] in one call
         (mmhn_order_positions): float64 log_evidence [n_pat], pos_pt and pos_mt [n_pat, N, N] (event, position; NaN for an
         event the row does not carry in that lineage), int32 status [n_pat] (low half 0 ok, 2 invalid row - reason code in
         status >> 16 -, 3 lattice larger than the workspace; NaN outputs wherever it is not 0)."""
-        keep, (ltp, ap, bp) = self._params(log_theta, obs1, obs2)
-        d = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
-        if d.ndim != 2:
-            raise ValueError("dat must be a 2-D array [n_pat, 2 n_mut + 3]")
-        n_pat = d.shape[0]
-        le = np.zeros(n_pat)
-        pos_pt = np.empty((n_pat, self.N, self.N))
-        pos_mt = np.empty((n_pat, self.N, self.N))
-        status = np.zeros(n_pat, dtype=np.int32)
-        _lib.check(self.lib.mmhn_order_positions(self.h, ltp, ap, bp, d.ctypes.data_as(i8p), n_pat, int(d.shape[1]),
-                                                 le.ctypes.data_as(f64p), pos_pt.ctypes.data_as(f64p),
-                                                 pos_mt.ctypes.data_as(f64p), status.ctypes.data_as(_lib.i32p)))
-        return le, pos_pt, pos_mt, status
+        NN = (self.N, self.N)
+        return self._order_rows(self.lib.mmhn_order_positions, log_theta, obs1, obs2, dat, NN, NN)
 
     # ---- measurement
     def bench_kronvec(self, log_theta, state, batch, iters, transpose=False, jacobi=False, tiles=False):

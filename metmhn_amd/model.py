@@ -271,15 +271,49 @@ class MetMHN:
         self.orders_fallback_rows = fallback
         return out
 
-    def _row_order(self, dat, i: int):
+    def _row_args(self, dat, i: int):
+        """Row i of a reference-format dat as the (state, met_status, first_obs) of the one-observation entry points."""
         row = dat[i]
         status = _ROW_STATUS.get(int(row[-1]), f"type {int(row[-1])}")
         first = _ROW_FIRST.get(int(row[-2]), "Met") if status == "isPaired" else None
+        return MetState.from_seq(row[:2 * self.n + 1]), status, first
+
+    def _row_order(self, dat, i: int):
         try:
-            order, p = self.likeliest_order(MetState.from_seq(row[:2 * self.n + 1]), status, first)
+            order, p = self.likeliest_order(*self._row_args(dat, i))
         except ValueError as e:
             raise ValueError(f"row {i}: {e}") from e
         return tuple(int(e) for e in order), float(p)
+
+    def _order_cohort(self, device, one, fields: tuple, shapes: tuple, dat, backend: str) -> list:
+        """What order_posteriors / order_precedences / order_positions share: [log_evidence, the arrays of `fields` ...,
+        the number of rows the device turned away] of every row of dat, from the Engine method `device(engine)` with the
+        rows it turned away recomputed by `one` (the entry point of one observation), or from `one` alone (backend="host")."""
+        dat = np.asarray(dat)
+        if dat.ndim != 2 or dat.shape[1] != 2 * self.n + 3:
+            raise ValueError(f"dat must have shape [n_pat, {2 * self.n + 3}]")
+        if backend not in ("device", "host"):
+            raise ValueError("backend must be 'device' or 'host'")
+        P = dat.shape[0]
+        if backend == "host":
+            out = [np.zeros((P,) + shape) for shape in ((),) + shapes]
+            redo = range(P)
+        else:
+            from .jx import engine
+            *out, status = device(engine(self.n))(self.log_theta, self.obs1, self.obs2, dat)
+            bad = np.flatnonzero((status & 0xFFFF) == 2)
+            if bad.size:
+                i = int(bad[0])
+                raise ValueError(f"row {i}: {_ROW_ERRORS[int(status[i]) >> 16]}")
+            redo = [int(i) for i in np.flatnonzero(status != 0)]
+        for i in redo:
+            try:
+                r = one(*self._row_args(dat, i))
+            except ValueError as e:
+                raise ValueError(f"row {i}: {e}") from e
+            for a, field in zip(out, ("log_evidence",) + fields):
+                a[i] = getattr(r, field)
+        return out + [0 if backend == "host" else len(redo)]
 
     def order_posterior(self, state, met_status: str, first_obs: str = None) -> "OrderPosterior":
         """The sum over every admissible order where likeliest_order takes the maximum (same arguments, checks and
@@ -302,37 +336,10 @@ class MetMHN:
         fit the workspace is recomputed here with order_posterior - how many were is left in
         `self.posteriors_fallback_rows`.  backend="host": order_posterior row by row.  An invalid row raises
         likeliest_order's ValueError, with its index."""
-        dat = np.asarray(dat)
-        if dat.ndim != 2 or dat.shape[1] != 2 * self.n + 3:
-            raise ValueError(f"dat must have shape [n_pat, {2 * self.n + 3}]")
-        if backend not in ("device", "host"):
-            raise ValueError("backend must be 'device' or 'host'")
-        P = dat.shape[0]
-        if backend == "host":
-            le, pre, sp = np.zeros(P), np.zeros((P, self.n)), np.zeros((P, self.n + 1))
-            redo = range(P)
-        else:
-            from .jx import engine
-            le, pre, sp, status = engine(self.n).order_posteriors(self.log_theta, self.obs1, self.obs2, dat)
-            bad = np.flatnonzero((status & 0xFFFF) == 2)
-            if bad.size:
-                i = int(bad[0])
-                raise ValueError(f"row {i}: {_ROW_ERRORS[int(status[i]) >> 16]}")
-            redo = [int(i) for i in np.flatnonzero(status != 0)]
-        for i in redo:
-            r = self._row_posterior(dat, i)
-            le[i], pre[i], sp[i] = r.log_evidence, r.pre, r.seed_pos
-        self.posteriors_fallback_rows = 0 if backend == "host" else len(redo)
-        return OrderPosteriors(le, pre, sp)
-
-    def _row_posterior(self, dat, i: int):
-        row = dat[i]
-        status = _ROW_STATUS.get(int(row[-1]), f"type {int(row[-1])}")
-        first = _ROW_FIRST.get(int(row[-2]), "Met") if status == "isPaired" else None
-        try:
-            return self.order_posterior(MetState.from_seq(row[:2 * self.n + 1]), status, first)
-        except ValueError as e:
-            raise ValueError(f"row {i}: {e}") from e
+        shapes = ((self.n,), (self.n + 1,))
+        *out, self.posteriors_fallback_rows = self._order_cohort(
+            lambda eng: eng.order_posteriors, self.order_posterior, ("pre", "seed_pos"), shapes, dat, backend)
+        return OrderPosteriors(*out)
 
     def order_precedence(self, state, met_status: str, first_obs: str = None) -> "OrderPrecedence":
         """Which of two events came first, summed over every admissible order (same arguments, checks and errors as
@@ -359,37 +366,10 @@ class MetMHN:
         fit the workspace is recomputed here with order_precedence - how many were is left in
         `self.precedences_fallback_rows`.  backend="host": order_precedence row by row.  An invalid row raises
         likeliest_order's ValueError, with its index."""
-        dat = np.asarray(dat)
-        if dat.ndim != 2 or dat.shape[1] != 2 * self.n + 3:
-            raise ValueError(f"dat must have shape [n_pat, {2 * self.n + 3}]")
-        if backend not in ("device", "host"):
-            raise ValueError("backend must be 'device' or 'host'")
-        P, L = dat.shape[0], 2 * self.n + 1
-        if backend == "host":
-            le, prec = np.zeros(P), np.zeros((P, L, L))
-            redo = range(P)
-        else:
-            from .jx import engine
-            le, prec, status = engine(self.n).order_precedences(self.log_theta, self.obs1, self.obs2, dat)
-            bad = np.flatnonzero((status & 0xFFFF) == 2)
-            if bad.size:
-                i = int(bad[0])
-                raise ValueError(f"row {i}: {_ROW_ERRORS[int(status[i]) >> 16]}")
-            redo = [int(i) for i in np.flatnonzero(status != 0)]
-        for i in redo:
-            r = self._row_precedence(dat, i)
-            le[i], prec[i] = r.log_evidence, r.prec
-        self.precedences_fallback_rows = 0 if backend == "host" else len(redo)
-        return OrderPrecedences(le, prec)
-
-    def _row_precedence(self, dat, i: int):
-        row = dat[i]
-        status = _ROW_STATUS.get(int(row[-1]), f"type {int(row[-1])}")
-        first = _ROW_FIRST.get(int(row[-2]), "Met") if status == "isPaired" else None
-        try:
-            return self.order_precedence(MetState.from_seq(row[:2 * self.n + 1]), status, first)
-        except ValueError as e:
-            raise ValueError(f"row {i}: {e}") from e
+        L = 2 * self.n + 1
+        *out, self.precedences_fallback_rows = self._order_cohort(
+            lambda eng: eng.order_precedences, self.order_precedence, ("prec",), ((L, L),), dat, backend)
+        return OrderPrecedences(*out)
 
     def order_position(self, state, met_status: str, first_obs: str = None) -> "OrderPosition":
         """At which position of its lineage every event happened, summed over every admissible order (same arguments,
@@ -419,37 +399,10 @@ class MetMHN:
         fit the workspace is recomputed here with order_position - how many were is left in
         `self.positions_fallback_rows`.  backend="host": order_position row by row.  An invalid row raises
         likeliest_order's ValueError, with its index."""
-        dat = np.asarray(dat)
-        if dat.ndim != 2 or dat.shape[1] != 2 * self.n + 3:
-            raise ValueError(f"dat must have shape [n_pat, {2 * self.n + 3}]")
-        if backend not in ("device", "host"):
-            raise ValueError("backend must be 'device' or 'host'")
-        P, N = dat.shape[0], self.n + 1
-        if backend == "host":
-            le, pos_pt, pos_mt = np.zeros(P), np.zeros((P, N, N)), np.zeros((P, N, N))
-            redo = range(P)
-        else:
-            from .jx import engine
-            le, pos_pt, pos_mt, status = engine(self.n).order_positions(self.log_theta, self.obs1, self.obs2, dat)
-            bad = np.flatnonzero((status & 0xFFFF) == 2)
-            if bad.size:
-                i = int(bad[0])
-                raise ValueError(f"row {i}: {_ROW_ERRORS[int(status[i]) >> 16]}")
-            redo = [int(i) for i in np.flatnonzero(status != 0)]
-        for i in redo:
-            r = self._row_position(dat, i)
-            le[i], pos_pt[i], pos_mt[i] = r.log_evidence, r.pos_pt, r.pos_mt
-        self.positions_fallback_rows = 0 if backend == "host" else len(redo)
-        return OrderPositions(le, pos_pt, pos_mt)
-
-    def _row_position(self, dat, i: int):
-        row = dat[i]
-        status = _ROW_STATUS.get(int(row[-1]), f"type {int(row[-1])}")
-        first = _ROW_FIRST.get(int(row[-2]), "Met") if status == "isPaired" else None
-        try:
-            return self.order_position(MetState.from_seq(row[:2 * self.n + 1]), status, first)
-        except ValueError as e:
-            raise ValueError(f"row {i}: {e}") from e
+        NN = (self.n + 1, self.n + 1)
+        *out, self.positions_fallback_rows = self._order_cohort(
+            lambda eng: eng.order_positions, self.order_position, ("pos_pt", "pos_mt"), (NN, NN), dat, backend)
+        return OrderPositions(*out)
 
     def likelihood(self, order, met_status: str, first_obs: str = None) -> float:
         """model.py:295-376: probability of exactly this order of events being what is observed."""
