@@ -284,6 +284,28 @@ int mmhn_order_positions(mmhn_handle h, const double* log_theta, const double* o
                          const int8_t* dat, int64_t n_pat, int n_cols, double* log_evidence, double* pos_pt,
                          double* pos_mt, int32_t* status);
 
+/* ---- posterior samples of the event orders of a cohort ---------------------------------------
+ * mmhn_order_samples: for every row of a reference-format `dat` (read as mmhn_likeliest_orders reads it), orders drawn from
+ * the exact posterior over the admissible orders mmhn_order_posteriors sums over: an order comes with the probability
+ * likelihood(order) / evidence.  The draw is metmhn_amd/model.py MetMHN.sample_order, move by move on the backward weights of
+ * the row's lattice (metmhn_amd/csrc/ordersample.h).  Samples first ... first + n_samples - 1 of every row; Philox4x32-10, key
+ * = `seed`, counter = (sample index low word, high word, move number, cohort row + 1) - a sample depends on (seed, cohort row,
+ * sample index) only, not on n_samples or the batching; counter word 3 = 0 is mmhn_simulate's stream.  No reference
+ * counterpart.  fp64 engines only.
+ *   log_evidence [n_pat]                        as mmhn_order_posteriors
+ *   orders [n_pat][n_samples][2 n_mut + 1]      event codes as in mmhn_likeliest_orders, padded with -1
+ *   log_prob [n_pat][n_samples]                 log P(order | the row); log_evidence + log_prob = log likelihood(order)
+ *   status [n_pat]: as mmhn_order_precedences (rows of more than 10 joint events are MMHN_ORD_TOO_LARGE); where it is not 0
+ *   the row's orders are all -1 and its log_prob NaN.  Workspace of a row: the lattice of mmhn_order_posteriors plus its
+ *   share of the output, n_samples x (2 n_mut + 1 + 8) bytes.
+ * n_samples = 0 is valid and returns the evidence only (orders and log_prob may be null).  No atomics: two calls return the
+ * same bytes, whatever the batching.  Rows are cut into batches that fit mmhn_set_workspace_limit; the call leaves a loaded
+ * cohort as it was.
+ */
+int mmhn_order_samples(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, const int8_t* dat,
+                       int64_t n_pat, int n_cols, int64_t first, int64_t n_samples, uint64_t seed, double* log_evidence,
+                       int8_t* orders, double* log_prob, int32_t* status);
+
 /* ---- measurement -------------------------------------------------------------------
  * mmhn_bench_kronvec: `batch` resident copies of a 2^k vector, `iters` back-to-back
  * launches of mmhn_kronvec_batched's launch (diag = 0: y = Q_off p into a NaN-filled y, every tile of every vector,
@@ -314,7 +336,7 @@ typedef struct {
   int32_t comm_rank;  /* this engine's rank in it (ncclCommUserRank), -1: none */
 } mmhn_counters;
 /* ABI version of this header: bumped whenever an exported signature or structure changes (4: mmhn_bench_kronvec has its
- * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences and mmhn_order_positions were added within version 8, purely additive changes).  A client built against another header must refuse to run:
+ * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions and mmhn_order_samples were added within version 8, purely additive changes).  A client built against another header must refuse to run:
  * mmhn_abi_version() != MMHN_ABI_VERSION (metmhn_amd/_lib.py checks it on load). */
 #define MMHN_ABI_VERSION 8
 int mmhn_abi_version(void);

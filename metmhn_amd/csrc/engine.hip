@@ -2,8 +2,8 @@
 // C ABI of include/metmhn_amd.h.  One engine = one GPU, one HIP stream.
 // The rest of the host side lives in headers of this one translation unit: plan.h (the cohort planner, host-only:
 // batches, routes, work lists, offsets), host.h (errors, device arrays, MMHN_* knob readers), comm.h (RCCL),
-// prims.h / orders_host.h / orderpost_host.h (the batching of the three order-posterior entry points, opr_rows) /
-// orderprec_host.h / orderpos_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
+// prims.h / orders_host.h / orderpost_host.h (the batching of the order-posterior entry points, opr_rows) /
+// orderprec_host.h / orderpos_host.h / ordersample_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
 //
 // Pipeline of one evaluation (reference call graph: regularized_optimization.py:163-267 ->
 // likelihood.py:_g_coupled_*, _grad_prim_obs, _grad_met_obs), run batch by batch with every
@@ -1018,6 +1018,7 @@ struct Engine : EngineBase {
 #include "orderpost_host.h"
 #include "orderprec_host.h"
 #include "orderpos_host.h"
+#include "ordersample_host.h"
 #include "sampler_host.h"
 #include "bench.h"
 
@@ -1510,6 +1511,25 @@ int mmhn_order_positions(mmhn_handle h, const double* log_theta, const double* o
   REQUIRE(h->dtype == MMHN_F64, "order positions need an fp64 engine (MMHN_F64)");
   order_positions(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, log_evidence, pos_pt,
                   pos_mt, status);
+  API_END
+}
+
+// ---- posterior samples of the event orders of a cohort: orders drawn with their exact probability given the row
+int mmhn_order_samples(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, const int8_t* dat,
+                       int64_t n_pat, int n_cols, int64_t first, int64_t n_samples, uint64_t seed, double* log_evidence,
+                       int8_t* orders, double* log_prob, int32_t* status) {
+  API_BEGIN
+  GUARD(h);
+  REQUIRE(log_theta && obs1 && obs2 && log_evidence && status, "null pointer");
+  REQUIRE(dat || n_pat == 0, "null dat");
+  REQUIRE(n_pat >= 0 && n_pat < ((int64_t)1 << 31), "n_pat out of range");
+  REQUIRE(first >= 0, "first must be non-negative");
+  REQUIRE(n_samples >= 0 && n_samples < ((int64_t)1 << 31), "n_samples out of range");
+  REQUIRE(n_samples <= INT64_MAX - first, "first + n_samples overflows 64 bits");
+  REQUIRE((orders && log_prob) || n_samples == 0, "null pointer");
+  REQUIRE(h->dtype == MMHN_F64, "order samples need an fp64 engine (MMHN_F64)");
+  order_samples(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, first, n_samples, seed,
+                log_evidence, orders, log_prob, status);
   API_END
 }
 

@@ -13,10 +13,11 @@ namespace mmhn {
 template <typename T, class Scatter>
 void opr_move_rows(Engine<T>& E, const double* lt, const double* obs1, const double* obs2, const int8_t* dat, long long npat,
                    int ncols, double* log_ev, int32_t* status, OprKernel k256, OprKernel k1024, Scatter scatter) {
-  opr_rows(E, lt, obs1, obs2, dat, npat, ncols, log_ev, status, k256, k1024,
+  opr_rows(E, lt, obs1, obs2, dat, npat, ncols, log_ev, status, opr_launch(k256, k1024),
            [](const ORow& r) { return oprec_doubles(r, r.k >= ORD_BIG_K ? 1024 : 256); },
-           [](const ORow& r) { return (long long)r.k * r.k; },
-           [](const ORow& r) { return __builtin_popcount(r.joint) <= OPO_CB; }, scatter);
+           [](const ORow& r) { return (long long)r.k * r.k; }, [](const ORow&) { return 0ll; }, false,
+           [](const ORow& r) { return __builtin_popcount(r.joint) <= OPO_CB; },
+           [&](const ORow& r, long long i, const double* in, const int8_t*) { scatter(r, i, in); });
 }
 
 // prec [npat][2n+1][2n+1] over the event codes: NaN where a code is not in the row.

@@ -31,7 +31,7 @@ struct ORow {
   int mode;            // ORD_PT / ORD_MT / ORD_PAIRED
   int pt_first, mt_first;
   int row;             // row of the output arrays
-  int pad_;
+  int pad_;            // the cohort row (opr_rows sets it; `row` is the row of the batch there)
   long long toff;      // tables: paired den, o1, o2, den_mt, den_pt (5 x 2^k); one tumour den, best (2 x 2^k)
   long long foff;      // front slots (paired: 2^k x cap) / back-pointers of the Viterbi (2^k)
   long long coff;      // front sizes (paired: 2^k)

@@ -431,6 +431,30 @@ class Engine:
         NN = (self.N, self.N)
         return self._order_rows(self.lib.mmhn_order_positions, log_theta, obs1, obs2, dat, NN, NN)
 
+    def order_samples(self, log_theta, obs1, obs2, dat, n_samples, seed=0, first=0):
+        """MetMHN.sample_order of every row of a reference-format `dat` [n_pat, 2n+3] in one call (mmhn_order_samples), row
+        i with row=i, the sample indices first ... first + n_samples - 1 under the 64-bit `seed`: float64 log_evidence
+        [n_pat], int8 orders [n_pat, n_samples, 2n+1] padded with -1, float64 log_prob [n_pat, n_samples], int32 status
+        [n_pat] (low half 0 ok, 2 invalid row - reason code in status >> 16 -, 3 lattice and samples larger than the
+        workspace; orders -1 and log_prob NaN wherever it is not 0)."""
+        keep, (ltp, ap, bp) = self._params(log_theta, obs1, obs2)
+        d = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
+        if d.ndim != 2:
+            raise ValueError("dat must be a 2-D array [n_pat, 2 n_mut + 3]")
+        n_samples, first = int(n_samples), int(first)
+        if n_samples < 0 or first < 0:
+            raise ValueError(f"n_samples and first must be non-negative, got n_samples={n_samples}, first={first}")
+        n_pat = d.shape[0]
+        le = np.zeros(n_pat)
+        orders = np.empty((n_pat, n_samples, 2 * self.n + 1), dtype=np.int8)      # (the library fills them first)
+        log_prob = np.empty((n_pat, n_samples))
+        status = np.zeros(n_pat, dtype=np.int32)
+        _lib.check(self.lib.mmhn_order_samples(self.h, ltp, ap, bp, d.ctypes.data_as(i8p), n_pat, int(d.shape[1]), first,
+                                               n_samples, int(seed) & (2 ** 64 - 1), le.ctypes.data_as(f64p),
+                                               orders.ctypes.data_as(i8p), log_prob.ctypes.data_as(f64p),
+                                               status.ctypes.data_as(_lib.i32p)))
+        return le, orders, log_prob, status
+
     # ---- measurement
     def bench_kronvec(self, log_theta, state, batch, iters, transpose=False, jacobi=False, tiles=False):
         """ms per launch of mmhn_kronvec_batched's launch (or the fused Jacobi step); tiles=True also returns

@@ -33,6 +33,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
+from . import _philox
 from .jx import kronvec as _kronvec
 from .state import MetState, State
 
@@ -169,6 +170,80 @@ class OrderPositions(OrderPosition):
         return out
 
 
+class OrderSample(SimpleNamespace):
+    """Orders of one observation drawn from its exact posterior: log_evidence, orders [n_samples, 2n+1] (int8 event codes
+    of likeliest_order, padded with -1), log_prob [n_samples] = log P(order | the observation), margin [n_samples] = the
+    smallest |u total - cumulative boundary| / total over the sample's moves (how far its draws stayed from every
+    boundary: a last-bit difference of a weight cannot change a sample whose margin is larger than that difference), and
+    totals [n_samples, moves] = the summed candidate weights of every move (NaN past the sample's last move)."""
+
+    def __init__(self, log_evidence, orders, log_prob, margin, totals=None):
+        super().__init__(log_evidence=log_evidence, orders=orders, log_prob=log_prob, margin=margin, totals=totals)
+
+
+def _entry_times(orders: np.ndarray):
+    """Of sampled orders [..., L] (event codes padded with -1): the codes as int64, whether an order holds the seeding,
+    the seeding's index, and which entries are the second code of a joint event (2i, 2i+1 written next to each other
+    before the seeding: both happen at the moment of the first)."""
+    o = orders.astype(np.int64)
+    L = o.shape[-1]
+    pos = np.arange(L)
+    is_seed = o == L - 1
+    seeded = is_seed.any(axis=-1)
+    sp = np.where(seeded, is_seed.argmax(axis=-1), 0)
+    second = np.zeros(o.shape, dtype=bool)
+    second[..., 1:] = (o[..., 1:] == o[..., :-1] + 1) & (o[..., :-1] % 2 == 0) & (pos[1:] < sp[..., None])
+    return o, seeded, sp, second
+
+
+class OrderSamples(SimpleNamespace):
+    """Orders of every row of a cohort drawn from the rows' exact posteriors: log_evidence [n_pat], orders
+    [n_pat, n_samples, 2n+1] (int8, padded with -1), log_prob [n_pat, n_samples]."""
+
+    def __init__(self, log_evidence, orders, log_prob):
+        super().__init__(log_evidence=log_evidence, orders=orders, log_prob=log_prob)
+
+    def preseeding(self, rows_per_step: int = 256) -> np.ndarray:
+        """[n_pat, n]: the share of a row's samples in which mutation m occurred before the seeding - the sample mean
+        that estimates order_posteriors().pre; NaN in the rows without the seeding (and without samples)."""
+        P, S, L = self.orders.shape
+        n = (L - 1) // 2
+        out = np.full((P, n), np.nan)
+        if S == 0:
+            return out
+        pos = np.arange(L)
+        for lo in range(0, P, rows_per_step):
+            o, seeded, sp, second = _entry_times(self.orders[lo:lo + rows_per_step])
+            R = o.shape[0]
+            count = (pos < sp[..., None]) & ~second & (o >= 0)            # an event before the seeding, counted once
+            idx = (np.arange(R)[:, None, None] * n + (o >> 1))[count]
+            share = np.bincount(idx, minlength=R * n).reshape(R, n) / S
+            out[lo:lo + R] = np.where(seeded[:, :1], share, np.nan)
+        return out
+
+    def precedence(self) -> np.ndarray:
+        """[n_pat, 2n+1, 2n+1]: the share of a row's samples in which code c happened strictly earlier than code d - the
+        sample mean that estimates order_precedences().prec (the two codes of a joint event before the seeding happen at
+        the same moment); NaN where a code is not in the row."""
+        P, S, L = self.orders.shape
+        out = np.full((P, L, L), np.nan)
+        if S == 0:
+            return out
+        pos, rows = np.arange(L), np.arange(S)[:, None]
+        for p in range(P):
+            o, _, _, second = _entry_times(self.orders[p])
+            k = int((o[0] >= 0).sum())
+            if k == 0:
+                continue
+            t = np.broadcast_to(pos, (S, L)) - second                     # the moment of every entry
+            when = np.zeros((S, L), dtype=np.int64)
+            when[rows, o[:, :k]] = t[:, :k]                               # ... and of every code
+            codes = np.sort(o[0, :k])
+            w = when[:, codes]
+            out[p][np.ix_(codes, codes)] = (w[:, :, None] < w[:, None, :]).mean(axis=0)
+        return out
+
+
 class MetMHN:
     """The metastasis MHN with its two observation-rate vectors (model.py:175-211)."""
 
@@ -186,6 +261,7 @@ class MetMHN:
         self.posteriors_fallback_rows = 0   # ... and the last order_posteriors call
         self.precedences_fallback_rows = 0  # ... and the last order_precedences call
         self.positions_fallback_rows = 0    # ... and the last order_positions call
+        self.samples_fallback_rows = 0      # ... and the last sample_orders call
 
     # ------------------------------------------------------------------ diagonals
     def _get_diag_unpaired(self, state: State, seeding: bool = True) -> np.ndarray:
@@ -285,10 +361,13 @@ class MetMHN:
             raise ValueError(f"row {i}: {e}") from e
         return tuple(int(e) for e in order), float(p)
 
-    def _order_cohort(self, device, one, fields: tuple, shapes: tuple, dat, backend: str) -> list:
-        """What order_posteriors / order_precedences / order_positions share: [log_evidence, the arrays of `fields` ...,
-        the number of rows the device turned away] of every row of dat, from the Engine method `device(engine)` with the
-        rows it turned away recomputed by `one` (the entry point of one observation), or from `one` alone (backend="host")."""
+    def _order_cohort(self, device, one, fields: tuple, shapes: tuple, dat, backend: str, dtypes: tuple = None,
+                      with_row: bool = False) -> list:
+        """What order_posteriors / order_precedences / order_positions / sample_orders share: [log_evidence, the arrays of
+        `fields` ..., the number of rows the device turned away] of every row of dat, from the Engine method
+        `device(engine)` with the rows it turned away recomputed by `one` (the entry point of one observation), or from
+        `one` alone (backend="host").  dtypes: of the arrays of `fields` (float64 each by default); with_row: `one` also
+        takes the row's index (row=i)."""
         dat = np.asarray(dat)
         if dat.ndim != 2 or dat.shape[1] != 2 * self.n + 3:
             raise ValueError(f"dat must have shape [n_pat, {2 * self.n + 3}]")
@@ -296,7 +375,8 @@ class MetMHN:
             raise ValueError("backend must be 'device' or 'host'")
         P = dat.shape[0]
         if backend == "host":
-            out = [np.zeros((P,) + shape) for shape in ((),) + shapes]
+            kinds = (np.float64,) + tuple(dtypes or (np.float64,) * len(shapes))
+            out = [np.zeros((P,) + shape, dtype=kind) for shape, kind in zip(((),) + shapes, kinds)]
             redo = range(P)
         else:
             from .jx import engine
@@ -308,7 +388,7 @@ class MetMHN:
             redo = [int(i) for i in np.flatnonzero(status != 0)]
         for i in redo:
             try:
-                r = one(*self._row_args(dat, i))
+                r = one(*self._row_args(dat, i), row=i) if with_row else one(*self._row_args(dat, i))
             except ValueError as e:
                 raise ValueError(f"row {i}: {e}") from e
             for a, field in zip(out, ("log_evidence",) + fields):
@@ -403,6 +483,62 @@ class MetMHN:
         *out, self.positions_fallback_rows = self._order_cohort(
             lambda eng: eng.order_positions, self.order_position, ("pos_pt", "pos_mt"), (NN, NN), dat, backend)
         return OrderPositions(*out)
+
+    def sample_order(self, state, met_status: str, first_obs: str = None, n_samples: int = 1, key: int = 0, first: int = 0,
+                     row: int = 0) -> "OrderSample":
+        """Orders drawn from the exact posterior over the admissible orders of one observation (same arguments, checks and
+        errors as order_posterior): an order comes with the probability likelihood(order) / evidence.  This is the
+        definition the device kernel (csrc/ordersample.h: k_order_sample) follows operation by operation.
+
+        A path starts at the empty sub-state and makes moves up to the full state.  The candidates of a move are visited
+        in a fixed order, their weights w - the move's factor times the backward weight of the state it leads to - summed
+        in that order to `total`; the move taken is the first candidate whose cumulative weight exceeds u * total (if
+        rounding lets the loop fall through, the last candidate with w > 0: gillespie_step's rule), and log_prob
+        accumulates log(w / total).
+          one tumour              from x every slot b not in x, ascending: w = num_b[x | b] G[x | b]  (_single_passes)
+          paired, before seeding  from the joint events e the joint move of every event not in e, ascending (its PT code,
+                                  then its MT code), then the seeding: _unseeded_backward's terms, total = Bu
+          paired, after seeding   the path carries its own prefix vector f; at x, (fa, fp, fm) = _settle(x, f), every slot
+                                  b < k - 1 not in x, ascending, y = x | b: g = _advance's vector, w = B[y] . g, and
+                                  f = g / w after the choice, so that the next total is 1 up to rounding.  The seeding move
+                                  is a choice like any other: it leaves f = (1 / B[y]_a, 0, 0)
+        u: one Philox4x32-10 uniform per move (_philox.order_uniforms), key = the 64-bit `key`, counter = (sample index low
+        word, high word, move number, row + 1) for the sample indices first ... first + n_samples - 1: a sample depends on
+        (key, row, its index) only."""
+        n_samples, first = int(n_samples), int(first)
+        if n_samples < 0 or first < 0:
+            raise ValueError(f"n_samples and first must be non-negative, got n_samples={n_samples}, first={first}")
+        chain, st = self._route(state, met_status, first_obs)
+        samples = np.uint64(first) + np.arange(n_samples, dtype=np.uint64)
+        if chain == "mt":
+            T = self._single_tables(self.log_theta, st, self.obs2)
+            return self._sample_single(T, [2 * self.n if e == self.n else 2 * e + 1 for e in T.ev], samples, key, row)
+        if chain == "pt":
+            T = self._single_tables(self._pt_log_theta, st, self.obs1)
+            return self._sample_single(T, [2 * e for e in T.ev], samples, key, row)
+        return self._sample_paired(st, first_obs, samples, key, row)
+
+    def sample_orders(self, dat, n_samples: int, key: int = 0, first: int = 0, backend: str = "device") -> "OrderSamples":
+        """sample_order of every row of a reference-format `dat` [n_pat, 2n+3], rows read as order_posteriors reads them,
+        row i with row=i: arrays log_evidence [n_pat], orders [n_pat, n_samples, 2n+1] (int8), log_prob [n_pat, n_samples].
+
+        backend="device": every row in one call of the HIP library (mmhn_order_samples); a row whose lattice and samples
+        do not fit the workspace is drawn here with sample_order - how many were is left in `self.samples_fallback_rows`.
+        backend="host": sample_order row by row.  An invalid row raises likeliest_order's ValueError, with its index."""
+        dat = np.asarray(dat)
+        if dat.ndim != 2 or dat.shape[1] != 2 * self.n + 3:
+            raise ValueError(f"dat must have shape [n_pat, {2 * self.n + 3}]")
+        if backend not in ("device", "host"):
+            raise ValueError("backend must be 'device' or 'host'")
+        n_samples, first = int(n_samples), int(first)
+        if n_samples < 0 or first < 0:
+            raise ValueError(f"n_samples and first must be non-negative, got n_samples={n_samples}, first={first}")
+        *out, self.samples_fallback_rows = self._order_cohort(
+            lambda eng: lambda lt, o1, o2, d: eng.order_samples(lt, o1, o2, d, n_samples, key, first),
+            lambda st, status, fo, row: self.sample_order(st, status, fo, n_samples, key, first, row),
+            ("orders", "log_prob"), ((n_samples, 2 * self.n + 1), (n_samples,)), dat, backend,
+            dtypes=(np.int8, np.float64), with_row=True)
+        return OrderSamples(*out)
 
     def likelihood(self, order, met_status: str, first_obs: str = None) -> float:
         """model.py:295-376: probability of exactly this order of events being what is observed."""
@@ -569,6 +705,41 @@ class MetMHN:
             w = F[xs] * T.num[d][xs | 1 << d] * G[xs | 1 << d]
             pos[T.ev[d]] = np.minimum(np.bincount(held[xs], weights=w, minlength=self.n + 1) / Z, 1.0)
         return float(np.log(Z)), pos
+
+    @staticmethod
+    def _draw(W, u):
+        """One move of every sample: W [M, C] the candidates' weights in visiting order (0: not a candidate), u [M] the
+        uniforms.  Returns the candidate taken, its weight, the total and |u total - boundary| / total of the nearest
+        boundary of a candidate with w > 0."""
+        cum = np.add.accumulate(W, axis=1)                  # one after the other, as the kernel's loop
+        total = cum[:, -1]
+        t = u * total
+        above = cum > t[:, None]
+        last = W.shape[1] - 1 - np.argmax(W[:, ::-1] > 0.0, axis=1)
+        pick = np.where(above.any(axis=1), np.argmax(above, axis=1), last)
+        dist = np.where(W > 0.0, np.abs(cum - t[:, None]), np.inf).min(axis=1) / total
+        return pick, W[np.arange(len(pick)), pick], total, dist
+
+    def _sample_single(self, T, codes, samples, key, row) -> "OrderSample":
+        """sample_order on a one-tumour chain: the weights of _single_passes' backward pass, move by move."""
+        _, Z, G = self._single_passes(T)
+        k, M = T.k, len(samples)
+        codes = np.array(codes, dtype=np.int8)
+        orders = np.full((M, 2 * self.n + 1), -1, dtype=np.int8)
+        log_prob, margin, totals = np.zeros(M), np.full(M, np.inf), np.full((M, k), np.nan)
+        x = np.zeros(M, dtype=np.int64)
+        for move in range(k):
+            W = np.zeros((M, k))
+            for b in range(k):
+                y = x | 1 << b
+                W[:, b] = np.where(x >> b & 1, 0.0, T.num[b][y] * G[y])
+            pick, w, total, dist = self._draw(W, _philox.order_uniforms(key, row, samples, move))
+            orders[:, move] = codes[pick]
+            log_prob += np.log(w / total)
+            margin = np.minimum(margin, dist)
+            totals[:, move] = total
+            x |= 1 << pick
+        return OrderSample(float(np.log(Z)), orders, log_prob, margin, totals)
 
     def _likelihood_unpaired_mt(self, order) -> float:
         """model.py:1391-1426: a metastasis seen once (obs2), the chain feeling the seeding."""
@@ -848,6 +1019,81 @@ class MetMHN:
                         P[c, b] += w
                         P[c, b + 1] += w
         return OrderPrecedence(float(np.log(Z)), self._precedence_matrix(T.slots, P, Z))
+
+    def _sample_paired(self, state: MetState, first_obs: str, samples, key, row) -> "OrderSample":
+        """sample_order on a paired row: _unseeded_backward's terms before the seeding, then the three terms of a seeded
+        move's mass (_precedence_paired) with the path's own prefix vector in F's place."""
+        T, F, Z, B = self._paired_passes(state, first_obs)
+        Bu = self._unseeded_backward(T, F, B)
+        k, M = T.k, len(samples)
+        top, full = 1 << (k - 1), (1 << k) - 1
+        Ba, Bua = np.zeros((1 << k, 3)), np.zeros(1 << k)
+        Ba[list(B)] = list(B.values())
+        Bua[list(Bu)] = list(Bu.values())
+        jslot = np.array([b for b in range(k - 1) if T.joint >> b & 1], dtype=np.int64)
+        kj = len(jslot)
+        slots = np.array(T.slots, dtype=np.int8)
+        orders = np.full((M, 2 * self.n + 1), -1, dtype=np.int8)
+        log_prob, margin, totals = np.zeros(M), np.full(M, np.inf), np.full((M, k), np.nan)
+        x, held = np.zeros(M, dtype=np.int64), np.zeros(M, dtype=np.int64)
+        f = np.zeros((M, 3))
+        move = 0
+        while M and (x != full).any():
+            u = _philox.order_uniforms(key, row, samples, move)
+            before, after = np.flatnonzero(x < top), np.flatnonzero((x >= top) & (x != full))
+            if before.size:
+                xs = x[before]
+                W = np.zeros((before.size, kj + 1))
+                for q, b in enumerate(jslot):
+                    y = xs | 3 << b
+                    W[:, q] = np.where(xs >> b & 1, 0.0, T.num[b][y] / T.den[y] * Bua[y])
+                y = xs | top
+                W[:, kj] = T.num[k - 1][y] / T.den[y] * Ba[y, 0]
+                pick, w, total, dist = self._draw(W, u[before])
+                log_prob[before] += np.log(w / total)
+                margin[before] = np.minimum(margin[before], dist)
+                totals[before, move] = total
+                jm = pick < kj
+                a, b = before[jm], jslot[pick[jm]] if kj else pick[jm]
+                orders[a, held[a]], orders[a, held[a] + 1] = slots[b], slots[b + 1]      # the PT code, then the MT code
+                held[a] += 2
+                x[a] |= 3 << b
+                a = before[~jm]
+                orders[a, held[a]] = slots[k - 1]
+                held[a] += 1
+                x[a] |= top
+                f[a] = 0.0
+                f[a, 0] = 1.0 / Ba[x[a], 0]
+            if after.size:
+                xs = x[after]
+                fa, fp, fm = f[after].T
+                if T.pt_first:                                              # _settle
+                    fp = np.where(xs & T.pt_mask == T.pt_mask, fp + fa * T.o1[xs] / T.den_mt[xs], fp)
+                if T.mt_first:
+                    fm = np.where(xs & T.mt_mask == T.mt_mask, fm + fa * T.o2[xs] / T.den_pt[xs], fm)
+                W, g = np.zeros((after.size, k - 1)), np.zeros((after.size, k - 1, 3))
+                for b in range(k - 1):
+                    y = xs | 1 << b
+                    num = T.num[b][y]
+                    g[:, b, 0] = fa * num / T.den[y]
+                    w = Ba[y, 0] * g[:, b, 0]
+                    if T.pt_first and T.kind[b] == 1:
+                        g[:, b, 1] = fp * num / T.den_mt[y]
+                        w = w + Ba[y, 1] * g[:, b, 1]
+                    if T.mt_first and T.kind[b] == 0:
+                        g[:, b, 2] = fm * num / T.den_pt[y]
+                        w = w + Ba[y, 2] * g[:, b, 2]
+                    W[:, b] = np.where(xs >> b & 1, 0.0, w)
+                pick, w, total, dist = self._draw(W, u[after])
+                log_prob[after] += np.log(w / total)
+                margin[after] = np.minimum(margin[after], dist)
+                totals[after, move] = total
+                f[after] = g[np.arange(after.size), pick] / w[:, None]
+                orders[after, held[after]] = slots[pick]
+                held[after] += 1
+                x[after] |= 1 << pick
+            move += 1
+        return OrderSample(float(np.log(Z)), orders, log_prob, margin, totals)
 
     def _likeliest_order_paired(self, state: MetState, first_obs: str):
         """model.py:503-1389 (_likeliest_order_pt_mt / _mt_pt / _unknown / _sync)."""
