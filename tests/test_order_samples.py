@@ -9,64 +9,30 @@ Anchors:
     difference of a weight (exp may round differently on the device) cannot change them;
   * on rows too large for the host code, the sample means against the exact marginals of order_posteriors and
     order_precedences, which the samples do not share a reduction with.
+What sample_orders shares with the other cohort entry points: order_common.check_* and tests/test_order_contract.py.
 
 Bars.  Statistical: a frequency of M samples against its exact probability p, |freq - p| <= 5 sqrt(p (1 - p) / M) + 1 / M.
 Numerical: 1e-12 relative for what the host computes twice (likelihoods, totals), 1e-10 for log_prob between device and
 host (a sum of at most k logs of quotients that differ by a few ulp) and for the device's likelihoods of large rows.  The
-keys are fixed here.  Every test prints the worst value it saw before it asserts.
+keys are fixed in tests/order_common.py.  Every test prints the worst value it saw before it asserts.
 """
 import itertools
-import os
-import re
 import warnings
 
 import numpy as np
 import pytest
 
-from metmhn_amd import _lib, _philox
-from metmhn_amd.model import MetMHN, OrderSamples, _ROW_ERRORS
+from metmhn_amd import _philox
+from metmhn_amd.model import OrderSamples
 from metmhn_amd.state import MetState
+from order_common import (ENTRIES, FIRST, KEY, all_orders, check_arguments_before_the_library, check_errors_name_the_row,
+                          check_too_large_rows_get_the_host_value, large_rows, luad, luad_selection, model,
+                          random_paired_states, row, small_shapes_n8)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KEY = 0x9E3779B97F4A7C15          # a seed with a non-zero high word
-FIRST = 2 ** 32 - 100             # sample indices that cross the low counter word
+ENTRY = ENTRIES["sample_orders"]
+
 MARGIN = 1e-9                     # a sample whose closest draw is nearer than this to a boundary is not compared
 MAX_EXCLUDED = 1e-3               # share of one test's samples that may be set aside
-
-
-def _model(n=5, seed=0):
-    rng = np.random.default_rng(seed)
-    th = rng.normal(0.0, 0.5, (n + 1, n + 1))
-    th[np.diag_indices(n + 1)] = rng.normal(-1.0, 0.5, n + 1)
-    return MetMHN(th, 2 * rng.random(n + 1) + 1, 2 * rng.random(n + 1) + 1)
-
-
-def _row(n, slots, typ, diag_order=-99):
-    r = np.zeros(2 * n + 3, dtype=np.int8)
-    r[list(slots)] = 1
-    r[-2], r[-1] = diag_order, typ
-    return r
-
-
-def _paired(n, pt, mt, diag_order):
-    return _row(n, [2 * i for i in pt] + [2 * i + 1 for i in mt] + [2 * n], 3, diag_order)
-
-
-def _luad(golden, prefix):
-    d = golden("luad28")
-    return MetMHN(d[prefix + "_theta"], d[prefix + "_dp"], d[prefix + "_dm"]), d["dat"]
-
-
-def _paired_orders(state: MetState):
-    """Every order the chain can take to a seeded paired `state`."""
-    n = state.n
-    both = [i for i in state.PT_events if i in state.MT_events]
-    for r in range(len(both) + 1):
-        for pre in itertools.permutations(both, r):
-            head = [c for i in pre for c in (2 * i, 2 * i + 1)] + [2 * n]
-            rest = [2 * i for i in state.PT_events if i not in pre] + [2 * i + 1 for i in state.MT_events if i not in pre]
-            for tail in itertools.permutations(rest):
-                yield tuple(head) + tail
 
 
 def _bound(p, M):
@@ -118,36 +84,14 @@ def test_philox_known_answers_and_the_replay_generator():
     np.testing.assert_array_equal(_philox.order_uniforms(KEY, 17, ids, 4), R.uniform53(r0, r1))
 
 
-def test_abi_carries_the_symbol_and_version_8():
-    hdr = open(os.path.join(ROOT, "include", "metmhn_amd.h")).read()
-    assert "mmhn_order_samples" in _lib.SIGNATURES
-    assert len(_lib.SIGNATURES["mmhn_order_samples"]) == 14
-    assert re.search(r"\bint mmhn_order_samples\s*\(", hdr)
-    assert _lib.ABI_VERSION == 8 == int(re.search(r"#define MMHN_ABI_VERSION (\d+)", hdr).group(1))
-
-
 def test_arguments_are_checked_before_the_library(monkeypatch):
-    import metmhn_amd.jx as jx
-
-    def no_engine(*a, **k):
-        raise AssertionError("the library was reached")
-    monkeypatch.setattr(jx, "engine", no_engine)
-    mod = _model()
-    dat = np.array([_row(5, [0, 4, 6], 0), _row(5, [0, 1, 10], 3, 1)])
-    for bad in (dat[0], dat[:, :-1], np.zeros((2, 3, 4))):
-        with pytest.raises(ValueError, match=r"dat must have shape \[n_pat, 13\]"):
-            mod.sample_orders(bad, 4)
-    with pytest.raises(ValueError, match="backend must be 'device' or 'host'"):
-        mod.sample_orders(dat, 4, backend="cpu")
+    mod = check_arguments_before_the_library(ENTRY, monkeypatch)
+    dat = np.array([row(5, [0, 4, 6], 0), row(5, [0, 1, 10], 3, 1)])
     for kw in (dict(n_samples=-1), dict(n_samples=4, first=-1)):
         with pytest.raises(ValueError, match="n_samples and first must be non-negative"):
             mod.sample_orders(dat, **kw)
         with pytest.raises(ValueError, match="n_samples and first must be non-negative"):
             mod.sample_order(MetState([0, 4, 6], size=11), "absent", **kw)
-    with pytest.raises(ValueError, match="met_status must be one of"):
-        mod.sample_order(MetState([0, 1, 10], size=11), "paired")
-    with pytest.raises(ValueError, match="first_obs must be one of"):
-        mod.sample_order(MetState([0, 1, 10], size=11), "isPaired", "first")
 
 
 @pytest.mark.parametrize("n", [4, 5])
@@ -155,7 +99,7 @@ def test_one_tumour_rows_against_enumeration(n):
     """sample_order of "isMetastasis", "present" and "absent" states with k = 0 ... 5 slots, 20 000 samples each, against
     every permutation."""
     M, S = 20000, 2 * n
-    mod = _model(n, seed=500 + n)
+    mod = model(n, seed=500 + n)
     worst = {"likelihood": 0.0, "freq - bound": -np.inf, "total": 0.0}
     cases = 0
     for k in range(6):
@@ -223,26 +167,17 @@ def test_host_against_enumeration_paired(n):
     """Random paired states with k <= 7, all four first_obs values, 20 000 samples each; events only in PT, only in MT and in
     both must all occur.  (The diagonal of a paired state comes from the device.)"""
     M, S = 20000, 2 * n
-    rng = np.random.default_rng(140 + n)
-    mod = _model(n, seed=600 + n)
     worst = {"likelihood": 0.0, "freq - bound": -np.inf, "|total - 1|": 0.0}
-    seen = {"pt_only": 0, "mt_only": 0, "joint": 0}
-    cases = drawn = 0
+    cases = 0
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", DeprecationWarning)
-        while drawn < 6:
-            slots = [s for s in range(2 * n) if rng.random() < 0.45]
-            if len(slots) > 6:
-                continue                                       # k <= 7: under 6! x 2^3 orders per state
-            drawn += 1
-            pt, mt = {s // 2 for s in slots if s % 2 == 0}, {s // 2 for s in slots if s % 2 == 1}
-            seen["pt_only"] += len(pt - mt); seen["mt_only"] += len(mt - pt); seen["joint"] += len(pt & mt)
+        for drawn, (mod, slots, seen) in enumerate(random_paired_states(n, 140 + n, (600 + n,), 6), start=1):
             state = MetState(slots + [S], size=S + 1)
-            orders = list(_paired_orders(state))
+            orders = list(all_orders(state))
             for first in ("PT", "Met", "unknown", "sync"):
                 got = mod.sample_order(state, "isPaired", first, n_samples=M, key=KEY ^ drawn, first=FIRST, row=cases)
                 rel, over, outside = _check_against_enumeration(mod, got, orders, "isPaired", first, M)
-                # (outside == 0: every event before the seeding came as the adjacent pair 2i, 2i+1 - _paired_orders has no
+                # (outside == 0: every event before the seeding came as the adjacent pair 2i, 2i+1 - all_orders has no
                 # other orders)
                 assert outside == 0, (slots, first)
                 o = got.orders.astype(np.int64)
@@ -263,29 +198,10 @@ def test_host_against_enumeration_paired(n):
     assert worst["|total - 1|"] <= 1e-12
 
 
-def _small_shapes():
-    """(model, dat): the rows of tests/test_order_positions.py _small_shapes - paired k = 1, 2, 3, 6 ... 11 under every
-    diagnosis order, without joint events, with joint events only, one tumour with k = 0, 1, 6, 7, 8."""
-    n = 8
-    S = 2 * n
-    rows = []
-    for d in (0, 1, 2, -99):
-        rows += [_paired(n, [], [], d), _paired(n, [2], [3], d), _paired(n, [2], [], d), _paired(n, [], [3], d),
-                 _paired(n, [0], [0], d), _paired(n, [0, 1, 3], [0, 2], d), _paired(n, [0, 2, 4], [0, 2, 5], d),
-                 _paired(n, [0, 1, 2, 3], [0, 1, 4], d), _paired(n, [0, 1, 2, 3, 4], [0, 5, 6], d),
-                 _paired(n, [0, 1, 2, 3, 4], [0, 1, 2, 3], d), _paired(n, [0, 1, 2, 3, 4], [0, 1, 2, 5, 6], d),
-                 _paired(n, [0, 1, 2], [3, 4, 5], d), _paired(n, [0, 1, 2, 3], [0, 1, 2, 3], d)]
-    ev = lambda k, odd: [2 * i + odd for i in range(k)]
-    rows += [_row(n, ev(k, 0), 0) for k in (0, 1, 6, 7, 8)]               # "absent"
-    rows += [_row(n, ev(k - 1, 0) + [S], 1) for k in (1, 6, 7, 8)]        # "present"
-    rows += [_row(n, ev(k - 1, 1) + [S], 2) for k in (1, 6, 7, 8)]        # "isMetastasis"
-    return _model(n, seed=21), np.array(rows)
-
-
 @pytest.fixture(scope="module")
 def small_run():
     """The small shapes: 300 samples per row from the device and from the host, row by row (with the margins)."""
-    mod, dat = _small_shapes()
+    mod, dat = small_shapes_n8()
     dev = mod.sample_orders(dat, 300, key=KEY, first=FIRST)
     assert mod.samples_fallback_rows == 0
     with warnings.catch_warnings():
@@ -319,8 +235,8 @@ def test_device_against_host_small_shapes(small_run):
     assert d_lp[safe].max() <= 1e-10
     assert rel.max() <= 1e-12
     # every order holds the row's codes once, the seeding where the row has it, padded with -1
-    for i, row in enumerate(dat):
-        codes = np.flatnonzero(row[:2 * mod.n + 1])
+    for i, r in enumerate(dat):
+        codes = np.flatnonzero(r[:2 * mod.n + 1])
         o = np.sort(dev.orders[i].astype(int), axis=1)
         assert np.all(o[:, len(o[0]) - len(codes):] == codes) and np.all(o[:, :len(o[0]) - len(codes)] == -1), i
 
@@ -359,36 +275,14 @@ def _check_likelihoods(tag, mod, dat, run, count):
     assert worst <= 1e-10
 
 
-def _large_rows(n):
-    """The rows of tests/test_order_positions.py test_large_synthetic_rows_by_identities: paired k = 14 ... 17 (n = 9) and
-    one tumour k = 14 ... 17 (n = 16), both sides of the 1024-thread switch at 15 slots."""
-    rows = []
-    if n == 9:
-        for j, k in enumerate((14, 15, 16, 17)):
-            nj = (5, 5, 6, 7)[j]
-            rest = k - 1 - 2 * nj
-            pt_only = list(range(nj, nj + (rest + 1) // 2))
-            mt_only = list(range(nj + (rest + 1) // 2, nj + rest))
-            rows.append(_paired(n, list(range(nj)) + pt_only, list(range(nj)) + mt_only, (0, 1, 2, -99)[j]))
-        rows += [_paired(n, range(8), range(8), 0), _paired(n, [0, 1, 2, 3, 4, 5, 6], [7, 8, 0, 1, 2, 3, 4], 1),
-                 _row(n, list(range(0, 18, 2)) + [18], 1), _row(n, list(range(1, 18, 2)) + [18], 2),
-                 _row(n, list(range(0, 18, 2)), 0), _row(n, [0, 4, 18], 1), _row(n, [18], 2)]
-    else:
-        for k in (14, 15, 16, 17):
-            rows += [_row(n, [2 * i for i in range(k - 1)] + [2 * n], 1), _row(n, [2 * i + 1 for i in range(k - 1)] + [2 * n], 2)]
-            if k <= n:
-                rows.append(_row(n, [2 * i for i in range(k)], 0))
-    return np.array(rows)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("n, seed", [(9, 31), (16, 32)])
 def test_large_synthetic_rows(n, seed):
     """4 096 samples per row against the exact marginals; the first 16 of them against the likelihoods of their orders."""
-    dat = _large_rows(n)
+    dat = large_rows(n)
     k = dat[:, :-2].astype(int).sum(1)
     assert {14, 15, 16, 17} <= set(int(v) for v in k)
-    mod = _model(n, seed=seed)
+    mod = model(n, seed=seed)
     run = mod.sample_orders(dat, 4096, key=KEY + n, first=FIRST)
     assert mod.samples_fallback_rows == 0
     _check_likelihoods(f"synthetic n = {n}", mod, dat, run, 16)
@@ -399,13 +293,10 @@ def test_large_synthetic_rows(n, seed):
 def test_luad_rows_against_the_exact_marginals(golden):
     """LUAD-28 at the fit point: the 71 rows with k >= 15 (k = 21 among them), 300 rows with k <= 12 and up to 200 with
     k = 13, 14; 256 samples per row."""
-    mod, dat = _luad(golden, "fit")
-    k = dat[:, :-2].astype(int).sum(1)
-    small = np.flatnonzero(k <= 12)
-    sel = np.concatenate((np.flatnonzero(k >= 15), small[np.linspace(0, len(small) - 1, 300).astype(int)],
-                          np.flatnonzero((k >= 13) & (k <= 14))[:200]))
-    sub = dat[sel]
-    assert (k[sel] >= 15).sum() == 71 and k[sel].max() == 21
+    mod, dat = luad(golden, "fit")
+    sub = dat[luad_selection(dat)]
+    k = sub[:, :-2].astype(int).sum(1)
+    assert (k >= 15).sum() == 71 and k.max() == 21
     run = mod.sample_orders(sub, 256, key=KEY, first=FIRST)
     assert mod.samples_fallback_rows == 0
     _check_means("LUAD-28 fit", mod, sub, run, 256)
@@ -450,29 +341,10 @@ def test_reproducible_whatever_the_call(small_run):
 
 @pytest.mark.gpu
 def test_too_large_rows_get_the_host_samples(monkeypatch):
-    """The Python layer draws MMHN_ORD_TOO_LARGE rows with sample_order and counts them."""
-    import metmhn_amd.jx as jx
-    from metmhn_amd.engine import Engine
-    n = 9
-    mod = _model(n, seed=11)
-    S = 2 * n
-    wide = _paired(n, [0, 1, 2, 3, 4, 5, 6], [0, 1, 2, 3, 7, 8], 0)         # k = 14: 1.2 MiB, over the 1 MiB limit below
-    dat = np.vstack((wide[None], [_row(n, [0, 1, 2, 3, 6, S], 3, 1), _row(n, [0, 2, S], 1), _row(n, [0, 2], 0)]))
-    ref = mod.sample_orders(dat, 64, key=KEY, first=FIRST)
-    assert mod.samples_fallback_rows == 0
-    with Engine(n, workspace_bytes=1 << 20) as small:
-        st = small.order_samples(mod.log_theta, mod.obs1, mod.obs2, dat, 64, KEY, FIRST)
-        assert st[3].tolist() == [3, 0, 0, 0]
-        assert np.isnan(st[0][0]) and np.all(st[1][0] == -1) and np.all(np.isnan(st[2][0]))
-        monkeypatch.setattr(jx, "engine", lambda n_mut: small)
-        got = mod.sample_orders(dat, 64, key=KEY, first=FIRST)
-    assert mod.samples_fallback_rows == 1
-    host = mod.sample_order(MetState.from_seq(wide[:S + 1]), "isPaired", "unknown", n_samples=64, key=KEY, first=FIRST, row=0)
-    assert got.log_evidence[0] == host.log_evidence
-    np.testing.assert_array_equal(got.orders[0], host.orders)
-    np.testing.assert_array_equal(got.log_prob[0], host.log_prob)
-    for name in ("log_evidence", "orders", "log_prob"):
-        np.testing.assert_array_equal(getattr(got, name)[1:], getattr(ref, name)[1:])
+    """... with sample_order: the k = 14 row (1.2 MiB, over the 1 MiB workspace), what the device leaves in its place, and
+    the host's samples against the device's own where the host margin allows."""
+    mod, dat, ref, st, host = check_too_large_rows_get_the_host_value(ENTRY, monkeypatch)
+    assert np.isnan(st[0][0]) and np.all(st[1][0] == -1) and np.all(np.isnan(st[2][0]))
     safe = host.margin >= MARGIN
     d_lp = np.abs(host.log_prob - ref.log_prob[0])[safe].max()
     print(f"host fallback, k = 14: {int(safe.sum())} of 64 samples compared with the device's, worst |log_prob| difference "
@@ -483,27 +355,8 @@ def test_too_large_rows_get_the_host_samples(monkeypatch):
 
 @pytest.mark.gpu
 def test_errors_name_the_row_and_no_samples_is_valid():
-    from metmhn_amd.engine import Engine
-    mod = _model()
-    n = mod.n
-    S = 2 * n
-    good = np.array([_row(n, [0, 4, 6], 0), _row(n, [], 0), _row(n, [2, 4, 8, S], 1), _row(n, [1, 5, 9, S], 2),
-                     _row(n, [0, 1, 2, 5, 6, 7, S], 3, 0), _row(n, [0, 1, 4, 5, 3, S], 3, 1), _row(n, [1, S], 3, 2)])
-    # one row per MMHN_ORD_* reason, in the order of the enum (1 ... 7)
-    bad = [_row(n, [0], 5), _row(n, [0, 3], 3, 1), _row(n, [0, 1], 3, 0), _row(n, [0, 1, 2 * n], 2), _row(n, [1, 3], 2),
-           _row(n, [1], 0), _row(n, [0, 1, 2 * n], 1)]
-    for reason, b in enumerate(bad, start=1):
-        dat = np.vstack((good[:3], b[None], good[3:]))
-        with pytest.raises(ValueError) as dev_err:
-            mod.sample_orders(dat, 8)
-        assert str(dev_err.value) == f"row 3: {_ROW_ERRORS[reason]}"
-        with pytest.raises(ValueError, match=r"^row 3: "):
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore", DeprecationWarning)
-                mod.sample_orders(dat, 8, backend="host")
-    with Engine(n, dtype="f32") as e32:
-        with pytest.raises(RuntimeError, match="fp64"):
-            e32.order_samples(mod.log_theta, mod.obs1, mod.obs2, good, 8)
+    mod, good = check_errors_name_the_row(ENTRY)
+    S = 2 * mod.n
     none = mod.sample_orders(good, 0)
     post = mod.order_posteriors(good)
     assert none.orders.shape == (len(good), 0, S + 1) and none.log_prob.shape == (len(good), 0)

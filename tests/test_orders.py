@@ -13,25 +13,13 @@ import warnings
 import numpy as np
 import pytest
 
-import metmhn_amd.model as model_mod
 from metmhn_amd.model import MetMHN
 from metmhn_amd.state import MetState, State
 from oracle import metmhn_oracle as orc
+from order_common import all_orders, host_only, model  # noqa: F401 (host_only: a fixture)
 
 KINDS = ["isMetastasis", "PT", "Met", "unknown", "sync"]
 REL = 1e-10      # fp64 products of <= 2k factors; the golden values agree to ~1e-15
-
-
-class _OracleDiag:
-    @staticmethod
-    def kron_diag(log_theta, state, n_state):
-        return orc.kron_diag(np.asarray(log_theta), np.asarray(state), n_state)
-
-
-@pytest.fixture
-def host_only(monkeypatch):
-    monkeypatch.setattr(model_mod, "_kronvec", _OracleDiag)
-    warnings.simplefilter("ignore", DeprecationWarning)
 
 
 def _call(kind):
@@ -85,18 +73,11 @@ def test_paired_diag_device_matches_oracle():
     np.testing.assert_allclose(got, ref, rtol=1e-12)
 
 
-def _model(n=5, seed=0):
-    rng = np.random.default_rng(seed)
-    th = rng.normal(0.0, 0.5, (n + 1, n + 1))
-    th[np.diag_indices(n + 1)] = rng.normal(-1.0, 0.5, n + 1)
-    return MetMHN(th, 2 * rng.random(n + 1) + 1, 2 * rng.random(n + 1) + 1)
-
-
 def test_unpaired_closed_forms(host_only):
     """The three expansions of the reference's tests/test_orders.py:66-128, n = 5: a primary tumour
     without / with a later metastasis (the observation-MHN the reference takes from PyPI `mhn`),
     and a lone metastasis."""
-    mod = _model()
+    mod = model()
     n, th, o1, o2, e = mod.n, mod.log_theta, mod.obs1, mod.obs2, np.exp
     seeding = 2 * n
     every = State.from_seq([1] * (n + 1))
@@ -125,7 +106,7 @@ def test_paired_timed_closed_form(host_only):
     """In the manner of the reference's tests/test_orders.py:130-221: the order (0,1,S,4,3,5) with
     the primary tumour seen first, every factor written out.  The first observation can fall after
     the PT event 4, after the MT event 3 or after the MT event 5 (model.py:139-144)."""
-    mod = _model(seed=3)
+    mod = model(seed=3)
     n, th, o1, o2, e = mod.n, mod.log_theta, mod.obs1, mod.obs2, np.exp
     S = 2 * n
     st = MetState([0, 1, 3, 4, 5, S], size=2 * n + 1)
@@ -151,25 +132,13 @@ def test_paired_timed_closed_form(host_only):
     assert got == pytest.approx(split_early + split_mid + split_late, rel=1e-12)
 
 
-def _all_orders(state: MetState):
-    """Every order the chain can take to a seeded `state`."""
-    n = state.n
-    both = [i for i in state.PT_events if i in state.MT_events]
-    for r in range(len(both) + 1):
-        for pre in itertools.permutations(both, r):
-            head = [c for i in pre for c in (2 * i, 2 * i + 1)] + [2 * n]
-            rest = [2 * i for i in state.PT_events if i not in pre] + [2 * i + 1 for i in state.MT_events if i not in pre]
-            for tail in itertools.permutations(rest):
-                yield tuple(head) + tail
-
-
 @pytest.mark.parametrize("first_obs", ["PT", "Met", "unknown", "sync"])
 def test_likeliest_is_the_maximum_over_all_orders(host_only, first_obs):
-    mod = _model(n=4, seed=11)
+    mod = model(n=4, seed=11)
     for slots in ([0, 1, 2, 5, 6, 7, 8], [0, 1, 4, 5, 3, 8], [2, 3, 4, 7, 8], [1, 8], [0, 8], [8]):
         st = MetState(slots, size=9)
         order, p = mod.likeliest_order(st, "isPaired", first_obs)
-        table = {o: mod.likelihood(o, "isPaired", first_obs) for o in _all_orders(st)}
+        table = {o: mod.likelihood(o, "isPaired", first_obs) for o in all_orders(st)}
         best = max(table, key=table.get)
         assert p == pytest.approx(table[best], rel=1e-12)
         assert table[tuple(order)] == pytest.approx(p, rel=1e-12)
@@ -177,7 +146,7 @@ def test_likeliest_is_the_maximum_over_all_orders(host_only, first_obs):
 
 
 def test_unpaired_likeliest_is_the_maximum(host_only):
-    mod = _model(n=5, seed=2)
+    mod = model(n=5, seed=2)
     S = 10
     for slots, status in (([1, 5, 9, S], "isMetastasis"), ([2, 4, 8, S], "present"), ([0, 4, 6], "absent")):
         st = MetState(slots, size=11)
@@ -188,7 +157,7 @@ def test_unpaired_likeliest_is_the_maximum(host_only):
 
 
 def test_unknown_is_the_sum_of_both_first_observations(host_only):
-    mod = _model(n=4, seed=5)
+    mod = model(n=4, seed=5)
     order = (2, 3, 8, 0, 5, 7, 1)
     assert mod.likelihood(order, "isPaired", "unknown") == pytest.approx(
         mod.likelihood(order, "isPaired", "PT") + mod.likelihood(order, "isPaired", "Met"), rel=1e-13)
@@ -205,7 +174,7 @@ def _random_order(rng, state: MetState):
 
 def test_beyond_the_reference_size_limit(host_only):
     """k = 14 occupied slots: past the reference's factorial-base int32 order code (k <= 12)."""
-    mod = _model(n=7, seed=8)
+    mod = model(n=7, seed=8)
     st = MetState([0, 1, 2, 3, 4, 5, 6, 8, 9, 10, 11, 12, 13, 14], size=15)
     rng = np.random.default_rng(0)
     orders = [_random_order(rng, st) for _ in range(300)]
@@ -225,7 +194,7 @@ def test_beyond_the_reference_size_limit(host_only):
 
 def test_unreachable_and_invalid_states(host_only):
     """tests/test_orders.py:18-64 (reference)."""
-    mod = _model(n=4)
+    mod = model(n=4)
     for first_obs in ("PT", "Met", "unknown", "sync"):
         with pytest.raises(ValueError):
             mod.likeliest_order(np.array([0, 1, 1, 1, 0, 0, 0, 1, 0]), "isPaired", first_obs)

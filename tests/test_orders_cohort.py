@@ -13,79 +13,30 @@ import warnings
 import numpy as np
 import pytest
 
-import metmhn_amd.model as model_mod
 from metmhn_amd.model import MetMHN
-from metmhn_amd.state import MetState
-from oracle import metmhn_oracle as orc
+from order_common import Row, all_orders, host_only, luad, mixed_cohort, model, row  # noqa: F401 (host_only: a fixture)
 
 KINDS = ["isMetastasis", "PT", "Met", "unknown", "sync"]
 DIAG_ORDER = {"unknown": 0, "PT": 1, "Met": 2}
 
 
-class _OracleDiag:
-    @staticmethod
-    def kron_diag(log_theta, state, n_state):
-        return orc.kron_diag(np.asarray(log_theta), np.asarray(state), n_state)
-
-
-@pytest.fixture
-def host_only(monkeypatch):
-    monkeypatch.setattr(model_mod, "_kronvec", _OracleDiag)
-    warnings.simplefilter("ignore", DeprecationWarning)
-
-
-def _model(n=5, seed=0):
-    rng = np.random.default_rng(seed)
-    th = rng.normal(0.0, 0.5, (n + 1, n + 1))
-    th[np.diag_indices(n + 1)] = rng.normal(-1.0, 0.5, n + 1)
-    return MetMHN(th, 2 * rng.random(n + 1) + 1, 2 * rng.random(n + 1) + 1)
-
-
-def _row(n, slots, typ, diag_order=-99):
-    r = np.zeros(2 * n + 3, dtype=np.int8)
-    r[list(slots)] = 1
-    r[-2], r[-1] = diag_order, typ
-    return r
-
-
-def _mixed_cohort(n=5):
-    """Every status and every diagnosis order of a paired row (-99 reads as "Met", as in the objective)."""
-    S = 2 * n
-    rows = [_row(n, [0, 4, 6], 0), _row(n, [], 0), _row(n, [2, 4, 8, S], 1), _row(n, [S], 1),
-            _row(n, [1, 5, 9, S], 2), _row(n, [S], 2)]
-    for d in (0, 1, 2, -99):
-        rows += [_row(n, [0, 1, 2, 5, 6, 7, S], 3, d), _row(n, [0, 1, 4, 5, 3, S], 3, d), _row(n, [1, S], 3, d)]
-    return np.array(rows)
-
-
-def _expected_call(row, n):
-    typ, d = int(row[-1]), int(row[-2])
-    status = ["absent", "present", "isMetastasis", "isPaired"][typ]
-    first = {0: "unknown", 1: "PT"}.get(d, "Met") if typ == 3 else None
-    return MetState.from_seq(row[:2 * n + 1]), status, first
-
-
-def _slots(row, n):
-    return set(int(s) for s in np.flatnonzero(row[:2 * n + 1]))
-
-
 def test_host_backend_decodes_every_row(host_only):
-    mod = _model()
-    dat = _mixed_cohort(mod.n)
+    mod = model()
+    dat = mixed_cohort(mod.n)
     got = mod.likeliest_orders(dat, backend="host")
     assert len(got) == len(dat) and mod.orders_fallback_rows == 0
-    for row, (order, p) in zip(dat, got):
-        o, q = mod.likeliest_order(*_expected_call(row, mod.n))
+    for r, (order, p) in zip(dat, got):
+        o, q = mod.likeliest_order(*Row(r, mod.n).call())
         assert order == tuple(int(e) for e in o) and p == q
-        assert set(order) == _slots(row, mod.n)
-        status, first = _expected_call(row, mod.n)[1:]
+        assert set(order) == Row(r, mod.n).slots
+        status, first = Row(r, mod.n).call()[1:]
         assert mod.likelihood(order, status, first) == pytest.approx(p, rel=1e-12)
 
 
 def test_host_backend_errors_carry_the_row(host_only):
-    mod = _model()
-    dat = _mixed_cohort(mod.n)
-    bad = _row(mod.n, [0, 3], 3, 1)                          # no seeding and the tumours differ
+    mod = model()
+    dat = mixed_cohort(mod.n)
+    bad = row(mod.n, [0, 3], 3, 1)                          # no seeding and the tumours differ
     with pytest.raises(ValueError, match=r"^row 4: This state is not reachable by mhn\.$"):
         mod.likeliest_orders(np.vstack((dat[:4], bad[None], dat[4:])), backend="host")
     with pytest.raises(ValueError, match="backend"):
@@ -93,11 +44,6 @@ def test_host_backend_errors_carry_the_row(host_only):
 
 
 # ---------------------------------------------------------------------------------------------------- GPU
-def _luad(golden, prefix):
-    d = golden("luad28")
-    return MetMHN(d[prefix + "_theta"], d[prefix + "_dp"], d[prefix + "_dm"]), d["dat"]
-
-
 def _host(mod, dat, i):
     return mod._row_order(dat, i)
 
@@ -106,7 +52,7 @@ def _same_or_tie(mod, row, got, want, rel=1e-12):
     (go, gp), (wo, wp) = got, want
     assert abs(gp - wp) <= rel * wp, (row, gp, wp)
     if go != wo:                                               # a tie: the device's order is as likely as the host's
-        _, status, first = _expected_call(row, mod.n)
+        _, status, first = Row(row, mod.n).call()
         assert abs(mod.likelihood(go, status, first) - wp) <= rel * wp, (row, go, wo)
 
 
@@ -137,7 +83,7 @@ def test_golden_orders_device(golden):
 @pytest.mark.gpu
 @pytest.mark.parametrize("prefix", ["fit", "indep"])
 def test_luad28_rows_match_the_host(golden, prefix):
-    mod, dat = _luad(golden, prefix)
+    mod, dat = luad(golden, prefix)
     k = dat[:, :-2].astype(int).sum(1)
     paired = dat[:, -1] == 3
     big = np.flatnonzero(paired & (k >= 16) & (k <= 18))[:6]
@@ -151,30 +97,18 @@ def test_luad28_rows_match_the_host(golden, prefix):
 @pytest.mark.gpu
 def test_luad28_whole_cohort_one_call(golden):
     from metmhn_amd.jx import engine
-    mod, dat = _luad(golden, "fit")
+    mod, dat = luad(golden, "fit")
     k = dat[:, :-2].astype(int).sum(1)
     assert k.max() == 21
     orders, prob, status = engine(mod.n).likeliest_orders(mod.log_theta, mod.obs1, mod.obs2, dat)
     assert set(np.unique(status)) <= {0, 1}
     got = mod.likeliest_orders(dat[status == 0])
     assert mod.orders_fallback_rows == 0
-    for row, (order, p), q in zip(dat[status == 0], got, prob[status == 0]):
+    for r, (order, p), q in zip(dat[status == 0], got, prob[status == 0]):
         assert p == q
-        assert set(order) == _slots(row, mod.n) and len(order) == len(set(order))
-        _, st, first = _expected_call(row, mod.n)
-        assert abs(mod.likelihood(order, st, first) - p) <= 1e-10 * p, row
-
-
-def _all_orders(state: MetState):
-    """Every order the chain can take to a seeded `state`."""
-    n = state.n
-    both = [i for i in state.PT_events if i in state.MT_events]
-    for r in range(len(both) + 1):
-        for pre in itertools.permutations(both, r):
-            head = [c for i in pre for c in (2 * i, 2 * i + 1)] + [2 * n]
-            rest = [2 * i for i in state.PT_events if i not in pre] + [2 * i + 1 for i in state.MT_events if i not in pre]
-            for tail in itertools.permutations(rest):
-                yield tuple(head) + tail
+        assert set(order) == Row(r, mod.n).slots and len(order) == len(set(order))
+        _, st, first = Row(r, mod.n).call()
+        assert abs(mod.likelihood(order, st, first) - p) <= 1e-10 * p, r
 
 
 @pytest.mark.gpu
@@ -182,33 +116,33 @@ def test_brute_force_random_models():
     n = 5
     rng = np.random.default_rng(21)
     for seed in range(3):
-        mod = _model(n, seed=100 + seed)
+        mod = model(n, seed=100 + seed)
         rows = []
         while len(rows) < 36:
             slots = [s for s in range(2 * n) if rng.random() < 0.4]
             if len(slots) > 6:
                 continue                                       # keep the enumeration short
             for first in ("PT", "Met", "unknown"):
-                rows.append(_row(n, slots + [2 * n], 3, DIAG_ORDER[first]))
-            rows.append(_row(n, [s for s in slots if s % 2 == 1] + [2 * n], 2))
-            rows.append(_row(n, [s for s in slots if s % 2 == 0] + [2 * n], 1))
-            rows.append(_row(n, [s for s in slots if s % 2 == 0], 0))
+                rows.append(row(n, slots + [2 * n], 3, DIAG_ORDER[first]))
+            rows.append(row(n, [s for s in slots if s % 2 == 1] + [2 * n], 2))
+            rows.append(row(n, [s for s in slots if s % 2 == 0] + [2 * n], 1))
+            rows.append(row(n, [s for s in slots if s % 2 == 0], 0))
         got = mod.likeliest_orders(np.array(rows))
-        for row, (order, p) in zip(rows, got):
-            st, status, first = _expected_call(row, n)
+        for r, (order, p) in zip(rows, got):
+            st, status, first = Row(r, n).call()
             if status == "isPaired":
-                cands = list(_all_orders(st))
+                cands = list(all_orders(st))
             else:
-                cands = list(itertools.permutations(sorted(_slots(row, n))))
+                cands = list(itertools.permutations(sorted(Row(r, n).slots)))
             best = max(mod.likelihood(o, status, first) for o in cands)
-            assert p == pytest.approx(best, rel=1e-12), (row, order)
+            assert p == pytest.approx(best, rel=1e-12), (r, order)
             assert mod.likelihood(order, status, first) == pytest.approx(best, rel=1e-12)
 
 
 @pytest.mark.gpu
 def test_front_overflow_falls_back_to_the_host(golden):
     from metmhn_amd.jx import engine
-    mod, dat = _luad(golden, "fit")
+    mod, dat = luad(golden, "fit")
     eng = engine(mod.n)
     o_def, p_def, s_def = eng.likeliest_orders(mod.log_theta, mod.obs1, mod.obs2, dat)
     o_1, p_1, s_1 = eng.likeliest_orders(mod.log_theta, mod.obs1, mod.obs2, dat, front_cap=1)
@@ -224,15 +158,15 @@ def test_front_overflow_falls_back_to_the_host(golden):
     got = mod.likeliest_orders(sub, front_cap=1)
     assert mod.orders_fallback_rows == (s_1[k <= 14] == 1).sum() > 0
     ref = mod.likeliest_orders(sub)
-    for row, a, b in zip(sub, got, ref):
-        _same_or_tie(mod, row, a, b)
+    for r, a, b in zip(sub, got, ref):
+        _same_or_tie(mod, r, a, b)
 
 
 @pytest.mark.gpu
 def test_deterministic_under_shuffle_and_batching(golden):
     from metmhn_amd.engine import Engine
     from metmhn_amd.jx import engine
-    mod, dat = _luad(golden, "indep")
+    mod, dat = luad(golden, "indep")
     k = dat[:, :-2].astype(int).sum(1)
     sub = dat[k <= 14]
     args = (mod.log_theta, mod.obs1, mod.obs2)
@@ -260,11 +194,11 @@ def test_deterministic_under_shuffle_and_batching(golden):
 @pytest.mark.gpu
 def test_errors_name_the_row():
     from metmhn_amd.engine import Engine
-    mod = _model()
+    mod = model()
     n = mod.n
-    good = _mixed_cohort(n)
-    bad = [_row(n, [0, 3], 3, 1), _row(n, [0, 1], 3, 0), _row(n, [0, 1, 2 * n], 2), _row(n, [1, 3], 2),
-           _row(n, [0, 2 * n], 0), _row(n, [1], 0), _row(n, [0, 1, 2 * n], 1), _row(n, [0], 1), _row(n, [0], 5)]
+    good = mixed_cohort(n)
+    bad = [row(n, [0, 3], 3, 1), row(n, [0, 1], 3, 0), row(n, [0, 1, 2 * n], 2), row(n, [1, 3], 2),
+           row(n, [0, 2 * n], 0), row(n, [1], 0), row(n, [0, 1, 2 * n], 1), row(n, [0], 1), row(n, [0], 5)]
     for b in bad:
         dat = np.vstack((good[:3], b[None], good[3:]))
         with pytest.raises(ValueError) as host_err:
