@@ -5,7 +5,9 @@
 //     T = c | beta << RB | Tx << (RB + HB)     c: column inside a block, beta: block inside a window, Tx: external
 //     Sigma = Tx | Sx << nXc            external index
 //     position(S, T) = (((Sigma * H + beta) * 1024 + rho(w, l)) * NC + c
-// rho sorts the rows of a block by lane-level (popcount of l).  The seed = 0 half keeps its natural positions.
+// rho orders the rows of a block by wave-level (popcount of w), then lane-level (popcount of l): the rows one step of the
+// solve requests together are whole 128-byte lines wherever the class sizes allow (below).  The seed = 0 half keeps its
+// natural positions.
 // Reference: the index convention being re-ordered is kronvec.py:223-250 (active slots in slot order = index bits).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -87,9 +89,23 @@ struct WDesc {
   int8_t prt[WMAXB];         // column bit of the partner of row bit i, -1: none
 };
 
-// rows of a block sorted by lane-level: rho(w, l) = 16 * (rows of lower levels) + w * C(6, m) + rank of l in its level
+// Storage rows of a block.  A wave instruction of the solve requests the rows of one (w, m) group (wave w, lanes of
+// lane-level m = popcount of l): C(6, m) rows of 32 bytes, one contiguous run.  The waves of one wave-level lam =
+// popcount of w request their groups of level m in the same step, so a CLASS (lam, m) - C(4, lam) * C(6, m) rows - is kept
+// contiguous too and a 128-byte line is requested twice only where two classes meet inside it.  Order of the classes:
+// lam-major (the classes of lam = 1 and 3 are whole lines), and inside one lam the lane-levels in the order
+// 0 2 | 1 5 | 3 | 4 6, in which the left-over rows of two neighbours fill one line (1 + 15, 6 + 6, 15 + 1 rows at lam = 0
+// and 4; 6 + 90, 90 + 6 at lam = 2): 8 lines of a block lie in two classes - the least sixteen classes that are no whole
+// number of lines allow - against 48 when the rows are sorted by (m, w) and 16 when by (lam, m, w)
+// (tests/host/wlayout_check.hip counts them).
+//     rho(w, l) = base[w][m] + rank of l in its level,   base[w][m] = rows of the classes before (lam, m)
+//                                                                     + C(6, m) * (waves of level lam below w)
 struct W6 {
-  uint8_t rank[64], order[64], off[8], cnt[8];
+  uint8_t rank[64], order[64], off[8], cnt[8];   // lanes sorted by level: rank inside the level, lane at a sorted position
+  uint8_t mseq[8];                               // lane-levels in storage order
+  uint8_t wseq[16], lamoff[6];                   // waves sorted by (lam, w); first entry of a wave-level in wseq
+  uint16_t lamrow[6];                            // first storage row of a wave-level
+  uint16_t base[16][8];                          // first storage row of group (w, m)
 };
 constexpr W6 make_w6() {
   W6 t{};
@@ -105,20 +121,39 @@ constexpr W6 make_w6() {
     t.cnt[m] = (uint8_t)r;
   }
   t.off[7] = 64; t.cnt[7] = 0;
+  constexpr int mseq[7] = {0, 2, 1, 5, 3, 4, 6};
+  for (int i = 0; i < 7; ++i) t.mseq[i] = (uint8_t)mseq[i];
+  int row = 0, nw = 0;
+  for (int lam = 0; lam <= WWB; ++lam) {
+    t.lamoff[lam] = (uint8_t)nw;
+    t.lamrow[lam] = (uint16_t)row;
+    int first = nw;
+    for (int w = 0; w < (1 << WWB); ++w) {
+      int pc = 0;
+      for (int b = 0; b < WWB; ++b) pc += (w >> b) & 1;
+      if (pc == lam) t.wseq[nw++] = (uint8_t)w;
+    }
+    for (int i = 0; i < 7; ++i)
+      for (int j = first; j < nw; ++j) { t.base[t.wseq[j]][mseq[i]] = (uint16_t)row; row += t.cnt[mseq[i]]; }
+  }
+  t.lamoff[WWB + 1] = (uint8_t)nw; t.lamrow[WWB + 1] = (uint16_t)row;
   return t;
 }
 __host__ __device__ inline uint32_t wrho(uint32_t w, uint32_t l) {
   constexpr W6 t = make_w6();
-  const int m = popc32(l);
-  return 16u * t.off[m] + w * t.cnt[m] + t.rank[l];
+  return (uint32_t)t.base[w][popc32(l)] + t.rank[l];
 }
 // inverse: row index w << 6 | l of storage row r
 __host__ __device__ inline uint32_t wrho_inv(uint32_t r) {
   constexpr W6 t = make_w6();
-  int m = 0;
-  while (r >= 16u * t.off[m + 1]) ++m;
-  const uint32_t q = r - 16u * t.off[m];
-  return ((q / t.cnt[m]) << 6) | t.order[t.off[m] + q % t.cnt[m]];
+  int lam = 0;
+  while (r >= t.lamrow[lam + 1]) ++lam;
+  const uint32_t nw = (uint32_t)(t.lamoff[lam + 1] - t.lamoff[lam]);      // waves of the level
+  uint32_t q = r - t.lamrow[lam];
+  int i = 0;
+  while (q >= nw * t.cnt[t.mseq[i]]) { q -= nw * t.cnt[t.mseq[i]]; ++i; }
+  const int m = t.mseq[i];
+  return ((uint32_t)t.wseq[t.lamoff[lam] + q / t.cnt[m]] << 6) | t.order[t.off[m] + q % t.cnt[m]];
 }
 template <typename T>
 __host__ __device__ inline long long wpos(uint32_t Sigma, uint32_t beta, uint32_t rho, uint32_t c) {
@@ -145,7 +180,7 @@ __host__ __device__ inline long long wpos_marg(const WDesc& w, int k, bool free_
     return half + wpos<T>(Sigma, (1u << HB) - 1u, wrho((f >> WLB) & ((1u << WWB) - 1u), f & 63u), (1u << RB) - 1u);
   }
   const uint32_t Sigma = (f >> (RB + HB)) | (((1u << w.nXr) - 1u) << w.nXc);
-  return half + wpos<T>(Sigma, (f >> RB) & ((1u << HB) - 1u), (uint32_t)WROWS - 1u, f & ((1u << RB) - 1u));
+  return half + wpos<T>(Sigma, (f >> RB) & ((1u << HB) - 1u), wrho((1u << WWB) - 1u, 63u), f & ((1u << RB) - 1u));
 }
 
 }  // namespace mmhn

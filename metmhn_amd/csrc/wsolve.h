@@ -25,8 +25,11 @@
 // Storage of the seeded half ("window layout", wlayout.h):
 //     position(S, T) = (((Sigma * H + beta) * 1024 + rho(w, l)) * NC + c,   T = c | beta << RB | Tx << (RB + HB),
 //     Sigma = Tx | Sx << nXc,  S = l | w << 6 | Sx << 10,
-// rho sorts the rows of a block by lane-level so that the lanes of a wave which work on the same external index
-// (= the same lane-level) touch one contiguous run of memory.  The seed = 0 half keeps its natural positions.
+// rho keeps the rows of the lanes of a wave which work on the same external index (= the same lane-level m) in one
+// contiguous run of memory, and the runs of the waves that request them in the same step (= the same wave-level lam) side
+// by side: rows ordered by (lam, m, wave, lane), the lane-levels of one lam in the order that lets two classes which are
+// no whole number of 128-byte lines share their partial line (wlayout.h) - 264 lines requested per block of 256, against
+// 304 with the rows sorted by lane-level alone.  The seed = 0 half keeps its natural positions.
 // (Measured and dropped: a block as two planes of 16 bytes per row - no line requested by two instructions, but runs
 // half as long: adjoint 18.6 -> 22.9 ms; a one-dword LDS-DMA touch of the next step's external rows: +2.5 / +6 ms.)
 #pragma once
