@@ -188,6 +188,22 @@ int mmhn_simulate(mmhn_handle h, const double* log_theta, const double* pt_d_ef,
  */
 int mmhn_simulate_summary(mmhn_handle h, const double* log_theta, const double* pt_d_ef, const double* mt_d_ef,
                           int64_t first, int64_t n_sim, uint64_t seed, int64_t* counts);
+/* mmhn_simulate_pairs: the same trajectories again, counted to second order: which events occur together, per class of
+ * sample, and how many mutations a tumour carries.  The model-side counterpart of a cohort's co-occurrence table; exact
+ * pairwise marginals do not exist (2^(2 n_mut + 1) joint states), this is their Monte-Carlo estimate.  Sample indices, seed,
+ * chunking (MMHN_SIM_CHUNK) and the argument checks are those of mmhn_simulate_summary; works on fp32 engines too (the
+ * sampler is fp64 throughout).  With G the genotype columns [PT_0, MT_0, PT_1, MT_1, ...] of the rows mmhn_simulate
+ * returns for these indices, B = 2 n_mut, and the class of a row = its last column (0 unseeded / 1 seeded, PT observed
+ * first / 2 seeded, MT observed first), all outputs overwritten:
+ *   n_class int64 [3]                 rows of each class
+ *   pairs   int64 [3][B][B]           pairs[c] = G_c^T G_c over the rows of class c: full and symmetric, the diagonal holds
+ *                                     the marginal counts, pairs[c][2i][2i+1] the rows with event i in both tumours
+ *   burden  int64 [3][5][n_mut + 1]   per class the histogram of |PT|, |MT|, |PT & MT|, |PT & ~MT|, |MT & ~PT| over the
+ *                                     mutations of a row (seeding and diagnosis excluded); every row of it sums to n_class[c]
+ * Integer counts: the result does not depend on the chunking or the launch geometry.
+ */
+int mmhn_simulate_pairs(mmhn_handle h, const double* log_theta, const double* pt_d_ef, const double* mt_d_ef,
+                        int64_t first, int64_t n_sim, uint64_t seed, int64_t* n_class, int64_t* pairs, int64_t* burden);
 
 /* ---- likeliest event orders -------------------------------------------------
  * mmhn_likeliest_orders: MetMHN.likeliest_order (metmhn/model.py:213-293) of every row of a reference-format `dat`
@@ -336,7 +352,7 @@ typedef struct {
   int32_t comm_rank;  /* this engine's rank in it (ncclCommUserRank), -1: none */
 } mmhn_counters;
 /* ABI version of this header: bumped whenever an exported signature or structure changes (4: mmhn_bench_kronvec has its
- * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions and mmhn_order_samples were added within version 8, purely additive changes).  A client built against another header must refuse to run:
+ * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions, mmhn_order_samples and mmhn_simulate_pairs were added within version 8, purely additive changes).  A client built against another header must refuse to run:
  * mmhn_abi_version() != MMHN_ABI_VERSION (metmhn_amd/_lib.py checks it on load). */
 #define MMHN_ABI_VERSION 8
 int mmhn_abi_version(void);

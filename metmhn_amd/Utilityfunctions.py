@@ -3,7 +3,8 @@ examples/analysis.py that sit directly around score / learn_mhn.  Host-side NumP
 names and argument meaning as the reference; the likelihood work goes to the GPU engine through
 metmhn_amd.regularized_optimization.
 
-`marg_frequs` tabulates a cohort for comparison with `simulations.simulate_summary(...).marg_frequs`.
+`marg_frequs` tabulates a cohort for comparison with `simulations.simulate_summary(...).marg_frequs`, `pair_counts` for
+`simulations.simulate_pairs(...).compare`.
 
 Not mirrored (plots, Gillespie sampling, state-space helpers): out of scope, see DESIGN.md.
 """
@@ -159,6 +160,21 @@ def marg_frequs(dat, events: list):
               ["PT-Private", "MT-Private", "Shared"] + ["Present"] * 3]
     inds = pd.MultiIndex.from_tuples(list(zip(*labels)))
     return pd.DataFrame(np.around(counts, 2), columns=events, index=inds).T
+
+
+def pair_counts(dat) -> tuple[np.ndarray, np.ndarray]:
+    """Observed co-occurrence counts of a cohort `dat` [n_pat, 2n+3] per row type 0 - 3 (NM, EM-PT, EM-MT, paired):
+    (n_type int64 [4], pairs int64 [4, 2n, 2n]) with pairs[t] = G.T @ G over the genotype columns [PT_0, MT_0, ...] of
+    the rows of type t - the observed side of `simulations.PairSummary.compare`."""
+    dat = np.asarray(dat)
+    B = dat.shape[1] - 3
+    n_type = np.zeros(4, dtype=np.int64)
+    pairs = np.zeros((4, B, B), dtype=np.int64)
+    for t in range(4):
+        g = dat[dat[:, -1] == t][:, :B].astype(np.int64)
+        n_type[t] = g.shape[0]
+        pairs[t] = g.T @ g
+    return n_type, pairs
 
 
 def save_params(path: str, theta, d_p, d_m, events: list[str]):

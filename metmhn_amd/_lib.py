@@ -74,6 +74,7 @@ SIGNATURES = {
     "mmhn_bench_kronvec": [C.c_void_p, f64p, i8p, C.c_int64, C.c_int, C.c_int, C.c_int, f64p, i64p],
     "mmhn_simulate": [C.c_void_p, f64p, f64p, f64p, C.c_int64, C.c_uint64, i8p, i8p],
     "mmhn_simulate_summary": [C.c_void_p, f64p, f64p, f64p, C.c_int64, C.c_int64, C.c_uint64, i64p],
+    "mmhn_simulate_pairs": [C.c_void_p, f64p, f64p, f64p, C.c_int64, C.c_int64, C.c_uint64, i64p, i64p, i64p],
     "mmhn_get_counters": [C.c_void_p, C.POINTER(Counters)],
     "mmhn_reset_counters": [C.c_void_p],
     "mmhn_debug_lane_moves": [C.c_void_p, C.c_int, C.POINTER(C.c_int)],

@@ -73,7 +73,7 @@ struct Config {
   int coop_wgs = 0;             // MMHN_COOP_WGS: workgroups of a cooperative launch (default: one per CU - with two the launch holds every
                                 // wave slot of the chip and the side streams' kernels wait for its end: 1.65 against 1.47 ms on the 28-event LUAD cohort)
   bool coop = true;             // MMHN_COOP=0: tile solves as one launch per level (k_tsolve) instead of one cooperative launch
-  long long sim_chunk = 1ll << 26;   // MMHN_SIM_CHUNK: samples per launch of mmhn_simulate_summary
+  long long sim_chunk = 1ll << 26;   // MMHN_SIM_CHUNK: samples per launch of mmhn_simulate_summary / mmhn_simulate_pairs
   int stream_blocks = 256 * 8;  // MMHN_STREAM_BLOCKS: workgroups of mmhn_bench_stream's kernel
   bool trace_host = false;      // MMHN_TRACE_HOST: print the host time to issue an evaluation against its total (diagnostic)
   Config() {
@@ -1557,6 +1557,21 @@ int mmhn_simulate_summary(mmhn_handle h, const double* lt, const double* pt_d_ef
   const int N = h->n + 1;
   REQUIRE(N < SIM_MAXN, "too many events for the sampler (n_mut <= 30: event and diagnosis flags share one 32-bit set)");
   simulate_summary(h->impl->stream, h->impl->device, h->impl->cfg.sim_chunk, lt, pt_d_ef, mt_d_ef, h->n, first, n_sim, seed, counts);
+  API_END
+}
+
+int mmhn_simulate_pairs(mmhn_handle h, const double* lt, const double* pt_d_ef, const double* mt_d_ef, int64_t first,
+                        int64_t n_sim, uint64_t seed, int64_t* n_class, int64_t* pairs, int64_t* burden) {
+  API_BEGIN
+  GUARD(h);
+  REQUIRE(h && lt && pt_d_ef && mt_d_ef && n_class && pairs && burden, "null pointer");
+  REQUIRE(first >= 0, "first must be non-negative");
+  REQUIRE(n_sim >= 0, "n_sim must be non-negative");
+  REQUIRE(n_sim <= INT64_MAX - first, "first + n_sim overflows 64 bits");
+  const int N = h->n + 1;
+  REQUIRE(N < SIM_MAXN, "too many events for the sampler (n_mut <= 30: event and diagnosis flags share one 32-bit set)");
+  simulate_pairs(h->impl->stream, h->impl->device, h->impl->cfg.sim_chunk, lt, pt_d_ef, mt_d_ef, h->n, first, n_sim, seed, n_class,
+                 pairs, burden);
   API_END
 }
 

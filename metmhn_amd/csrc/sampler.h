@@ -11,7 +11,8 @@
 // from jax.random's threefry, the distribution does not (tests/test_montecarlo.py); tests/test_sampler_replay.py
 // replays this stream and gillespie_step in NumPy (oracle/sampler_replay.py) and compares every trajectory exactly.
 // k_gillespie writes every trajectory (mmhn_simulate); k_gillespie_summary draws the same ones through the same step
-// function and only counts them (mmhn_simulate_summary, the layout is above the kernel).
+// function and only counts them (mmhn_simulate_summary, the layout is above the kernel); k_gillespie_pairs counts their
+// pairwise co-occurrences and mutation burdens (mmhn_simulate_pairs).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -210,6 +211,124 @@ __global__ __launch_bounds__(SIM_BLOCK) void k_gillespie_summary(const double* _
     for (int w = 0; w < SIM_BLOCK / SIM_WAVE; ++w) s += part[w][c];
     if (s) atomicAdd(counts + c, s);
   }
+}
+
+// Fused sampler that counts second-order tables (mmhn_simulate_pairs): the same trajectories `first + i` again.  With
+// B = 2 n_mut genotype columns [PT_0, MT_0, PT_1, MT_1, ...] as simulate_dat orders them, P = B (B + 1) / 2 pairs (a <= b)
+// numbered row by row of the upper triangle, and the class of a sample = simulate_dat's last column (0 unseeded, 1 seeded
+// and PT observed first, 2 seeded and MT observed first), counts [3 + 3 P + 15 (n_mut + 1)] (int64) is ADDED to:
+//   [c]                                      samples of class c
+//   [3 + c P + p]                            samples of class c with both columns of pair p set (a = b: the marginal)
+//   [3 + 3 P + (5 c + k)(n_mut + 1) + v]     samples of class c whose mutation count of kind k is v;
+//                                            k: 0 |PT|  1 |MT|  2 |PT & MT|  3 |PT & ~MT|  4 |MT & ~PT|
+// Per pass of the grid-stride loop a wave turns its 64 trajectories into B column masks and 3 class masks (one ballot
+// each, dead lanes in no class) in LDS; after a barrier thread t owns the pairs t, t + 256, ... and adds
+// popcount(mask_a & mask_b & class_c) of the four waves to registers of its own (SIM_PAIRS_PER_THREAD x 3, indexed at
+// compile time); the burden histogram takes five LDS atomics per live trajectory.  After the loop every non-zero counter
+// goes out as one 64-bit global atomic.  Integers only: no dependence on the geometry or the order of the atomics.
+// A 32-bit counter receives at most SIM_BLOCK per pass; the host bounds the passes of a launch by SIM_PAIRS_MAX_PASSES.
+constexpr int SIM_PAIR_COLS = 2 * (SIM_MAXN - 2);                                        // 60
+constexpr int SIM_PAIRS_MAX = SIM_PAIR_COLS * (SIM_PAIR_COLS + 1) / 2;                   // 1 830
+constexpr int SIM_PAIRS_PER_THREAD = (SIM_PAIRS_MAX + SIM_BLOCK - 1) / SIM_BLOCK;        // 8
+constexpr int SIM_CLASSES = 3, SIM_BURDEN_KINDS = 5;
+constexpr long long SIM_PAIRS_MAX_PASSES = 1ll << 23;                                    // x SIM_BLOCK = 2^31 per counter
+__host__ __device__ constexpr int sim_pairs_counts(int n_mut) {
+  return SIM_CLASSES + SIM_CLASSES * (n_mut * (2 * n_mut + 1)) + SIM_CLASSES * SIM_BURDEN_KINDS * (n_mut + 1);
+}
+__global__ __launch_bounds__(SIM_BLOCK) void k_gillespie_pairs(const double* __restrict__ log_theta,
+                                                               const double* __restrict__ pt_d,
+                                                               const double* __restrict__ mt_d, int N, long long first,
+                                                               long long n, uint64_t seed,
+                                                               unsigned long long* __restrict__ counts) {
+  constexpr int WAVES = SIM_BLOCK / SIM_WAVE, HIST = SIM_CLASSES * SIM_BURDEN_KINDS * (SIM_MAXN - 1);
+  __shared__ double lt[SIM_MAXN * SIM_MAXN], ltp[SIM_MAXN * SIM_MAXN], dp[SIM_MAXN], dm[SIM_MAXN];
+  __shared__ unsigned long long mask[WAVES][SIM_WAVE];      // [0, B) columns, [B, B + 3) classes; B + 3 <= 63
+  __shared__ uint16_t pair_ab[SIM_PAIRS_MAX];               // pair p -> a | b << 8
+  __shared__ uint32_t hist[HIST + SIM_CLASSES];             // burden [c][k][v], then the class sizes
+  gillespie_load(log_theta, pt_d, mt_d, N, lt, ltp, dp, dm);
+  const int n_mut = N - 1, B = 2 * n_mut, P = B * (B + 1) / 2, V = n_mut + 1;
+  for (int a = threadIdx.x; a < B; a += SIM_BLOCK) {        // row a of the triangle starts at a B - a (a - 1) / 2
+    const int off = a * B - a * (a - 1) / 2;
+    for (int b = a; b < B; ++b) pair_ab[off + b - a] = (uint16_t)(a | (b << 8));
+  }
+  for (int e = threadIdx.x; e < HIST + SIM_CLASSES; e += SIM_BLOCK) hist[e] = 0u;
+  uint32_t acc[SIM_CLASSES][SIM_PAIRS_PER_THREAD];
+#pragma unroll
+  for (int c = 0; c < SIM_CLASSES; ++c)
+#pragma unroll
+    for (int k = 0; k < SIM_PAIRS_PER_THREAD; ++k) acc[c][k] = 0u;
+  __syncthreads();
+  const int wave = threadIdx.x / SIM_WAVE, lane = threadIdx.x % SIM_WAVE;
+  const uint32_t sbit = 1u << (N - 1), muts = sbit - 1u;
+  const int L = 2 * N + 2;
+  for (long long base = (long long)blockIdx.x * SIM_BLOCK; base < n; base += (long long)gridDim.x * SIM_BLOCK) {
+    const long long i = base + threadIdx.x;
+    const bool live = i < n;
+    const long long id = first + i;
+    uint32_t pt = 0, mt = 0;
+    int t_pt = -1, t_mt = -1;
+    if (live)
+      for (int step = 0; step < L; ++step) {
+        if (gillespie_done(pt, mt, N)) break;
+        gillespie_step(lt, ltp, dp, dm, N, id, step, seed, pt, mt, t_pt, t_mt);
+      }
+    const int cls = !(pt & sbit) ? 0 : (t_pt < t_mt ? 1 : 2);
+    // lane a keeps the ballot of column a, lanes B .. B + 2 those of the classes: one LDS write per wave and pass
+    unsigned long long mine = 0ull;
+    for (int m = 0; m < n_mut; ++m) {
+      const unsigned long long bp = __ballot(live && ((pt >> m) & 1u)), bm = __ballot(live && ((mt >> m) & 1u));
+      if (lane == 2 * m) mine = bp;
+      if (lane == 2 * m + 1) mine = bm;
+    }
+#pragma unroll
+    for (int c = 0; c < SIM_CLASSES; ++c) {
+      const unsigned long long bc = __ballot(live && cls == c);
+      if (lane == B + c) mine = bc;
+    }
+    mask[wave][lane] = mine;
+    if (live) {
+      const uint32_t p = pt & muts, m = mt & muts;
+      uint32_t* h = hist + cls * SIM_BURDEN_KINDS * V;
+      atomicAdd(h + __popc(p), 1u);
+      atomicAdd(h + V + __popc(m), 1u);
+      atomicAdd(h + 2 * V + __popc(p & m), 1u);
+      atomicAdd(h + 3 * V + __popc(p & ~m), 1u);
+      atomicAdd(h + 4 * V + __popc(m & ~p), 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < SIM_CLASSES) {
+      uint32_t s = 0;
+      for (int w = 0; w < WAVES; ++w) s += (uint32_t)__popcll(mask[w][B + threadIdx.x]);
+      hist[HIST + threadIdx.x] += s;
+    }
+#pragma unroll
+    for (int k = 0; k < SIM_PAIRS_PER_THREAD; ++k) {
+      const int p = threadIdx.x + k * SIM_BLOCK;
+      if (p < P) {
+        const int a = pair_ab[p] & 0xff, b = pair_ab[p] >> 8;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) {
+          const unsigned long long ab = mask[w][a] & mask[w][b];
+#pragma unroll
+          for (int c = 0; c < SIM_CLASSES; ++c) acc[c][k] += (uint32_t)__popcll(ab & mask[w][B + c]);
+        }
+      }
+    }
+    __syncthreads();                                        // the next pass overwrites the masks
+  }
+  for (int e = threadIdx.x; e < SIM_CLASSES; e += SIM_BLOCK)
+    if (hist[HIST + e]) atomicAdd(counts + e, (unsigned long long)hist[HIST + e]);
+#pragma unroll
+  for (int k = 0; k < SIM_PAIRS_PER_THREAD; ++k) {
+    const int p = threadIdx.x + k * SIM_BLOCK;
+    if (p < P) {
+#pragma unroll
+      for (int c = 0; c < SIM_CLASSES; ++c)
+        if (acc[c][k]) atomicAdd(counts + SIM_CLASSES + c * P + p, (unsigned long long)acc[c][k]);
+    }
+  }
+  for (int e = threadIdx.x; e < SIM_CLASSES * SIM_BURDEN_KINDS * V; e += SIM_BLOCK)
+    if (hist[e]) atomicAdd(counts + SIM_CLASSES + SIM_CLASSES * P + e, (unsigned long long)hist[e]);
 }
 
 }  // namespace mmhn

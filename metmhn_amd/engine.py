@@ -376,6 +376,23 @@ class Engine:
                                                   counts.ctypes.data_as(i64p)))
         return counts
 
+    def simulate_pairs(self, log_theta, pt_d_ef, mt_d_ef, n_sim, seed=0, first=0):
+        """Pairwise co-occurrence and burden counts of the Gillespie samples [first, first + n_sim) without the samples
+        (mmhn_simulate_pairs): int64 n_class [3], pairs [3, 2n, 2n] (per class G.T @ G of simulate's genotype columns) and
+        burden [3, 5, n+1] (histograms of |PT|, |MT|, |PT & MT|, |PT & ~MT|, |MT & ~PT|); classes 0 unseeded, 1 seeded
+        and PT observed first, 2 seeded and MT observed first; include/metmhn_amd.h has the definition."""
+        lt, ltp = self._theta(log_theta); a, ap = self._rates(pt_d_ef, "pt_d_ef"); b, bp = self._rates(mt_d_ef, "mt_d_ef")
+        n_sim, first = int(n_sim), int(first)
+        if n_sim < 0 or first < 0:
+            raise ValueError(f"n_sim and first must be non-negative, got n_sim={n_sim}, first={first}")
+        n_class = np.zeros(3, dtype=np.int64)
+        pairs = np.zeros((3, 2 * self.n, 2 * self.n), dtype=np.int64)
+        burden = np.zeros((3, 5, self.n + 1), dtype=np.int64)
+        _lib.check(self.lib.mmhn_simulate_pairs(self.h, ltp, ap, bp, first, n_sim, int(seed) & (2 ** 64 - 1),
+                                                n_class.ctypes.data_as(i64p), pairs.ctypes.data_as(i64p),
+                                                burden.ctypes.data_as(i64p)))
+        return n_class, pairs, burden
+
     # ---- likeliest event orders
     def likeliest_orders(self, log_theta, obs1, obs2, dat, front_cap=0):
         """MetMHN.likeliest_order of every row of a reference-format `dat` [n_pat, 2n+3] in one call

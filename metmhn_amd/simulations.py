@@ -1,7 +1,9 @@
 """Gillespie sampling of the joint PT/MT process on the GPU - the reference's `metmhn/simulations.py` call
 surface (`simulate_dat`, `simulate_orders`, :87-147) over `mmhn_simulate` (csrc/sampler.h), its reductions of
 trajectories on the host (`extract_bse`, `preseeding_probs`, :150-240), and the same reductions counted on the
-device without the samples (`simulate_summary`, `simulate_preseeding_probs` over `mmhn_simulate_summary`).
+device without the samples (`simulate_summary`, `simulate_preseeding_probs` over `mmhn_simulate_summary`), and the
+second-order counterpart: pairwise co-occurrence and burden tables (`simulate_pairs`, `PairSummary` over
+`mmhn_simulate_pairs`) to hold a fit against the co-occurrence structure of its cohort.
 
 `original_key` takes the place of the `jax.random.PRNGKey`: an int, or anything array-like whose integers are
 folded into the 64-bit Philox key.  Streams differ from jax.random's; distributions do not."""
@@ -156,3 +158,112 @@ def simulate_summary(log_theta, pt_d_ef, mt_d_ef, n_sim: int, original_key=0, fi
 def simulate_preseeding_probs(log_theta, pt_d_ef, mt_d_ef, n_sim: int, original_key=0):
     """simulate_summary(...).preseeding_probs(): the pre-seeding probabilities of n_sim samples, counted on the GPU."""
     return simulate_summary(log_theta, pt_d_ef, mt_d_ef, n_sim, original_key).preseeding_probs()
+
+
+# ---- second order: which events occur together (mmhn_simulate_pairs)
+
+STRATA = ("NM", "EM-PT", "EM-MT", "paired")          # cohort row types 0 - 3, the strata of SimSummary.marg_frequs
+BURDEN_KINDS = ("pt", "mt", "shared", "pt_private", "mt_private")
+
+
+class PairSummary:
+    """Pairwise co-occurrence and burden counts of Gillespie samples (mmhn_simulate_pairs), per class of sample: 0
+    unseeded, 1 seeded and PT observed first, 2 seeded and MT observed first (simulate_dat's last column).
+
+    n_class int64 [3]; pairs int64 [3, B, B], B = 2 n_mut: pairs[c] = G.T @ G over the class's rows of simulate_dat's
+    genotype columns [PT_0, MT_0, PT_1, MT_1, ...] - symmetric, marginal counts on the diagonal, [2i, 2i+1] = event i in
+    both tumours; burden int64 [3, 5, n_mut + 1]: histograms of |PT|, |MT|, |PT & MT|, |PT & ~MT|, |MT & ~PT|
+    (BURDEN_KINDS).  The strata (STRATA) are what a cohort's row types observe: "NM" the PT columns of the unseeded
+    samples, "EM-PT" / "EM-MT" the PT / MT columns of the seeded ones, "paired" all columns of the seeded ones."""
+
+    def __init__(self, n_class, pairs, burden, n_mut: int):
+        self.n_mut = n = int(n_mut)
+        self.n_class = np.asarray(n_class, dtype=np.int64).reshape(3)
+        self.pairs = np.asarray(pairs, dtype=np.int64).reshape(3, 2 * n, 2 * n)
+        self.burden = np.asarray(burden, dtype=np.int64).reshape(3, 5, n + 1)
+
+    def __repr__(self):
+        return f"PairSummary(n_mut={self.n_mut}, n_class={self.n_class.tolist()})"
+
+    def seeded(self):
+        """(pairs[1] + pairs[2], n_class[1] + n_class[2]): the seeded samples, which a cohort's paired rows stand for."""
+        return self.pairs[1] + self.pairs[2], int(self.n_class[1] + self.n_class[2])
+
+    def _stratum(self, stratum):
+        """(pair counts [B, B], samples, observed columns bool [B]) of a stratum."""
+        if stratum not in STRATA:
+            raise ValueError(f"stratum must be one of {STRATA}, got {stratum!r}")
+        counts, n = (self.pairs[0], int(self.n_class[0])) if stratum == "NM" else self.seeded()
+        is_pt = np.arange(2 * self.n_mut) % 2 == 0
+        seen = {"NM": is_pt, "EM-PT": is_pt, "EM-MT": ~is_pt, "paired": np.ones_like(is_pt)}[stratum]
+        return counts, n, seen
+
+    def frequencies(self, stratum) -> np.ndarray:
+        """pairs / samples of the stratum, float64 [B, B]: joint frequencies of two columns, marginal ones on the
+        diagonal; NaN in the blocks the stratum does not observe (and everywhere if it has no sample)."""
+        counts, n, seen = self._stratum(stratum)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            f = counts / np.float64(n)
+        f[~(seen[:, None] & seen[None, :])] = np.nan
+        return f
+
+    def log_odds(self, stratum) -> np.ndarray:
+        """Log odds ratio of every two columns from the stratum's 2x2 table: log(n11 n00 / (n10 n01)) with n11 the pair
+        count and the other cells from the marginal counts; NaN where a cell is 0 (the diagonal included) and in the
+        blocks the stratum does not observe."""
+        counts, n, seen = self._stratum(stratum)
+        m = np.diag(counts)
+        n11 = counts.astype(np.float64)
+        n10, n01 = m[:, None] - n11, m[None, :] - n11
+        n00 = n - m[:, None] - m[None, :] + n11
+        cells = np.stack((n11, n10, n01, n00))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            lo = np.log(n11) + np.log(n00) - np.log(n10) - np.log(n01)
+        lo[(cells <= 0).any(axis=0) | ~(seen[:, None] & seen[None, :])] = np.nan
+        return lo
+
+    def burden_pmf(self, kind, stratum) -> np.ndarray:
+        """Normalised histogram [n_mut + 1] of a tumour's mutation count: kind 0 - 4 or its name in BURDEN_KINDS; "NM"
+        and "EM-PT" observe |PT| only, "EM-MT" |MT| only, "paired" all five - NaN for a kind the stratum does not observe."""
+        k = BURDEN_KINDS.index(kind) if isinstance(kind, str) else int(kind)
+        if not 0 <= k < 5:
+            raise ValueError(f"kind must be 0 - 4 or one of {BURDEN_KINDS}, got {kind!r}")
+        _, n, _ = self._stratum(stratum)
+        if k not in {"NM": (0,), "EM-PT": (0,), "EM-MT": (1,), "paired": range(5)}[stratum]:
+            return np.full(self.n_mut + 1, np.nan)
+        h = self.burden[0, k] if stratum == "NM" else self.burden[1, k] + self.burden[2, k]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return h / np.float64(n)
+
+    def compare(self, dat) -> dict:
+        """The posterior-predictive check of a cohort `dat` [n_pat, 2 n_mut + 3] (reference format, type in the last
+        column): per row type present {stratum: residuals [B, B]}, the standardised residuals (obs - n p) / sqrt(n p (1 - p))
+        of the observed pair counts (Utilityfunctions.pair_counts) against n = rows of the type and p = frequencies(stratum);
+        NaN where p is 0, 1 or not observed by the type."""
+        from .Utilityfunctions import pair_counts
+        dat = np.asarray(dat)
+        if dat.ndim != 2 or dat.shape[1] != 2 * self.n_mut + 3:
+            raise ValueError(f"dat must have shape (n_pat, {2 * self.n_mut + 3}), got {dat.shape}")
+        n_type, obs = pair_counts(dat)
+        out = {}
+        for t, stratum in enumerate(STRATA):
+            if n_type[t] == 0:
+                continue
+            p = self.frequencies(stratum)
+            n = np.float64(n_type[t])
+            with np.errstate(divide="ignore", invalid="ignore"):
+                r = (obs[t] - n * p) / np.sqrt(n * p * (1.0 - p))
+            r[~((p > 0.0) & (p < 1.0))] = np.nan
+            out[stratum] = r
+        return out
+
+
+def simulate_pairs(log_theta, pt_d_ef, mt_d_ef, n_sim: int, original_key=0, first: int = 0) -> PairSummary:
+    """Pairwise co-occurrence and burden tables of the samples [first, first + n_sim) on the GPU without materialising
+    them (mmhn_simulate_pairs); the samples are those of simulate_dat / simulate_summary under the same key."""
+    lt = _check_params(log_theta, pt_d_ef, mt_d_ef)
+    if int(n_sim) < 0 or int(first) < 0:
+        raise ValueError(f"n_sim and first must be non-negative, got n_sim={n_sim}, first={first}")
+    n_mut = lt.shape[0] - 1
+    out = _engine(n_mut).simulate_pairs(lt, pt_d_ef, mt_d_ef, int(n_sim), _seed(original_key), first=int(first))
+    return PairSummary(*out, n_mut)
