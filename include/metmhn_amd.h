@@ -74,7 +74,11 @@ int mmhn_cohort_wsums_begin(mmhn_handle h, const double* log_theta, const double
                             const double* log_d_m, int with_grad, double w);
 int mmhn_cohort_wsums_end(mmhn_handle h, double* wsums);
 /* One more double riding in the SAME all-reduce as the wsums buffer (ABI 5): the value set here travels with the NEXT
- * mmhn_cohort_wsums_begin, is summed over the ranks of the communicator, and is read back after its _end.  The Python host
+ * mmhn_cohort_wsums_begin, is summed over the ranks of the communicator, and is read back after its _end.  That call
+ * takes the value (it is 0 again for the one after it), whether or not its evaluation succeeds; calls in between that are
+ * no mmhn_cohort_wsums_begin - mmhn_cohort_sums, mmhn_cohort_sums_begin, mmhn_patient_grads - leave it where it is, and so
+ * does a _begin that is refused because an evaluation is still pending.  After the _end of a plain
+ * mmhn_cohort_sums_begin, mmhn_get_reduce_flag reads 0.  The Python host
  * uses it for the "this rank's cohort array was edited in place" bit of its layout cache, which used to be a second
  * collective per evaluation (metmhn_amd/regularized_optimization.py: _result). */
 int mmhn_set_reduce_flag(mmhn_handle h, double value);

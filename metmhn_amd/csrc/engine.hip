@@ -946,13 +946,17 @@ struct Engine : EngineBase {
     // without a communicator the packing kernel writes the result straight into the pinned buffer; with one the
     // all-reduce works on device memory and the copy engine brings its result down
     double* packed = (cfg.zero_copy && !comm) ? h_abi_dev : abi_sums.p;
+    // the reduce flag belongs to the weighted evaluation alone: a plain one in between leaves it for the next weighted one.
+    // Taken out of the member before anything is issued, so that an evaluation that throws cannot leave it to a later one.
+    double flag = 0.0;
+    if (w_combined) { flag = reduce_flag; reduce_flag = 0.0; }
     pack_mode = w_combined ? 2 : 1;
-    pack_a = w_combined ? *w_combined : (double)n_em; pack_b = w_combined ? reduce_flag : (double)n_pat; pack_dst = packed;
+    pack_a = w_combined ? *w_combined : (double)n_em; pack_b = w_combined ? flag : (double)n_pat; pack_dst = packed;
     packed_in_eval = false;
     struct Unset { int& m; ~Unset() { m = 0; } } unset{pack_mode};
     evaluate(lt, ldp, ldm, grad, nullptr, nullptr);
     if (!packed_in_eval) {                                 // (no batch: an empty cohort)
-      if (w_combined) hipLaunchKernelGGL(k_pack_wsums, dim3(2), dim3(256), 0, stream, sums.p, N, *w_combined, packed, reduce_flag);
+      if (w_combined) hipLaunchKernelGGL(k_pack_wsums, dim3(2), dim3(256), 0, stream, sums.p, N, *w_combined, packed, flag);
       else hipLaunchKernelGGL(k_pack_sums, dim3(2), dim3(256), 0, stream, sums.p, N, n_em, (double)n_pat, packed);
       HIPCHECK(hipGetLastError());
     }
@@ -960,7 +964,6 @@ struct Engine : EngineBase {
     if (comm) RCCLCHECK(rccl().AllReduce(abi_sums.p, abi_sums.p, (size_t)moved, ncclFloat64, ncclSum, comm, stream));
     if (packed == abi_sums.p) HIPCHECK(hipMemcpyAsync(h_abi, abi_sums.p, moved * sizeof(double), hipMemcpyDeviceToHost, stream));
     flag_pending = w_combined != nullptr;
-    reduce_flag = 0.0;
     sums_issued = std::chrono::steady_clock::now();
     sums_pending = true;
     sums_len = total;
