@@ -304,6 +304,33 @@ int mmhn_order_positions(mmhn_handle h, const double* log_theta, const double* o
                          const int8_t* dat, int64_t n_pat, int n_cols, double* log_evidence, double* pos_pt,
                          double* pos_mt, int32_t* status);
 
+/* ---- posterior event and observation times of a cohort ---------------------------------------
+ * mmhn_order_times: for every row of a reference-format `dat` (read as mmhn_likeliest_orders reads it), over the same
+ * admissible orders as mmhn_order_posteriors and every point of them at which the first observation can fall: the
+ * posterior mean of the time at which every event and every observation happened.  Time 0 is the event-free state, the unit
+ * the one in which an event-free tumour is observed at rate 1.  Given a path the chain holds in a state x for an
+ * Exp(den[x]) time, so a mean time is a sum over the lattice of occupancy / den (metmhn_amd/csrc/ordertime.h).  No
+ * reference counterpart.  fp64 engines only.
+ *   log_evidence [n_pat]                        as mmhn_order_posteriors
+ *   time [n_pat][2 n_mut + 1]                   E(time of the event with code c | the row), event codes as in
+ *                                               mmhn_order_precedences; the two codes of an event that occurred before the
+ *                                               seeding share its moment.  NaN where c is not in the row.
+ *   obs [n_pat][2]                              E(time of the first observation | the row), E(time of the second); a
+ *                                               one-tumour row has (its observation, NaN)
+ *   pt_first [n_pat]                            P(the primary tumour was observed first | the row): exactly 1 / 0 for a
+ *                                               paired row of diagnosis order 1 / neither 0 nor 1, NaN for a one-tumour row
+ *   status [n_pat]: as mmhn_order_precedences - low half MMHN_ORD_OK, MMHN_ORD_INVALID (reason in the HIGH half) or
+ *   MMHN_ORD_TOO_LARGE (the row does not fit the workspace limit on its own, or has more than 10 joint events); every
+ *   output of a row is NaN where its status != 0.  Workspace of a row of k slots, in doubles: the lattice of
+ *   mmhn_order_posteriors + the chunk partials of mmhn_order_precedences' reduction for 2 vectors of k - 1 index bits
+ *   (paired) or 1 vector of k (one tumour) instead of k vectors: less than mmhn_order_precedences' from 4 slots on.
+ * No atomics: two calls return the same bits, whatever the batching.  Rows are cut into batches that fit
+ * mmhn_set_workspace_limit (allocated once per call); the call leaves a loaded cohort as it was.
+ */
+int mmhn_order_times(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, const int8_t* dat,
+                     int64_t n_pat, int n_cols, double* log_evidence, double* time, double* obs, double* pt_first,
+                     int32_t* status);
+
 /* ---- posterior samples of the event orders of a cohort ---------------------------------------
  * mmhn_order_samples: for every row of a reference-format `dat` (read as mmhn_likeliest_orders reads it), orders drawn from
  * the exact posterior over the admissible orders mmhn_order_posteriors sums over: an order comes with the probability
@@ -356,7 +383,7 @@ typedef struct {
   int32_t comm_rank;  /* this engine's rank in it (ncclCommUserRank), -1: none */
 } mmhn_counters;
 /* ABI version of this header: bumped whenever an exported signature or structure changes (4: mmhn_bench_kronvec has its
- * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions, mmhn_order_samples and mmhn_simulate_pairs were added within version 8, purely additive changes).  A client built against another header must refuse to run:
+ * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions, mmhn_order_samples, mmhn_simulate_pairs and mmhn_order_times were added within version 8, purely additive changes).  A client built against another header must refuse to run:
  * mmhn_abi_version() != MMHN_ABI_VERSION (metmhn_amd/_lib.py checks it on load). */
 #define MMHN_ABI_VERSION 8
 int mmhn_abi_version(void);

@@ -3,7 +3,7 @@
 // The rest of the host side lives in headers of this one translation unit: plan.h (the cohort planner, host-only:
 // batches, routes, work lists, offsets), host.h (errors, device arrays, MMHN_* knob readers), comm.h (RCCL),
 // prims.h / orders_host.h / orderpost_host.h (the batching of the order-posterior entry points, opr_rows) /
-// orderprec_host.h / orderpos_host.h / ordersample_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
+// orderprec_host.h / orderpos_host.h / ordertime_host.h / ordersample_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
 //
 // Pipeline of one evaluation (reference call graph: regularized_optimization.py:163-267 ->
 // likelihood.py:_g_coupled_*, _grad_prim_obs, _grad_met_obs), run batch by batch with every
@@ -1021,6 +1021,7 @@ struct Engine : EngineBase {
 #include "orderpost_host.h"
 #include "orderprec_host.h"
 #include "orderpos_host.h"
+#include "ordertime_host.h"
 #include "ordersample_host.h"
 #include "sampler_host.h"
 #include "bench.h"
@@ -1514,6 +1515,21 @@ int mmhn_order_positions(mmhn_handle h, const double* log_theta, const double* o
   REQUIRE(h->dtype == MMHN_F64, "order positions need an fp64 engine (MMHN_F64)");
   order_positions(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, log_evidence, pos_pt,
                   pos_mt, status);
+  API_END
+}
+
+// ---- posterior event and observation times of a cohort: when every event and observation happened, over the same orders
+int mmhn_order_times(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, const int8_t* dat,
+                     int64_t n_pat, int n_cols, double* log_evidence, double* time, double* obs, double* pt_first,
+                     int32_t* status) {
+  API_BEGIN
+  GUARD(h);
+  REQUIRE(log_theta && obs1 && obs2 && log_evidence && time && obs && pt_first && status, "null pointer");
+  REQUIRE(dat || n_pat == 0, "null dat");
+  REQUIRE(n_pat >= 0 && n_pat < ((int64_t)1 << 31), "n_pat out of range");
+  REQUIRE(h->dtype == MMHN_F64, "order times need an fp64 engine (MMHN_F64)");
+  order_times(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, log_evidence, time, obs,
+              pt_first, status);
   API_END
 }
 

@@ -11,8 +11,9 @@
 //   orders.h     likeliest event orders of a cohort: k_orders                 (model.py:213-1389)
 // Tile solves (k_tsolve, k_csolve) live in tsolve.h, the window-layout kernels in wsolve.h / wclass.h, the small-space
 // kernels in small.h, the Gillespie sampler in sampler.h, the sum-product passes over a row's orders in orderpass.h and
-// their three kernels: the pre-seeding posteriors (k_order_post) in orderpost.h, the pairwise precedence posteriors
-// (k_order_prec) in orderprec.h, the event positions (k_order_pos) in orderpos.h.
+// their kernels: the pre-seeding posteriors (k_order_post) in orderpost.h, the pairwise precedence posteriors
+// (k_order_prec) in orderprec.h, the event positions (k_order_pos) in orderpos.h, the event and observation times
+// (k_order_time) in ordertime.h.
 #pragma once
 #include "common.h"
 #include "kv.h"

@@ -448,6 +448,14 @@ class Engine:
         NN = (self.N, self.N)
         return self._order_rows(self.lib.mmhn_order_positions, log_theta, obs1, obs2, dat, NN, NN)
 
+    def order_times(self, log_theta, obs1, obs2, dat):
+        """MetMHN.order_time of every row of a reference-format `dat` [n_pat, 2n+3] in one call (mmhn_order_times): float64
+        log_evidence [n_pat], time [n_pat, 2n+1] over the event codes (NaN where a code is not in the row), obs [n_pat, 2]
+        (first, second observation; a one-tumour row has one), pt_first [n_pat] (NaN for a one-tumour row), int32 status
+        [n_pat] (low half 0 ok, 2 invalid row - reason code in status >> 16 -, 3 lattice larger than the workspace; NaN
+        outputs wherever it is not 0)."""
+        return self._order_rows(self.lib.mmhn_order_times, log_theta, obs1, obs2, dat, (2 * self.n + 1,), (2,), ())
+
     def order_samples(self, log_theta, obs1, obs2, dat, n_samples, seed=0, first=0):
         """MetMHN.sample_order of every row of a reference-format `dat` [n_pat, 2n+3] in one call (mmhn_order_samples), row
         i with row=i, the sample indices first ... first + n_samples - 1 under the 64-bit `seed`: float64 log_evidence

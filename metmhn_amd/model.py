@@ -170,6 +170,40 @@ class OrderPositions(OrderPosition):
         return out
 
 
+class OrderTime(SimpleNamespace):
+    """One observation summed over its admissible orders and first-observation points: log_evidence, time [2n+1] over the
+    event codes (the posterior mean of the time at which the code's event happened; NaN where the observation does not
+    carry the code), obs [2] (the posterior mean time of the first and of the second observation; a one-tumour observation
+    has (its observation, NaN)) and pt_first = P(the primary tumour was observed first | the observation), NaN for one
+    tumour and for "sync".  Time 0 is the event-free state, the unit the one in which an event-free tumour is observed at
+    rate 1."""
+
+    def __init__(self, log_evidence, time, obs, pt_first):
+        super().__init__(log_evidence=log_evidence, time=time, obs=obs, pt_first=pt_first)
+
+
+class OrderTimes(OrderTime):
+    """The same for every row of a cohort: log_evidence [n_pat], time [n_pat, 2n+1], obs [n_pat, 2], pt_first [n_pat]."""
+
+    def relative(self, to: str = "last") -> np.ndarray:
+        """[n_pat, 2n+1]: `time` over the row's last observation time (obs[:, 1] where the row has a second observation,
+        obs[:, 0] elsewhere), or over its first (to="first").  A ratio of two expectations, NOT the expectation of the
+        ratio: the posterior mean of (event time / observation time) is another number, which these arrays do not give."""
+        if to not in ("first", "last"):
+            raise ValueError("to must be 'first' or 'last'")
+        first, second = self.obs[:, 0], self.obs[:, 1]
+        scale = first if to == "first" else np.where(np.isnan(second), first, second)
+        return self.time / scale[:, None]
+
+    def cohort_mean(self, to: str = "last") -> np.ndarray:
+        """[2n+1]: per event code the mean of relative(to) over the rows that carry the code; NaN where no row does."""
+        rel = self.relative(to)
+        have = ~np.isnan(rel)
+        rows = have.sum(axis=0)
+        total = np.where(have, rel, 0.0).sum(axis=0)
+        return np.where(rows > 0, total / np.maximum(rows, 1), np.nan)
+
+
 class OrderSample(SimpleNamespace):
     """Orders of one observation drawn from its exact posterior: log_evidence, orders [n_samples, 2n+1] (int8 event codes
     of likeliest_order, padded with -1), log_prob [n_samples] = log P(order | the observation), margin [n_samples] = the
@@ -261,6 +295,7 @@ class MetMHN:
         self.posteriors_fallback_rows = 0   # ... and the last order_posteriors call
         self.precedences_fallback_rows = 0  # ... and the last order_precedences call
         self.positions_fallback_rows = 0    # ... and the last order_positions call
+        self.times_fallback_rows = 0        # ... and the last order_times call
         self.samples_fallback_rows = 0      # ... and the last sample_orders call
 
     # ------------------------------------------------------------------ diagonals
@@ -363,8 +398,8 @@ class MetMHN:
 
     def _order_cohort(self, device, one, fields: tuple, shapes: tuple, dat, backend: str, dtypes: tuple = None,
                       with_row: bool = False) -> list:
-        """What order_posteriors / order_precedences / order_positions / sample_orders share: [log_evidence, the arrays of
-        `fields` ..., the number of rows the device turned away] of every row of dat, from the Engine method
+        """What order_posteriors / order_precedences / order_positions / order_times / sample_orders share: [log_evidence,
+        the arrays of `fields` ..., the number of rows the device turned away] of every row of dat, from the Engine method
         `device(engine)` with the rows it turned away recomputed by `one` (the entry point of one observation), or from
         `one` alone (backend="host").  dtypes: of the arrays of `fields` (float64 each by default); with_row: `one` also
         takes the row's index (row=i)."""
@@ -483,6 +518,38 @@ class MetMHN:
         *out, self.positions_fallback_rows = self._order_cohort(
             lambda eng: eng.order_positions, self.order_position, ("pos_pt", "pos_mt"), (NN, NN), dat, backend)
         return OrderPositions(*out)
+
+    def order_time(self, state, met_status: str, first_obs: str = None) -> "OrderTime":
+        """When every event and every observation happened, summed over every admissible order and every point of it at
+        which the first observation can fall (same arguments, checks and errors as order_precedence): `time[c]` = the
+        posterior mean of the time of the event with code c (2i PT, 2i+1 MT, 2n seeding; NaN where the observation does
+        not carry it), `obs` = the posterior mean times of the first and the second observation (one tumour: its
+        observation, NaN), `pt_first` = P(the primary tumour was observed first | the observation) - exactly 1.0 for
+        first_obs "PT", 0.0 for "Met", NaN for "sync" and for one tumour.  Time 0 is the event-free state; an event-free
+        tumour is observed at rate 1.  Exact: given a path the chain holds in a state x for an Exp(den[x]) time that does
+        not depend on the move that follows, so a mean time is the sum over the lattice of (the probability that the chain
+        passes through x in a regime, forward vector times backward weight over the evidence) / (that regime's den[x]) over
+        the states before the moment in question - for the event of a slot, the states that do not hold the slot."""
+        chain, st = self._route(state, met_status, first_obs)
+        if chain == "mt":
+            T = self._single_tables(self.log_theta, st, self.obs2)
+            return self._time_single(T, [2 * self.n if e == self.n else 2 * e + 1 for e in T.ev])
+        if chain == "pt":
+            T = self._single_tables(self._pt_log_theta, st, self.obs1)
+            return self._time_single(T, [2 * e for e in T.ev])
+        return self._time_paired(st, first_obs)
+
+    def order_times(self, dat, backend: str = "device") -> "OrderTimes":
+        """order_time of every row of a reference-format `dat` [n_pat, 2n+3], rows read as order_posteriors reads them:
+        arrays log_evidence [n_pat], time [n_pat, 2n+1], obs [n_pat, 2], pt_first [n_pat].
+
+        backend="device": every row in one call of the HIP library (mmhn_order_times); a row whose lattice does not fit the
+        workspace is recomputed here with order_time - how many were is left in `self.times_fallback_rows`.
+        backend="host": order_time row by row.  An invalid row raises likeliest_order's ValueError, with its index."""
+        shapes = ((2 * self.n + 1,), (2,), ())
+        *out, self.times_fallback_rows = self._order_cohort(
+            lambda eng: eng.order_times, self.order_time, ("time", "obs", "pt_first"), shapes, dat, backend)
+        return OrderTimes(*out)
 
     def sample_order(self, state, met_status: str, first_obs: str = None, n_samples: int = 1, key: int = 0, first: int = 0,
                      row: int = 0) -> "OrderSample":
@@ -705,6 +772,18 @@ class MetMHN:
             w = F[xs] * T.num[d][xs | 1 << d] * G[xs | 1 << d]
             pos[T.ev[d]] = np.minimum(np.bincount(held[xs], weights=w, minlength=self.n + 1) / Z, 1.0)
         return float(np.log(Z)), pos
+
+    def _time_single(self, T, codes) -> "OrderTime":
+        """order_time on a one-tumour chain: h[x] = F[x] G[x] (_single_passes: F carries 1 / den[x], G = B / den) is the
+        time the chain spends in x times the evidence; the event of slot d is still to come in the states without bit d."""
+        k, V = T.k, 1 << T.k
+        F, Z, G = self._single_passes(T)
+        h = F * G
+        idx = np.arange(V)
+        time = np.full(2 * self.n + 1, np.nan)
+        for d in range(k):
+            time[codes[d]] = h[(idx >> d & 1) == 0].sum() / Z
+        return OrderTime(float(np.log(Z)), time, np.array([h.sum() / Z, np.nan]), float("nan"))
 
     @staticmethod
     def _draw(W, u):
@@ -985,6 +1064,42 @@ class MetMHN:
                     pos_pt[ev[b], j] += w
                     pos_mt[ev[b], j] += w
         return OrderPosition(float(np.log(Z)), np.minimum(pos_pt / Z, 1.0), np.minimum(pos_mt / Z, 1.0))
+
+    def _time_paired(self, state: MetState, first_obs: str) -> "OrderTime":
+        """order_time on a paired row: _paired_passes and _unseeded_backward, then per state the time the chain spends
+        there times the evidence - hu before the seeding, ha after it with no observation made yet, hb with the first
+        observation made and the other tumour running on alone under its own den - added to every slot the state does not
+        hold yet."""
+        T, F, Z, B = self._paired_passes(state, first_obs)
+        Bu = self._unseeded_backward(T, F, B)
+        k = T.k
+        top, full = 1 << (k - 1), (1 << k) - 1
+        slot = [0.0] * k
+        su = sa = sb = 0.0
+        for x in sorted(F):
+            if not x & top:
+                h = F[x][0] * Bu[x] / T.den[x]
+                su += h
+            else:
+                _, bp, bm = self._settle(T, x, F[x])
+                g = B[x]
+                ha = F[x][0] * g[0] / T.den[x]
+                hb = 0.0
+                if T.pt_first:
+                    hb += bp * g[1] / T.den_mt[x]
+                if T.mt_first:
+                    hb += bm * g[2] / T.den_pt[x]
+                sa += ha
+                sb += hb
+                h = ha + hb
+            for d in range(k):
+                if not x >> d & 1:
+                    slot[d] += h
+        time = np.full(2 * self.n + 1, np.nan)
+        time[T.slots] = np.array(slot) / Z
+        first = su + sa
+        pt_first = float("nan") if T.sync else float(self._settle(T, full, F[full])[1] * T.o2[full] / Z)
+        return OrderTime(float(np.log(Z)), time, np.array([first / Z, (first + sb) / Z]), pt_first)
 
     def _precedence_paired(self, state: MetState, first_obs: str) -> "OrderPrecedence":
         """_posterior_paired's passes, the backward pass continued over the unseeded states whose tumours agree (a scalar:
