@@ -331,6 +331,43 @@ int mmhn_order_times(mmhn_handle h, const double* log_theta, const double* obs1,
                      int64_t n_pat, int n_cols, double* log_evidence, double* time, double* obs, double* pt_first,
                      int32_t* status);
 
+/* ---- posterior genotypes at the first observation of a cohort's paired rows ------------------
+ * mmhn_order_snapshots: for every row of a reference-format `dat` (read as mmhn_likeliest_orders reads it), over the same
+ * admissible orders as mmhn_order_posteriors and every point of them at which the first observation can fall: what the two
+ * tumours held at the moment of the first observation.  The first observation of a paired row falls in a seeded state x
+ * that holds every event of the tumour it is made of; with r = 0 the primary tumour observed first and r = 1 the metastasis,
+ * mass(r, x) / evidence is the posterior probability that the first observation was of tumour r and found the chain in x
+ * (metmhn_amd/csrc/ordersnap.h).  No reference counterpart (the reference sums the observation point away).  fp64 engines
+ * only.
+ *   log_evidence [n_pat]                        as mmhn_order_posteriors
+ *   held [n_pat][2][2 n_mut + 1]                held[r][c] = P(the first observation was of tumour r and the event with code
+ *                                               c had happened by then | the row), event codes as in mmhn_order_precedences.
+ *                                               held[0][2 n_mut] + held[1][2 n_mut] = 1, held[0][2 n_mut] is pt_first of
+ *                                               mmhn_order_times, and held[r][c] = held[r][2 n_mut] for the codes of tumour r.
+ *                                               Exactly 0 throughout the r that the row's diagnosis order excludes (1: r = 1;
+ *                                               neither 0 nor 1: r = 0).  NaN where c is not in the row.
+ *   late [n_pat][2][n_mut + 1]                  late[r][j] = P(the first observation was of tumour r and exactly j events of
+ *                                               the other tumour happened after it | the row); 0 past the number of events the
+ *                                               other tumour has; the 2 (n_mut + 1) entries sum to 1
+ *   map_first [n_pat], map_state [n_pat][2 n_mut + 1], map_prob [n_pat]
+ *                                               the single most probable (r, x): r; per code 1 = held in x, 0 = in the row and
+ *                                               still to come, -1 = not in the row; mass(r, x) / evidence.  Of equal masses
+ *                                               r = 0 wins over r = 1, then the x that is the smaller number over the row's
+ *                                               occupied columns of dat (the first column the lowest bit).
+ *   A one-tumour row (types 0, 1, 2) has one observation: a valid log_evidence, NaN in held, late and map_prob, -1 in
+ *   map_first and map_state.
+ *   status [n_pat]: as mmhn_order_posteriors - low half MMHN_ORD_OK, MMHN_ORD_INVALID (reason in the HIGH half) or
+ *   MMHN_ORD_TOO_LARGE (the row does not fit the workspace limit on its own; the number of joint events does not matter
+ *   here); where it is not 0 every double of the row is NaN and every integer -1.  Workspace of a row of k slots, in doubles:
+ *   the lattice of mmhn_order_posteriors, for a paired row + the chunk partials of mmhn_order_precedences' reduction for 2
+ *   vectors of k - 1 index bits, as mmhn_order_times'.
+ * No atomics: two calls return the same bytes, whatever the batching.  Rows are cut into batches that fit
+ * mmhn_set_workspace_limit (allocated once per call); the call leaves a loaded cohort as it was.
+ */
+int mmhn_order_snapshots(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, const int8_t* dat,
+                         int64_t n_pat, int n_cols, double* log_evidence, double* held, double* late, int8_t* map_state,
+                         int32_t* map_first, double* map_prob, int32_t* status);
+
 /* ---- posterior samples of the event orders of a cohort ---------------------------------------
  * mmhn_order_samples: for every row of a reference-format `dat` (read as mmhn_likeliest_orders reads it), orders drawn from
  * the exact posterior over the admissible orders mmhn_order_posteriors sums over: an order comes with the probability
@@ -383,7 +420,7 @@ typedef struct {
   int32_t comm_rank;  /* this engine's rank in it (ncclCommUserRank), -1: none */
 } mmhn_counters;
 /* ABI version of this header: bumped whenever an exported signature or structure changes (4: mmhn_bench_kronvec has its
- * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions, mmhn_order_samples, mmhn_simulate_pairs and mmhn_order_times were added within version 8, purely additive changes).  A client built against another header must refuse to run:
+ * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions, mmhn_order_samples, mmhn_simulate_pairs, mmhn_order_times and mmhn_order_snapshots were added within version 8, purely additive changes).  A client built against another header must refuse to run:
  * mmhn_abi_version() != MMHN_ABI_VERSION (metmhn_amd/_lib.py checks it on load). */
 #define MMHN_ABI_VERSION 8
 int mmhn_abi_version(void);

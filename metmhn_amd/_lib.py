@@ -83,6 +83,7 @@ SIGNATURES = {
     "mmhn_order_precedences": [C.c_void_p, f64p, f64p, f64p, i8p, C.c_int64, C.c_int, f64p, f64p, i32p],
     "mmhn_order_positions": [C.c_void_p, f64p, f64p, f64p, i8p, C.c_int64, C.c_int, f64p, f64p, f64p, i32p],
     "mmhn_order_times": [C.c_void_p, f64p, f64p, f64p, i8p, C.c_int64, C.c_int, f64p, f64p, f64p, f64p, i32p],
+    "mmhn_order_snapshots": [C.c_void_p, f64p, f64p, f64p, i8p, C.c_int64, C.c_int, f64p, f64p, f64p, i8p, i32p, f64p, i32p],
     "mmhn_order_samples": [C.c_void_p, f64p, f64p, f64p, i8p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_uint64, f64p, i8p,
                            f64p, i32p],
 }

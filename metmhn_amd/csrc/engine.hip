@@ -3,7 +3,7 @@
 // The rest of the host side lives in headers of this one translation unit: plan.h (the cohort planner, host-only:
 // batches, routes, work lists, offsets), host.h (errors, device arrays, MMHN_* knob readers), comm.h (RCCL),
 // prims.h / orders_host.h / orderpost_host.h (the batching of the order-posterior entry points, opr_rows) /
-// orderprec_host.h / orderpos_host.h / ordertime_host.h / ordersample_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
+// orderprec_host.h / orderpos_host.h / ordertime_host.h / ordersnap_host.h / ordersample_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
 //
 // Pipeline of one evaluation (reference call graph: regularized_optimization.py:163-267 ->
 // likelihood.py:_g_coupled_*, _grad_prim_obs, _grad_met_obs), run batch by batch with every
@@ -1022,6 +1022,7 @@ struct Engine : EngineBase {
 #include "orderprec_host.h"
 #include "orderpos_host.h"
 #include "ordertime_host.h"
+#include "ordersnap_host.h"
 #include "ordersample_host.h"
 #include "sampler_host.h"
 #include "bench.h"
@@ -1530,6 +1531,22 @@ int mmhn_order_times(mmhn_handle h, const double* log_theta, const double* obs1,
   REQUIRE(h->dtype == MMHN_F64, "order times need an fp64 engine (MMHN_F64)");
   order_times(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, log_evidence, time, obs,
               pt_first, status);
+  API_END
+}
+
+// ---- posterior genotypes at the first observation of a cohort's paired rows: what the two tumours held then, over the same orders
+int mmhn_order_snapshots(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, const int8_t* dat,
+                         int64_t n_pat, int n_cols, double* log_evidence, double* held, double* late, int8_t* map_state,
+                         int32_t* map_first, double* map_prob, int32_t* status) {
+  API_BEGIN
+  GUARD(h);
+  REQUIRE(log_theta && obs1 && obs2 && log_evidence && held && late && map_state && map_first && map_prob && status,
+          "null pointer");
+  REQUIRE(dat || n_pat == 0, "null dat");
+  REQUIRE(n_pat >= 0 && n_pat < ((int64_t)1 << 31), "n_pat out of range");
+  REQUIRE(h->dtype == MMHN_F64, "order snapshots need an fp64 engine (MMHN_F64)");
+  order_snapshots(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, log_evidence, held, late,
+                  map_state, map_first, map_prob, status);
   API_END
 }
 

@@ -13,7 +13,7 @@
 // kernels in small.h, the Gillespie sampler in sampler.h, the sum-product passes over a row's orders in orderpass.h and
 // their kernels: the pre-seeding posteriors (k_order_post) in orderpost.h, the pairwise precedence posteriors
 // (k_order_prec) in orderprec.h, the event positions (k_order_pos) in orderpos.h, the event and observation times
-// (k_order_time) in ordertime.h.
+// (k_order_time) in ordertime.h, the genotypes at the first observation (k_order_snap) in ordersnap.h.
 #pragma once
 #include "common.h"
 #include "kv.h"

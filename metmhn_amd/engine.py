@@ -411,18 +411,22 @@ class Engine:
                                                   status.ctypes.data_as(_lib.i32p)))
         return orders, prob, status
 
-    def _order_rows(self, fn, log_theta, obs1, obs2, dat, *shapes):
-        """One call of an mmhn_order_* entry point `fn` on a reference-format `dat`: log_evidence [n_pat], one float64 array
-        [n_pat, *shape] per result of the entry point, int32 status [n_pat]."""
+    def _order_rows(self, fn, log_theta, obs1, obs2, dat, *shapes, dtypes=None):
+        """One call of an mmhn_order_* entry point `fn` on a reference-format `dat`: log_evidence [n_pat], one array
+        [n_pat, *shape] per result of the entry point (float64, or the int8 / int32 / float64 of `dtypes`), int32 status
+        [n_pat]."""
         keep, (ltp, ap, bp) = self._params(log_theta, obs1, obs2)
         d = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
         if d.ndim != 2:
             raise ValueError("dat must be a 2-D array [n_pat, 2 n_mut + 3]")
         n_pat = d.shape[0]
-        out = [np.zeros(n_pat)] + [np.empty((n_pat,) + shape) for shape in shapes]      # (the library fills them with NaN first)
+        kinds = dtypes or (np.float64,) * len(shapes)
+        # (the library fills them with NaN / -1 first)
+        out = [np.zeros(n_pat)] + [np.empty((n_pat,) + shape, dtype=kind) for shape, kind in zip(shapes, kinds)]
         status = np.zeros(n_pat, dtype=np.int32)
+        ptr = {np.dtype(np.float64): f64p, np.dtype(np.int8): i8p, np.dtype(np.int32): _lib.i32p}
         _lib.check(fn(self.h, ltp, ap, bp, d.ctypes.data_as(i8p), n_pat, int(d.shape[1]),
-                      *(a.ctypes.data_as(f64p) for a in out), status.ctypes.data_as(_lib.i32p)))
+                      *(a.ctypes.data_as(ptr[a.dtype]) for a in out), status.ctypes.data_as(_lib.i32p)))
         return (*out, status)
 
     def order_posteriors(self, log_theta, obs1, obs2, dat):
@@ -455,6 +459,16 @@ class Engine:
         [n_pat] (low half 0 ok, 2 invalid row - reason code in status >> 16 -, 3 lattice larger than the workspace; NaN
         outputs wherever it is not 0)."""
         return self._order_rows(self.lib.mmhn_order_times, log_theta, obs1, obs2, dat, (2 * self.n + 1,), (2,), ())
+
+    def order_snapshots(self, log_theta, obs1, obs2, dat):
+        """MetMHN.order_snapshot of every row of a reference-format `dat` [n_pat, 2n+3] in one call (mmhn_order_snapshots):
+        float64 log_evidence [n_pat], held [n_pat, 2, 2n+1] over the event codes (NaN where a code is not in the row), late
+        [n_pat, 2, N], int8 map_state [n_pat, 2n+1], int32 map_first [n_pat], float64 map_prob [n_pat] (NaN / -1 throughout a
+        one-tumour row, which has no first observation), int32 status [n_pat] (low half 0 ok, 2 invalid row - reason code in
+        status >> 16 -, 3 lattice larger than the workspace; NaN / -1 outputs wherever it is not 0)."""
+        L = 2 * self.n + 1
+        return self._order_rows(self.lib.mmhn_order_snapshots, log_theta, obs1, obs2, dat, (2, L), (2, self.N), (L,), (), (),
+                                dtypes=(np.float64, np.float64, np.int8, np.int32, np.float64))
 
     def order_samples(self, log_theta, obs1, obs2, dat, n_samples, seed=0, first=0):
         """MetMHN.sample_order of every row of a reference-format `dat` [n_pat, 2n+3] in one call (mmhn_order_samples), row

@@ -204,6 +204,49 @@ class OrderTimes(OrderTime):
         return np.where(rows > 0, total / np.maximum(rows, 1), np.nan)
 
 
+class OrderSnapshot(SimpleNamespace):
+    """What the two tumours of one paired observation held at the moment of the first observation, summed over its
+    admissible orders and first-observation points; r = 0: the primary tumour was observed first, r = 1: the metastasis.
+    log_evidence; held [2, 2n+1] over the event codes, held[r, c] = P(the first observation was of tumour r and the event
+    with code c had happened by then | the observation), NaN where the observation does not carry c, exactly 0 throughout
+    the r that first_obs excludes; late [2, n+1], late[r, j] = P(the first observation was of tumour r and exactly j events of
+    the other tumour happened after it | the observation); and the single most probable snapshot: map_first = its r,
+    map_state [2n+1] (int8: 1 the code is held, 0 it is carried and still to come, -1 the observation does not carry it),
+    map_prob its posterior probability.  An observation without a first observation - one tumour, or "sync" - has its
+    log_evidence, NaN in held, late and map_prob and -1 in map_first and map_state."""
+
+    def __init__(self, log_evidence, held, late, map_state, map_first, map_prob):
+        super().__init__(log_evidence=log_evidence, held=held, late=late, map_state=map_state, map_first=map_first,
+                         map_prob=map_prob)
+
+
+class OrderSnapshots(OrderSnapshot):
+    """The same for every row of a cohort: log_evidence [n_pat], held [n_pat, 2, 2n+1], late [n_pat, 2, n+1], map_state
+    [n_pat, 2n+1] (int8), map_first [n_pat] (int32), map_prob [n_pat]."""
+
+    def cohort_late(self) -> np.ndarray:
+        """[n]: per mutation i the mean, over the paired rows that carry i in the later-observed tumour only, of the
+        probability that i arose after the first observation.  A row that carries i in the metastasis and not in the
+        primary tumour counts where the primary tumour can have been observed first (held[0, seeding] > 0: its diagnosis
+        order is "PT" or "unknown"), with the term held[0, seeding] - held[0, 2i+1] = P(the primary tumour was observed first
+        and i had not yet happened in the metastasis | the row); a row that carries i in the primary tumour only counts
+        where the metastasis can have been observed first, with held[1, seeding] - held[1, 2i].  A term is divided by
+        nothing: it is the joint probability of "this tumour was observed first" and "i came later", not the probability of
+        the latter given the former, so an "unknown" row adds less than a row whose diagnosis order is known.  NaN where no
+        row qualifies."""
+        L = self.held.shape[-1]
+        n = (L - 1) // 2
+        have = ~np.isnan(self.held[:, 0, :])
+        pt, mt = have[:, 0:2 * n:2], have[:, 1:2 * n:2]
+        first = np.where(have[:, 2 * n, None], self.held[:, :, 2 * n], 0.0)          # [n_pat, 2]; 0: not a paired row
+        after_pt = (mt & ~pt) & (first[:, 0, None] > 0.0)
+        after_mt = (pt & ~mt) & (first[:, 1, None] > 0.0)
+        term = (np.where(after_pt, first[:, 0, None] - self.held[:, 0, 1:2 * n:2], 0.0)
+                + np.where(after_mt, first[:, 1, None] - self.held[:, 1, 0:2 * n:2], 0.0))
+        rows = (after_pt | after_mt).sum(axis=0)
+        return np.where(rows > 0, term.sum(axis=0) / np.maximum(rows, 1), np.nan)
+
+
 class OrderSample(SimpleNamespace):
     """Orders of one observation drawn from its exact posterior: log_evidence, orders [n_samples, 2n+1] (int8 event codes
     of likeliest_order, padded with -1), log_prob [n_samples] = log P(order | the observation), margin [n_samples] = the
@@ -296,6 +339,7 @@ class MetMHN:
         self.precedences_fallback_rows = 0  # ... and the last order_precedences call
         self.positions_fallback_rows = 0    # ... and the last order_positions call
         self.times_fallback_rows = 0        # ... and the last order_times call
+        self.snapshots_fallback_rows = 0    # ... and the last order_snapshots call
         self.samples_fallback_rows = 0      # ... and the last sample_orders call
 
     # ------------------------------------------------------------------ diagonals
@@ -398,7 +442,7 @@ class MetMHN:
 
     def _order_cohort(self, device, one, fields: tuple, shapes: tuple, dat, backend: str, dtypes: tuple = None,
                       with_row: bool = False) -> list:
-        """What order_posteriors / order_precedences / order_positions / order_times / sample_orders share: [log_evidence,
+        """What order_posteriors / order_precedences / order_positions / order_times / order_snapshots / sample_orders share: [log_evidence,
         the arrays of `fields` ..., the number of rows the device turned away] of every row of dat, from the Engine method
         `device(engine)` with the rows it turned away recomputed by `one` (the entry point of one observation), or from
         `one` alone (backend="host").  dtypes: of the arrays of `fields` (float64 each by default); with_row: `one` also
@@ -550,6 +594,44 @@ class MetMHN:
         *out, self.times_fallback_rows = self._order_cohort(
             lambda eng: eng.order_times, self.order_time, ("time", "obs", "pt_first"), shapes, dat, backend)
         return OrderTimes(*out)
+
+    def order_snapshot(self, state, met_status: str, first_obs: str = None) -> "OrderSnapshot":
+        """What the two tumours looked like at the moment of the first observation, summed over every admissible order and
+        every point of it at which the first observation can fall (same arguments, checks and errors as order_precedence).
+        With r = 0 the primary tumour observed first and r = 1 the metastasis: `held[r, c]` = P(the first observation was of
+        tumour r and the event with code c - 2i PT, 2i+1 MT, 2n seeding - had happened by then | the observation), so
+        held[0, 2n] + held[1, 2n] = 1, held[0, 2n] is order_time's pt_first and held[r, c] = held[r, 2n] for the codes of
+        tumour r itself; `late[r, j]` = P(the first observation was of tumour r and exactly j events of the other tumour
+        happened after it | the observation), 0 past the number of events the other tumour has, the whole block summing to
+        1; `map_first`, `map_state`, `map_prob`: the single most probable (r, state at the first observation) - of equal
+        masses r = 0 before r = 1, then the state that is the smaller number over the observation's slots - and its
+        probability.  Exact: the first observation falls in a seeded state x that holds every event of the tumour it is made
+        of, and with _paired_passes' F, B and Z the mass F[x]_a o1[x] / den_mt[x] B[x]_P (the primary tumour; F[x]_a o2[x] /
+        den_pt[x] B[x]_M the metastasis) over Z is the posterior probability that it fell there.  One tumour has one
+        observation and "sync" no first one: log_evidence, NaN and -1 elsewhere."""
+        chain, st = self._route(state, met_status, first_obs)
+        if chain == "mt":
+            Z = self._single_passes(self._single_tables(self.log_theta, st, self.obs2))[1]
+            return self._snapshot_none(float(np.log(Z)))
+        if chain == "pt":
+            Z = self._single_passes(self._single_tables(self._pt_log_theta, st, self.obs1))[1]
+            return self._snapshot_none(float(np.log(Z)))
+        return self._snapshot_paired(st, first_obs)
+
+    def order_snapshots(self, dat, backend: str = "device") -> "OrderSnapshots":
+        """order_snapshot of every row of a reference-format `dat` [n_pat, 2n+3], rows read as order_posteriors reads them:
+        arrays log_evidence [n_pat], held [n_pat, 2, 2n+1], late [n_pat, 2, n+1], map_state [n_pat, 2n+1] (int8), map_first
+        [n_pat] (int32), map_prob [n_pat].
+
+        backend="device": every row in one call of the HIP library (mmhn_order_snapshots); a row whose lattice does not fit
+        the workspace is recomputed here with order_snapshot - how many were is left in `self.snapshots_fallback_rows`.
+        backend="host": order_snapshot row by row.  An invalid row raises likeliest_order's ValueError, with its index."""
+        L = 2 * self.n + 1
+        *out, self.snapshots_fallback_rows = self._order_cohort(
+            lambda eng: eng.order_snapshots, self.order_snapshot, ("held", "late", "map_state", "map_first", "map_prob"),
+            ((2, L), (2, self.n + 1), (L,), (), ()), dat, backend,
+            dtypes=(np.float64, np.float64, np.int8, np.int32, np.float64))
+        return OrderSnapshots(*out)
 
     def sample_order(self, state, met_status: str, first_obs: str = None, n_samples: int = 1, key: int = 0, first: int = 0,
                      row: int = 0) -> "OrderSample":
@@ -1100,6 +1182,45 @@ class MetMHN:
         first = su + sa
         pt_first = float("nan") if T.sync else float(self._settle(T, full, F[full])[1] * T.o2[full] / Z)
         return OrderTime(float(np.log(Z)), time, np.array([first / Z, (first + sb) / Z]), pt_first)
+
+    def _snapshot_none(self, log_evidence: float) -> "OrderSnapshot":
+        """order_snapshot of an observation without a first observation."""
+        L = 2 * self.n + 1
+        return OrderSnapshot(log_evidence, np.full((2, L), np.nan), np.full((2, self.n + 1), np.nan),
+                             np.full(L, -1, dtype=np.int8), -1, float("nan"))
+
+    def _snapshot_paired(self, state: MetState, first_obs: str) -> "OrderSnapshot":
+        """order_snapshot on a paired row: _paired_passes, then per regime r the masses of the seeded states that hold every
+        slot of the first-observed tumour, added to every slot the state holds and to the number of slots it lacks; the
+        largest mass is kept, the first of equal ones in the order (r, x)."""
+        T, F, Z, B = self._paired_passes(state, first_obs)
+        le = float(np.log(Z))
+        if T.sync:
+            return self._snapshot_none(le)
+        n, k = self.n, T.k
+        top, full = 1 << (k - 1), (1 << k) - 1
+        slot, late = np.zeros((2, k)), np.zeros((2, n + 1))
+        best = (-1.0, -1, 0)
+        regimes = ((T.pt_first, T.pt_mask, T.o1, getattr(T, "den_mt", None), 1),
+                   (T.mt_first, T.mt_mask, T.o2, getattr(T, "den_pt", None), 2))
+        for r, (possible, own, o, den, comp) in enumerate(regimes):
+            if not possible:
+                continue
+            for x in range(top, full + 1):
+                if x & own != own:
+                    continue
+                s = F[x][0] * o[x] / den[x] * B[x][comp]
+                for d in range(k):
+                    if x >> d & 1:
+                        slot[r, d] += s
+                late[r, bin(full ^ x).count("1")] += s
+                if s > best[0]:
+                    best = (s, r, x)
+        held = np.full((2, 2 * n + 1), np.nan)
+        held[:, T.slots] = np.minimum(slot / Z, 1.0)             # the quotient of two roundings may pass 1
+        map_state = np.full(2 * n + 1, -1, dtype=np.int8)
+        map_state[T.slots] = [best[2] >> d & 1 for d in range(k)]
+        return OrderSnapshot(le, held, np.minimum(late / Z, 1.0), map_state, best[1], float(min(best[0] / Z, 1.0)))
 
     def _precedence_paired(self, state: MetState, first_obs: str) -> "OrderPrecedence":
         """_posterior_paired's passes, the backward pass continued over the unseeded states whose tumours agree (a scalar:
