@@ -17,6 +17,22 @@
  *   state  int8 [2n+1]  joint observation;  [n+1] for the single-tumour functions
  *   vectors have 2^k entries, k = #ones in state; index bit b <-> b-th active slot.
  *   log_theta fp64 [n+1][n+1], log_d_p / log_d_m fp64 [n+1].
+ *
+ * Size limits (every one is checked on the host before anything is launched; the text is mmhn_last_error()):
+ *   n_mut in [1, 31] for the engine, the single-vector functions and the mmhn_order_* / mmhn_likeliest_orders entry points:
+ *     mmhn_create fails with "n_mut must be in [1, 31]".
+ *   n_mut <= 30 for mmhn_simulate, mmhn_simulate_summary and mmhn_simulate_pairs; on an engine with n_mut = 31 they fail with
+ *     "too many events for the sampler (n_mut <= 30: event and diagnosis flags share one 32-bit set)".
+ *   At most 30 active slots (index bits) in any one restricted space.  For a row of dat that is its joint space (type 3: PT
+ *     slots + MT slots + seeding) or its single-tumour space (types 0 / 1: PT slots + seeding, type 2: MT slots + seeding):
+ *     mmhn_set_cohort fails with "too many active events for one patient" and leaves the engine without a cohort.  For a
+ *     state of the single-vector functions: "too many active events".  The order entry points give such a row the status
+ *     MMHN_ORD_TOO_LARGE.
+ *   Verified sizes: spaces of up to 30 bits are accepted; the largest ones a test compares with a reference have k = 27
+ *     (fp32 window route), k = 26 (tile route, fp64) and k = 25 (fp64 window route, both class sizes at their maximum), and
+ *     n_mut = 31 is compared with small spaces (k <= 20).  Nothing above k = 27 has been compared with a reference: a vector
+ *     of a 30-bit space is 8 GB per argument of the single-vector interface, and the CPU reference needs tens of seconds and
+ *     tens of GB for one such row.
  */
 #ifndef METMHN_AMD_H
 #define METMHN_AMD_H

@@ -79,7 +79,11 @@ struct PatRec {
 
 inline int popc(uint32_t v) { return __builtin_popcount(v); }
 
-// joint space of `state` (length 2n+1)
+// joint space of `state` (length 2n+1).  d.k is always the number of active slots; their roles (ev, cls, bitP / bitM, the
+// masks) are recorded for the slots 0 .. 31 only, so that no shift or array index reaches 32 whatever the state holds.  A
+// Desc with d.k > MAXK is therefore incomplete and must not be used: plan.h (decode_row) and prims.h refuse d.k > MAXK
+// themselves; orders_host.h and orderpost_host.h call this only for rows that passed their own r.k > MAXK filter (status
+// MMHN_ORD_TOO_LARGE for the others)
 inline Desc make_joint(const int8_t* state, int n) {
   Desc d{};
   d.mode = JOINT; d.N = n + 1; d.seedbit = -1; d.pset = PS_THETA; d.obs = OBS_JOINT; d.wl = -1;
@@ -87,12 +91,14 @@ inline Desc make_joint(const int8_t* state, int n) {
   int k = 0;
   for (int j = 0; j < n; ++j) {
     const bool p = state[2 * j] != 0, m = state[2 * j + 1] != 0;
-    if (p) { d.ev[k] = (int8_t)j; d.cls[k] = CP; d.bitP[j] = (int8_t)k; d.maskP |= 1u << k;
-             if (m) d.pairP |= 1u << k; else d.lone |= 1u << k; ++k; }
-    if (m) { d.ev[k] = (int8_t)j; d.cls[k] = CM; d.bitM[j] = (int8_t)k; d.maskM |= 1u << k;
-             if (!p) d.lone |= 1u << k; ++k; }
+    if (p) { if (k < 32) { d.ev[k] = (int8_t)j; d.cls[k] = CP; d.bitP[j] = (int8_t)k; d.maskP |= 1u << k;
+                           if (m) d.pairP |= 1u << k; else d.lone |= 1u << k; }
+             ++k; }
+    if (m) { if (k < 32) { d.ev[k] = (int8_t)j; d.cls[k] = CM; d.bitM[j] = (int8_t)k; d.maskM |= 1u << k;
+                           if (!p) d.lone |= 1u << k; }
+             ++k; }
   }
-  if (state[2 * n]) { d.ev[k] = (int8_t)n; d.cls[k] = CS; d.seedbit = k; ++k; }
+  if (state[2 * n]) { if (k < 32) { d.ev[k] = (int8_t)n; d.cls[k] = CS; d.seedbit = k; } ++k; }
   d.k = k;
   return d;
 }

@@ -610,7 +610,19 @@ struct Engine : EngineBase {
     batches.clear();
     dev.clear();
     n_em = 0;
-    batches = plan_cohort<T>(cfg.plan, dat.data(), np, nc, n, n_em);
+    // a cohort that is refused, or whose plan cannot be brought to the device, leaves the engine without one (no patient
+    // count next to an empty or half-uploaded plan)
+    try {
+      batches = plan_cohort<T>(cfg.plan, dat.data(), np, nc, n, n_em);
+      place_cohort();
+    } catch (...) {
+      dat.clear(); batches.clear(); dev.clear();
+      n_pat = 0; n_em = 0;
+      throw;
+    }
+  }
+  // device copies of the plan and the workspace
+  void place_cohort() {
     dev.resize(batches.size());
     // the workspace: sized for the largest batch
     long long mvJ = 0, mvS = 0, mtJ = 0, mtS = 0, mvM = 0;

@@ -296,6 +296,13 @@ static RowProblems decode_row(const int8_t* row, long long r, int n, int nc) {
   PatRec& pr = p.pr;
   pr.kind = type; pr.order = (order == 0 || order == 1) ? order : 2; pr.j = -1; pr.s[0] = pr.s[1] = -1;
   pr.row = (int)r;
+  // active slots of every problem of the row, counted before any Desc is built: a restricted space - joint or
+  // single-tumour - holds at most MAXK index bits (the marginal problems of a paired row are smaller than its joint one)
+  int npt = 0, nmt = 0;
+  for (int j = 0; j < n; ++j) { npt += row[2 * j]; nmt += row[2 * j + 1]; }
+  const int kmax = type == 3 ? npt + nmt + 1 : type == 2 ? nmt + 1 : npt + row[2 * n];
+  const bool unseeded_pair = type == 3 && row[2 * n] != 1;   // refused below with its own message
+  REQUIRE(unseeded_pair || kmax <= MAXK, "too many active events for one patient");
   std::vector<int8_t> st(2 * n + 2);
   if (type == 0 || type == 1) {
     for (int j = 0; j <= n; ++j) st[j] = row[2 * j];          // PT slots + seeding (regularized_optimization.py:189)
@@ -324,7 +331,6 @@ static RowProblems decode_row(const int8_t* row, long long r, int n, int nc) {
       p.has[1] = true;
     }
   }
-  REQUIRE(!p.hasJ || p.dj.k <= MAXK, "too many active events for one patient");
   return p;
 }
 

@@ -92,7 +92,14 @@ class Engine:
         dat = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
         if dat.ndim != 2 or dat.shape[1] != 2 * self.n + 3:
             raise ValueError(f"dat must be [n_pat, {2 * self.n + 3}]")
-        _lib.check(self.lib.mmhn_set_cohort(self.h, dat.ctypes.data_as(i8p), dat.shape[0], dat.shape[1]))
+        try:
+            _lib.check(self.lib.mmhn_set_cohort(self.h, dat.ctypes.data_as(i8p), dat.shape[0], dat.shape[1]))
+        except RuntimeError as err:
+            # a cohort that the library refused or could not place leaves it without one; a call turned away while an
+            # evaluation is pending never read the rows, and the library keeps the cohort it has
+            if "has not been collected" not in str(err):
+                self.n_pat = 0
+            raise
         self.n_pat = dat.shape[0]
 
     def _params(self, log_theta, log_d_p, log_d_m):

@@ -235,6 +235,33 @@ static Cohort window_cohort(const char* name, int n) {
   return c;
 }
 
+// n = 31, the largest event count: rows over the events 26 .. 30 and the seeding (event index 31, column 62) at every type
+// and order, and a few paired rows over the events 24 .. 30 that pass the tile bits (k = 13, 14)
+static Cohort top_event_cohort(const char* name, int count, uint64_t seed) {
+  Cohort c;
+  c.name = name; c.n = 31;
+  Lcg g(seed);
+  const double dens[4] = {0.3, 0.5, 0.8, 1.0};
+  for (int i = 0; i < count; ++i) {
+    const double d = dens[g.below(4)];
+    const int type = g.below(4);
+    std::string ev(26, '-');
+    for (int j = 26; j < 31; ++j) {
+      const bool p = g.unit() < d, m = g.unit() < d;
+      ev += type <= 1 ? (p ? 'P' : '-') : type == 2 ? (m ? 'M' : '-') : (p && m ? 'J' : p ? 'P' : m ? 'M' : '-');
+    }
+    add_pattern(c, ev, type == 0 ? 0 : 1, type == 3 ? ORDERS[g.below(4)] : -99, type);
+  }
+  for (const char* tail : {"JJJJJJ-", "JJJJJPJ", "JJJJJMJ", "PJJJJJJ", "JJJJJJP", "JJJJJJM", "PPMMJJJ"})
+    for (int o = 0; o < 4; ++o) add_pattern(c, rep('-', 24) + tail, 1, ORDERS[o], 3);
+  add_pattern(c, rep('-', 30) + "P", 0, -99, 0);
+  add_pattern(c, rep('-', 30) + "P", 1, -99, 1);
+  add_pattern(c, rep('-', 30) + "M", 1, -99, 2);
+  add_pattern(c, "", 0, -99, 0);
+  for (int type = 1; type <= 3; ++type) add_pattern(c, "", 1, type == 3 ? 0 : -99, type);
+  return c;
+}
+
 // ------------------------------------------------------------------------------------ configurations
 struct NamedCfg { PlanCfg c; std::string name; };
 static std::string cfg_name(const PlanCfg& c) {
@@ -843,15 +870,18 @@ static void check_plan(const PlanCfg& c, const Cohort& co, const char* tname) {
 }
 
 // ------------------------------------------------------------------------------------ rejections
+static const char* TOO_MANY = "too many active events for one patient";
 static void check_rejections() {
   g_ctx = "rejections";
   PlanCfg c;
   c.ws_limit = (size_t)1 << 30;
-  auto throws = [&](const Cohort& co) {
+  // the planner's message, "" when the cohort is accepted
+  auto refusal = [&](const Cohort& co) -> std::string {
     double n_em;
-    try { plan_cohort<double>(c, co.dat.data(), co.np(), 2 * co.n + 3, co.n, n_em); } catch (const Fail&) { return true; }
-    return false;
+    try { plan_cohort<double>(c, co.dat.data(), co.np(), 2 * co.n + 3, co.n, n_em); } catch (const Fail& f) { return f.msg.empty() ? "?" : f.msg; }
+    return "";
   };
+  auto throws = [&](const Cohort& co) { return !refusal(co).empty(); };
   Cohort a; a.n = 4; add_pattern(a, "JP", 1, 0, 4);
   Cohort a2; a2.n = 4; add_pattern(a2, "JP", 1, 0, -1);
   Cohort b; b.n = 4; add_pattern(b, "JP", 1, 0, 3); b.dat[1] = 2;
@@ -862,9 +892,91 @@ static void check_rejections() {
   CHECK(throws(a) && throws(a2), "rejections", "a type outside 0 .. 3 is accepted");
   CHECK(throws(b) && throws(b2), "rejections", "an event column other than 0 / 1 is accepted");
   CHECK(throws(s), "rejections", "a paired row without seeding is accepted");
-  CHECK(throws(k), "rejections", "a row of more than MAXK active events is accepted");
+  CHECK(refusal(k) == TOO_MANY, "rejections", "a row of more than MAXK active events is accepted");
   CHECK(!throws(ok), "rejections", "a valid row is refused");
   g_cnt["rejections"].plans += 7;
+  // single-tumour spaces of more than MAXK bits: unpaired rows, alone, behind a valid row (the last row of the cohort) and
+  // between two valid rows.  Every cohort is planned before the first verdict, so that a run on a planner that accepts
+  // them still shows what the sanitizers say about the 32-bit row
+  struct Wide { const char* what; int n, type, seed; char ch; int events; };
+  const Wide wide[] = {{"type 0, n = 31, 31 PT events (k = 31)", 31, 0, 0, 'P', 31},
+                       {"type 1, n = 31, 31 PT events and the seeding (k = 32)", 31, 1, 1, 'P', 31},
+                       {"type 2, n = 30, 30 MT events and the seeding (k = 31)", 30, 2, 1, 'M', 30},
+                       {"type 3, n = 31, 31 joint events and the seeding (k = 63)", 31, 3, 1, 'J', 31}};
+  std::vector<std::pair<std::string, std::string>> got;
+  for (const Wide& w : wide)
+    for (int place = 0; place < 3; ++place) {
+      Cohort co; co.n = w.n;
+      if (place >= 1) add_pattern(co, "JP", 1, 0, 3);
+      add_pattern(co, rep(w.ch, w.events), w.seed, w.type == 3 ? 0 : -99, w.type);
+      if (place == 2) add_pattern(co, "P", 1, -99, 1);
+      got.push_back({std::string(w.what) + (place == 0 ? ", alone" : place == 1 ? ", last behind a valid row" : ", between valid rows"), refusal(co)});
+    }
+  for (auto& e : got) std::printf("refusal of %s: \"%s\"\n", e.first.c_str(), e.second.c_str());
+  for (auto& e : got) CHECK(e.second == TOO_MANY, "rejections", "%s: %s", e.first.c_str(), e.second.empty() ? "accepted" : e.second.c_str());
+  // a paired row without seeding keeps its own message whatever its size
+  Cohort s31; s31.n = 31; add_pattern(s31, rep('J', 31), 0, 0, 3);
+  CHECK(refusal(s31) == "dat: paired rows (type 3) must have seeding = 1", "rejections", "a wide paired row without seeding: \"%s\"", refusal(s31).c_str());
+  g_cnt["rejections"].plans += (long long)got.size() + 1;
+}
+
+// ------------------------------------------------------------------------------------ the size limits
+// Spaces of exactly MAXK = 30 bits at n = 31 are planned; their 2^30 states are not enumerated - sizes only
+template <typename T>
+static void check_limit_sizes(const char* tname) {
+  PlanCfg c;
+  c.ws_limit = (size_t)64 << 30;
+  const int n = 31, nc = 2 * n + 3, N = n + 1;
+  struct Case { const char* name; std::string ev; int order, type; };
+  const Case cases[] = {{"type 1, 29 PT events and the seeding", rep('P', 29), -99, 1},
+                        {"paired, 15 PT and 14 MT events and the seeding", rep('P', 15) + rep('M', 14), 0, 3},
+                        {"paired, 10 joint, 5 PT and 4 MT events and the seeding", rep('J', 10) + rep('P', 5) + rep('M', 4), 2, 3}};
+  for (const Case& cs : cases) {
+    g_ctx = std::string("limit sizes (") + tname + "): " + cs.name;
+    Cohort co; co.n = n;
+    add_pattern(co, "JP", 1, 1, 3);                       // a small row (k = 4) in front: the offsets of the large one are not 0
+    add_pattern(co, cs.ev, 1, cs.order, cs.type);
+    double n_em = -1;
+    std::vector<Batch> plan;
+    try { plan = plan_cohort<T>(c, co.dat.data(), co.np(), nc, n, n_em); } catch (const Fail& f) { fail("limits", "refused: %s", f.msg.c_str()); }
+    CHECK(plan.size() == 1 && plan[0].pats.size() == 2 && n_em == 2.0, "limits", "%zu batches", plan.size());
+    const Batch& b = plan[0];
+    const long long big = 1ll << MAXK;
+    long long prev = -1, as = 0, tabs = 0;
+    if (cs.type == 3) {
+      CHECK(b.dJ.size() == 2 && b.dJ[1].k == MAXK && b.vecJ == big + 16 && b.maxkJ == MAXK, "limits", "vecJ %lld", b.vecJ);
+      CHECK(b.mapJ.size() == (size_t)(1 << (MAXK - TB)) + 1, "limits", "%zu joint tiles", b.mapJ.size());
+      CHECK(b.mapJ.back().x == 1 && b.mapJ.back().y == (1 << (MAXK - TB)) - 1, "limits", "last joint tile %d", b.mapJ.back().y);
+      CHECK(b.dS.size() == (cs.order == 0 ? 3u : 2u), "limits", "%zu single-tumour problems", b.dS.size());
+      std::vector<long long> offs;
+      for (const Desc& d : b.dJ) offs.push_back(d.off);
+      std::sort(offs.begin(), offs.end());
+      CHECK(offs[0] == 0 && (offs[1] == 16 || offs[1] == big), "limits", "joint offsets %lld, %lld", offs[0], offs[1]);
+    } else {
+      CHECK(b.dJ.size() == 1 && b.dS.size() == 2 && b.dS[1].k == MAXK && b.dS[1].seedbit == MAXK - 1, "limits", "single-tumour problems");
+      CHECK(b.vecS == big + 4 && b.dS[1].off == 4, "limits", "vecS %lld", b.vecS);
+      CHECK(b.mapS.size() == (size_t)(1 << (MAXK - TB)) + 1 && b.mapS.back().y == (1 << (MAXK - TB)) - 1, "limits", "%zu single-tumour tiles", b.mapS.size());
+      CHECK(b.stg[0].map.size() == (size_t)1 << (MAXK - TB) && b.stg[0].maxk == MAXK && b.stg[0].lmap.size() == b.stg[0].map.size(),
+            "limits", "%zu staged tiles", b.stg[0].map.size());
+      CHECK(b.stg[0].cl[0].items.size() == b.stg[0].map.size() && b.stg[0].cl[1].items.size() == b.stg[0].map.size(), "limits", "cooperative lists");
+      CHECK(b.stg[0].grc.size() == (size_t)1 << (MAXK - GR_CHUNK), "limits", "%zu gradient chunks", b.stg[0].grc.size());
+    }
+    for (const Desc& d : b.dS) {
+      CHECK(d.off > prev && d.off >= 0 && d.toff >= 0 && d.off + (1ll << d.k) <= b.vecS, "limits", "single-tumour offset %lld after %lld", d.off, prev);
+      prev = d.off;
+      tabs += table_size(d);
+    }
+    for (const Desc& d : b.dJ) {
+      CHECK(d.off >= 0 && d.off + (1ll << d.k) <= b.vecJ && d.aoff >= 0 && d.toff >= 0, "limits", "joint offsets %lld / %lld / %lld", d.off, d.aoff, d.toff);
+      as += a_size(d); tabs += table_size(d);
+    }
+    CHECK(b.tabJ + b.tabS == tabs && b.asize >= as && b.asize <= as + 3, "limits", "tables %lld + %lld, class arrays %lld", b.tabJ, b.tabS, b.asize);
+    // the footprint in 64-bit size_t against the sum of its large terms in long double: not wrapped, within the workspace
+    const size_t fp = footprint<T>(c, N, b.vecJ, b.vecS, b.asize, tabs, b.dJ.size(), b.dS.size(), b.pats.size());
+    const long double lower = ((long double)2 * b.vecJ + (long double)4 * b.vecS + (long double)b.asize + (long double)tabs) * sizeof(T);
+    CHECK((long double)fp >= lower && (long double)fp <= lower + (long double)(1 << 20) && fp <= c.ws_limit, "limits", "footprint %zu for %.0Lf bytes of vectors", fp, lower);
+    ++g_shape["plans with a space of MAXK bits"];
+  }
 }
 
 static void print_counts() {
@@ -924,9 +1036,16 @@ int main(int argc, char** argv) {
     sweep<double>(co, cfgs, "double");
     sweep<float>(co, cfgs, "float");
   }
+  // the largest event count: the seeding is event 31, dat has 65 columns
+  const Cohort top = top_event_cohort("top-events-31", 120, 31);
+  sweep<double>(top, cfgs, "double");
+  sweep<float>(top, cfgs, "float");
+  g_shape["rows planned at n = 31"] += top.np();
   check_rejections();
+  check_limit_sizes<double>("double");
+  check_limit_sizes<float>("float");
   print_counts();
-  const char* must[] = {"straddling tiles", "straddling tiles live without seeding", "dead tiles", "batches with dealt chains", "window chains of several rows", "rows merged into the 256-thread launch",
+  const char* must[] = {"rows planned at n = 31", "plans with a space of MAXK bits", "straddling tiles", "straddling tiles live without seeding", "dead tiles", "batches with dealt chains", "window chains of several rows", "rows merged into the 256-thread launch",
                         "batches with a launch of the 1024-thread class", "batches with an empty pcl (nJ > prep_split_max)", "plans with a cut cohort",
                         "patients with a single-tumour space beyond a tile", "problems on the window route", "problems on the per-patient route",
                         "problems on the tile route", "cooperative dependencies required by the model"};

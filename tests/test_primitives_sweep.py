@@ -2,7 +2,8 @@
 
 The 15 entry points of the reference's module surface (jx.kronvec, jx.likelihood, jx.vanilla -> Engine.kronvec ...
 Engine.v_x_partial_D_y -> the api_* paths of csrc/prims.h) are swept over k = 0 .. 18, past the 12 tile bits
-(MMHN_TB), on unseeded joint states and on joint states with one tumour plus seeding, on fp64 and fp32 engines, under
+(MMHN_TB), on unseeded joint states and on joint states with one tumour plus seeding, at the largest event count
+(n = 31: the last slots of a joint state and the last events of a single-tumour one), on fp64 and fp32 engines, under
 both solvers, and with MMHN_POISON=1 on half of the cases: a poisoned engine NaN-fills every result buffer as soon as it
 is allocated, so an element that no launch or memset writes shows in the output.
 
@@ -44,11 +45,20 @@ def _rng(tag):
     return np.random.default_rng(zlib.crc32(tag.encode()))
 
 
+N_TOP = 31               # the largest event count (MAXN = 32 events with the seeding, csrc/desc.h)
+
+
 def joint_state(layout, k, rng):
     """(n, int8 state [2n+1]) with exactly k active slots; two events stay inactive.
 
     seeded: seeding + a mix of pairs and lone PT / MT slots; unseeded: the same without seeding; pt_seed / mt_seed: one
-    tumour + seeding; paired: pairs only (+ seeding when k is odd); lone: lone PT / MT slots + seeding."""
+    tumour + seeding; paired: pairs only (+ seeding when k is odd); lone: lone PT / MT slots + seeding; top: n = 31, the
+    pairs of the events 0 - 2 and 28 - 30 and the seeding (slots 0 - 5 and 56 - 62, k = 13: one bit past the tile)."""
+    if layout == "top":
+        st = np.zeros(2 * N_TOP + 1, dtype=np.int8)
+        st[[0, 1, 2, 3, 4, 5, 56, 57, 58, 59, 60, 61, 62]] = 1
+        assert k == 13
+        return N_TOP, st
     seed = layout in ("seeded", "pt_seed", "mt_seed", "lone") or (layout == "paired" and k % 2 == 1)
     if k == 0:
         seed = False
@@ -74,7 +84,13 @@ def joint_state(layout, k, rng):
 
 
 def single_state(layout, k, rng):
-    """(n, int8 state [n+1]) with k active events; two events stay inactive.  seeded: the seeding event is one of them."""
+    """(n, int8 state [n+1]) with k active events; two events stay inactive.  seeded: the seeding event is one of them;
+    top: n = 31, the events 0 - 9, 29, 30 and the seeding (event 31), k = 13."""
+    if layout == "top":
+        st = np.zeros(N_TOP + 1, dtype=np.int8)
+        st[list(range(10)) + [29, 30, 31]] = 1
+        assert k == 13
+        return N_TOP, st
     seed = layout == "seeded" and k > 0
     n = max(k, 1) + 1
     st = np.zeros(n + 1, dtype=np.int8)
@@ -106,6 +122,7 @@ def _joint_cases():
                 continue
             seen.add(key)
             out.append((f"joint-k{k}-{lay}", k, lay))
+    out.append(("joint-k13-top", 13, "top"))                     # (last: the poisoned half of the cases above stays as it was)
     return out
 
 
@@ -114,6 +131,7 @@ def _single_cases():
     for k in (0, 1, 5, 11, 12, 13, 14, 16):
         for lay in (("unseeded",) if k == 0 else ("seeded", "unseeded")):
             out.append((f"single-k{k}-{lay}", k, lay))
+    out.append(("single-k13-top", 13, "top"))
     return out
 
 
@@ -690,7 +708,13 @@ def test_sweep_covers_the_tile_boundary():
     ks = {k for _, k, _ in joint}
     assert {0, 1, 2, 11, 12, 13, 14, 16, 18} <= ks
     for k in (13, 14, 16):
-        assert {lay for _, kk, lay in joint if kk == k} == set(JOINT_LAYOUTS_LARGE)
+        assert {lay for _, kk, lay in joint if kk == k and lay != "top"} == set(JOINT_LAYOUTS_LARGE)
+    # n = 31: the last slots and the seeding slot 62 of a joint state, the events 29 - 31 of a single-tumour state, fp64 and fp32
+    for cases, state, last in ((joint, joint_state, [56, 57, 58, 59, 60, 61, 62]), (_single_cases(), single_state, [29, 30, 31])):
+        top = [c for c in cases if c[2] == "top"]
+        assert len(top) == 1 and top[0][1] == 13 > TB and 13 in FP32_K
+        n, st = state("top", 13, None)
+        assert n == 31 and int(st.sum()) == 13 and st[last].all() and len(st) == last[-1] + 1
     n, st = joint_state("lone", 14, _rng("joint-14-lone"))
     slots = D._slots(st)
     assert slots[-1][1] == 2 and len(slots) - 1 >= TB and slots[TB][1] != 2
