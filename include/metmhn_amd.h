@@ -14,6 +14,16 @@
  *
  * Layout conventions (regularized_optimization.py:63-66, metmhn/jx/kronvec.py:223-250):
  *   dat    int8 [n_pat][2n+3]  = PT_0,MT_0,...,PT_{n-1},MT_{n-1},seed, order, type
+ *          type 0 "absent", 1 "present", 2 "isMetastasis", 3 "isPaired" as in the reference, and
+ *          type 4: a primary tumour was sequenced and its metastatic status is unknown.  PT columns 0 / 1; every MT column and
+ *          the seeding column must be 0 (mmhn_set_cohort refuses the cohort otherwise, naming the row); the order column is
+ *          ignored.  With lp0 the log-probability of the same genotype as a type-0 row and lp1 as a type-1 row with seeding = 1,
+ *          the row's lp = logaddexp(lp0, lp1), P(seeded | genotype) = exp(lp1 - lp), and its gradient is the mixture of the two
+ *          rows' gradients under those posterior weights (d_dm = 0).  In the objective a type-4 row has weight 1: n_em (the sum
+ *          of the seeding column) is not changed by it, n_nm = n_pat - n_em - n_unknown, w as before from n_em and n_nm,
+ *          n_full = w n_em + n_nm + n_unknown, and its lp and gradient ride in the "NM" sums below.
+ *          The mmhn_order_* / mmhn_likeliest_orders entry points take types 0..3 only: a type-4 row gets MMHN_ORD_BAD_STATUS
+ *          there, filter such rows out first.
  *   state  int8 [2n+1]  joint observation;  [n+1] for the single-tumour functions
  *   vectors have 2^k entries, k = #ones in state; index bit b <-> b-th active slot.
  *   log_theta fp64 [n+1][n+1], log_d_p / log_d_m fp64 [n+1].
@@ -24,7 +34,8 @@
  *   n_mut <= 30 for mmhn_simulate, mmhn_simulate_summary and mmhn_simulate_pairs; on an engine with n_mut = 31 they fail with
  *     "too many events for the sampler (n_mut <= 30: event and diagnosis flags share one 32-bit set)".
  *   At most 30 active slots (index bits) in any one restricted space.  For a row of dat that is its joint space (type 3: PT
- *     slots + MT slots + seeding) or its single-tumour space (types 0 / 1: PT slots + seeding, type 2: MT slots + seeding):
+ *     slots + MT slots + seeding) or its single-tumour space (types 0 / 1: PT slots + seeding, type 2: MT slots + seeding,
+ *     type 4: PT slots + 1 - the message then ends with " (row R)"):
  *     mmhn_set_cohort fails with "too many active events for one patient" and leaves the engine without a cohort.  For a
  *     state of the single-vector functions: "too many active events".  The order entry points give such a row the status
  *     MMHN_ORD_TOO_LARGE.
@@ -62,8 +73,9 @@ int mmhn_set_workspace_limit(mmhn_handle h, size_t bytes);
  * mmhn_cohort_sums returns the UNWEIGHTED partial sums of this handle's patients so that
  * patient shards on several GPUs can be combined with one all-reduce:
  *   sums[0]            = sum of log-probs of the rows with type != 0 ("EM")
- *   sums[1]            = sum of log-probs of the rows with type == 0 ("NM")
- *   sums[2]            = number of rows with seeding == 1,  sums[3] = number of rows
+ *   sums[1]            = sum of log-probs of the rows with type == 0 ("NM") and of those with type == 4 (weight 1 as well)
+ *   sums[2]            = number of rows with seeding == 1,  sums[3] = number of rows (type 4 included: mmhn_get_unknown_rows
+ *                        says how many of them are)
  *   then d_theta_EM [N*N], d_theta_NM [N*N], d_dp_EM [N], d_dp_NM [N], d_dm_EM [N]
  * (N = n_mut + 1; 4 + 2*N*N + 3*N doubles; gradient blocks are zero if with_grad == 0).
  */
@@ -84,7 +96,7 @@ int mmhn_cohort_sums_begin(mmhn_handle h, const double* log_theta, const double*
 int mmhn_cohort_sums_end(mmhn_handle h, double* sums);
 /* The same evaluation with the EM / NM weighting of regularized_optimization.py:256-266 applied on the device:
  * wsums[1 + N*N + 2 N] = [w s_EM + s_NM, w G_EM + G_NM, w p_EM + p_NM, w m_EM]; the caller divides by
- * n_full = w n_em + n_nm.  w needs the GLOBAL counts only (known to every rank once the cohort is set), so with a
+ * n_full = w n_em + n_nm (+ n_unknown, the rows of type 4, which ride in the NM terms).  w needs the GLOBAL counts only (known to every rank once the cohort is set), so with a
  * communicator attached the all-reduce carries 1 + N^2 + 2 N doubles (484 at n = 20). */
 int mmhn_cohort_wsums_begin(mmhn_handle h, const double* log_theta, const double* log_d_p,
                             const double* log_d_m, int with_grad, double w);
@@ -103,6 +115,15 @@ int mmhn_get_reduce_flag(mmhn_handle h, double* summed);
  * d_theta[n_pat][N*N], d_dp[n_pat][N], d_dm[n_pat][N]  (ssr._g_coupled_*, _grad_*_obs) */
 int mmhn_patient_grads(mmhn_handle h, const double* log_theta, const double* log_d_p,
                        const double* log_d_m, double* lp, double* d_theta, double* d_dp, double* d_dm);
+
+/* score-only evaluation of the current cohort: lp[n_pat] of every row, p_seeded[n_pat] = P(the metastasis had been seeded |
+ * PT genotype) for the rows of type 4 and NaN for every other row */
+int mmhn_patient_status(mmhn_handle h, const double* log_theta, const double* log_d_p, const double* log_d_m,
+                        double* lp, double* p_seeded);
+/* rows of type 4 in the cohort the handle was given (this handle's shard: mmhn_score / mmhn_score_and_grad use it for
+ * n_full, so with a communicator attached and type-4 rows present weight the all-reduced sums yourself from the global
+ * counts - mmhn_cohort_wsums_begin) */
+int mmhn_get_unknown_rows(mmhn_handle h, int64_t* n_unknown);
 
 /* ---- joint PT/MT primitives (metmhn/jx/kronvec.py, likelihood.py) ------------------
  * mmhn_kronvec        <-> kronvec.kronvec        (:499-539)   y = Q p, flags diag / transpose

@@ -19,8 +19,11 @@ from .regularized_optimization import learn_mhn, score
 
 
 def indep(dat) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """Initial estimate of theta, d_p, d_m from marginal event counts (Utilityfunctions.py:157-183)."""
+    """Initial estimate of theta, d_p, d_m from marginal event counts (Utilityfunctions.py:157-183).  Rows of type 4
+    (primary tumour, status unknown) count as single PT observations in the event frequencies; the seeding's rate is
+    taken from the rows of known status alone."""
     dat = np.asarray(dat)
+    n_unknown = int(np.sum(dat[:, -1] == 4))
     n_coupled = int(np.sum(dat[:, -1] == 3))
     n = (dat.shape[1] - 3) // 2
     n_single = dat.shape[0] - n_coupled
@@ -32,7 +35,7 @@ def indep(dat) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         else:
             theta[i, i] = np.log(mut_count / (2 * n_coupled + n_single - mut_count + 1e-10))
     seed_count = np.sum(dat[:, -3].astype(np.int64))
-    theta[n, n] = np.log(seed_count / (n_coupled + n_single - seed_count + 1e-10))
+    theta[n, n] = np.log(seed_count / (n_coupled + n_single - n_unknown - seed_count + 1e-10))
     return theta, np.zeros(n + 1), np.zeros(n + 1)
 
 
@@ -109,10 +112,13 @@ def categorize(x) -> int:
     return pd.NA
 
 
-def load_cohort(events_csv: str, annot_csv: str, muts: list[str] | None = None):
+def load_cohort(events_csv: str, annot_csv: str, muts: list[str] | None = None, keep_unknown: bool = False):
     """Events CSV + annotation CSV -> (dat int8 [n_pat, 2n+3], event names); examples/analysis.py:49-83.
 
     `muts`: the P./M. event columns to keep (pairs, PT column first); default: every event column.
+    `keep_unknown`: the unpaired primary tumours whose metaStatus is "unknown" - dropped by the reference and by default
+    here - are kept as rows of type 4 (seeding 0, MT columns 0), which the objective scores as the sum over both
+    statuses.  The order entry points (MetMHN.order_*, likeliest_order) do not take them: filter them out there.
     """
     import pandas as pd
     annot = pd.read_csv(annot_csv)
@@ -122,7 +128,11 @@ def load_cohort(events_csv: str, annot_csv: str, muts: list[str] | None = None):
     if muts is None:
         muts = list(d.columns[1:-4])
     d["type"] = d.apply(categorize, axis=1)
-    d["Seeding"] = d["type"].apply(lambda x: pd.NA if pd.isna(x) else 0 if x == 0 else 1)
+    if keep_unknown:
+        unknown = (d["paired"] == 0) & (d["metaStatus"] == "unknown")
+        d["type"] = d["type"].astype(object).where(~unknown, 4)
+        d.loc[unknown, [c for c in muts if c.startswith("M.")]] = 0
+    d["Seeding"] = d["type"].apply(lambda x: pd.NA if pd.isna(x) else 0 if x in (0, 4) else 1)
     d["M.AgeAtSeqRep"] = pd.to_numeric(d["M.AgeAtSeqRep"], errors="coerce")
     d["P.AgeAtSeqRep"] = pd.to_numeric(d["P.AgeAtSeqRep"], errors="coerce")
     d["diag_order"] = d["M.AgeAtSeqRep"] - d["P.AgeAtSeqRep"]
@@ -139,9 +149,11 @@ def marg_frequs(dat, events: list):
     coupled rows (type 3) split into PT-private / MT-private / shared, NM (type 0) and EM-PT (type 1) PT bits,
     EM-MT (type 2) MT bits; the seeding column from the seeding flag.  DataFrame [n+1 events x 6], rounded to two
     decimals, columns labelled with the stratum sizes.  The reference reads the sizes by position from np.unique
-    and is right only when all four types occur; a cohort without one of them raises ValueError here."""
+    and is right only when all four types occur; a cohort without one of them raises ValueError here.  Rows of type 4
+    (status unknown) belong to none of these strata and are ignored, here and in `pair_counts`."""
     import pandas as pd
     dat = np.asarray(dat)
+    dat = dat[dat[:, -1] != 4]
     n_mut = (dat.shape[1] - 3) // 2
     types = dat[:, -1]
     if set(np.unique(types).tolist()) != {0, 1, 2, 3}:
@@ -165,7 +177,7 @@ def marg_frequs(dat, events: list):
 def pair_counts(dat) -> tuple[np.ndarray, np.ndarray]:
     """Observed co-occurrence counts of a cohort `dat` [n_pat, 2n+3] per row type 0 - 3 (NM, EM-PT, EM-MT, paired):
     (n_type int64 [4], pairs int64 [4, 2n, 2n]) with pairs[t] = G.T @ G over the genotype columns [PT_0, MT_0, ...] of
-    the rows of type t - the observed side of `simulations.PairSummary.compare`."""
+    the rows of type t - the observed side of `simulations.PairSummary.compare`.  Rows of type 4 are ignored."""
     dat = np.asarray(dat)
     B = dat.shape[1] - 3
     n_type = np.zeros(4, dtype=np.int64)

@@ -50,6 +50,8 @@ SIGNATURES = {
     "mmhn_set_reduce_flag": [C.c_void_p, C.c_double],
     "mmhn_get_reduce_flag": [C.c_void_p, f64p],
     "mmhn_patient_grads": [C.c_void_p, f64p, f64p, f64p, f64p, f64p, f64p, f64p],
+    "mmhn_patient_status": [C.c_void_p, f64p, f64p, f64p, f64p, f64p],
+    "mmhn_get_unknown_rows": [C.c_void_p, i64p],
     "mmhn_kronvec": [C.c_void_p, f64p, i8p, f64p, f64p, C.c_int, C.c_int],
     "mmhn_kronvec_batched": [C.c_void_p, f64p, i8p, C.c_int64, f64p, f64p, C.c_int, C.c_int],
     "mmhn_jacobi_step_batched": [C.c_void_p, f64p, f64p, f64p, i8p, C.c_int64, f64p, f64p, f64p, C.c_int],

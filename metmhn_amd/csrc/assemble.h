@@ -36,6 +36,12 @@ __device__ __forceinline__ double assemble_elem(const AsmArgs<T>& a, const PatRe
   if (e < 1 + N * N) {                             // theta gradient
     const int q = e - 1, i = q / N, j = q % N;
     double g = 0;
+    if (pr.kind == 5 && pr.s[0] < 0 && i == j) {   // empty genotype of unknown status: r0 * (the row of kind 4); the solved
+      const Params<T>& P0 = a.par[PS_THETA];       // part's row below carries r1 already (its adjoint seed is 1 / (p0 + p1))
+      double s = 0;
+      for (int t = 0; t < N; ++t) s += (double)P0.th[t][t];
+      g = -exp(-log1p(s) - a.lp[pat]) * (double)P0.th[i][i] / (1.0 + s);
+    }
     for (int part = 0; part < 2; ++part)
       if (pr.s[part] >= 0) {
         const bool prim_space = a.dS[pr.s[part]].pset == PS_PRIM;
@@ -103,7 +109,7 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_rows(const PatRec* __restrict_
   for (int i = i0; i < i1; ++i) {
     const int kd = pats[i].kind;
     const double v = out[(long long)i * stride + e];
-    if (kd == 0 || kd == 4) acc1 += v; else acc0 += v;
+    if (kd == 0 || kd >= 4) acc1 += v; else acc0 += v;    // (4, 5: the closed-form row and the rows of unknown status)
   }
   part[((long long)blockIdx.y * 2 + 0) * stride + e] = acc0;
   part[((long long)blockIdx.y * 2 + 1) * stride + e] = acc1;

@@ -70,7 +70,8 @@ struct JLink {
 
 // one patient of a batch: which problems belong to it and how their results combine
 struct PatRec {
-  int kind;            // dat type 0..3; 4 = all-zero type-0 row (closed form)
+  int kind;            // dat type 0..3; 4 = all-zero type-0 row (closed form); 5 = dat type 4 (PT of unknown status): s[0] the
+                       // genotype without the seeding (absent when it is empty: closed form), s[1] with it - both its own
   int order;           // 0 / 1 / 2 (anything else -> 2, regularized_optimization.py:114,245)
   int j;               // joint problem index in the batch or -1
   int s[2];            // single problems: [0] = PT-first part (MT marginal) or the patient itself, [1] = MT-first part

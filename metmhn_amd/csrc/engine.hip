@@ -151,6 +151,9 @@ struct Engine : EngineBase {
   struct View { T* p = nullptr; } GJ, DJ, Abuf;
   int pi_owner = -1, qJ_owner = -1;   // batch whose (pruned) layout the zero-initialised buffers hold
   DevArr<double> lp, out, sums, abi_sums, redbuf;
+  DevArr<double> resp;                // [n_pat] by cohort row: P(seeded | genotype) of the rows of unknown status (dat type 4), written
+                                      // where their score is formed; NaN everywhere else (filled once, when the cohort is set)
+  long long n_unknown = 0;            // rows of dat type 4
   DevArr<JLink<T>> links;
   double* h_abi = nullptr;            // pinned landing buffer of the result download
   double* h_abi_dev = nullptr;        // device view of it
@@ -609,15 +612,16 @@ struct Engine : EngineBase {
     n_cols = nc;
     batches.clear();
     dev.clear();
-    n_em = 0;
+    n_em = 0; n_unknown = 0;
     // a cohort that is refused, or whose plan cannot be brought to the device, leaves the engine without one (no patient
     // count next to an empty or half-uploaded plan)
     try {
       batches = plan_cohort<T>(cfg.plan, dat.data(), np, nc, n, n_em);
+      for (long long r = 0; r < np; ++r) n_unknown += dat[(size_t)r * nc + nc - 1] == 4;
       place_cohort();
     } catch (...) {
       dat.clear(); batches.clear(); dev.clear();
-      n_pat = 0; n_em = 0;
+      n_pat = 0; n_em = 0; n_unknown = 0;
       throw;
     }
   }
@@ -645,6 +649,11 @@ struct Engine : EngineBase {
     seedS.alloc(mnS);
     GS.alloc(mnS * N * N); zarena.alloc(mZ);
     dots.alloc(2 * mp); bmJ.alloc(mnJ * 64); bmS.alloc(mnS * 64);
+    resp.alloc((size_t)std::max<long long>(n_pat, 1));
+    {
+      const std::vector<double> nans(resp.n, std::nan(""));
+      HIPCHECK(hipMemcpy(resp.p, nans.data(), resp.n * sizeof(double), hipMemcpyHostToDevice));
+    }
     lp.alloc(mp); out.alloc(mp * stride()); redbuf.alloc(((mp + red_per((int)mp) - 1) / red_per((int)mp)) * 2 * (size_t)stride());
   }
 
@@ -673,7 +682,7 @@ struct Engine : EngineBase {
       HIPCHECK(hipStreamWaitEvent(sd, ev_fork[which], 0));
     }
     fork_recorded[which] = false;
-#define SP_TAIL db.pats.p, db.dS.p, d_par.p, d_perm.p, d_lvl.p, db.dJ.p, db.wd.p, pi.p, links.p, pS.p, qS.p, GS.p, bmS.p, dots.p, lp.p
+#define SP_TAIL db.pats.p, db.dS.p, d_par.p, d_perm.p, d_lvl.p, db.dJ.p, db.wd.p, pi.p, links.p, pS.p, qS.p, GS.p, bmS.p, dots.p, lp.p, resp.p
     auto big_class = [&]() {
       if (!n2) return;
       const size_t lds = (spatient_lds<T>(N, mk2) + 15) / 16 * 16;
@@ -762,7 +771,7 @@ struct Engine : EngineBase {
         launch_diag(db.dS.p, dg.map.p, tG, nullptr, lidgS.p, nullptr, KD_LIDG);
         solve(false, LG, pS.p, lidgS.p, rhsS.p, 0, nullptr);
         hipLaunchKernelGGL((k_seeds<T>), dim3((nG + 255) / 256), dim3(256), 0, stream, db.pats.p, nG, db.dS.p,
-                           d_par.p, pS.p, seedS.p, lp.p, dg.pats.p);
+                           d_par.p, pS.p, seedS.p, lp.p, resp.p, N, dg.pats.p);
         HIPCHECK(hipGetLastError());
       };
       auto staged_adj = [&](int w) {
@@ -925,6 +934,14 @@ struct Engine : EngineBase {
       std::memcpy(host_sums, hs.data(), hs.size() * sizeof(double));
       finish_eval(t0);
     }
+  }
+  // score-only evaluation: lp of every row, P(seeded | genotype) of the rows of unknown status (NaN for the others)
+  void patient_status(const double* lt, const double* ldp, const double* ldm, double* lp_out, double* p_seeded) {
+    const int st = stride();
+    std::vector<double> rows((size_t)n_pat * st), s(2 * st);
+    evaluate(lt, ldp, ldm, false, s.data(), rows.data());
+    for (long long i = 0; i < n_pat; ++i) lp_out[i] = rows[(size_t)i * st];
+    if (n_pat > 0) HIPCHECK(hipMemcpy(p_seeded, resp.p, (size_t)n_pat * sizeof(double), hipMemcpyDeviceToHost));
   }
   void reset_counters() {                              // (what RCCL said about the communicator stays)
     const int r = cnt.comm_ranks, k = cnt.comm_rank;
@@ -1126,10 +1143,14 @@ int mmhn_set_cohort(mmhn_handle h, const int8_t* dat, int64_t n_pat, int n_cols)
   API_END
 }
 
-static void weights(double n_em, double n_pat, double perc_met, double* w, double* n_full) {
-  const double n_nm = n_pat - n_em;                       // regularized_optimization.py:121-128
+// n_unknown: rows of dat type 4 - weight 1, outside the EM / NM balance (they ride in the NM sums)
+static void weights(double n_em, double n_pat, double n_unknown, double perc_met, double* w, double* n_full) {
+  const double n_nm = n_pat - n_em - n_unknown;           // regularized_optimization.py:121-128
   *w = (n_em * n_nm != 0) ? perc_met * n_nm / ((1 - perc_met) * n_em) : 1.0;
-  *n_full = *w * n_em + n_nm;
+  *n_full = *w * n_em + n_nm + n_unknown;
+}
+static long long unknown_rows(mmhn_handle h) {
+  return h->dtype == MMHN_F64 ? static_cast<Engine<double>*>(h->impl)->n_unknown : static_cast<Engine<float>*>(h->impl)->n_unknown;
 }
 
 int mmhn_cohort_sums(mmhn_handle h, const double* lt, const double* ldp, const double* ldm, int with_grad,
@@ -1200,7 +1221,7 @@ int mmhn_score_and_grad(mmhn_handle h, const double* lt, const double* ldp, cons
   std::vector<double> s(4 + 2 * N * N + 3 * N);
   DISPATCH(h, cohort_sums(lt, ldp, ldm, grad, s.data()));
   double w, nf;
-  weights(s[2], s[3], perc_met, &w, &nf);
+  weights(s[2], s[3], (double)unknown_rows(h), perc_met, &w, &nf);
   *score = (w * s[0] + s[1]) / nf;
   if (grad) {
     const double* gem = s.data() + 4;
@@ -1240,6 +1261,22 @@ int mmhn_patient_grads(mmhn_handle h, const double* lt, const double* ldp, const
       if (d_dm) std::memcpy(d_dm + (size_t)i * N, r + 1 + N * N + N, N * sizeof(double));
     }
   }
+  API_END
+}
+
+int mmhn_patient_status(mmhn_handle h, const double* lt, const double* ldp, const double* ldm, double* lp, double* p_seeded) {
+  API_BEGIN
+  GUARD(h);
+  REQUIRE(lt && ldp && ldm && lp && p_seeded, "null pointer");
+  DISPATCH(h, patient_status(lt, ldp, ldm, lp, p_seeded));
+  API_END
+}
+
+int mmhn_get_unknown_rows(mmhn_handle h, int64_t* n_unknown) {
+  API_BEGIN
+  GUARD(h);
+  REQUIRE(n_unknown, "null pointer");
+  *n_unknown = unknown_rows(h);
   API_END
 }
 

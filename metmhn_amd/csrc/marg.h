@@ -109,7 +109,7 @@ __global__ __launch_bounds__(BLOCK) void k_staged_init(const PatRec* __restrict_
       for (int e = threadIdx.x; e < N * N; e += BLOCK) GS[(long long)sp * N * N + e] = T(0);
       if (threadIdx.x < 64) bmS[(long long)sp * 64 + threadIdx.x] = T(0);
     }
-    if (pr.kind <= 2 && part == 0) {
+    if ((pr.kind <= 2 && part == 0) || pr.kind == 5) {     // (kind 5: both parts are the patient's own)
       const long long off = dS[sp].off, V = 1ll << dS[sp].k;
       for (long long e = threadIdx.x; e < V; e += BLOCK) rhsS[off + e] = e == 0 ? e0_scale<T>() : T(0);
     }
@@ -120,18 +120,26 @@ __global__ __launch_bounds__(BLOCK) void k_staged_init(const PatRec* __restrict_
 template <typename T>
 __global__ void k_seeds(const PatRec* __restrict__ pats, int npat, const Desc* __restrict__ dS,
                         const Params<T>* __restrict__ par, const T* __restrict__ pS, T* seedS,
-                        double* lp, const int* __restrict__ plist) {
+                        double* lp, double* resp, int N, const int* __restrict__ plist) {
   const int ii = blockIdx.x * blockDim.x + threadIdx.x;
   if (ii >= npat) return;
   const int i = plist ? plist[ii] : ii;                    // (plist: the patients on the staged kernels)
   const PatRec pr = pats[i];
   if (pr.kind == 4) return;
-  T full = 0;
+  T full = 0, last = 0;
   for (int part = 0; part < 2; ++part)
     if (pr.s[part] >= 0) {
       const Desc& ds = dS[pr.s[part]];
-      full += pS[ds.off + (1ll << ds.k) - 1];
+      last = pS[ds.off + (1ll << ds.k) - 1];
+      full += last;
     }
+  if (pr.kind == 5 && pr.s[0] < 0) {                       // empty genotype of unknown status: closed-form share (small.h)
+    const Params<T>& PT = par[PS_THETA];
+    T s = 0;
+    for (int t = 0; t < N; ++t) s += PT.th[t][t];
+    full += e0_scale<T>() / (T(1) + s);
+  }
+  if (pr.kind == 5) resp[pr.row] = (double)last / (double)full;
   for (int part = 0; part < 2; ++part)
     if (pr.s[part] >= 0) seedS[pr.s[part]] = T(1) / full;
   double l = log((double)full) - log((double)e0_scale<T>());

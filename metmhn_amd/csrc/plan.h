@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "host.h"
@@ -258,6 +259,8 @@ static CutTargets batch_targets(const PlanCfg& c, const int8_t* dat, long long n
       ++npJ;
       el = (c.use_jacobi || c.wsolve_mode == 2 ? 4.0 : 2.0) * std::ldexp(1.0, kp + km + 1) + 4.0 * (std::ldexp(1.0, km + 1) + std::ldexp(1.0, kp + 1)) +
            (kp + 1) * std::ldexp(1.0, kp) + (km + 1) * std::ldexp(1.0, km) + (ke + 2) * std::ldexp(1.0, ke);
+    } else if (type == 4) {
+      el = 4.0 * (std::ldexp(1.0, kp) + std::ldexp(1.0, kp + 1));      // both parts of an unknown-status row
     } else {
       el = 4.0 * std::ldexp(1.0, (type == 2 ? km : kp) + 1);
     }
@@ -290,8 +293,14 @@ struct RowProblems {
 static RowProblems decode_row(const int8_t* row, long long r, int n, int nc) {
   const int type = row[nc - 1];
   const int order = row[nc - 2];
-  REQUIRE(type >= 0 && type <= 3, "dat: type column must be 0..3");
+  const std::string at = " (row " + std::to_string(r) + ")";
+  REQUIRE(type >= 0 && type <= 4, "dat: type column must be 0..4" + at);
   for (int c = 0; c < 2 * n + 1; ++c) REQUIRE(row[c] == 0 || row[c] == 1, "dat: event columns must be 0/1");
+  if (type == 4) {
+    // a primary tumour of unknown metastatic status: nothing but PT events may be set
+    for (int j = 0; j < n; ++j) REQUIRE(row[2 * j + 1] == 0, "dat: rows of unknown status (type 4) must have no MT event" + at);
+    REQUIRE(row[2 * n] == 0, "dat: rows of unknown status (type 4) must have seeding = 0" + at);
+  }
   RowProblems p;
   PatRec& pr = p.pr;
   pr.kind = type; pr.order = (order == 0 || order == 1) ? order : 2; pr.j = -1; pr.s[0] = pr.s[1] = -1;
@@ -300,11 +309,21 @@ static RowProblems decode_row(const int8_t* row, long long r, int n, int nc) {
   // single-tumour - holds at most MAXK index bits (the marginal problems of a paired row are smaller than its joint one)
   int npt = 0, nmt = 0;
   for (int j = 0; j < n; ++j) { npt += row[2 * j]; nmt += row[2 * j + 1]; }
-  const int kmax = type == 3 ? npt + nmt + 1 : type == 2 ? nmt + 1 : npt + row[2 * n];
+  const int kmax = type == 4 ? npt + 1 : type == 3 ? npt + nmt + 1 : type == 2 ? nmt + 1 : npt + row[2 * n];
   const bool unseeded_pair = type == 3 && row[2 * n] != 1;   // refused below with its own message
-  REQUIRE(unseeded_pair || kmax <= MAXK, "too many active events for one patient");
+  REQUIRE(unseeded_pair || kmax <= MAXK, type == 4 ? "too many active events for one patient" + at : std::string("too many active events for one patient"));
   std::vector<int8_t> st(2 * n + 2);
-  if (type == 0 || type == 1) {
+  if (type == 4) {
+    // the PT genotype without the seeding (what a type-0 row scores) and with it (a type-1 row with seeding = 1): two problems of
+    // the patient's own, their final entries are added.  An empty genotype has no part 0: its share is the closed form of kind 4
+    pr.kind = 5;
+    for (int j = 0; j < n; ++j) st[j] = row[2 * j];
+    st[n] = 0;
+    if (npt > 0) { p.ds[0] = make_single(st.data(), n, PS_PRIM, OBS_ONE); p.has[0] = true; }
+    st[n] = 1;
+    p.ds[1] = make_single(st.data(), n, PS_PRIM, OBS_ONE);
+    p.has[1] = true;
+  } else if (type == 0 || type == 1) {
     for (int j = 0; j <= n; ++j) st[j] = row[2 * j];          // PT slots + seeding (regularized_optimization.py:189)
     int np_ = 0;
     for (int j = 0; j <= n; ++j) np_ += st[j];

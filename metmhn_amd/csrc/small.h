@@ -47,7 +47,7 @@ __device__ __forceinline__ void spatient_body(const int* __restrict__ plist, int
                                               const Desc* __restrict__ dJ, const WDesc* __restrict__ wds, const T* __restrict__ pi, JLink<T>* __restrict__ links,
                                               T* __restrict__ pS, T* __restrict__ qS,
                                               T* __restrict__ GS, T* __restrict__ bmS, T* __restrict__ dots,
-                                              double* __restrict__ lp, int maxk, int N, int with_grad, int block) {
+                                              double* __restrict__ lp, double* __restrict__ resp, int maxk, int N, int with_grad, int block) {
   constexpr int SPW = SPB / 64;
   static_assert(PAIR ? (PPB == 2 || (SPB == 64 && PPB % 2 == 0)) : (PPB == 1 || SPB == 64),
                 "several patients per workgroup: one wave each; a pair of problems: two slots");
@@ -245,14 +245,14 @@ __device__ __forceinline__ void spatient_body(const int* __restrict__ plist, int
   // ---- forward solves of the patient's problems
   STAMP_DECL;
   STAMP_START;
-  T full_score = 0;
+  T full_score = 0, last_score = 0;
   for (int part = 0; part < 2; ++part) {
     const int sp = part == 0 ? ps0 : ps1;
     if (sp < 0 || (PAIR && part != mypart)) continue;
     setup(dS[sp]);
     STAMP(0);
     const Desc& d = dsh;
-    const bool own = pr.kind <= 2;                         // the patient's own space: right-hand side e_0
+    const bool own = pr.kind <= 2 || pr.kind == 5;         // the patient's own space(s): right-hand side e_0
     Marg mg{};
     if (!own) {
       mg = marg_of(part, d.k);
@@ -262,13 +262,20 @@ __device__ __forceinline__ void spatient_body(const int* __restrict__ plist, int
     const bool stash = !PAIR && part == 1 && ps0 >= 0;     // second part of a two-part patient: solved in Q, parked in pS
     T* yv = stash ? Qv : P0;
     solve(d, yv, false, [&](uint32_t x) { return own ? (x == 0 ? e0_scale<T>() : T(0)) : marg_rhs(mg, x); });
-    full_score += yv[(1u << d.k) - 1u];
+    last_score = yv[(1u << d.k) - 1u];
+    full_score += last_score;
     if (stash) for (uint32_t x = tid; x < (1u << d.k); x += SPB) pS[d.off + x] = yv[x];
     STAMP(1);
   }
   if (pr.kind == 3 && !PAIR && tid == 0) {                 // a part the row does not have: nothing feeds the joint adjoint
     if (ps0 < 0) { links[pr.j].soff[0] = -1; links[pr.j].sk[0] = 0; links[pr.j].cst[0] = 0; }
     if (ps1 < 0) { links[pr.j].soff[1] = -1; links[pr.j].sk[1] = 0; links[pr.j].cst[1] = 0; }
+  }
+  if (pr.kind == 5 && ps0 < 0) {                           // empty genotype of unknown status: the share without the seeding
+    const Params<T>& PT = par[PS_THETA];                   // is the closed form of kind 4 (assemble.h), 1 / (1 + sum_i theta_ii)
+    T s = 0;
+    for (int i = 0; i < N; ++i) s += PT.th[i][i];
+    full_score += e0_scale<T>() / (T(1) + s);
   }
   if (PAIR) {                                              // score of part 0 + score of part 1, in that order
     if (tid == 0) xch[pslot] = full_score;
@@ -286,6 +293,7 @@ __device__ __forceinline__ void spatient_body(const int* __restrict__ plist, int
       l += log(dr);
     }
     lp[pat] = l;
+    if (pr.kind == 5) resp[pr.row] = (double)last_score / (double)full_score;   // P(seeded | genotype): part 1 is the last one solved
   }
   STAMP(2);
   if (!with_grad) { STAMP_FLUSH(0); return; }
@@ -461,8 +469,8 @@ __device__ __forceinline__ void spatient_body(const int* __restrict__ plist, int
     const uint16_t* __restrict__ perm, const int* __restrict__ lvl, const Desc* __restrict__ dJ, const WDesc* __restrict__ wds, \
     const T* __restrict__ pi, \
     JLink<T>* __restrict__ links, T* __restrict__ pS, \
-    T* __restrict__ qS, T* __restrict__ GS, T* __restrict__ bmS, T* __restrict__ dots, double* __restrict__ lp
-#define SPATIENT_ARGS pats, dS, par, perm, lvl, dJ, wds, pi, links, pS, qS, GS, bmS, dots, lp
+    T* __restrict__ qS, T* __restrict__ GS, T* __restrict__ bmS, T* __restrict__ dots, double* __restrict__ lp, double* __restrict__ resp
+#define SPATIENT_ARGS pats, dS, par, perm, lvl, dJ, wds, pi, links, pS, qS, GS, bmS, dots, lp, resp
 
 // one size class per launch (the 1024-thread class)
 template <typename T, int SPB, int PPB, bool PAIR = false>

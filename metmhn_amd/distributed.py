@@ -21,7 +21,9 @@ def patient_cost(dat: np.ndarray) -> np.ndarray:
     k_pt = bits[:, 0::2].sum(axis=1)
     k_mt = bits[:, 1:-1:2].sum(axis=1) + 1
     k = np.where(typ == 3, k_joint, np.where(typ == 2, k_mt, k_pt))
-    return np.exp2(k.astype(np.float64)) * (k + 1)
+    cost = np.exp2(k.astype(np.float64)) * (k + 1)
+    # a row of unknown status (type 4) is two problems: its genotype without and with the seeding
+    return np.where(typ == 4, cost + np.exp2(k + 1.0) * (k + 2), cost)
 
 
 def shard_rows(dat: np.ndarray, world_size: int) -> list[np.ndarray]:
@@ -166,14 +168,15 @@ def allreduce_sums_fixed_order(sums: np.ndarray, group=None) -> np.ndarray:
     return out
 
 
-def em_weight(n_em: float, n_pat: float, perc_met: float):
+def em_weight(n_em: float, n_pat: float, perc_met: float, n_unknown: float = 0):
     """(w, n_full) of regularized_optimization.py:121-128 from the GLOBAL counts.  perc_met = 1 with both kinds of
-    rows present makes the reference's weight infinite (its score NaN): rejected here instead of reaching the device."""
-    n_nm = n_pat - n_em
+    rows present makes the reference's weight infinite (its score NaN): rejected here instead of reaching the device.
+    n_unknown: rows of type 4 (primary tumour, status unknown) among the n_pat - weight 1, outside the EM / NM balance."""
+    n_nm = n_pat - n_em - n_unknown
     if n_em * n_nm != 0 and not (0.0 <= float(perc_met) < 1.0):
         raise ValueError(f"perc_met must be in [0, 1) for a cohort with EM and NM rows, got {perc_met!r}")
     w = perc_met * n_nm / ((1 - perc_met) * n_em) if n_em * n_nm != 0 else 1.0
-    return w, w * n_em + n_nm
+    return w, w * n_em + n_nm + n_unknown
 
 
 def split_wsums(ws: np.ndarray, N: int, n_full: float):
@@ -185,13 +188,13 @@ def split_wsums(ws: np.ndarray, N: int, n_full: float):
     return ws[0] / n_full, g / n_full, p / n_full, m / n_full
 
 
-def combine_sums(sums: np.ndarray, N: int, perc_met: float):
+def combine_sums(sums: np.ndarray, N: int, perc_met: float, n_unknown: float = 0):
     """(score, d_theta, d_dp, d_dm) from the buffer of mmhn_cohort_sums
-    (regularized_optimization.py:256-266)."""
+    (regularized_optimization.py:256-266).  n_unknown: rows of type 4 among sums[3] (their terms ride in the NM blocks)."""
     s_em, s_nm, n_em, n_pat = sums[:4]
-    n_nm = n_pat - n_em
+    n_nm = n_pat - n_em - n_unknown
     w = perc_met * n_nm / ((1 - perc_met) * n_em) if n_em * n_nm != 0 else 1.0
-    n_full = w * n_em + n_nm
+    n_full = w * n_em + n_nm + n_unknown
     o = 4
     g_em = sums[o:o + N * N].reshape(N, N); o += N * N
     g_nm = sums[o:o + N * N].reshape(N, N); o += N * N

@@ -172,6 +172,22 @@ class Engine:
                                                gp.ctypes.data_as(f64p), gm.ctypes.data_as(f64p)))
         return lp, g, gp, gm
 
+    def patient_status(self, log_theta, log_d_p, log_d_m):
+        """Score-only evaluation of the current cohort (mmhn_patient_status): lp [n_pat] of every row and p_seeded [n_pat],
+        P(the metastasis had been seeded | PT genotype) for the rows of type 4 (primary tumour, status unknown), NaN for
+        every other row."""
+        keep, (a, b, c) = self._params(log_theta, log_d_p, log_d_m)
+        lp, ps = np.zeros(self.n_pat), np.full(self.n_pat, np.nan)
+        _lib.check(self.lib.mmhn_patient_status(self.h, a, b, c, lp.ctypes.data_as(f64p), ps.ctypes.data_as(f64p)))
+        return lp, ps
+
+    @property
+    def n_unknown(self) -> int:
+        """Rows of type 4 in the cohort the engine was given."""
+        out = C.c_int64()
+        _lib.check(self.lib.mmhn_get_unknown_rows(self.h, C.byref(out)))
+        return int(out.value)
+
     # ---- argument checks of the single-vector primitives: everything the C side reads through a raw pointer has the
     # length it will read (make_joint / make_single read the whole state, build_params N x N / N entries, up() and down()
     # 2^k elements)

@@ -187,7 +187,8 @@ def _load_rows(eng: Engine, dat, rank: int, world: int, arr=None):
     rows = arr if world == 1 else arr[_dist.shard_rows(arr, world)[rank]]
     eng.set_cohort(rows)
     # global EM / NM counts (every rank holds the whole `dat`): the weight of :121-128 is known without communication
-    eng._global_counts = (float(arr[:, -3].sum()), float(arr.shape[0]))
+    # (n_em, n_pat, n_unknown: n_nm = n_pat - n_em - the rows of type 4, which have weight 1 of their own)
+    eng._global_counts = (float(arr[:, -3].sum()), float(arr.shape[0]), float(np.count_nonzero(arr[:, -1] == 4)))
     eng._sample_crc = _sample_crc(dat) if isinstance(dat, np.ndarray) else None
 
 
@@ -219,7 +220,8 @@ def _result(eng: Engine, log_theta, log_d_p, log_d_m, perc_met: float, with_grad
     `meanwhile()` (host work that does not need the result: the penalty terms) runs while the GPU evaluates, and so
     does the cache guard of `guard` (the caller's `dat`, engine from _engine_for(dat, check=False)): if the array was
     edited in place since its layout was built, the result is dropped and the evaluation repeated on a fresh layout."""
-    w, n_full = _dist.em_weight(*eng._global_counts, perc_met)
+    n_em, n_pat, n_unknown = eng._global_counts
+    w, n_full = _dist.em_weight(n_em, n_pat, perc_met, n_unknown)
     guarded = isinstance(guard, np.ndarray)                   # (anything else was keyed by content: cannot be stale)
     many = eng._sharded and eng.world_size_hint > 1
     stale = False
@@ -302,6 +304,26 @@ def score_and_grad(log_theta, log_d_p, log_d_m, dat, perc_met: float):
     """(score, d_theta, d_d_p, d_d_m)  (regularized_optimization.py:163-267)."""
     eng = _engine_for(dat, check=False)
     return _result(eng, log_theta, log_d_p, log_d_m, perc_met, True, guard=dat)[0]
+
+
+def met_status_posterior(log_theta, log_d_p, log_d_m, dat):
+    """P(the metastasis had been seeded | PT genotype) under the model, for every row of `dat` with a primary tumour of
+    its own (types 0, 1 and 4): the row is scored as a tumour of unknown status (type 4) on a relabelled copy with the
+    MT, seeding and order columns cleared.  NaN for the rows of types 2 and 3.  float64 [n_pat]."""
+    arr = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
+    out = np.full(arr.shape[0], np.nan)
+    pick = np.isin(arr[:, -1], (0, 1, 4))
+    if not pick.any():
+        return out
+    rows = arr[pick].copy()
+    rows[:, 1:-3:2] = 0
+    rows[:, -3] = 0
+    rows[:, -2] = 0
+    rows[:, -1] = 4
+    with Engine((arr.shape[1] - 3) // 2, device=_OPTIONS["device"], dtype=_OPTIONS["dtype"]) as eng:
+        eng.set_cohort(rows)
+        out[pick] = eng.patient_status(log_theta, log_d_p, log_d_m)[1]
+    return out
 
 
 def _unpack(params, n_total):
