@@ -1,9 +1,12 @@
 """What the tests of the order family share (test_orders*.py, test_order_*.py): the random models, the rows and cohorts they
 run on, what a row carries, the enumeration of a paired state's orders, the host stand-in for the one device call of the
 host code, and the contract every cohort entry point keeps: ENTRIES and the check_* bodies that the tests of the entry
-points' own files call (the checks without a part of their own are the tests of tests/test_order_contract.py).  Imported by
+points' own files call (the checks without a part of their own are the tests of tests/test_order_contract.py), and the
+host values of rows with 15 - 21 slots (tests/golden/orders_big.npz: big_rows, check_big_rows, check_big_samples).  Imported by
 name (`from order_common import ...`); tests/ is on sys.path.  The bars are derived in tests/test_order_posteriors.py."""
+import glob
 import itertools
+import os
 import warnings
 from types import SimpleNamespace
 
@@ -227,6 +230,248 @@ def too_large_cohort_k17(n=9):
     S = 2 * n
     wide = row(n, list(range(16)) + [S], 3, 0)
     return np.vstack((wide[None], [row(n, [0, 1, 2, 3, 6, S], 3, 1), row(n, [0, 2, S], 1), row(n, [0, 2], 0)]))
+
+
+# ---------------------------------------------------------------------------------------------------- rows of 15 - 21 slots
+# tests/golden/orders_big*.npz (tests/tools/make_golden_orders_big.py): the host values of rows with k = 15 ... 21, which
+# run on the 1 024-thread kernels and take the host code seconds to minutes each.  One layout, used by the generator
+# (big_pack), the loader (big_rows, big_host) and the comparators (check_big_rows, check_big_samples).
+BIG_MODELS = (("n9", 9, 31), ("n16", 16, 32), ("luad", 28, None))      # name, n, the seed of model() - None: LUAD-28 "fit"
+BIG_ENTRIES = {            # cohort method -> (key in the fixture, one-observation method, result class, fields)
+    "order_posteriors": ("post", "order_posterior", model_mod.OrderPosteriors, ("pre", "seed_pos")),
+    "order_precedences": ("prec", "order_precedence", model_mod.OrderPrecedences, ("prec",)),
+    "order_positions": ("pos", "order_position", model_mod.OrderPositions, ("pos_pt", "pos_mt")),
+    "order_times": ("time", "order_time", model_mod.OrderTimes, ("time", "obs", "pt_first")),
+    "order_snapshots": ("snap", "order_snapshot", model_mod.OrderSnapshots,
+                        ("held", "late", "map_state", "map_first", "map_prob"))}
+BIG_SAMPLES = 64           # samples per synthetic row, key = KEY + n, first = FIRST
+BIG_GAP = 1e-12            # two best snapshots closer than this (relative): map_first / map_state are not compared
+
+
+def _big_cells(entry, w):
+    """[(field, index into that field's array of one row)]: the cells of a row's block of doubles, in the block's order -
+    the entries over the row's own codes (k; k x k; one L x L per lineage; k + 3; 4 k + 3, less where late is narrower)."""
+    n, codes = w.n, w.codes
+    if entry == "order_posteriors":
+        ev = sorted({c // 2 for c in codes if c != 2 * n})
+        return [] if w.typ == 0 else [("pre", (ev,)), ("seed_pos", (slice(0, len(ev) + 1),))]
+    if entry == "order_precedences":
+        return [("prec", np.ix_(codes, codes))]
+    if entry == "order_positions":
+        return [("pos_" + name, np.ix_([c // 2 for c in w.lineages[name]], range(len(w.lineages[name]))))
+                for name in ("pt", "mt") if name in w.lineages]
+    if entry == "order_times":
+        return [("time", (codes,)), ("obs", (slice(None),)), ("pt_first", ())]
+    if w.typ != 3:
+        return []
+    return [("held", np.ix_((0, 1), codes)), ("late", (slice(None), slice(0, min(len(codes), n + 1)))), ("map_prob", ())]
+
+
+def _big_blank(entry, w):
+    """{field: one row's array} with what a row has outside its block: NaN / -1 where it does not carry a code, 0 where it
+    does and the entry is one by construction (pre of an event only one tumour has, positions past a lineage's length, late
+    past the other tumour's events)."""
+    n = w.n
+    L, N = 2 * n + 1, n + 1
+    nan = lambda *shape: np.full(shape, np.nan)
+    if entry == "order_posteriors":
+        return {"pre": nan(n), "seed_pos": nan(N)} if w.typ == 0 else {"pre": np.zeros(n), "seed_pos": np.zeros(N)}
+    if entry == "order_precedences":
+        return {"prec": nan(L, L)}
+    if entry == "order_positions":
+        out = {"pos_pt": nan(N, N), "pos_mt": nan(N, N)}
+        for name, codes in w.lineages.items():
+            out["pos_" + name][[c // 2 for c in codes]] = 0.0
+        return out
+    if entry == "order_times":
+        return {"time": nan(L), "obs": nan(2), "pt_first": nan()}
+    return {"held": nan(2, L), "late": np.zeros((2, N)) if w.typ == 3 else nan(2, N),
+            "map_state": np.full(L, -1, dtype=np.int8), "map_first": np.array(-1, dtype=np.int32), "map_prob": nan()}
+
+
+def big_pack(entry, w, res):
+    """The block of doubles of one host result (of BIG_ENTRIES[entry]'s one-observation method) of the row w."""
+    return np.concatenate([np.zeros(0)] + [np.asarray(getattr(res, f), dtype=np.float64)[ix].ravel()
+                                           for f, ix in _big_cells(entry, w)])
+
+
+def big_unpack(entry, w, block, map_state=None, map_first=-1):
+    """{field: one row's array in the shape and with the NaN / -1 padding of the API} from a block of big_pack (snapshots:
+    and the chosen snapshot over the row's codes)."""
+    out, at = _big_blank(entry, w), 0
+    for f, ix in _big_cells(entry, w):
+        size = out[f][ix].size
+        out[f][ix] = block[at:at + size].reshape(out[f][ix].shape)
+        at += size
+    assert at == len(block), (entry, at, len(block))
+    if entry == "order_snapshots" and w.typ == 3:
+        out["map_state"][w.codes] = map_state
+        out["map_first"][()] = map_first
+    return out
+
+
+def _big_files():
+    here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    return sorted(glob.glob(os.path.join(here, "orders_big*.npz")))
+
+
+_big_cache = {}
+
+
+def big_rows():
+    """{name: (mod: the MetMHN, n, dat: the rows in the fixture's order, index: their indices in the LUAD-28 cohort or
+    None, raw: the fixture's arrays of this model without the name's prefix)} of the models of BIG_MODELS, and under
+    "rows" the number of rows of the whole fixture.  Loaded once; nothing in it may be written to."""
+    if not _big_cache:
+        raw = {}
+        for path in _big_files():
+            with np.load(path) as z:
+                raw.update({key: z[key] for key in z.files})
+        assert raw, "tests/golden/orders_big*.npz is missing: tests/tools/make_golden_orders_big.py writes it"
+        for name, n, seed in BIG_MODELS:
+            if seed is None:
+                luad28 = np.load(os.path.join(os.path.dirname(_big_files()[0]), "luad28.npz"))
+                prefix = str(raw[name + "_prefix"])
+                mod = MetMHN(luad28[prefix + "_theta"], luad28[prefix + "_dp"], luad28[prefix + "_dm"])
+                np.testing.assert_array_equal(luad28["dat"][raw[name + "_index"]], raw[name + "_dat"])
+            else:
+                assert int(raw[name + "_seed"]) == seed
+                mod = model(n, seed=seed)
+            mine = {key[len(name) + 1:]: a for key, a in raw.items() if key.startswith(name + "_")}
+            for a in mine.values():
+                a.setflags(write=False)
+            _big_cache[name] = SimpleNamespace(mod=mod, n=n, dat=mine["dat"], index=mine.get("index"), raw=mine)
+        _big_cache["rows"] = int(raw["rows"])
+        assert _big_cache["rows"] == sum(len(_big_cache[name].dat) for name, _, _ in BIG_MODELS)
+    return _big_cache
+
+
+def big_models(synthetic_only=False):
+    """(name, what big_rows() holds under it) of the fixture's models, or of those with rows made up for it alone."""
+    return [(name, big_rows()[name]) for name, _, seed in BIG_MODELS if seed is not None or not synthetic_only]
+
+
+def big_host(entry, name, rows=None):
+    """The host result of a cohort entry point on the fixture's rows of one model (all of them, or those of `rows`), in the
+    API's shapes: an object of the entry point's result class."""
+    m = big_rows()[name]
+    key, _, cls, fields = BIG_ENTRIES[entry]
+    off = m.raw[key + "_off"]
+    rows = range(len(m.dat)) if rows is None else rows
+    per_row, so = [], 0
+    if entry == "order_snapshots":
+        so = np.concatenate(([0], np.cumsum([len(Row(r, m.n).codes) if r[-1] == 3 else 0 for r in m.dat])))
+    for i in rows:
+        w = Row(m.dat[i], m.n)
+        extra = (m.raw["snap_state"][so[i]:so[i + 1]], m.raw["snap_first"][i]) if entry == "order_snapshots" else ()
+        per_row.append(big_unpack(entry, w, m.raw[key + "_val"][off[i]:off[i + 1]], *extra))
+    return cls(m.raw[key + "_le"][list(rows)].copy(), *(np.array([r[f] for r in per_row]) for f in fields))
+
+
+def _over(d, bar):
+    """Largest entry of d over the bar, NaN (in both operands: the patterns are compared first) left out."""
+    d = np.asarray(d, dtype=np.float64)
+    return float(np.max(np.where(np.isnan(d), 0.0, d), initial=0.0)) / bar
+
+
+def check_big_rows(entry, device, bar):
+    """device: {name: the result of the cohort method `entry` on big_rows()[name].dat} against the fixture's host values.
+    The NaN / -1 patterns are equal; every field is within the entry point's own device-against-host bar `bar` (absolute on
+    probabilities; times and observation times over the row's last observation time, as tests/test_order_times.py has it);
+    exp(log_evidence) within 1e-12 relative; map_first / map_state equal except where the host's two best snapshots are
+    within BIG_GAP of each other, at most one row.  Prints the worst error over its bar per field before it asserts, and
+    asserts that every row of the fixture (all have k >= 15) was compared.  Returns {field: worst error over its bar}."""
+    big = big_rows()
+    fields = BIG_ENTRIES[entry][3]
+    worst, bad, compared, exempt = {"log_evidence": 0.0}, [], 0, 0
+    for name, _, _ in BIG_MODELS:
+        m, dev, host = big[name], device[name], big_host(entry, name)
+        k = m.dat[:, :-2].astype(int).sum(1)
+        if np.shape(dev.log_evidence) != host.log_evidence.shape:
+            bad.append(f"{name}: {np.shape(dev.log_evidence)} evidences for {len(m.dat)} rows")
+            continue
+        compared += int((k >= 15).sum())
+        zd, zh = np.exp(dev.log_evidence), np.exp(host.log_evidence)
+        worst["log_evidence"] = max(worst["log_evidence"], _over(np.abs(zd - zh) / zh, 1e-12))
+        if not np.all(np.isfinite(dev.log_evidence)):
+            bad.append(f"{name}: log_evidence not finite")
+        scale = 1.0
+        if entry == "order_times":
+            scale = np.where(np.isnan(host.obs[:, 1]), host.obs[:, 0], host.obs[:, 1])
+        tied = np.zeros(len(m.dat), dtype=bool)
+        if entry == "order_snapshots":
+            tied = m.raw["snap_gap"] <= BIG_GAP                    # (NaN, a row without a first observation: compared)
+            exempt += int(tied.sum())
+        for f in fields:
+            d, h = np.asarray(getattr(dev, f)), getattr(host, f)
+            if d.shape != h.shape:
+                bad.append(f"{name}: {f} has shape {d.shape}, not {h.shape}")
+            elif f in ("map_state", "map_first"):
+                rows = np.flatnonzero((d != h).reshape(len(h), -1).any(axis=1) & ~tied)
+                worst[f] = max(worst.get(f, 0.0), float(len(rows)))
+                if len(rows):
+                    bad.append(f"{name}: {f} differs in rows {rows.tolist()}")
+            else:
+                if not np.array_equal(np.isnan(d), np.isnan(h)):
+                    bad.append(f"{name}: NaN pattern of {f} differs in rows "
+                               f"{np.flatnonzero((np.isnan(d) != np.isnan(h)).reshape(len(h), -1).any(axis=1)).tolist()}")
+                s = scale if f in ("time", "obs") else 1.0
+                s = np.reshape(s, np.shape(s) + (1,) * (h.ndim - np.ndim(s)))
+                worst[f] = max(worst.get(f, 0.0), _over(np.abs(d - h) / s, bar))
+    print(f"rows of 15 - 21 slots against the host values, {entry}: {compared} rows with k >= 15 compared (the fixture has "
+          f"{big['rows']}), worst error over its bar (log_evidence: 1e-12 relative, the others {bar:g}; map_*: rows that "
+          f"differ) {({f: float(f'{v:.3g}') for f, v in worst.items()})}, {exempt} rows with tied snapshots")
+    assert compared == big["rows"], (compared, big["rows"])
+    assert not bad, bad
+    assert exempt <= 1
+    for f, v in worst.items():
+        assert v <= (0.0 if f in ("map_state", "map_first") else 1.0), (f, v)
+    return worst
+
+
+def big_host_samples(name):
+    """The host's samples of the fixture's rows of a synthetic model: (log_evidence [R], orders [R, BIG_SAMPLES, 2n+1]
+    padded with -1, log_prob, margin [R, BIG_SAMPLES])."""
+    m = big_rows()[name]
+    ks = [len(Row(r, m.n).codes) for r in m.dat]
+    orders = np.full((len(m.dat), BIG_SAMPLES, 2 * m.n + 1), -1, dtype=np.int8)
+    at = 0
+    for i, k in enumerate(ks):
+        orders[i, :, :k] = m.raw["samp_orders"][at:at + BIG_SAMPLES * k].reshape(BIG_SAMPLES, k)
+        at += BIG_SAMPLES * k
+    assert at == len(m.raw["samp_orders"]) and np.array_equal(m.raw["samp_row"], np.arange(len(m.dat)))
+    return m.raw["samp_le"], orders, m.raw["samp_log_prob"], m.raw["samp_margin"]
+
+
+def check_big_samples(device, margin, max_excluded):
+    """device: {name: sample_orders(big_rows()[name].dat, BIG_SAMPLES, key=KEY + n, first=FIRST)} of the synthetic models
+    against the host's samples, with the comparison of test_order_samples.test_device_against_host_small_shapes: the orders
+    equal wherever the host margin is at least `margin`, log_prob within 1e-10 there, at most max_excluded of the samples
+    set aside, exp(log_evidence) within 1e-12 relative."""
+    total = excluded = differ = rows = 0
+    d_lp = rel = 0.0
+    least = np.inf
+    for name, n, seed in BIG_MODELS:
+        if seed is None:
+            continue
+        le, orders, log_prob, mg = big_host_samples(name)
+        dev = device[name]
+        assert dev.orders.shape == orders.shape and dev.orders.dtype == np.int8 and dev.log_prob.shape == log_prob.shape
+        safe = mg >= margin
+        same = (dev.orders == orders).all(axis=2)
+        total, excluded, rows = total + safe.size, excluded + int((~safe).sum()), rows + len(le)
+        differ += int((~same & safe).sum())
+        d_lp = max(d_lp, float(np.abs(dev.log_prob - log_prob)[safe].max()))
+        rel = max(rel, float((np.abs(np.exp(dev.log_evidence) - np.exp(le)) / np.exp(le)).max()))
+        least = min(least, float(mg.min()))
+    print(f"rows of 15 - 17 slots against the host's samples: {rows} rows x {BIG_SAMPLES} samples, {excluded} set aside "
+          f"(smallest margin {least:.2e}), {differ} of the others differ, worst |log_prob| difference {d_lp:.2e}, rel. "
+          f"evidence {rel:.2e}")
+    assert rows == sum(len(big_rows()[name].dat) for name, _, seed in BIG_MODELS if seed is not None)
+    assert excluded <= max_excluded * total
+    assert differ == 0
+    assert d_lp <= 1e-10
+    assert rel <= 1e-12
 
 
 # ---------------------------------------------------------------------------------------------------- the shared contract

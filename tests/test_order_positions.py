@@ -6,8 +6,9 @@ Anchors:
     MT lineage of an order is the order without its even codes other than the seeding, the PT lineage the order without its
     odd codes;
   * the device kernel against the host code;
-  * on rows too large for the host code, identities that tie the positions to themselves, to order_posteriors and to
-    order_precedences.
+  * on rows too slow for a live comparison with the host code (k >= 15), the host values of tests/golden/orders_big.npz
+    on a selection of them, and on all of them identities that tie the positions to themselves, to order_posteriors and
+    to order_precedences.
 What order_positions shares with the other cohort entry points: order_common.check_* and tests/test_order_contract.py.
 
 Bars: those of tests/test_order_posteriors.py, where they are derived.  Device against host 1e-12 absolute on the positions
@@ -21,9 +22,9 @@ import numpy as np
 import pytest
 
 from metmhn_amd.state import MetState
-from order_common import (ENTRIES, Row, all_orders, check_arguments_before_the_library, check_errors_name_the_row,
-                          check_too_large_rows_get_the_host_value, large_rows, luad, luad_selection, model,
-                          random_paired_states, small_shapes_n8, split)
+from order_common import (ENTRIES, Row, all_orders, big_models, check_arguments_before_the_library, check_big_rows,
+                          check_errors_name_the_row, check_too_large_rows_get_the_host_value, large_rows, luad,
+                          luad_selection, model, random_paired_states, small_shapes_n8, split)
 
 ENTRY = ENTRIES["order_positions"]
 
@@ -191,6 +192,17 @@ def test_device_against_host_small_shapes():
     np.testing.assert_array_equal(np.isnan(dev.pos_mt), np.isnan(host.pos_mt))
     assert rel.max() <= 1e-12
     assert worst_abs <= 1e-12
+
+
+@pytest.mark.gpu
+def test_big_rows_against_host_values():
+    """The rows of tests/golden/orders_big.npz, k = 15 ... 21: every one on the device (the 1 024-thread instantiation),
+    evidence and positions at the bars of test_device_against_host_small_shapes against the host values the fixture holds."""
+    device = {}
+    for name, m in big_models():
+        device[name] = m.mod.order_positions(m.dat)
+        assert m.mod.positions_fallback_rows == 0
+    check_big_rows("order_positions", device, 1e-12)
 
 
 def _check_identities(mod, dat, le, pos_pt, pos_mt, post, prec, tag):

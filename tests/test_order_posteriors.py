@@ -4,14 +4,19 @@ Three independent anchors:
   * the host sum-product against the brute-force sum of MetMHN.likelihood (pinned to the reference by
     tests/golden/orders.npz) over every admissible order;
   * the device kernel against the host code, same summation order;
-  * the device evidence against the likelihood engine (Engine.patient_grads), a second implementation of the model.
+  * the device evidence against the likelihood engine (Engine.patient_grads), a second implementation of the model;
+  * on rows of 15 - 21 slots (the 1 024-thread kernel), too slow for a live comparison, the device against the host values
+    of tests/golden/orders_big.npz.
 What order_posteriors shares with the other cohort entry points: order_common.check_* and tests/test_order_contract.py.
 
 Bars (none taken from the code under test).  Every sum in both passes runs over non-negative terms, so nothing cancels:
 the relative error of an output is a small multiple of (k + depth of the sums) x 2^-52, about 1e-14 at k = 21.  Device
 against host 1e-12 relative on exp(log_evidence) and 1e-12 absolute on pre / seed_pos; host against enumeration 1e-12
 relative; against patient_grads the project's bar for fp64 log-probs, 1e-9 relative on lp.  Every test prints the worst
-value it saw before it asserts.
+value it saw before it asserts.  (The count holds for sums formed by trees, as the kernels form them.  The host code of
+order_precedence, order_position and order_time adds the 2^(k-1) masses of a paired row one after the other: on the rows
+with k = 19 ... 21 of tests/golden/orders_big.npz its own rounding, measured against math.fsum of the same terms, is a few
+1e-13, and that is what the comparison with the device then shows - up to 0.69 of the 1e-12 bar)
 """
 import itertools
 import warnings
@@ -20,8 +25,9 @@ import numpy as np
 import pytest
 
 from metmhn_amd.state import MetState
-from order_common import (ENTRIES, all_orders, check_arguments_before_the_library, check_errors_name_the_row,
-                          check_too_large_rows_get_the_host_value, luad, mixed_cohort, model, random_paired_states, row)
+from order_common import (ENTRIES, all_orders, big_models, check_arguments_before_the_library, check_big_rows,
+                          check_errors_name_the_row, check_too_large_rows_get_the_host_value, luad, mixed_cohort, model,
+                          random_paired_states, row)
 
 ENTRY = ENTRIES["order_posteriors"]
 
@@ -121,6 +127,17 @@ def test_device_against_host_mixed_cohorts():
             [row(4, [0, 1, 2, 3, 8], 3, d) for d in (0, 1, 2)] + [row(4, [8], 3, 0), row(4, [0, 2, 6, 8], 1),
                                                                  row(4, [1, 3, 5, 7, 8], 2), row(4, [0, 2, 4, 6], 0)])
         _check_device_host(mod, dat, np.arange(len(dat)), f"mixed cohort n = {n}")
+
+
+@pytest.mark.gpu
+def test_big_rows_against_host_values():
+    """The rows of tests/golden/orders_big.npz, k = 15 ... 21: every one on the device (the 1 024-thread instantiation),
+    evidence, pre and seed_pos at the bars of _check_device_host against the host values the fixture holds."""
+    device = {}
+    for name, m in big_models():
+        device[name] = m.mod.order_posteriors(m.dat)
+        assert m.mod.posteriors_fallback_rows == 0
+    check_big_rows("order_posteriors", device, 1e-12)
 
 
 @pytest.fixture(scope="module")

@@ -4,7 +4,8 @@ Anchors:
   * the host sum-product against brute force over MetMHN.likelihood (pinned to the reference by tests/golden/orders.npz)
     for every admissible order: prec[c, d] = the likelihood-weighted share of the orders with c strictly before d;
   * the device kernel against the host code;
-  * on rows too large for the host code, identities that tie prec to itself and to order_posteriors.
+  * on rows too slow for a live comparison with the host code (k >= 15), the host values of tests/golden/orders_big.npz
+    on a selection of them, and on all of them identities that tie prec to itself and to order_posteriors.
 What order_precedences shares with the other cohort entry points: order_common.check_* and tests/test_order_contract.py.
 
 Bars: those of tests/test_order_posteriors.py, where they are derived.  Device against host 1e-12 absolute on prec and
@@ -18,9 +19,9 @@ import numpy as np
 import pytest
 
 from metmhn_amd.state import MetState
-from order_common import (ENTRIES, Row, check_arguments_before_the_library, check_errors_name_the_row,
-                          check_too_large_rows_get_the_host_value, large_rows, luad, luad_selection, model, moments, paired,
-                          paired_orders, random_paired_states, row)
+from order_common import (ENTRIES, Row, big_models, check_arguments_before_the_library, check_big_rows,
+                          check_errors_name_the_row, check_too_large_rows_get_the_host_value, large_rows, luad,
+                          luad_selection, model, moments, paired, paired_orders, random_paired_states, row)
 
 ENTRY = ENTRIES["order_precedences"]
 
@@ -198,6 +199,17 @@ def test_device_against_host_small_shapes():
     assert ks >= {0, 1, 2, 3, 6, 7, 8, 9, 10, 11}
     assert worst_rel <= 1e-12
     assert worst_abs <= 1e-12
+
+
+@pytest.mark.gpu
+def test_big_rows_against_host_values():
+    """The rows of tests/golden/orders_big.npz, k = 15 ... 21: every one on the device (the 1 024-thread instantiation),
+    evidence and prec at the bars of test_device_against_host_small_shapes against the host values the fixture holds."""
+    device = {}
+    for name, m in big_models():
+        device[name] = m.mod.order_precedences(m.dat)
+        assert m.mod.precedences_fallback_rows == 0
+    check_big_rows("order_precedences", device, 1e-12)
 
 
 def _check_identities(mod, dat, le, prec, post, tag):

@@ -7,8 +7,9 @@ Anchors:
     likelihood / Z says;
   * the device kernel against the host draw, sample by sample, on the samples whose host margin says that a last-bit
     difference of a weight (exp may round differently on the device) cannot change them;
-  * on rows too large for the host code, the sample means against the exact marginals of order_posteriors and
-    order_precedences, which the samples do not share a reduction with.
+  * on rows too slow for a live comparison with the host code (k >= 15), the device's samples against the host's of
+    tests/golden/orders_big.npz on the synthetic rows, and on all of them the sample means against the exact marginals of
+    order_posteriors and order_precedences, which the samples do not share a reduction with.
 What sample_orders shares with the other cohort entry points: order_common.check_* and tests/test_order_contract.py.
 
 Bars.  Statistical: a frequency of M samples against its exact probability p, |freq - p| <= 5 sqrt(p (1 - p) / M) + 1 / M.
@@ -25,8 +26,8 @@ import pytest
 from metmhn_amd import _philox
 from metmhn_amd.model import OrderSamples
 from metmhn_amd.state import MetState
-from order_common import (ENTRIES, FIRST, KEY, all_orders, check_arguments_before_the_library, check_errors_name_the_row,
-                          check_too_large_rows_get_the_host_value, large_rows, luad, luad_selection, model,
+from order_common import (BIG_SAMPLES, ENTRIES, FIRST, KEY, all_orders, big_models, check_arguments_before_the_library,
+                          check_big_samples, check_errors_name_the_row, check_too_large_rows_get_the_host_value, large_rows, luad, luad_selection, model,
                           random_paired_states, row, small_shapes_n8)
 
 ENTRY = ENTRIES["sample_orders"]
@@ -239,6 +240,17 @@ def test_device_against_host_small_shapes(small_run):
         codes = np.flatnonzero(r[:2 * mod.n + 1])
         o = np.sort(dev.orders[i].astype(int), axis=1)
         assert np.all(o[:, len(o[0]) - len(codes):] == codes) and np.all(o[:, :len(o[0]) - len(codes)] == -1), i
+
+
+@pytest.mark.gpu
+def test_big_rows_against_host_values():
+    """The synthetic rows of tests/golden/orders_big.npz, k = 15 ... 17 (the 1 024-thread instantiation), 64 samples each,
+    with the comparison of test_device_against_host_small_shapes against the host's samples the fixture holds."""
+    device = {}
+    for name, m in big_models(synthetic_only=True):
+        device[name] = m.mod.sample_orders(m.dat, BIG_SAMPLES, key=KEY + m.n, first=FIRST)
+        assert m.mod.samples_fallback_rows == 0
+    check_big_samples(device, MARGIN, MAX_EXCLUDED)
 
 
 def _check_means(tag, mod, dat, run, M):

@@ -8,7 +8,8 @@ Anchors:
   * identities: the late block sums to 1; its rows sum to held[r, seeding], and held[0, seeding] is order_time's pt_first;
     the mean number of late events equals the summed deficits of the other tumour's codes (two different reductions); an
     "unknown" diagnosis order is the mixture of "PT" and "Met"; the regime a diagnosis order excludes is exactly 0;
-  * the device kernel against the host code, and on rows too large for the host code the identities, order_posteriors'
+  * the device kernel against the host code; on rows too slow for a live comparison with it (k >= 15) against the host
+    values of tests/golden/orders_big.npz on a selection of them, and on all of them the identities, order_posteriors'
     evidence and order_times' pt_first.
 What order_snapshots shares with the other cohort entry points: order_common.check_*.
 
@@ -28,7 +29,7 @@ import pytest
 from metmhn_amd import _lib
 from metmhn_amd.model import OrderSnapshot, OrderSnapshots
 from metmhn_amd.state import MetState
-from order_common import (Row, check_arguments_before_the_library, check_errors_name_the_row,
+from order_common import (Row, big_models, check_arguments_before_the_library, check_big_rows, check_errors_name_the_row,
                           check_too_large_rows_get_the_host_value, error_rows, host_only, large_rows, luad, luad_selection,
                           model, random_paired_states, small_shapes_n8, too_large_cohort_k14)
 
@@ -406,6 +407,18 @@ def test_large_synthetic_rows():
         assert max((max(m) for m in mix), default=0.0) <= BAR
         assert ident[:4].max() <= BAR and ident[4] == 0.0
         assert d_le <= BAR and d_pt <= BAR and max(d) <= BAR
+
+
+@pytest.mark.gpu
+def test_big_rows_against_host_values():
+    """The rows of tests/golden/orders_big.npz, k = 15 ... 21: every one on the device (the 1 024-thread instantiation),
+    held, late and map_prob at BAR against the host values the fixture holds; map_first and map_state equal, except on a
+    row (one at the most) whose two best snapshots the host has within 1e-12 relative of each other."""
+    device = {}
+    for name, m in big_models():
+        device[name] = m.mod.order_snapshots(m.dat)
+        assert m.mod.snapshots_fallback_rows == 0
+    check_big_rows("order_snapshots", device, BAR)
 
 
 @pytest.mark.gpu

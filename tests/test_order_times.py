@@ -8,7 +8,8 @@ Anchors:
     MetMHN.likelihood of that order (pinned to the reference by tests/golden/orders.npz);
   * identities: an "unknown" diagnosis order is the mixture of "PT" and "Met" with the weight pt_first; the seeding precedes
     the first observation, that the second, and every event the last observation;
-  * the device kernel against the host code, and on rows too large for the host code the identities and order_posteriors'
+  * the device kernel against the host code; on rows too slow for a live comparison with it (k >= 15) against the host
+    values of tests/golden/orders_big.npz on a selection of them, and on all of them the identities and order_posteriors'
     evidence.
 What order_times shares with the other cohort entry points: order_common.check_*.
 
@@ -31,7 +32,7 @@ import pytest
 from metmhn_amd import _lib
 from metmhn_amd.model import OrderTimes
 from metmhn_amd.state import MetState
-from order_common import (Row, check_arguments_before_the_library, check_errors_name_the_row,
+from order_common import (Row, big_models, check_arguments_before_the_library, check_big_rows, check_errors_name_the_row,
                           check_too_large_rows_get_the_host_value, error_rows, host_only, large_rows, luad, luad_selection,
                           model, random_paired_states, small_shapes_n8, too_large_cohort_k14)
 
@@ -406,6 +407,17 @@ def test_large_synthetic_rows():
         assert triples == (6 if n == 9 else 0)
         assert max((max(m) for m in mix), default=0.0) <= BAR
         assert order <= BAR and d_le <= BAR and max(d) <= BAR
+
+
+@pytest.mark.gpu
+def test_big_rows_against_host_values():
+    """The rows of tests/golden/orders_big.npz, k = 15 ... 21: every one on the device (the 1 024-thread instantiation),
+    every field at BAR against the host values the fixture holds, times over the row's last observation time as in _diff."""
+    device = {}
+    for name, m in big_models():
+        device[name] = m.mod.order_times(m.dat)
+        assert m.mod.times_fallback_rows == 0
+    check_big_rows("order_times", device, BAR)
 
 
 @pytest.mark.gpu
