@@ -125,6 +125,27 @@ int mmhn_patient_status(mmhn_handle h, const double* log_theta, const double* lo
  * counts - mmhn_cohort_wsums_begin) */
 int mmhn_get_unknown_rows(mmhn_handle h, int64_t* n_unknown);
 
+/* ---- per-row weights of the cohort objective (additive: the ABI version is unchanged) ----------------------------------
+ * mmhn_set_row_weights gives row i of the current cohort the weight w[i] >= 0 (finite, not all zero; n = the cohort's row
+ * count).  With weights set every cohort sum is the weighted sum of the per-row values v_i (lp, or an element of the
+ * gradient row):
+ *   S_EM = sum_{i in EM} w_i v_i      S_NM = sum_{i in NM or type 4} w_i v_i
+ *   n_em = sum_i w_i [seeding == 1]   n_pat = sum_i w_i   n_unknown = sum_i w_i [type == 4]
+ * and mmhn_score, mmhn_score_and_grad and slots [2], [3] of the mmhn_cohort_sums buffer use these real-valued counts in the
+ * place of the integer ones.  For integer weights this is the objective of the cohort in which row i is written w_i times.
+ * A row of weight 0 contributes exactly nothing, to the sums and to the counts: it is selected out, not multiplied by 0
+ * (it is still solved: dropping it would need a new plan).  The plan, the solves and the per-row values do not change;
+ * mmhn_patient_grads and mmhn_patient_status stay per row and UNWEIGHTED.
+ * w == NULL removes the weights (n is ignored), and so does every mmhn_set_cohort.  The call is refused - the message of
+ * mmhn_last_error names the first offending row, the weights held before stay - for a wrong n, a negative or non-finite
+ * entry, an all-zero vector, an engine without cohort rows, and between a _begin and its _end.  The weights go to the device
+ * here, once: an evaluation does no extra upload and no extra synchronisation, and without weights it launches what it
+ * launched before this entry point existed. */
+int mmhn_set_row_weights(mmhn_handle h, const double* w, int64_t n);
+/* out3 = [n_em, n_pat, n_unknown] as defined above (this handle's shard), summed on the host in row order - exact for dyadic
+ * weights; the integer counts of the cohort when no weights are set */
+int mmhn_get_row_weight_sums(mmhn_handle h, double* out3);
+
 /* ---- joint PT/MT primitives (metmhn/jx/kronvec.py, likelihood.py) ------------------
  * mmhn_kronvec        <-> kronvec.kronvec        (:499-539)   y = Q p, flags diag / transpose
  * mmhn_kron_diag      <-> kronvec.kron_diag      (:964-999)

@@ -86,6 +86,67 @@ def cross_val(dat, penal_fun: Callable, splits, n_folds: int, m_p_corr: float, k
     return pd.DataFrame(runs, columns=splits, index=np.arange(n_folds))
 
 
+def collapse_rows(dat) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Distinct rows of a cohort with their multiplicities: (rows [U, 2n+3] in order of first occurrence, counts float64
+    [U], inverse int64 [P]) with rows[inverse] == dat.  `counts` as the row weights of `rows` (learn_mhn(..., weights=counts))
+    gives the objective of `dat` itself; rows of type 4 collapse like any others."""
+    dat = np.asarray(dat)
+    if dat.ndim != 2:
+        raise ValueError(f"dat must be [n_pat, 2n+3], got shape {dat.shape}")
+    if dat.shape[0] == 0:
+        return dat.copy(), np.zeros(0), np.zeros(0, dtype=np.int64)
+    _, first, inv, cnt = np.unique(dat, axis=0, return_index=True, return_inverse=True, return_counts=True)
+    order = np.argsort(first, kind="stable")                  # np.unique sorts the rows: back to first occurrence
+    rank = np.empty_like(order)
+    rank[order] = np.arange(order.size)
+    return dat[first[order]].copy(), cnt[order].astype(np.float64), rank[np.asarray(inv).reshape(-1)].astype(np.int64)
+
+
+class BootstrapFits:
+    """Result of `bootstrap_fits`: theta [B, N, N], d_p [B, N], d_m [B, N] of the B replicates and weights [B, U], the
+    weight of every distinct row (`rows`, from collapse_rows) in every replicate."""
+
+    def __init__(self, theta, d_p, d_m, weights, rows):
+        self.theta, self.d_p, self.d_m, self.weights, self.rows = theta, d_p, d_m, weights, rows
+
+    def _all(self):
+        return {"theta": self.theta, "d_p": self.d_p, "d_m": self.d_m}
+
+    def interval(self, level: float = 0.95):
+        """Percentile interval per entry: dict of (lower, upper) for theta, d_p, d_m."""
+        if not 0.0 < level < 1.0:
+            raise ValueError(f"level must be in (0, 1), got {level!r}")
+        q = [50.0 * (1.0 - level), 100.0 - 50.0 * (1.0 - level)]
+        return {k: tuple(np.percentile(v, q, axis=0)) for k, v in self._all().items()}
+
+    def sign_stability(self):
+        """Share of the replicates in which an entry has the sign of the replicate median: dict of arrays in [0, 1]."""
+        return {k: np.mean(np.sign(v) == np.sign(np.median(v, axis=0)), axis=0) for k, v in self._all().items()}
+
+
+def bootstrap_fits(dat, n_boot: int, perc_met: float, penal: Callable, w_penal: float, key: int = 0, start=None,
+                   opt_iter: int = 1e5, opt_ftol: float = 1e-4) -> BootstrapFits:
+    """Nonparametric bootstrap of the penalised fit: `n_boot` resamples of the P rows of `dat` with replacement, each
+    fitted with learn_mhn.  `dat` is collapsed once (collapse_rows) and a replicate is a vector of weights on its distinct
+    rows - row b of np.random.default_rng(key).multinomial(P, np.full(P, 1 / P), size=n_boot), the draw over the ORIGINAL P
+    rows, folded with np.bincount(inverse, weights=draw) - so all replicates share one engine and one plan and cost one
+    weight upload each.  `start`: (theta, d_p, d_m) every replicate starts from, e.g. the full-data fit; default: indep(dat).
+    Distinct rows that a replicate does not draw have weight 0 there: they do not count, but they are still solved
+    (dropping them would need a new plan per replicate)."""
+    dat = np.asarray(dat)
+    rows, _, inverse = collapse_rows(dat)
+    P, U = dat.shape[0], rows.shape[0]
+    if P == 0 or n_boot < 1:
+        raise ValueError("bootstrap_fits needs at least one row and one replicate")
+    draws = np.random.default_rng(key).multinomial(P, np.full(P, 1 / P), size=n_boot)
+    weights = np.stack([np.bincount(inverse, weights=d, minlength=U) for d in draws]).astype(np.float64)
+    th0, dp0, dm0 = indep(dat) if start is None else start
+    fits = [learn_mhn(th0, dp0, dm0, rows, perc_met, penal, w_penal, opt_iter=opt_iter, opt_ftol=opt_ftol, opt_v=False,
+                      weights=w) for w in weights]
+    return BootstrapFits(np.stack([f[0] for f in fits]), np.stack([f[1] for f in fits]), np.stack([f[2] for f in fits]),
+                         weights, rows)
+
+
 def create_dat(dat_sim_full, n_em: int, n_nm: int, n_c: int, n_pm: int, n_mo: int, rng) -> np.ndarray:
     """Subsample simulated patients (rows of `simulate_dat`) to a cohort with the given composition and append
     the type column (examples/recall_study.py:32-47): `n_nm` never-metastasised PT-only rows (type 0, all-zero

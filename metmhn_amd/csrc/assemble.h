@@ -115,6 +115,28 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_rows(const PatRec* __restrict_
   part[((long long)blockIdx.y * 2 + 1) * stride + e] = acc1;
 }
 
+// k_reduce_rows with one weight per patient of the batch (mmhn_set_row_weights; wrow in BATCH order, as pats): the same rows
+// in the same order, chunks and part[] layout, every addend w * v.  A row of weight 0 is selected out, not multiplied (its
+// values may be anything, inf and NaN included: the row is absent).  The weight is uniform over the workgroup: a scalar load.
+__global__ __launch_bounds__(BLOCK) void k_reduce_rows_w(const PatRec* __restrict__ pats, int npat, int per,
+                                                         const double* __restrict__ out, int stride, int nelem,
+                                                         const double* __restrict__ wrow, double* __restrict__ part) {
+  const int e = blockIdx.x * BLOCK + threadIdx.x;
+  if (e >= nelem) return;
+  const int i0 = blockIdx.y * per, i1 = min(npat, i0 + per);
+  double acc0 = 0, acc1 = 0;
+#pragma unroll 8
+  for (int i = i0; i < i1; ++i) {
+    const int kd = pats[i].kind;
+    const double w = wrow[i];
+    const double v = out[(long long)i * stride + e];
+    const double a = w == 0.0 ? 0.0 : w * v;
+    if (kd == 0 || kd >= 4) acc1 += a; else acc0 += a;
+  }
+  part[((long long)blockIdx.y * 2 + 0) * stride + e] = acc0;
+  part[((long long)blockIdx.y * 2 + 1) * stride + e] = acc1;
+}
+
 // sums[cls][e] += the chunk sums in chunk order
 __global__ __launch_bounds__(BLOCK) void k_reduce_parts(const double* __restrict__ part, int stride, int nelem, int nchunk,
                                                         double* sums) {

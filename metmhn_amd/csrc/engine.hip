@@ -17,7 +17,7 @@
 //   5  rhs_J = D_obs * scatter(q_S), q_J = (D - Q)^-T rhs_J  k_scatter_marg, k_sweep<true>
 //   6  joint gradient: class marginals, eq block, flow rows, observation-rate marginals
 //                                      k_class_marg, k_eq_flows, k_grad_rows, k_bit_marg
-//   7  per-patient assembly and deterministic cohort reduction  k_finalize, k_reduce_rows, k_reduce_parts
+//   7  per-patient assembly and deterministic cohort reduction  k_finalize, k_reduce_rows (k_reduce_rows_w with row weights), k_reduce_parts
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -57,6 +57,7 @@ struct BatchDev {
   DevArr<WDesc> wd;
   DevArr<WChain> wchains;
   DevArr<int4> pcl;
+  DevArr<double> wrow;          // mmhn_set_row_weights: the weight of every patient of the batch, in batch order (null: no weights)
   CListDev clJ[2];
   StagedDev stg[2];
 };
@@ -154,6 +155,9 @@ struct Engine : EngineBase {
   DevArr<double> resp;                // [n_pat] by cohort row: P(seeded | genotype) of the rows of unknown status (dat type 4), written
                                       // where their score is formed; NaN everywhere else (filled once, when the cohort is set)
   long long n_unknown = 0;            // rows of dat type 4
+  // ---- row weights (mmhn_set_row_weights): by cohort row, empty = none; their three sums, taken on the host in row order
+  std::vector<double> row_w;
+  double w_em = 0, w_pat = 0, w_unknown = 0;
   DevArr<JLink<T>> links;
   double* h_abi = nullptr;            // pinned landing buffer of the result download
   double* h_abi_dev = nullptr;        // device view of it
@@ -612,6 +616,7 @@ struct Engine : EngineBase {
     n_cols = nc;
     batches.clear();
     dev.clear();
+    row_w.clear();                                          // (the weights belong to the rows they were set for)
     n_em = 0; n_unknown = 0;
     // a cohort that is refused, or whose plan cannot be brought to the device, leaves the engine without one (no patient
     // count next to an empty or half-uploaded plan)
@@ -624,6 +629,50 @@ struct Engine : EngineBase {
       n_pat = 0; n_em = 0; n_unknown = 0;
       throw;
     }
+  }
+  // the three counts of the objective: sum of w [seeding = 1], sum of w, sum of w [type 4] - the integer counts without weights
+  double count_em() const { return row_w.empty() ? n_em : w_em; }
+  double count_pat() const { return row_w.empty() ? (double)n_pat : w_pat; }
+  double count_unknown() const { return row_w.empty() ? (double)n_unknown : w_unknown; }
+  void row_weight_sums(double* out3) const { out3[0] = count_em(); out3[1] = count_pat(); out3[2] = count_unknown(); }
+  // one weight per cohort row (nullptr: none).  Everything an evaluation needs is brought to the device here, one array per
+  // batch in the batch's own order of patients (PatRec::row); an evaluation then only picks k_reduce_rows_w.
+  void set_row_weights(const double* w, long long nw) {
+    REQUIRE(!sums_pending, "mmhn_set_row_weights: an evaluation begun with mmhn_cohort_sums_begin has not been collected");
+    if (!w) {
+      row_w.clear();
+      for (BatchDev& d : dev) d.wrow.release();
+      return;
+    }
+    const std::string rows = std::to_string(n_pat);
+    REQUIRE(n_pat > 0 && !batches.empty(), "mmhn_set_row_weights: the engine holds no cohort (row 0 does not exist)");
+    REQUIRE(nw == n_pat, "mmhn_set_row_weights: " + std::to_string(nw) + " weights for a cohort of " + rows + " rows (" +
+                             (nw < n_pat ? "row " + std::to_string(std::max<long long>(nw, 0)) + " has no weight"
+                                         : "row " + rows + " does not exist") + ")");
+    double s_em = 0, s_pat = 0, s_unknown = 0;
+    bool any = false;
+    for (long long r = 0; r < n_pat; ++r) {
+      const std::string at = "mmhn_set_row_weights: the weight of row " + std::to_string(r);
+      REQUIRE(std::isfinite(w[r]), at + " is not finite");
+      REQUIRE(w[r] >= 0, at + " is negative");
+      any = any || w[r] != 0;
+      const int8_t* row = dat.data() + (size_t)r * n_cols;
+      if (row[2 * n] == 1) s_em += w[r];
+      s_pat += w[r];
+      if (row[n_cols - 1] == 4) s_unknown += w[r];
+    }
+    REQUIRE(any, "mmhn_set_row_weights: every weight is 0 (row 0 is the first of " + rows + ")");
+    std::vector<DevArr<double>> fresh(batches.size());
+    std::vector<double> hw;
+    for (const Batch& b : batches) {
+      hw.resize(b.pats.size());
+      for (size_t i = 0; i < hw.size(); ++i) hw[i] = w[b.pats[i].row];
+      fresh[b.id].alloc(hw.size());
+      if (!hw.empty()) HIPCHECK(hipMemcpy(fresh[b.id].p, hw.data(), hw.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    for (const Batch& b : batches) dev[b.id].wrow = std::move(fresh[b.id]);
+    row_w.assign(w, w + n_pat);
+    w_em = s_em; w_pat = s_pat; w_unknown = s_unknown;
   }
   // device copies of the plan and the workspace
   void place_cohort() {
@@ -905,7 +954,11 @@ struct Engine : EngineBase {
       {
         const int per = red_per(npat), nchunk = (npat + per - 1) / per;
         const dim3 cols((nelem + BLOCK - 1) / BLOCK);
-        hipLaunchKernelGGL(k_reduce_rows, dim3(cols.x, nchunk), dim3(BLOCK), 0, stream, db.pats.p, npat, per, out.p, st, nelem, redbuf.p);
+        if (row_w.empty())
+          hipLaunchKernelGGL(k_reduce_rows, dim3(cols.x, nchunk), dim3(BLOCK), 0, stream, db.pats.p, npat, per, out.p, st, nelem, redbuf.p);
+        else
+          hipLaunchKernelGGL(k_reduce_rows_w, dim3(cols.x, nchunk), dim3(BLOCK), 0, stream, db.pats.p, npat, per, out.p, st, nelem,
+                             db.wrow.p, redbuf.p);
         HIPCHECK(hipGetLastError());
         if (pack_mode && &b == &batches.back()) {
           hipLaunchKernelGGL(k_reduce_parts_pack, dim3((st + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, redbuf.p, st, nelem, nchunk,
@@ -980,13 +1033,13 @@ struct Engine : EngineBase {
     double flag = 0.0;
     if (w_combined) { flag = reduce_flag; reduce_flag = 0.0; }
     pack_mode = w_combined ? 2 : 1;
-    pack_a = w_combined ? *w_combined : (double)n_em; pack_b = w_combined ? flag : (double)n_pat; pack_dst = packed;
+    pack_a = w_combined ? *w_combined : count_em(); pack_b = w_combined ? flag : count_pat(); pack_dst = packed;
     packed_in_eval = false;
     struct Unset { int& m; ~Unset() { m = 0; } } unset{pack_mode};
     evaluate(lt, ldp, ldm, grad, nullptr, nullptr);
     if (!packed_in_eval) {                                 // (no batch: an empty cohort)
       if (w_combined) hipLaunchKernelGGL(k_pack_wsums, dim3(2), dim3(256), 0, stream, sums.p, N, *w_combined, packed, flag);
-      else hipLaunchKernelGGL(k_pack_sums, dim3(2), dim3(256), 0, stream, sums.p, N, n_em, (double)n_pat, packed);
+      else hipLaunchKernelGGL(k_pack_sums, dim3(2), dim3(256), 0, stream, sums.p, N, count_em(), count_pat(), packed);
       HIPCHECK(hipGetLastError());
     }
     const int moved = total + (w_combined ? 1 : 0);            // (the reduce flag rides behind the pre-combined buffer)
@@ -1153,6 +1206,21 @@ static long long unknown_rows(mmhn_handle h) {
   return h->dtype == MMHN_F64 ? static_cast<Engine<double>*>(h->impl)->n_unknown : static_cast<Engine<float>*>(h->impl)->n_unknown;
 }
 
+int mmhn_set_row_weights(mmhn_handle h, const double* w, int64_t n) {
+  API_BEGIN
+  GUARD(h);
+  DISPATCH(h, set_row_weights(w, n));
+  API_END
+}
+
+int mmhn_get_row_weight_sums(mmhn_handle h, double* out3) {
+  API_BEGIN
+  GUARD(h);
+  REQUIRE(out3, "null pointer");
+  DISPATCH(h, row_weight_sums(out3));
+  API_END
+}
+
 int mmhn_cohort_sums(mmhn_handle h, const double* lt, const double* ldp, const double* ldm, int with_grad,
                      double* sums) {
   API_BEGIN
@@ -1221,7 +1289,9 @@ int mmhn_score_and_grad(mmhn_handle h, const double* lt, const double* ldp, cons
   std::vector<double> s(4 + 2 * N * N + 3 * N);
   DISPATCH(h, cohort_sums(lt, ldp, ldm, grad, s.data()));
   double w, nf;
-  weights(s[2], s[3], (double)unknown_rows(h), perc_met, &w, &nf);
+  double c3[3];
+  DISPATCH(h, row_weight_sums(c3));
+  weights(s[2], s[3], c3[2], perc_met, &w, &nf);
   *score = (w * s[0] + s[1]) / nf;
   if (grad) {
     const double* gem = s.data() + 4;

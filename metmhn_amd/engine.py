@@ -65,6 +65,7 @@ class Engine:
         _lib.check(self.lib.mmhn_create(int(device), self.n, F64 if dtype == "f64" else F32, C.byref(h)))
         self.h = h
         self.n_pat = 0
+        self._row_weights = None
         self.comm_size = 1
         if workspace_bytes:
             _lib.check(self.lib.mmhn_set_workspace_limit(self.h, int(workspace_bytes)))
@@ -99,8 +100,42 @@ class Engine:
             # evaluation is pending never read the rows, and the library keeps the cohort it has
             if "has not been collected" not in str(err):
                 self.n_pat = 0
+                self._row_weights = None
             raise
         self.n_pat = dat.shape[0]
+        self._row_weights = None                              # (mmhn_set_cohort clears them)
+
+    def set_row_weights(self, w):
+        """One weight per row of the current cohort (mmhn_set_row_weights): w_i >= 0, finite, not all zero; None removes
+        them.  Every cohort sum becomes the weighted sum of the per-row values, the counts the weighted counts
+        (`row_weight_sums`); for integer weights that is the objective of the cohort with row i written w_i times.  A row of
+        weight 0 counts as absent (it is still solved).  patient_grads / patient_status stay per row and unweighted.  The
+        weights go to the device here, once; set_cohort clears them."""
+        if w is None:
+            _lib.check(self.lib.mmhn_set_row_weights(self.h, None, 0))
+            self._row_weights = None
+            return
+        w = np.ascontiguousarray(np.asarray(w, dtype=np.float64))
+        if w.ndim != 1:
+            raise ValueError(f"weights must have shape ({self.n_pat},), got {w.shape}")
+        if self.n_pat > 0 and w.shape[0] != self.n_pat:
+            raise ValueError(f"weights must have shape ({self.n_pat},), got {w.shape}: one weight per cohort row "
+                             f"(row {min(w.shape[0], self.n_pat)} has no counterpart)")
+        _lib.check(self.lib.mmhn_set_row_weights(self.h, w.ctypes.data_as(f64p), w.shape[0]))
+        self._row_weights = w.copy()
+
+    @property
+    def row_weights(self):
+        """A copy of the weights the engine holds, or None."""
+        w = getattr(self, "_row_weights", None)
+        return None if w is None else w.copy()
+
+    @property
+    def row_weight_sums(self):
+        """(n_em, n_pat, n_unknown) of this engine's rows: the weighted sums with weights set, else the integer counts."""
+        out = np.zeros(3)
+        _lib.check(self.lib.mmhn_get_row_weight_sums(self.h, out.ctypes.data_as(f64p)))
+        return float(out[0]), float(out[1]), float(out[2])
 
     def _params(self, log_theta, log_d_p, log_d_m):
         lt, ltp = _f(log_theta)

@@ -154,7 +154,7 @@ def _engine_for(dat, check: bool = True) -> Engine:
         if not check or not isinstance(dat, np.ndarray) or not _stale_anywhere(hit[0], dat, world):
             return hit[0]
         # same array object, edited in place: the SAME engine (callers may hold it; its communicator stays) gets the new rows
-        _load_rows(hit[0], dat, rank, world)
+        _load_rows(hit[0], dat, rank, world, weights=hit[0]._weights)
         return hit[0]
     if hit is not None:                                       # the id was recycled for another array
         _CACHE.pop(key)[0].close()
@@ -180,16 +180,63 @@ def _engine_for(dat, check: bool = True) -> Engine:
     return eng
 
 
-def _load_rows(eng: Engine, dat, rank: int, world: int, arr=None):
-    """(Re)build the device layout of this rank's shard of `dat` on `eng`."""
+def _check_weights(weights, n_rows: int):
+    """float64 copy of `weights` [n_rows] (one per row of `dat`), or None."""
+    if weights is None:
+        return None
+    w = np.array(weights, dtype=np.float64, copy=True)
+    if w.shape != (n_rows,):
+        raise ValueError(f"weights must have shape ({n_rows},): one per row of dat, got {w.shape}")
+    return w
+
+
+def _global_counts(arr: np.ndarray, weights=None):
+    """(n_em, n_pat, n_unknown) over the WHOLE `dat` (every rank holds it): the weight of :121-128 is known without
+    communication.  n_nm = n_pat - n_em - the rows of type 4, which have weight 1 of their own.  With row weights: the three
+    weighted sums (a row of weight 0 counts as absent)."""
+    if weights is None:
+        return (float(arr[:, -3].sum()), float(arr.shape[0]), float(np.count_nonzero(arr[:, -1] == 4)))
+    w = np.asarray(weights, dtype=np.float64)
+    return (float(w[arr[:, -3] == 1].sum()), float(w.sum()), float(w[arr[:, -1] == 4].sum()))
+
+
+def _shard_weights(weights: np.ndarray, arr: np.ndarray, rank: int, world: int) -> np.ndarray:
+    """The weights of this rank's rows: sliced with the same indices as the rows themselves."""
+    return weights if world == 1 else weights[_dist.shard_rows(arr, world)[rank]]
+
+
+def _load_rows(eng: Engine, dat, rank: int, world: int, arr=None, weights=None):
+    """(Re)build the device layout of this rank's shard of `dat` on `eng`; weights (optional): one per row of `dat`."""
     if arr is None:
         arr = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
     rows = arr if world == 1 else arr[_dist.shard_rows(arr, world)[rank]]
     eng.set_cohort(rows)
-    # global EM / NM counts (every rank holds the whole `dat`): the weight of :121-128 is known without communication
-    # (n_em, n_pat, n_unknown: n_nm = n_pat - n_em - the rows of type 4, which have weight 1 of their own)
-    eng._global_counts = (float(arr[:, -3].sum()), float(arr.shape[0]), float(np.count_nonzero(arr[:, -1] == 4)))
+    eng._weights = None                                       # (set_cohort cleared them)
+    eng._global_counts = _global_counts(arr)
     eng._sample_crc = _sample_crc(dat) if isinstance(dat, np.ndarray) else None
+    if weights is not None:
+        _set_weights(eng, arr, weights, rank, world)
+
+
+def _set_weights(eng: Engine, arr: np.ndarray, weights, rank: int, world: int):
+    """Give the engine that holds `arr`'s layout the row weights `weights` (None: remove them): one upload, no re-plan."""
+    eng.set_row_weights(None if weights is None else _shard_weights(weights, arr, rank, world))
+    eng._weights = None if weights is None else np.array(weights, dtype=np.float64, copy=True)
+    eng._global_counts = _global_counts(arr, weights)
+
+
+def _weighted_engine(dat, weights) -> Engine:
+    """_engine_for(dat, check=False) holding `weights` (one per row of `dat`, or None).  The engine keeps a copy of the
+    weights it was given; when the call's differ they are uploaded and the global counts recomputed - the plan stays."""
+    eng = _engine_for(dat, check=False)
+    held = eng._weights
+    if weights is None and held is None:
+        return eng
+    w = _check_weights(weights, np.shape(dat)[0])
+    if w is None or held is None or not np.array_equal(w, held):
+        rank, world = _rank_world() if _OPTIONS["shard"] else (0, 1)
+        _set_weights(eng, np.asarray(dat), w, rank, world)
+    return eng
 
 
 def _stale_anywhere(eng: Engine, dat, world: int) -> bool:
@@ -246,7 +293,7 @@ def _result(eng: Engine, log_theta, log_d_p, log_d_m, perc_met: float, with_grad
         stale = bool(stale_any)
     if stale:
         rank, world = _rank_world() if _OPTIONS["shard"] else (0, 1)
-        _load_rows(eng, guard, rank, world)                   # the same engine (and communicator), the new rows
+        _load_rows(eng, guard, rank, world, weights=eng._weights)      # the same engine (and communicator), the new rows, the weights again
         return _result(eng, log_theta, log_d_p, log_d_m, perc_met, with_grad, meanwhile)
     if aside is None and meanwhile is not None:
         aside = meanwhile()
@@ -294,15 +341,20 @@ def symmetric_penal(params, n_total: int, eps=1e-05):
 
 # ---- objective -------------------------------------------------------------------------
 
-def score(log_theta, log_d_p, log_d_m, dat, perc_met: float):
-    """Log-likelihood of the dataset (regularized_optimization.py:55-130)."""
-    eng = _engine_for(dat, check=False)
+def score(log_theta, log_d_p, log_d_m, dat, perc_met: float, weights=None):
+    """Log-likelihood of the dataset (regularized_optimization.py:55-130).
+
+    weights (keyword, here and in score_and_grad, score_reg, score_and_grad_reg, learn_mhn): one weight w_i >= 0 per row of
+    `dat`, finite and not all zero.  The objective is then the one of the cohort in which row i occurs w_i times (every sum
+    over the rows and the three counts n_em, n_pat, n_unknown weighted; a row of weight 0 counts as absent).  Changing the
+    weights of a cached cohort costs one upload, not a new plan; rows of weight 0 are still solved."""
+    eng = _weighted_engine(dat, weights)
     return _result(eng, log_theta, log_d_p, log_d_m, perc_met, False, guard=dat)[0][0]
 
 
-def score_and_grad(log_theta, log_d_p, log_d_m, dat, perc_met: float):
-    """(score, d_theta, d_d_p, d_d_m)  (regularized_optimization.py:163-267)."""
-    eng = _engine_for(dat, check=False)
+def score_and_grad(log_theta, log_d_p, log_d_m, dat, perc_met: float, weights=None):
+    """(score, d_theta, d_d_p, d_d_m)  (regularized_optimization.py:163-267).  weights: see score."""
+    eng = _weighted_engine(dat, weights)
     return _result(eng, log_theta, log_d_p, log_d_m, perc_met, True, guard=dat)[0]
 
 
@@ -332,33 +384,33 @@ def _unpack(params, n_total):
             params[n_total * (n_total + 1):])
 
 
-def score_reg(params, dat, perc_met: float, penal: Callable, w_penal: float):
-    """regularized_optimization.py:133-160."""
+def score_reg(params, dat, perc_met: float, penal: Callable, w_penal: float, weights=None):
+    """regularized_optimization.py:133-160.  weights: see score."""
     n_total = (np.asarray(dat).shape[1] - 3) // 2 + 1
     th, dp, dm = _unpack(params, n_total)
-    eng = _engine_for(dat, check=False)
+    eng = _weighted_engine(dat, weights)
     res, (pen, _) = _result(eng, th, dp, dm, perc_met, False, meanwhile=lambda: penal(params, n_total), guard=dat)    # penalty next to the GPU
     return np.array(-res[0] + w_penal * pen)
 
 
-def score_and_grad_reg(params, dat, perc_met: float, penal: Callable, w_penal: float):
-    """regularized_optimization.py:270-298."""
+def score_and_grad_reg(params, dat, perc_met: float, penal: Callable, w_penal: float, weights=None):
+    """regularized_optimization.py:270-298.  weights: see score."""
     n_total = (np.asarray(dat).shape[1] - 3) // 2 + 1
     th, dp, dm = _unpack(params, n_total)
-    eng = _engine_for(dat, check=False)
+    eng = _weighted_engine(dat, weights)
     (sc, d_th, d_d_p, d_d_m), (pen, pen_) = _result(eng, th, dp, dm, perc_met, True, meanwhile=lambda: penal(params, n_total), guard=dat)  # penalty next to the GPU
     grad_vec = np.concatenate((d_th.flatten(), d_d_p, d_d_m))
     return np.array(-sc + w_penal * pen), -grad_vec + w_penal * pen_
 
 
 def learn_mhn(th_init, dp_init, dm_init, dat, perc_met: float, penal: Callable, w_penal: float,
-              opt_iter: int = 1e05, opt_ftol: float = 1e-04, opt_v: bool = True):
-    """Infer a metMHN with SciPy's L-BFGS-B (regularized_optimization.py:301-334)."""
+              opt_iter: int = 1e05, opt_ftol: float = 1e-04, opt_v: bool = True, weights=None):
+    """Infer a metMHN with SciPy's L-BFGS-B (regularized_optimization.py:301-334).  weights: see score."""
     th_init = np.asarray(th_init, dtype=np.float64)
     n_total = th_init.shape[0]
     start = np.concatenate((th_init.flatten(), np.asarray(dp_init, float), np.asarray(dm_init, float)))
     x = opt.minimize(fun=score_and_grad_reg, jac=True, x0=start, method="L-BFGS-B",
-                     args=(dat, perc_met, penal, w_penal),
+                     args=(dat, perc_met, penal, w_penal, weights),
                      options={"maxiter": int(opt_iter), "disp": opt_v, "ftol": opt_ftol})
     theta = np.array(x.x[:n_total ** 2]).reshape((n_total, n_total))
     d_p = np.array(x.x[n_total ** 2:n_total * (n_total + 1)])
