@@ -146,6 +146,37 @@ int mmhn_set_row_weights(mmhn_handle h, const double* w, int64_t n);
  * weights; the integer counts of the cohort when no weights are set */
 int mmhn_get_row_weight_sums(mmhn_handle h, double* out3);
 
+/* ---- row groups: cohort rows as alternatives of one patient (additive: the ABI version is unchanged) -------------------
+ * A row with m unobserved entries has the likelihood of the sum of its 2^m completions, each an ordinary cohort row.
+ * mmhn_set_row_groups makes group g the list rows[ptr[g] .. ptr[g+1]) of row indices of the current cohort, with the weight
+ * w[g] >= 0 (n_groups + 1 entries of ptr, ptr[n_groups] of rows, n_groups of w).  With groups set
+ *   lp_g = log sum_{r in g} exp(lp_r)        rho_{g,r} = exp(lp_r - lp_g)
+ *   sum of element 0      = sum_g w_g lp_g
+ *   sum of element e >= 1 = sum_g w_g sum_{r in g} rho_{g,r} v_r[e]            (v_r: the row's gradient row)
+ * in each of the two blocks (EM; NM with type 4), and the counts are the group-weighted ones: n_pat = sum_g w_g, n_em over the
+ * groups whose rows have seeding = 1, n_unknown over the groups of type-4 rows (mmhn_get_row_weight_sums returns them;
+ * mmhn_score, mmhn_score_and_grad and slots [2], [3] of mmhn_cohort_sums use them).  The groups enter only in the cohort
+ * reduction, in fp64 whatever the engine's dtype: per row omega_r = sum_g w_g rho_{g,r} and lambda_r = sum_g w_g rho_{g,r} lp_g
+ * over the groups that hold r, then the reduction of the row weights with the addend omega_r v_r[e] (lambda_r for e = 0).
+ * Plan, solves and per-row values do not change: mmhn_patient_grads and mmhn_patient_status stay per row and UNMIXED.
+ * A row may be in any number of groups.  A row in no group, or only in groups of weight 0, is absent - selected out, its values
+ * may be anything - but it is still solved.  A cohort of several batches with a gradient is evaluated in two sweeps (a
+ * score-only one first: a group may span batches and lp_g must be known before a row is added).
+ * n_groups == 0 or null pointers remove the groups, and so does every mmhn_set_cohort.  The call is refused - the message
+ * names the first offending group or row, what was held before stays - for: ptr not non-decreasing from 0; an empty group;
+ * a row index outside the cohort; a negative or non-finite weight; all weights zero; a group whose rows are not all in one
+ * block of the sums (types 1-3, or types 0 and 4) or do not agree in "is type 4"; a call between a _begin and its _end; an
+ * engine without cohort rows; an engine that holds row weights (and mmhn_set_row_weights is refused while groups are held:
+ * the group weights take the role of the row weights); a communicator of more than one rank (sharding cuts through groups).
+ * Limits: one rank; rows of weight 0 or in no group are still solved; the cost of m unobserved entries is 2^m rows (the Python
+ * layer's Utilityfunctions.expand_missing builds the groups and refuses a row with more than max_alternatives = 1024 of them).
+ * Without groups an evaluation launches what it launched before these entry points existed. */
+int mmhn_set_row_groups(mmhn_handle h, const int64_t* ptr, int64_t n_groups, const int64_t* rows, const double* w);
+/* a score-only evaluation: lp_group[g] = lp_g, rho[ptr[g] + s] = rho of the s-th alternative of group g (also of groups of
+ * weight 0) */
+int mmhn_group_posteriors(mmhn_handle h, const double* log_theta, const double* log_d_p, const double* log_d_m,
+                          double* lp_group, double* rho);
+
 /* ---- joint PT/MT primitives (metmhn/jx/kronvec.py, likelihood.py) ------------------
  * mmhn_kronvec        <-> kronvec.kronvec        (:499-539)   y = Q p, flags diag / transpose
  * mmhn_kron_diag      <-> kronvec.kron_diag      (:964-999)

@@ -102,6 +102,71 @@ def collapse_rows(dat) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     return dat[first[order]].copy(), cnt[order].astype(np.float64), rank[np.asarray(inv).reshape(-1)].astype(np.int64)
 
 
+class RowGroups:
+    """Result of `expand_missing`: a cohort with unobserved entries as groups of complete rows.
+
+    rows [U, 2n+3] int8: the distinct completed rows in order of first occurrence (the cohort an engine is given);
+    ptr [P+1], idx [ptr[-1]]: group g = row g of the original `dat` = rows[idx[ptr[g]:ptr[g+1]]], alternative s of a row
+    with the expanded entries c_0 < c_1 < ... setting entry c_b to bit b of s;
+    weights [P]: the group weights (ones);
+    entries: one (row of dat, column, alts) per missing entry, alts = the positions s within the row's group whose
+    alternative sets the entry to 1 (empty for an entry in a column the row's type ignores, which is written as 0)."""
+
+    def __init__(self, rows, ptr, idx, weights, entries):
+        self.rows, self.ptr, self.idx, self.weights, self.entries = rows, ptr, idx, weights, entries
+
+    @property
+    def n_groups(self) -> int:
+        return self.ptr.shape[0] - 1
+
+
+def expand_missing(dat, missing=-1, max_alternatives: int = 1024) -> RowGroups:
+    """Rows with unobserved event entries as mixtures over their completions.  An entry equal to `missing` in an event
+    column means "not assayed"; the seeding, order and type columns must be known.  A row with m such entries in the columns
+    its type reads - PT columns for types 0, 1 and 4, MT columns for type 2, both (independently) for type 3 - becomes the
+    group of its 2^m completions; a missing entry in a column the type ignores becomes 0.  Completions shared between
+    patients appear once in `rows`.  Use as learn_mhn(..., groups.rows, ..., groups=groups).  A row with more than
+    `max_alternatives` completions is refused by name (the index label of a DataFrame, else the row number)."""
+    names = list(dat.index) if hasattr(dat, "index") and hasattr(dat, "columns") else None     # (a DataFrame)
+    arr = np.asarray(dat)
+    if arr.ndim != 2 or arr.shape[1] < 5 or arr.shape[1] % 2 == 0:
+        raise ValueError(f"dat must be [n_pat, 2n+3], got shape {arr.shape}")
+    P, nc = arr.shape
+    n = (nc - 3) // 2
+    name = (lambda r: repr(names[r])) if names is not None else (lambda r: str(r))
+    miss = arr == missing
+    for c, what in ((2 * n, "seeding"), (nc - 2, "order"), (nc - 1, "type")):
+        if miss[:, c].any():
+            raise ValueError(f"expand_missing: the {what} column of row {name(int(np.argmax(miss[:, c])))} is missing; it must be known")
+    blocks, ptr, entries = [], np.zeros(P + 1, dtype=np.int64), []
+    for r in range(P):
+        t = int(arr[r, -1])
+        read = np.zeros(nc, dtype=bool)
+        if t in (0, 1, 4, 3):
+            read[0:2 * n:2] = True
+        if t in (2, 3):
+            read[1:2 * n:2] = True
+        cols = np.flatnonzero(miss[r, :2 * n] & read[:2 * n])
+        m = cols.shape[0]
+        if m > 62 or (1 << m) > max_alternatives:
+            raise ValueError(f"expand_missing: row {name(r)} has {m} unobserved entries, 2^{m} completions: more than "
+                             f"max_alternatives = {max_alternatives}")
+        base = np.where(miss[r], 0, arr[r]).astype(np.int8)
+        s = np.arange(1 << m, dtype=np.int64)
+        block = np.repeat(base[None, :], 1 << m, axis=0)
+        for b, c in enumerate(cols):
+            block[:, c] = (s >> b) & 1
+        blocks.append(block)
+        ptr[r + 1] = ptr[r] + (1 << m)
+        where = {int(c): b for b, c in enumerate(cols)}
+        for c in np.flatnonzero(miss[r, :2 * n]):
+            b = where.get(int(c))
+            entries.append((r, int(c), np.flatnonzero((s >> b) & 1) if b is not None else np.zeros(0, dtype=np.int64)))
+    allrows = np.concatenate(blocks, axis=0) if blocks else np.zeros((0, nc), dtype=np.int8)
+    rows, _, inverse = collapse_rows(allrows)
+    return RowGroups(rows.astype(np.int8), ptr, inverse.astype(np.int64), np.ones(P), entries)
+
+
 class BootstrapFits:
     """Result of `bootstrap_fits`: theta [B, N, N], d_p [B, N], d_m [B, N] of the B replicates and weights [B, U], the
     weight of every distinct row (`rows`, from collapse_rows) in every replicate."""

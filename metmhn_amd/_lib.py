@@ -54,6 +54,8 @@ SIGNATURES = {
     "mmhn_get_unknown_rows": [C.c_void_p, i64p],
     "mmhn_set_row_weights": [C.c_void_p, f64p, C.c_int64],
     "mmhn_get_row_weight_sums": [C.c_void_p, f64p],
+    "mmhn_set_row_groups": [C.c_void_p, i64p, C.c_int64, i64p, f64p],
+    "mmhn_group_posteriors": [C.c_void_p, f64p, f64p, f64p, f64p, f64p],
     "mmhn_kronvec": [C.c_void_p, f64p, i8p, f64p, f64p, C.c_int, C.c_int],
     "mmhn_kronvec_batched": [C.c_void_p, f64p, i8p, C.c_int64, f64p, f64p, C.c_int, C.c_int],
     "mmhn_jacobi_step_batched": [C.c_void_p, f64p, f64p, f64p, i8p, C.c_int64, f64p, f64p, f64p, C.c_int],

@@ -17,7 +17,8 @@
 //   5  rhs_J = D_obs * scatter(q_S), q_J = (D - Q)^-T rhs_J  k_scatter_marg, k_sweep<true>
 //   6  joint gradient: class marginals, eq block, flow rows, observation-rate marginals
 //                                      k_class_marg, k_eq_flows, k_grad_rows, k_bit_marg
-//   7  per-patient assembly and deterministic cohort reduction  k_finalize, k_reduce_rows (k_reduce_rows_w with row weights), k_reduce_parts
+//   7  per-patient assembly and deterministic cohort reduction  k_finalize, k_reduce_rows (k_reduce_rows_w with row weights;
+//      with row groups k_mix_gather, k_group_lse, k_mix_weights, k_reduce_rows_mix - rowmix.h), k_reduce_parts
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -32,6 +33,7 @@
 #include "comm.h"
 #include "plan.h"
 #include "sampler.h"
+#include "rowmix.h"
 
 namespace mmhn {
 
@@ -158,6 +160,18 @@ struct Engine : EngineBase {
   // ---- row weights (mmhn_set_row_weights): by cohort row, empty = none; their three sums, taken on the host in row order
   std::vector<double> row_w;
   double w_em = 0, w_pat = 0, w_unknown = 0;
+  // ---- row groups (mmhn_set_row_groups, rowmix.h): the group lists and weights as given (grp_ptr empty = none), the
+  // transposed lists and the per-evaluation arrays on the device, the three group-weighted counts
+  std::vector<long long> grp_ptr;
+  std::vector<int> grp_rows;
+  std::vector<double> grp_w;
+  struct GroupsDev {
+    DevArr<long long> gptr, mptr;
+    DevArr<int> grows, mgrp;
+    DevArr<double> gw, lpc, lpg, omega, lambda, rho;
+  } gd;
+  double g_em = 0, g_pat = 0, g_unknown = 0;
+  bool want_rho = false;              // mmhn_group_posteriors: k_group_lse also writes rho
   DevArr<JLink<T>> links;
   double* h_abi = nullptr;            // pinned landing buffer of the result download
   double* h_abi_dev = nullptr;        // device view of it
@@ -617,6 +631,7 @@ struct Engine : EngineBase {
     batches.clear();
     dev.clear();
     row_w.clear();                                          // (the weights belong to the rows they were set for)
+    clear_row_groups();                                     // (and so do the groups)
     n_em = 0; n_unknown = 0;
     // a cohort that is refused, or whose plan cannot be brought to the device, leaves the engine without one (no patient
     // count next to an empty or half-uploaded plan)
@@ -631,9 +646,11 @@ struct Engine : EngineBase {
     }
   }
   // the three counts of the objective: sum of w [seeding = 1], sum of w, sum of w [type 4] - the integer counts without weights
-  double count_em() const { return row_w.empty() ? n_em : w_em; }
-  double count_pat() const { return row_w.empty() ? (double)n_pat : w_pat; }
-  double count_unknown() const { return row_w.empty() ? (double)n_unknown : w_unknown; }
+  // (with row groups: the group-weighted ones)
+  bool mixing() const { return !grp_ptr.empty(); }
+  double count_em() const { return mixing() ? g_em : row_w.empty() ? n_em : w_em; }
+  double count_pat() const { return mixing() ? g_pat : row_w.empty() ? (double)n_pat : w_pat; }
+  double count_unknown() const { return mixing() ? g_unknown : row_w.empty() ? (double)n_unknown : w_unknown; }
   void row_weight_sums(double* out3) const { out3[0] = count_em(); out3[1] = count_pat(); out3[2] = count_unknown(); }
   // one weight per cohort row (nullptr: none).  Everything an evaluation needs is brought to the device here, one array per
   // batch in the batch's own order of patients (PatRec::row); an evaluation then only picks k_reduce_rows_w.
@@ -644,6 +661,8 @@ struct Engine : EngineBase {
       for (BatchDev& d : dev) d.wrow.release();
       return;
     }
+    REQUIRE(!mixing(), "mmhn_set_row_weights: the engine holds row groups (group 0 of " + std::to_string(grp_w.size()) +
+                           "), whose weights take the role of row weights: remove them first");
     const std::string rows = std::to_string(n_pat);
     REQUIRE(n_pat > 0 && !batches.empty(), "mmhn_set_row_weights: the engine holds no cohort (row 0 does not exist)");
     REQUIRE(nw == n_pat, "mmhn_set_row_weights: " + std::to_string(nw) + " weights for a cohort of " + rows + " rows (" +
@@ -673,6 +692,107 @@ struct Engine : EngineBase {
     for (const Batch& b : batches) dev[b.id].wrow = std::move(fresh[b.id]);
     row_w.assign(w, w + n_pat);
     w_em = s_em; w_pat = s_pat; w_unknown = s_unknown;
+  }
+  void clear_row_groups() {
+    grp_ptr.clear(); grp_rows.clear(); grp_w.clear();
+    gd = GroupsDev{};
+  }
+  // mmhn_set_row_groups: group g = rows[ptr[g] .. ptr[g+1]) of the current cohort with weight w[g].  Checked in full, then
+  // brought to the device in full, then swapped in: a refused call leaves what was held before.
+  void set_row_groups(const int64_t* ptr, long long ng, const int64_t* rows, const double* w) {
+    const std::string fn = "mmhn_set_row_groups: ";
+    REQUIRE(!sums_pending, fn + "an evaluation begun with mmhn_cohort_sums_begin has not been collected");
+    if (ng == 0 || !ptr || !rows || !w) {
+      REQUIRE(ng == 0 || (!ptr && !rows && !w), fn + "null pointer next to " + std::to_string(ng) + " groups (group 0)");
+      clear_row_groups();
+      return;
+    }
+    REQUIRE(ng > 0 && ng < (1ll << 31), fn + "the number of groups must be in 0 .. 2^31 - 1 (group " + std::to_string(ng) + ")");
+    REQUIRE(n_pat > 0 && !batches.empty(), fn + "the engine holds no cohort (row 0 of group 0 does not exist)");
+    REQUIRE(row_w.empty(), fn + "the engine holds row weights (row 0), and group weights take their role: remove them first");
+    REQUIRE(comm_size <= 1, fn + "the engine is rank " + std::to_string(comm_rank) + " of " + std::to_string(comm_size) +
+                                ": sharding cuts through groups (group 0), so row groups need a one-rank engine");
+    REQUIRE(ptr[0] == 0, fn + "ptr[0] must be 0 (group 0)");
+    for (long long g = 0; g < ng; ++g) {
+      const std::string at = fn + "group " + std::to_string(g);
+      REQUIRE(ptr[g + 1] >= ptr[g], at + ": ptr is decreasing");
+      REQUIRE(ptr[g + 1] > ptr[g], at + " is empty");
+    }
+    double s_em = 0, s_pat = 0, s_unknown = 0;
+    bool any = false;
+    auto cls = [&](long long r) { const int t = dat[(size_t)r * n_cols + n_cols - 1]; return t == 0 || t == 4 ? 1 : 0; };
+    auto unk = [&](long long r) { return dat[(size_t)r * n_cols + n_cols - 1] == 4; };
+    auto seeded = [&](long long r) { return dat[(size_t)r * n_cols + 2 * n] == 1; };
+    for (long long g = 0; g < ng; ++g) {
+      const std::string at = fn + "group " + std::to_string(g);
+      for (long long k = ptr[g]; k < ptr[g + 1]; ++k)
+        REQUIRE(rows[k] >= 0 && rows[k] < n_pat, at + " holds row " + std::to_string(rows[k]) + ", outside the cohort of " +
+                                                     std::to_string(n_pat) + " rows");
+      REQUIRE(std::isfinite(w[g]), "mmhn_set_row_groups: the weight of group " + std::to_string(g) + " is not finite");
+      REQUIRE(w[g] >= 0, "mmhn_set_row_groups: the weight of group " + std::to_string(g) + " is negative");
+      const long long r0 = rows[ptr[g]];
+      for (long long k = ptr[g] + 1; k < ptr[g + 1]; ++k) {
+        REQUIRE(cls(rows[k]) == cls(r0), at + " mixes the two blocks of the cohort sums: row " + std::to_string(r0) + " is " +
+                                             (cls(r0) ? "NM / type 4" : "EM") + ", row " + std::to_string(rows[k]) + " is not");
+        REQUIRE(unk(rows[k]) == unk(r0), at + " mixes rows of type 4 with others (rows " + std::to_string(r0) + " and " +
+                                             std::to_string(rows[k]) + ")");
+      }
+      any = any || w[g] != 0;
+      if (seeded(r0)) s_em += w[g];
+      s_pat += w[g];
+      if (unk(r0)) s_unknown += w[g];
+    }
+    REQUIRE(any, fn + "every weight is 0 (group 0 is the first of " + std::to_string(ng) + ")");
+    const long long nnz = ptr[ng];
+    // the transposed lists: the memberships of every cohort row, in group order
+    std::vector<long long> mptr((size_t)n_pat + 1, 0);
+    for (long long k = 0; k < nnz; ++k) ++mptr[(size_t)rows[k] + 1];
+    for (long long r = 0; r < n_pat; ++r) mptr[(size_t)r + 1] += mptr[(size_t)r];
+    std::vector<int> mgrp((size_t)nnz), hrows((size_t)nnz);
+    {
+      std::vector<long long> at(mptr.begin(), mptr.end() - 1);
+      for (long long g = 0; g < ng; ++g)
+        for (long long k = ptr[g]; k < ptr[g + 1]; ++k) { mgrp[(size_t)at[(size_t)rows[k]]++] = (int)g; hrows[(size_t)k] = (int)rows[k]; }
+    }
+    GroupsDev fresh;
+    auto upv = [](auto& d, const auto* src, size_t cnt) {
+      d.alloc(cnt);
+      if (cnt) HIPCHECK(hipMemcpy(d.p, src, cnt * sizeof(*src), hipMemcpyHostToDevice));
+    };
+    upv(fresh.gptr, ptr, (size_t)ng + 1);
+    upv(fresh.grows, hrows.data(), (size_t)nnz);
+    upv(fresh.gw, w, (size_t)ng);
+    upv(fresh.mptr, mptr.data(), mptr.size());
+    upv(fresh.mgrp, mgrp.data(), mgrp.size());
+    fresh.lpc.alloc((size_t)n_pat); fresh.omega.alloc((size_t)n_pat); fresh.lambda.alloc((size_t)n_pat);
+    fresh.lpg.alloc((size_t)ng); fresh.rho.alloc((size_t)nnz);
+    gd = std::move(fresh);
+    grp_ptr.assign(ptr, ptr + ng + 1);
+    grp_rows = std::move(hrows);
+    grp_w.assign(w, w + ng);
+    g_em = s_em; g_pat = s_pat; g_unknown = s_unknown;
+  }
+  MixDev mix_dev() const {
+    return MixDev{gd.gptr.p, gd.grows.p, gd.gw.p, (int)grp_w.size(), gd.mptr.p, gd.mgrp.p, (int)n_pat,
+                  gd.lpc.p, gd.lpg.p, gd.omega.p, gd.lambda.p};
+  }
+  // lp_g of every group, then omega / lambda of every row: after the last batch has written its rows of lpc
+  void launch_mix() {
+    const MixDev m = mix_dev();
+    hipLaunchKernelGGL(k_group_lse, dim3((m.n_groups + MIX_WAVES - 1) / MIX_WAVES), dim3(BLOCK), 0, stream, m, want_rho ? gd.rho.p : nullptr);
+    HIPCHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_mix_weights, dim3((m.n_rows + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, m);
+    HIPCHECK(hipGetLastError());
+  }
+  // score-only evaluation: lp_g [n_groups], rho [ptr[n_groups]] in the order of the group lists
+  void group_posteriors(const double* lt, const double* ldp, const double* ldm, double* lp_group, double* rho) {
+    REQUIRE(mixing(), "mmhn_group_posteriors: the engine holds no row groups (mmhn_set_row_groups)");
+    std::vector<double> s(2 * stride());
+    want_rho = true;
+    struct Unset { bool& f; ~Unset() { f = false; } } unset{want_rho};
+    evaluate(lt, ldp, ldm, false, s.data(), nullptr);
+    HIPCHECK(hipMemcpy(lp_group, gd.lpg.p, grp_w.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(rho, gd.rho.p, grp_rows.size() * sizeof(double), hipMemcpyDeviceToHost));
   }
   // device copies of the plan and the workspace
   void place_cohort() {
@@ -758,9 +878,17 @@ struct Engine : EngineBase {
   }
 
   // host_out (optional): per-patient rows [n_pat][stride]; host_sums: [2][stride] (EM, NM)
-  void evaluate(const double* lt, const double* ldp, const double* ldm, bool grad, double* host_sums,
+  // With row groups (rowmix.h) the reduction needs lp of EVERY cohort row before the first row is added: one batch, or a
+  // score-only evaluation, is one sweep (the reductions of a score-only evaluation of several batches read no per-batch
+  // buffer and run behind the last batch); several batches with a gradient are a score-only sweep that fills lpc, then
+  // the sweep with gradient.
+  void evaluate(const double* lt, const double* ldp, const double* ldm, bool want_grad, double* host_sums,
                 double* host_out) {
     REQUIRE(!sums_pending, "an evaluation begun with mmhn_cohort_sums_begin has not been collected");
+    const bool mix = mixing();
+    const int nsweep = mix && want_grad && batches.size() > 1 ? 2 : 1;
+    const bool reduce_behind = mix && !want_grad && batches.size() > 1;
+    bool grad = want_grad && nsweep == 1;                   // (of the first sweep: what the head clears for)
     auto t0 = std::chrono::steady_clock::now();
     const int st = stride();
     // (an evaluation that threw between a fork and its join must not leave its flags to the next one: the side stream
@@ -787,196 +915,218 @@ struct Engine : EngineBase {
       build_params(lt, ldp, ldm);
       HIPCHECK(hipMemsetAsync(sums.p, 0, 2 * st * sizeof(double), stream));
     }
-    for (const Batch& b : batches) {
+    if (mix && cfg.poison) HIPCHECK(hipMemsetAsync(gd.lpc.p, 0xFF, (size_t)n_pat * sizeof(double), stream));
+    // cohort reduction of one batch (nelem elements of its rows) into sums; the last batch's also packs
+    auto reduce_batch = [&](const Batch& b, int nelem) {
       const BatchDev& db = dev[b.id];
-      const int npat = (int)b.pats.size(), nJ = (int)b.dJ.size(), nS = (int)b.dS.size();
-      const int tJ = (int)b.mapJ.size();
-      const PList LJ{db.dJ.p, db.mapJ.p, tJ, b.maxkJ, b.vecJ, db.lmapJ.p, &b.lofJ, tabJ.p};       // (Jacobi solver only)
-      const bool fused_small = b.has_small;
-      coop_alone = b.stg[0].empty();                          // (no second cooperative launch on a side stream next to the joint solves)
-      // the staged kernels of one group of patients (Batch::stg): forward part (tables, right-hand sides, 1/diag, forward solve,
-      // scores and adjoint seeds) and gradient part (adjoint solve, gradient rows, observation-rate marginals)
-      auto staged_fwd = [&](int w) {
-        const Staged& g = b.stg[w];
-        const StagedDev& dg = db.stg[w];
-        if (g.empty()) return;
-        const int nG = (int)g.pats.size(), tG = (int)g.map.size();
-        // (Jacobi / MMHN_SMALL=0: the group is every single-tumour problem, so that vec = every single-tumour vector)
-        const PList LG{db.dS.p, dg.map.p, tG, g.maxk, b.vecS, dg.lmap.p, &g.lof, tabS.p, g.cl, dg.cl};
-        // (the group's accumulators cleared, the e_0 right-hand sides written: before anything of the group runs)
-        hipLaunchKernelGGL((k_staged_init<T>), dim3(nG), dim3(BLOCK), 0, stream, db.pats.p, db.dS.p, rhsS.p, GS.p, bmS.p, N, grad ? 1 : 0, dg.pats.p);
-        HIPCHECK(hipGetLastError());
-        if (g.probs.size() >= 256)
-          hipLaunchKernelGGL((k_prep<T, false, 1024>), dim3((unsigned)g.probs.size()), dim3(1024), prep_lds<T>(N), stream, db.dS.p, d_par.p, tabS.p, dg.probs.p);
-        else
-          hipLaunchKernelGGL((k_prep<T, false>), dim3((unsigned)g.probs.size()), dim3(BLOCK), prep_lds<T>(N), stream, db.dS.p, d_par.p, tabS.p, dg.probs.p);
-        HIPCHECK(hipGetLastError());
-        // marginal right-hand sides (the small-space kernels read pi themselves and write the links)
-        if (!g.paired.empty()) {
-          hipLaunchKernelGGL((k_gather_marg<T>), dim3((unsigned)g.paired.size(), 2, g.maxk > 10 ? 8 : 1), dim3(BLOCK), 0, stream,
-                             db.pats.p, db.dJ.p, db.dS.p, d_par.p, pi.p, rhsS.p, links.p, dg.paired.p, db.wd.p);
-          HIPCHECK(hipGetLastError());
-        }
-        launch_diag(db.dS.p, dg.map.p, tG, nullptr, lidgS.p, nullptr, KD_LIDG);
-        solve(false, LG, pS.p, lidgS.p, rhsS.p, 0, nullptr);
-        hipLaunchKernelGGL((k_seeds<T>), dim3((nG + 255) / 256), dim3(256), 0, stream, db.pats.p, nG, db.dS.p,
-                           d_par.p, pS.p, seedS.p, lp.p, resp.p, N, dg.pats.p);
-        HIPCHECK(hipGetLastError());
-      };
-      auto staged_adj = [&](int w) {
-        const Staged& g = b.stg[w];
-        const StagedDev& dg = db.stg[w];
-        if (g.empty()) return;
-        const int tG = (int)g.map.size();
-        const PList LG{db.dS.p, dg.map.p, tG, g.maxk, b.vecS, dg.lmap.p, &g.lof, tabS.p, g.cl, dg.cl};
-        solve(true, LG, qS.p, lidgS.p, nullptr, 1, seedS.p);
-        launch_grad_rows(db.dS.p, (int)g.probs.size(), g.maxk, nullptr, pS.p, qS.p, GS.p, GK_S, dg.grc);
-        if (g.kind2) {
-          hipLaunchKernelGGL((k_bit_marg<T>), dim3(tG), dim3(BLOCK), 0, stream, db.dS.p, dg.map.p, d_par.p, pS.p, qS.p, bmS.p);
-          HIPCHECK(hipGetLastError());
-        }
-      };
-      time_kernels = cfg.force_timing || b.vecJ + b.vecS >= (1ll << 26);
-      const long long gjs = (long long)nJ * N * N;
-      GJ.p = zarena.p;
-      DJ.p = GJ.p + up4(3 * gjs);
-      Abuf.p = DJ.p + up4(3ll * nJ * N);
-      if (grad && nJ && !(head_done && &b == &batches.front())) zero(zarena.p, zclear_elems(b, N));
-      // (MMHN_POISON=1, tests: the arrays outside the memset start as NaNs - an entry that a consumer reads and no launch
-      // wrote shows in the gradient)
-      if (grad && nJ && cfg.poison) poison_fill(Abuf.p + b.aclr, b.asize - b.aclr);
-      prep(db.dJ.p, nJ, tabJ.p, true, b.maxkcJ);                    // (first: the head of the critical chain)
-      // staged patients that are their own problem: a side stream of their own from here to the assembly (a timed
-      // evaluation keeps them on the main stream - events are recorded there)
-      bool own_forked = false;
-      if (!b.stg[0].empty() && !time_kernels) {
-        HIPCHECK(hipEventRecord(ev_fork[2], stream));
-        HIPCHECK(hipStreamWaitEvent(side[2], ev_fork[2], 0));
-        hipStream_t keep = stream;
-        stream = side[2]; cur_lane = 1;
-        try {
-          staged_fwd(0);
-          if (grad) staged_adj(0);
-        } catch (...) { stream = keep; cur_lane = 0; throw; }
-        stream = keep; cur_lane = 0;
-        HIPCHECK(hipEventRecord(ev_join[2], side[2]));
-        own_forked = true;
-      }
-      // patients that are their own single-tumour problem need nothing of the joint path: their small-space kernels
-      // run on a side stream from here on, next to the joint forward solve (whose launch is issued first - it is the
-      // critical chain); the assembly waits for them
-      if (fused_small) small_fork(0);
-      // The tile solver skips dead tiles and its consumers read them: those parts of pi / q_J must hold zeros - the vectors
-      // of the tile route lie behind offT and are cleared once per batch.  The window and per-patient kernels never let a
-      // value of a dead tile into arithmetic (they are only ever loaded behind a per-state select): no clearing, which
-      // matters when a cohort takes several batches per evaluation; MMHN_POISON=1 (tests) NaN-fills their part.
-      if (!cfg.plan.use_jacobi && nJ) {
-        if (pi_owner != b.id) { zero(pi.p + b.offT, b.vecJ - b.offT); pi_owner = b.id; }
-        if (grad && qJ_owner != b.id) { zero(qJ.p + b.offT, b.vecJ - b.offT); qJ_owner = b.id; }
-        if (cfg.poison && b.offT > 0) {
-          HIPCHECK(hipMemsetAsync(pi.p, 0xFF, (size_t)b.offT * sizeof(T), stream));
-          if (grad) HIPCHECK(hipMemsetAsync(qJ.p, 0xFF, (size_t)b.offT * sizeof(T), stream));
-        }
-      }
-      // 1-2 joint forward
-      if (cfg.plan.use_jacobi) {
-        launch_diag(db.dJ.p, db.mapJ.p, tJ, nullptr, lidgJ.p, nullptr, KD_LIDG);
-        solve(false, LJ, pi.p, lidgJ.p, nullptr, 2, nullptr);
-      } else {
-        psolve(false, b, pi.p, 2);
-      }
-      if (fused_small) small_classes(b, 0, grad);
-      if (fused_small) small_classes(b, 1, grad);
-      // 3-4 the staged single-tumour problems (the paired rows' after the joint forward solve)
-      if (!own_forked) staged_fwd(0);
-      staged_fwd(1);
-      if (grad) {
-        if (!own_forked) staged_adj(0);
-        staged_adj(1);
-        // (the 1024-thread class of the paired small-space launches ran on its side stream next to the staged kernels above:
-        // the joint adjoint is the first consumer of what it wrote)
-        small_join(1);
-        if (nJ) {
-          // 5 joint adjoint: right-hand side D_obs * scatter(q_S) formed on the fly inside the solve
-          if (cfg.plan.use_jacobi) zero(rhsJ.p, b.vecJ);
-          for (int part = 0; part < 2 && !b.stg[1].paired.empty(); ++part) {
-            if (b.stg[1].paired.size() >= 256)
-              hipLaunchKernelGGL((k_scatter_marg<T, 1024>), dim3((unsigned)b.stg[1].paired.size()), dim3(1024), 0, stream, db.pats.p, db.dJ.p,
-                                 db.dS.p, d_par.p, qS.p, rhsS.p, cfg.plan.use_jacobi ? rhsJ.p : nullptr, dots.p, part, db.stg[1].paired.p);
-            else
-            hipLaunchKernelGGL((k_scatter_marg<T>), dim3((unsigned)b.stg[1].paired.size()), dim3(BLOCK), 0, stream, db.pats.p, db.dJ.p,
-                               db.dS.p, d_par.p, qS.p, rhsS.p, cfg.plan.use_jacobi ? rhsJ.p : nullptr, dots.p, part, db.stg[1].paired.p);
-            HIPCHECK(hipGetLastError());
-          }
-          if (cfg.plan.use_jacobi) solve(true, LJ, qJ.p, lidgJ.p, rhsJ.p, 0, nullptr);
-          else psolve(true, b, qJ.p, 3);
-          // 6 joint gradient (accumulators cleared at the start of the batch)
-          if (!cfg.plan.use_jacobi) {
-            // algorithmic bytes: the seeded halves of pi and q_J read once
-            const double mbytes = (double)b.vecJ * sizeof(T);
-            timed(MMHN_K_PCLASS, mbytes, [&]() {
-              if (b.wdirect) {                                                  // window-layout problems: both classes, two reads
-                const int nW = (int)b.wd.size();
-                hipLaunchKernelGGL((k_wclass<T>), dim3((unsigned)std::min(nW, cfg.plan.n_cu)), dim3(WROWS), wclass_lds<T>(), stream, db.dJ.p, db.wd.p, nW, pi.p, qJ.p, Abuf.p);
-              }
-              // the problems in index order: work items (class passes of a problem cut into ranges + its eq block's flows)
-              // on short launches, one workgroup per problem on long ones
-              if (!b.pcl.empty())
-                hipLaunchKernelGGL((k_pclass<T, true>), dim3((unsigned)b.pcl.size()), dim3(CMB), PC_LDS_ELEMS * sizeof(T), stream, db.dJ.p, db.wd.p, pi.p, qJ.p, Abuf.p, db.pcl.p);
-              else if ((int)b.wd.size() < nJ || !b.wdirect)
-                hipLaunchKernelGGL((k_pclass<T, false>), dim3(nJ), dim3(CMB), PC_LDS_ELEMS * sizeof(T), stream, db.dJ.p, db.wd.p, pi.p, qJ.p, Abuf.p);
-            });
-            if (!b.mapX.empty())
-              hipLaunchKernelGGL((k_class_marg<T>), dim3((unsigned)b.mapX.size()), dim3(CMB), 2 * sizeof(T) << TB, stream,
-                                 db.dJ.p, db.mapX.p, pi.p, qJ.p, Abuf.p);
-          } else {
-            hipLaunchKernelGGL((k_class_marg<T>), dim3(tJ), dim3(CMB), 2 * sizeof(T) << TB, stream, db.dJ.p,
-                               db.mapJ.p, pi.p, qJ.p, Abuf.p);
-          }
-          HIPCHECK(hipGetLastError());
-          // (its own launch: folded into the workgroups of k_pclass it cost more than the launch - k_pclass 20.5 -> 21.9 ms
-          // on the bench cohort, the LUAD evaluation +25 us; short launches run it as work items of k_pclass)
-          if (b.pcl.empty()) {
-            hipLaunchKernelGGL((k_eq_flows<T>), dim3(nJ), dim3(BLOCK), 0, stream, db.dJ.p, db.wd.p, pi.p, qJ.p, Abuf.p);
-            HIPCHECK(hipGetLastError());
-          }
-          launch_grad_rows(db.dJ.p, nJ, b.maxkcJ, Abuf.p, nullptr, nullptr, GJ.p, -1, db.grcJ, DJ.p, gjs);
-        }
-        // 7 assembly
-      }
-      if (fused_small) { small_join(0); small_join(1); }
-      if (own_forked) HIPCHECK(hipStreamWaitEvent(stream, ev_join[2], 0));
-      const AsmArgs<T> aa{db.pats.p, db.dJ.p, db.dS.p, d_par.p, GS.p, GJ.p, gjs, dots.p, DJ.p, (long long)nJ * N, bmS.p, lp.p, N,
-                          grad ? 1 : 0};
-      const int nelem = grad ? st : 1;
-      hipLaunchKernelGGL((k_finalize<T>), dim3(npat), dim3(BLOCK), 0, stream, aa, out.p);
+      const int npat = (int)b.pats.size();
+      const int per = red_per(npat), nchunk = (npat + per - 1) / per;
+      const dim3 cols((nelem + BLOCK - 1) / BLOCK);
+      if (mix)
+        hipLaunchKernelGGL(k_reduce_rows_mix, dim3(cols.x, nchunk), dim3(BLOCK), 0, stream, db.pats.p, npat, per, out.p, st, nelem,
+                           gd.omega.p, gd.lambda.p, redbuf.p);
+      else if (row_w.empty())
+        hipLaunchKernelGGL(k_reduce_rows, dim3(cols.x, nchunk), dim3(BLOCK), 0, stream, db.pats.p, npat, per, out.p, st, nelem, redbuf.p);
+      else
+        hipLaunchKernelGGL(k_reduce_rows_w, dim3(cols.x, nchunk), dim3(BLOCK), 0, stream, db.pats.p, npat, per, out.p, st, nelem,
+                           db.wrow.p, redbuf.p);
       HIPCHECK(hipGetLastError());
-      {
-        const int per = red_per(npat), nchunk = (npat + per - 1) / per;
-        const dim3 cols((nelem + BLOCK - 1) / BLOCK);
-        if (row_w.empty())
-          hipLaunchKernelGGL(k_reduce_rows, dim3(cols.x, nchunk), dim3(BLOCK), 0, stream, db.pats.p, npat, per, out.p, st, nelem, redbuf.p);
-        else
-          hipLaunchKernelGGL(k_reduce_rows_w, dim3(cols.x, nchunk), dim3(BLOCK), 0, stream, db.pats.p, npat, per, out.p, st, nelem,
-                             db.wrow.p, redbuf.p);
-        HIPCHECK(hipGetLastError());
-        if (pack_mode && &b == &batches.back()) {
-          hipLaunchKernelGGL(k_reduce_parts_pack, dim3((st + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, redbuf.p, st, nelem, nchunk,
-                             sums.p, pack_mode, N, pack_a, pack_b, pack_dst);
-          packed_in_eval = true;
-        } else {
-          hipLaunchKernelGGL(k_reduce_parts, dim3(cols.x, 2), dim3(BLOCK), 0, stream, redbuf.p, st, nelem, nchunk, sums.p);
+      if (pack_mode && &b == &batches.back()) {
+        hipLaunchKernelGGL(k_reduce_parts_pack, dim3((st + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, redbuf.p, st, nelem, nchunk,
+                           sums.p, pack_mode, N, pack_a, pack_b, pack_dst);
+        packed_in_eval = true;
+      } else {
+        hipLaunchKernelGGL(k_reduce_parts, dim3(cols.x, 2), dim3(BLOCK), 0, stream, redbuf.p, st, nelem, nchunk, sums.p);
+      }
+      HIPCHECK(hipGetLastError());
+    };
+    for (int sweep = 0; sweep < nsweep; ++sweep) {
+      const bool last_sweep = sweep == nsweep - 1;
+      grad = want_grad && last_sweep;
+      if (sweep > 0) { launch_mix(); head_done = false; }     // (lpc is whole; the head cleared nothing for a gradient)
+      for (const Batch& b : batches) {
+        const BatchDev& db = dev[b.id];
+        const int npat = (int)b.pats.size(), nJ = (int)b.dJ.size(), nS = (int)b.dS.size();
+        const int tJ = (int)b.mapJ.size();
+        const PList LJ{db.dJ.p, db.mapJ.p, tJ, b.maxkJ, b.vecJ, db.lmapJ.p, &b.lofJ, tabJ.p};       // (Jacobi solver only)
+        const bool fused_small = b.has_small;
+        coop_alone = b.stg[0].empty();                          // (no second cooperative launch on a side stream next to the joint solves)
+        // the staged kernels of one group of patients (Batch::stg): forward part (tables, right-hand sides, 1/diag, forward solve,
+        // scores and adjoint seeds) and gradient part (adjoint solve, gradient rows, observation-rate marginals)
+        auto staged_fwd = [&](int w) {
+          const Staged& g = b.stg[w];
+          const StagedDev& dg = db.stg[w];
+          if (g.empty()) return;
+          const int nG = (int)g.pats.size(), tG = (int)g.map.size();
+          // (Jacobi / MMHN_SMALL=0: the group is every single-tumour problem, so that vec = every single-tumour vector)
+          const PList LG{db.dS.p, dg.map.p, tG, g.maxk, b.vecS, dg.lmap.p, &g.lof, tabS.p, g.cl, dg.cl};
+          // (the group's accumulators cleared, the e_0 right-hand sides written: before anything of the group runs)
+          hipLaunchKernelGGL((k_staged_init<T>), dim3(nG), dim3(BLOCK), 0, stream, db.pats.p, db.dS.p, rhsS.p, GS.p, bmS.p, N, grad ? 1 : 0, dg.pats.p);
+          HIPCHECK(hipGetLastError());
+          if (g.probs.size() >= 256)
+            hipLaunchKernelGGL((k_prep<T, false, 1024>), dim3((unsigned)g.probs.size()), dim3(1024), prep_lds<T>(N), stream, db.dS.p, d_par.p, tabS.p, dg.probs.p);
+          else
+            hipLaunchKernelGGL((k_prep<T, false>), dim3((unsigned)g.probs.size()), dim3(BLOCK), prep_lds<T>(N), stream, db.dS.p, d_par.p, tabS.p, dg.probs.p);
+          HIPCHECK(hipGetLastError());
+          // marginal right-hand sides (the small-space kernels read pi themselves and write the links)
+          if (!g.paired.empty()) {
+            hipLaunchKernelGGL((k_gather_marg<T>), dim3((unsigned)g.paired.size(), 2, g.maxk > 10 ? 8 : 1), dim3(BLOCK), 0, stream,
+                               db.pats.p, db.dJ.p, db.dS.p, d_par.p, pi.p, rhsS.p, links.p, dg.paired.p, db.wd.p);
+            HIPCHECK(hipGetLastError());
+          }
+          launch_diag(db.dS.p, dg.map.p, tG, nullptr, lidgS.p, nullptr, KD_LIDG);
+          solve(false, LG, pS.p, lidgS.p, rhsS.p, 0, nullptr);
+          hipLaunchKernelGGL((k_seeds<T>), dim3((nG + 255) / 256), dim3(256), 0, stream, db.pats.p, nG, db.dS.p,
+                             d_par.p, pS.p, seedS.p, lp.p, resp.p, N, dg.pats.p);
+          HIPCHECK(hipGetLastError());
+        };
+        auto staged_adj = [&](int w) {
+          const Staged& g = b.stg[w];
+          const StagedDev& dg = db.stg[w];
+          if (g.empty()) return;
+          const int tG = (int)g.map.size();
+          const PList LG{db.dS.p, dg.map.p, tG, g.maxk, b.vecS, dg.lmap.p, &g.lof, tabS.p, g.cl, dg.cl};
+          solve(true, LG, qS.p, lidgS.p, nullptr, 1, seedS.p);
+          launch_grad_rows(db.dS.p, (int)g.probs.size(), g.maxk, nullptr, pS.p, qS.p, GS.p, GK_S, dg.grc);
+          if (g.kind2) {
+            hipLaunchKernelGGL((k_bit_marg<T>), dim3(tG), dim3(BLOCK), 0, stream, db.dS.p, dg.map.p, d_par.p, pS.p, qS.p, bmS.p);
+            HIPCHECK(hipGetLastError());
+          }
+        };
+        time_kernels = cfg.force_timing || b.vecJ + b.vecS >= (1ll << 26);
+        const long long gjs = (long long)nJ * N * N;
+        GJ.p = zarena.p;
+        DJ.p = GJ.p + up4(3 * gjs);
+        Abuf.p = DJ.p + up4(3ll * nJ * N);
+        if (grad && nJ && !(head_done && &b == &batches.front())) zero(zarena.p, zclear_elems(b, N));
+        // (MMHN_POISON=1, tests: the arrays outside the memset start as NaNs - an entry that a consumer reads and no launch
+        // wrote shows in the gradient)
+        if (grad && nJ && cfg.poison) poison_fill(Abuf.p + b.aclr, b.asize - b.aclr);
+        prep(db.dJ.p, nJ, tabJ.p, true, b.maxkcJ);                    // (first: the head of the critical chain)
+        // staged patients that are their own problem: a side stream of their own from here to the assembly (a timed
+        // evaluation keeps them on the main stream - events are recorded there)
+        bool own_forked = false;
+        if (!b.stg[0].empty() && !time_kernels) {
+          HIPCHECK(hipEventRecord(ev_fork[2], stream));
+          HIPCHECK(hipStreamWaitEvent(side[2], ev_fork[2], 0));
+          hipStream_t keep = stream;
+          stream = side[2]; cur_lane = 1;
+          try {
+            staged_fwd(0);
+            if (grad) staged_adj(0);
+          } catch (...) { stream = keep; cur_lane = 0; throw; }
+          stream = keep; cur_lane = 0;
+          HIPCHECK(hipEventRecord(ev_join[2], side[2]));
+          own_forked = true;
         }
+        // patients that are their own single-tumour problem need nothing of the joint path: their small-space kernels
+        // run on a side stream from here on, next to the joint forward solve (whose launch is issued first - it is the
+        // critical chain); the assembly waits for them
+        if (fused_small) small_fork(0);
+        // The tile solver skips dead tiles and its consumers read them: those parts of pi / q_J must hold zeros - the vectors
+        // of the tile route lie behind offT and are cleared once per batch.  The window and per-patient kernels never let a
+        // value of a dead tile into arithmetic (they are only ever loaded behind a per-state select): no clearing, which
+        // matters when a cohort takes several batches per evaluation; MMHN_POISON=1 (tests) NaN-fills their part.
+        if (!cfg.plan.use_jacobi && nJ) {
+          if (pi_owner != b.id) { zero(pi.p + b.offT, b.vecJ - b.offT); pi_owner = b.id; }
+          if (grad && qJ_owner != b.id) { zero(qJ.p + b.offT, b.vecJ - b.offT); qJ_owner = b.id; }
+          if (cfg.poison && b.offT > 0) {
+            HIPCHECK(hipMemsetAsync(pi.p, 0xFF, (size_t)b.offT * sizeof(T), stream));
+            if (grad) HIPCHECK(hipMemsetAsync(qJ.p, 0xFF, (size_t)b.offT * sizeof(T), stream));
+          }
+        }
+        // 1-2 joint forward
+        if (cfg.plan.use_jacobi) {
+          launch_diag(db.dJ.p, db.mapJ.p, tJ, nullptr, lidgJ.p, nullptr, KD_LIDG);
+          solve(false, LJ, pi.p, lidgJ.p, nullptr, 2, nullptr);
+        } else {
+          psolve(false, b, pi.p, 2);
+        }
+        if (fused_small) small_classes(b, 0, grad);
+        if (fused_small) small_classes(b, 1, grad);
+        // 3-4 the staged single-tumour problems (the paired rows' after the joint forward solve)
+        if (!own_forked) staged_fwd(0);
+        staged_fwd(1);
+        if (grad) {
+          if (!own_forked) staged_adj(0);
+          staged_adj(1);
+          // (the 1024-thread class of the paired small-space launches ran on its side stream next to the staged kernels above:
+          // the joint adjoint is the first consumer of what it wrote)
+          small_join(1);
+          if (nJ) {
+            // 5 joint adjoint: right-hand side D_obs * scatter(q_S) formed on the fly inside the solve
+            if (cfg.plan.use_jacobi) zero(rhsJ.p, b.vecJ);
+            for (int part = 0; part < 2 && !b.stg[1].paired.empty(); ++part) {
+              if (b.stg[1].paired.size() >= 256)
+                hipLaunchKernelGGL((k_scatter_marg<T, 1024>), dim3((unsigned)b.stg[1].paired.size()), dim3(1024), 0, stream, db.pats.p, db.dJ.p,
+                                   db.dS.p, d_par.p, qS.p, rhsS.p, cfg.plan.use_jacobi ? rhsJ.p : nullptr, dots.p, part, db.stg[1].paired.p);
+              else
+              hipLaunchKernelGGL((k_scatter_marg<T>), dim3((unsigned)b.stg[1].paired.size()), dim3(BLOCK), 0, stream, db.pats.p, db.dJ.p,
+                                 db.dS.p, d_par.p, qS.p, rhsS.p, cfg.plan.use_jacobi ? rhsJ.p : nullptr, dots.p, part, db.stg[1].paired.p);
+              HIPCHECK(hipGetLastError());
+            }
+            if (cfg.plan.use_jacobi) solve(true, LJ, qJ.p, lidgJ.p, rhsJ.p, 0, nullptr);
+            else psolve(true, b, qJ.p, 3);
+            // 6 joint gradient (accumulators cleared at the start of the batch)
+            if (!cfg.plan.use_jacobi) {
+              // algorithmic bytes: the seeded halves of pi and q_J read once
+              const double mbytes = (double)b.vecJ * sizeof(T);
+              timed(MMHN_K_PCLASS, mbytes, [&]() {
+                if (b.wdirect) {                                                  // window-layout problems: both classes, two reads
+                  const int nW = (int)b.wd.size();
+                  hipLaunchKernelGGL((k_wclass<T>), dim3((unsigned)std::min(nW, cfg.plan.n_cu)), dim3(WROWS), wclass_lds<T>(), stream, db.dJ.p, db.wd.p, nW, pi.p, qJ.p, Abuf.p);
+                }
+                // the problems in index order: work items (class passes of a problem cut into ranges + its eq block's flows)
+                // on short launches, one workgroup per problem on long ones
+                if (!b.pcl.empty())
+                  hipLaunchKernelGGL((k_pclass<T, true>), dim3((unsigned)b.pcl.size()), dim3(CMB), PC_LDS_ELEMS * sizeof(T), stream, db.dJ.p, db.wd.p, pi.p, qJ.p, Abuf.p, db.pcl.p);
+                else if ((int)b.wd.size() < nJ || !b.wdirect)
+                  hipLaunchKernelGGL((k_pclass<T, false>), dim3(nJ), dim3(CMB), PC_LDS_ELEMS * sizeof(T), stream, db.dJ.p, db.wd.p, pi.p, qJ.p, Abuf.p);
+              });
+              if (!b.mapX.empty())
+                hipLaunchKernelGGL((k_class_marg<T>), dim3((unsigned)b.mapX.size()), dim3(CMB), 2 * sizeof(T) << TB, stream,
+                                   db.dJ.p, db.mapX.p, pi.p, qJ.p, Abuf.p);
+            } else {
+              hipLaunchKernelGGL((k_class_marg<T>), dim3(tJ), dim3(CMB), 2 * sizeof(T) << TB, stream, db.dJ.p,
+                                 db.mapJ.p, pi.p, qJ.p, Abuf.p);
+            }
+            HIPCHECK(hipGetLastError());
+            // (its own launch: folded into the workgroups of k_pclass it cost more than the launch - k_pclass 20.5 -> 21.9 ms
+            // on the bench cohort, the LUAD evaluation +25 us; short launches run it as work items of k_pclass)
+            if (b.pcl.empty()) {
+              hipLaunchKernelGGL((k_eq_flows<T>), dim3(nJ), dim3(BLOCK), 0, stream, db.dJ.p, db.wd.p, pi.p, qJ.p, Abuf.p);
+              HIPCHECK(hipGetLastError());
+            }
+            launch_grad_rows(db.dJ.p, nJ, b.maxkcJ, Abuf.p, nullptr, nullptr, GJ.p, -1, db.grcJ, DJ.p, gjs);
+          }
+          // 7 assembly
+        }
+        if (fused_small) { small_join(0); small_join(1); }
+        if (own_forked) HIPCHECK(hipStreamWaitEvent(stream, ev_join[2], 0));
+        const AsmArgs<T> aa{db.pats.p, db.dJ.p, db.dS.p, d_par.p, GS.p, GJ.p, gjs, dots.p, DJ.p, (long long)nJ * N, bmS.p, lp.p, N,
+                            grad ? 1 : 0};
+        const int nelem = grad ? st : 1;
+        hipLaunchKernelGGL((k_finalize<T>), dim3(npat), dim3(BLOCK), 0, stream, aa, out.p);
         HIPCHECK(hipGetLastError());
+        if (mix && sweep == 0) {
+          hipLaunchKernelGGL(k_mix_gather, dim3((npat + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, db.pats.p, npat, out.p, st, gd.lpc.p);
+          HIPCHECK(hipGetLastError());
+          if (batches.size() == 1) launch_mix();
+        }
+        if (last_sweep && !reduce_behind) reduce_batch(b, nelem);
+        if (host_out && last_sweep) {
+          std::vector<double> tmp((size_t)npat * st);
+          HIPCHECK(hipMemcpyAsync(tmp.data(), out.p, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+          HIPCHECK(hipStreamSynchronize(stream));
+          check_abort();
+          for (int i = 0; i < npat; ++i)
+            std::memcpy(host_out + (size_t)b.pats[i].row * st, tmp.data() + (size_t)i * st, st * sizeof(double));
+        }
       }
-      if (host_out) {
-        std::vector<double> tmp((size_t)npat * st);
-        HIPCHECK(hipMemcpyAsync(tmp.data(), out.p, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIPCHECK(hipStreamSynchronize(stream));
-        check_abort();
-        for (int i = 0; i < npat; ++i)
-          std::memcpy(host_out + (size_t)b.pats[i].row * st, tmp.data() + (size_t)i * st, st * sizeof(double));
-      }
+    }
+    if (reduce_behind) {
+      launch_mix();
+      for (const Batch& b : batches) reduce_batch(b, 1);
     }
     time_kernels = true;
     if (host_sums) {
@@ -1073,6 +1223,7 @@ struct Engine : EngineBase {
 
   void comm_init(const ncclUniqueId& id, int rank, int nranks) {
     REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks, "comm_init: rank / n_ranks out of range");
+    REQUIRE(nranks == 1 || !mixing(), "comm_init: the engine holds row groups, which need a one-rank engine (remove them first)");
     comm_destroy();
     RCCLCHECK(rccl().CommInitRank(&comm, nranks, id, rank));
     comm_rank = rank; comm_size = nranks;
@@ -1218,6 +1369,21 @@ int mmhn_get_row_weight_sums(mmhn_handle h, double* out3) {
   GUARD(h);
   REQUIRE(out3, "null pointer");
   DISPATCH(h, row_weight_sums(out3));
+  API_END
+}
+
+int mmhn_set_row_groups(mmhn_handle h, const int64_t* ptr, int64_t n_groups, const int64_t* rows, const double* w) {
+  API_BEGIN
+  GUARD(h);
+  DISPATCH(h, set_row_groups(ptr, n_groups, rows, w));
+  API_END
+}
+
+int mmhn_group_posteriors(mmhn_handle h, const double* lt, const double* ldp, const double* ldm, double* lp_group, double* rho) {
+  API_BEGIN
+  GUARD(h);
+  REQUIRE(lt && ldp && ldm && lp_group && rho, "null pointer");
+  DISPATCH(h, group_posteriors(lt, ldp, ldm, lp_group, rho));
   API_END
 }
 

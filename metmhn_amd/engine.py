@@ -66,6 +66,7 @@ class Engine:
         self.h = h
         self.n_pat = 0
         self._row_weights = None
+        self._row_groups = None
         self.comm_size = 1
         if workspace_bytes:
             _lib.check(self.lib.mmhn_set_workspace_limit(self.h, int(workspace_bytes)))
@@ -101,9 +102,11 @@ class Engine:
             if "has not been collected" not in str(err):
                 self.n_pat = 0
                 self._row_weights = None
+                self._row_groups = None
             raise
         self.n_pat = dat.shape[0]
         self._row_weights = None                              # (mmhn_set_cohort clears them)
+        self._row_groups = None
 
     def set_row_weights(self, w):
         """One weight per row of the current cohort (mmhn_set_row_weights): w_i >= 0, finite, not all zero; None removes
@@ -136,6 +139,54 @@ class Engine:
         out = np.zeros(3)
         _lib.check(self.lib.mmhn_get_row_weight_sums(self.h, out.ctypes.data_as(f64p)))
         return float(out[0]), float(out[1]), float(out[2])
+
+    def set_row_groups(self, ptr, rows, w=None):
+        """Row groups of the current cohort (mmhn_set_row_groups): group g is the list rows[ptr[g]:ptr[g+1]] of cohort rows -
+        the alternatives of one patient, e.g. the completions of a row with unobserved entries - with the weight w[g] >= 0
+        (default: ones).  The group's likelihood is the sum of its rows': lp_g = logsumexp(lp_r), and every gradient sum takes
+        row r with rho = exp(lp_r - lp_g); the counts (`row_weight_sums`) are the group-weighted ones.  A row in no group, or
+        only in groups of weight 0, counts as absent (it is still solved).  patient_grads / patient_status stay per row and
+        unmixed.  ptr=None removes the groups; set_cohort clears them.  Row weights and row groups exclude each other, and
+        groups need a one-rank engine."""
+        if ptr is None:
+            _lib.check(self.lib.mmhn_set_row_groups(self.h, None, 0, None, None))
+            self._row_groups = None
+            return
+        ptr = np.ascontiguousarray(np.asarray(ptr, dtype=np.int64))
+        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64))
+        if ptr.ndim != 1 or rows.ndim != 1 or ptr.shape[0] < 1:
+            raise ValueError(f"ptr must have shape (n_groups + 1,) and rows (ptr[-1],), got {ptr.shape} and {rows.shape}")
+        ng = ptr.shape[0] - 1
+        w = np.ones(ng) if w is None else np.ascontiguousarray(np.asarray(w, dtype=np.float64))
+        if w.shape != (ng,):
+            raise ValueError(f"w must have shape ({ng},): one weight per group, got {w.shape}")
+        if ng > 0 and not (0 <= ptr[-1] <= rows.shape[0] and (ptr <= rows.shape[0]).all() and (ptr >= 0).all()):
+            bad = int(np.argmax((ptr > rows.shape[0]) | (ptr < 0)))
+            raise ValueError(f"ptr[{bad}] = {int(ptr[bad])} points outside rows (length {rows.shape[0]}): group {max(bad - 1, 0)}")
+        if ng == 0:
+            _lib.check(self.lib.mmhn_set_row_groups(self.h, None, 0, None, None))
+            self._row_groups = None
+            return
+        _lib.check(self.lib.mmhn_set_row_groups(self.h, ptr.ctypes.data_as(i64p), ng, rows.ctypes.data_as(i64p),
+                                                w.ctypes.data_as(f64p)))
+        self._row_groups = (ptr.copy(), rows[:int(ptr[-1])].copy(), w.copy())
+
+    @property
+    def row_groups(self):
+        """Copies of (ptr, rows, w) of the groups the engine holds, or None."""
+        g = getattr(self, "_row_groups", None)
+        return None if g is None else tuple(a.copy() for a in g)
+
+    def group_posteriors(self, log_theta, log_d_p, log_d_m):
+        """Score-only evaluation with row groups set (mmhn_group_posteriors): (lp_group [n_groups], rho [ptr[-1]]) with
+        rho[ptr[g] + s] = P(the s-th alternative of group g | the group) = exp(lp_r - lp_g)."""
+        if self._row_groups is None:
+            raise RuntimeError("metmhn_amd: group_posteriors needs row groups (set_row_groups)")
+        keep, (a, b, c) = self._params(log_theta, log_d_p, log_d_m)
+        ptr = self._row_groups[0]
+        lpg, rho = np.zeros(ptr.shape[0] - 1), np.zeros(int(ptr[-1]))
+        _lib.check(self.lib.mmhn_group_posteriors(self.h, a, b, c, lpg.ctypes.data_as(f64p), rho.ctypes.data_as(f64p)))
+        return lpg, rho
 
     def _params(self, log_theta, log_d_p, log_d_m):
         lt, ltp = _f(log_theta)

@@ -154,7 +154,7 @@ def _engine_for(dat, check: bool = True) -> Engine:
         if not check or not isinstance(dat, np.ndarray) or not _stale_anywhere(hit[0], dat, world):
             return hit[0]
         # same array object, edited in place: the SAME engine (callers may hold it; its communicator stays) gets the new rows
-        _load_rows(hit[0], dat, rank, world, weights=hit[0]._weights)
+        _load_rows(hit[0], dat, rank, world, weights=hit[0]._weights, groups=hit[0]._groups)
         return hit[0]
     if hit is not None:                                       # the id was recycled for another array
         _CACHE.pop(key)[0].close()
@@ -205,17 +205,21 @@ def _shard_weights(weights: np.ndarray, arr: np.ndarray, rank: int, world: int) 
     return weights if world == 1 else weights[_dist.shard_rows(arr, world)[rank]]
 
 
-def _load_rows(eng: Engine, dat, rank: int, world: int, arr=None, weights=None):
-    """(Re)build the device layout of this rank's shard of `dat` on `eng`; weights (optional): one per row of `dat`."""
+def _load_rows(eng: Engine, dat, rank: int, world: int, arr=None, weights=None, groups=None):
+    """(Re)build the device layout of this rank's shard of `dat` on `eng`; weights (optional): one per row of `dat`;
+    groups (optional): the (ptr, idx, w) the engine held (_set_groups)."""
     if arr is None:
         arr = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
     rows = arr if world == 1 else arr[_dist.shard_rows(arr, world)[rank]]
     eng.set_cohort(rows)
     eng._weights = None                                       # (set_cohort cleared them)
+    eng._groups = None                                        # (and the groups)
     eng._global_counts = _global_counts(arr)
     eng._sample_crc = _sample_crc(dat) if isinstance(dat, np.ndarray) else None
     if weights is not None:
         _set_weights(eng, arr, weights, rank, world)
+    if groups is not None:
+        _set_groups(eng, arr, groups, world)
 
 
 def _set_weights(eng: Engine, arr: np.ndarray, weights, rank: int, world: int):
@@ -225,10 +229,59 @@ def _set_weights(eng: Engine, arr: np.ndarray, weights, rank: int, world: int):
     eng._global_counts = _global_counts(arr, weights)
 
 
-def _weighted_engine(dat, weights) -> Engine:
-    """_engine_for(dat, check=False) holding `weights` (one per row of `dat`, or None).  The engine keeps a copy of the
-    weights it was given; when the call's differ they are uploaded and the global counts recomputed - the plan stays."""
+def _group_arrays(groups, n_rows: int):
+    """(ptr, idx, w) of a RowGroups (Utilityfunctions.expand_missing) over a cohort of n_rows rows, checked for shape."""
+    ptr = np.ascontiguousarray(np.asarray(groups.ptr, dtype=np.int64))
+    idx = np.ascontiguousarray(np.asarray(groups.idx, dtype=np.int64))
+    w = np.array(groups.weights, dtype=np.float64, copy=True)
+    if ptr.ndim != 1 or ptr.shape[0] < 2 or idx.ndim != 1 or w.shape != (ptr.shape[0] - 1,) or int(ptr[-1]) != idx.shape[0]:
+        raise ValueError(f"groups: ptr {ptr.shape}, idx {idx.shape} and weights {w.shape} do not describe group lists")
+    if idx.size and (idx.min() < 0 or idx.max() >= n_rows):
+        raise ValueError(f"groups: an index outside the {n_rows} rows of dat (dat must be groups.rows)")
+    return ptr, idx, w
+
+
+def _group_counts(arr: np.ndarray, ptr, idx, w):
+    """(n_em, n_pat, n_unknown) with row groups: the group-weighted counts, a group taking seeding and type of its rows."""
+    first = idx[ptr[:-1]]
+    return (float(w[arr[first, -3] == 1].sum()), float(w.sum()), float(w[arr[first, -1] == 4].sum()))
+
+
+def _set_groups(eng: Engine, arr: np.ndarray, groups, world: int):
+    """Give the engine that holds `arr`'s layout the row groups (ptr, idx, w) (None: remove them): no re-plan."""
+    if groups is None:
+        eng.set_row_groups(None, None)
+        eng._groups = None
+        eng._global_counts = _global_counts(arr)
+        return
+    if world > 1:
+        raise ValueError("metmhn_amd: groups= with configure(shard=True) and more than one rank: sharding cuts through "
+                         "groups, row groups are evaluated on one rank")
+    ptr, idx, w = groups
+    eng.set_row_groups(ptr, idx, w)
+    eng._groups = (ptr, idx, w)
+    eng._global_counts = _group_counts(arr, ptr, idx, w)
+
+
+def _weighted_engine(dat, weights, groups=None) -> Engine:
+    """_engine_for(dat, check=False) holding `weights` (one per row of `dat`, or None) or the row groups `groups` (a
+    RowGroups over `dat`, or None).  The engine keeps a copy of what it was given; when the call's differ they are
+    uploaded and the global counts recomputed - the plan stays."""
+    if groups is not None and weights is not None:
+        raise ValueError("groups= and weights= exclude each other: the group weights (groups.weights) take the role of the row weights")
     eng = _engine_for(dat, check=False)
+    if groups is not None or eng._groups is not None:
+        rank, world = _rank_world() if _OPTIONS["shard"] else (0, 1)
+        arr = np.asarray(dat)
+        if groups is None:
+            _set_groups(eng, arr, None, world)
+        else:
+            new = _group_arrays(groups, arr.shape[0])
+            if eng._groups is None or not all(np.array_equal(a, b) for a, b in zip(new, eng._groups)):
+                if eng._weights is not None:
+                    _set_weights(eng, arr, None, rank, world)
+                _set_groups(eng, arr, new, world)
+            return eng
     held = eng._weights
     if weights is None and held is None:
         return eng
@@ -293,7 +346,7 @@ def _result(eng: Engine, log_theta, log_d_p, log_d_m, perc_met: float, with_grad
         stale = bool(stale_any)
     if stale:
         rank, world = _rank_world() if _OPTIONS["shard"] else (0, 1)
-        _load_rows(eng, guard, rank, world, weights=eng._weights)      # the same engine (and communicator), the new rows, the weights again
+        _load_rows(eng, guard, rank, world, weights=eng._weights, groups=eng._groups)   # the same engine (and communicator), the new rows, the weights / groups again
         return _result(eng, log_theta, log_d_p, log_d_m, perc_met, with_grad, meanwhile)
     if aside is None and meanwhile is not None:
         aside = meanwhile()
@@ -341,20 +394,24 @@ def symmetric_penal(params, n_total: int, eps=1e-05):
 
 # ---- objective -------------------------------------------------------------------------
 
-def score(log_theta, log_d_p, log_d_m, dat, perc_met: float, weights=None):
+def score(log_theta, log_d_p, log_d_m, dat, perc_met: float, weights=None, groups=None):
     """Log-likelihood of the dataset (regularized_optimization.py:55-130).
 
     weights (keyword, here and in score_and_grad, score_reg, score_and_grad_reg, learn_mhn): one weight w_i >= 0 per row of
     `dat`, finite and not all zero.  The objective is then the one of the cohort in which row i occurs w_i times (every sum
     over the rows and the three counts n_em, n_pat, n_unknown weighted; a row of weight 0 counts as absent).  Changing the
-    weights of a cached cohort costs one upload, not a new plan; rows of weight 0 are still solved."""
-    eng = _weighted_engine(dat, weights)
+    weights of a cached cohort costs one upload, not a new plan; rows of weight 0 are still solved.
+
+    groups (keyword, same functions): a RowGroups from Utilityfunctions.expand_missing - rows with unobserved entries as
+    mixtures over their completions; `dat` is then groups.rows.  Every patient (group) scores logsumexp of its completions'
+    lp, the counts are the group-weighted ones.  groups and weights together are a ValueError; one rank only."""
+    eng = _weighted_engine(dat, weights, groups)
     return _result(eng, log_theta, log_d_p, log_d_m, perc_met, False, guard=dat)[0][0]
 
 
-def score_and_grad(log_theta, log_d_p, log_d_m, dat, perc_met: float, weights=None):
-    """(score, d_theta, d_d_p, d_d_m)  (regularized_optimization.py:163-267).  weights: see score."""
-    eng = _weighted_engine(dat, weights)
+def score_and_grad(log_theta, log_d_p, log_d_m, dat, perc_met: float, weights=None, groups=None):
+    """(score, d_theta, d_d_p, d_d_m)  (regularized_optimization.py:163-267).  weights, groups: see score."""
+    eng = _weighted_engine(dat, weights, groups)
     return _result(eng, log_theta, log_d_p, log_d_m, perc_met, True, guard=dat)[0]
 
 
@@ -384,35 +441,48 @@ def _unpack(params, n_total):
             params[n_total * (n_total + 1):])
 
 
-def score_reg(params, dat, perc_met: float, penal: Callable, w_penal: float, weights=None):
-    """regularized_optimization.py:133-160.  weights: see score."""
+def score_reg(params, dat, perc_met: float, penal: Callable, w_penal: float, weights=None, groups=None):
+    """regularized_optimization.py:133-160.  weights, groups: see score."""
     n_total = (np.asarray(dat).shape[1] - 3) // 2 + 1
     th, dp, dm = _unpack(params, n_total)
-    eng = _weighted_engine(dat, weights)
+    eng = _weighted_engine(dat, weights, groups)
     res, (pen, _) = _result(eng, th, dp, dm, perc_met, False, meanwhile=lambda: penal(params, n_total), guard=dat)    # penalty next to the GPU
     return np.array(-res[0] + w_penal * pen)
 
 
-def score_and_grad_reg(params, dat, perc_met: float, penal: Callable, w_penal: float, weights=None):
-    """regularized_optimization.py:270-298.  weights: see score."""
+def score_and_grad_reg(params, dat, perc_met: float, penal: Callable, w_penal: float, weights=None, groups=None):
+    """regularized_optimization.py:270-298.  weights, groups: see score."""
     n_total = (np.asarray(dat).shape[1] - 3) // 2 + 1
     th, dp, dm = _unpack(params, n_total)
-    eng = _weighted_engine(dat, weights)
+    eng = _weighted_engine(dat, weights, groups)
     (sc, d_th, d_d_p, d_d_m), (pen, pen_) = _result(eng, th, dp, dm, perc_met, True, meanwhile=lambda: penal(params, n_total), guard=dat)  # penalty next to the GPU
     grad_vec = np.concatenate((d_th.flatten(), d_d_p, d_d_m))
     return np.array(-sc + w_penal * pen), -grad_vec + w_penal * pen_
 
 
 def learn_mhn(th_init, dp_init, dm_init, dat, perc_met: float, penal: Callable, w_penal: float,
-              opt_iter: int = 1e05, opt_ftol: float = 1e-04, opt_v: bool = True, weights=None):
-    """Infer a metMHN with SciPy's L-BFGS-B (regularized_optimization.py:301-334).  weights: see score."""
+              opt_iter: int = 1e05, opt_ftol: float = 1e-04, opt_v: bool = True, weights=None, groups=None):
+    """Infer a metMHN with SciPy's L-BFGS-B (regularized_optimization.py:301-334).  weights, groups: see score."""
     th_init = np.asarray(th_init, dtype=np.float64)
     n_total = th_init.shape[0]
     start = np.concatenate((th_init.flatten(), np.asarray(dp_init, float), np.asarray(dm_init, float)))
     x = opt.minimize(fun=score_and_grad_reg, jac=True, x0=start, method="L-BFGS-B",
-                     args=(dat, perc_met, penal, w_penal, weights),
+                     args=(dat, perc_met, penal, w_penal, weights, groups),
                      options={"maxiter": int(opt_iter), "disp": opt_v, "ftol": opt_ftol})
     theta = np.array(x.x[:n_total ** 2]).reshape((n_total, n_total))
     d_p = np.array(x.x[n_total ** 2:n_total * (n_total + 1)])
     d_m = np.array(x.x[n_total * (n_total + 1):])
     return theta, d_p, d_m
+
+
+def impute_missing(log_theta, log_d_p, log_d_m, groups):
+    """Posterior of the unobserved entries of a cohort (groups: a RowGroups from Utilityfunctions.expand_missing):
+    (p [len(groups.entries)], lp [rows of the original dat]) with p[k] = P(entry k = 1 | the row's observed entries) - the
+    sum of rho over the completions that set it - and lp the log-likelihood of every original row.  An entry in a column
+    its row's type ignores was not expanded: NaN.  One score-only evaluation (Engine.group_posteriors)."""
+    eng = _weighted_engine(groups.rows, None, groups)
+    lpg, rho = eng.group_posteriors(log_theta, log_d_p, log_d_m)
+    ptr = np.asarray(groups.ptr, dtype=np.int64)
+    p = np.array([float(np.sum(rho[ptr[r] + np.asarray(alts, dtype=np.int64)])) if len(alts) else np.nan
+                  for r, _, alts in groups.entries], dtype=np.float64)
+    return p, lpg
