@@ -479,6 +479,39 @@ int mmhn_order_samples(mmhn_handle h, const double* log_theta, const double* obs
                        int64_t n_pat, int n_cols, int64_t first, int64_t n_samples, uint64_t seed, double* log_evidence,
                        int8_t* orders, double* log_prob, int32_t* status);
 
+/* ---- seeding forecasts from a tumour's genotype ---------------------------------------------
+ * mmhn_seeding_forecasts: the forward question.  A primary tumour holds the mutations of genotypes[r] and has not seeded;
+ * until the seeding (until = 0), or until the seeding or the model's own clock of the first observation, whichever comes
+ * first (until = 1), its chain runs on the supersets y of the genotype - a lattice over the f mutations it does NOT hold:
+ *   lambda_j(y) = exp(theta[j][j] + sum over i in y of theta[j][i])   j not in y
+ *   sigma(y)    = exp(theta[n][n] + sum over i in y of theta[n][i])   the seeding (theta[i][n], i < n, is never read)
+ *   kappa(y)    = until ? exp(sum over i in y of obs1[i]) : 0         the clock
+ *   den = sum of lambda_j + sigma + kappa,  F(genotype) = 1,  F(y) = sum over b of F(y - b) lambda_b(y - b) / den(y - b),
+ *   G = F / den (the expected time spent in y)
+ * One forward sum-product over the lattice, one launch per level over every row of the batch
+ * (metmhn_amd/csrc/forecast.h).  No reference counterpart.  fp64 engines only; independent of mmhn_set_cohort.
+ *   genotypes [n_rows][n_mut]                   int8, 1 = held, 0 = not
+ *   p_seed [n_rows]                             sum G sigma: P(the seeding comes before the clock); 1 for until = 0
+ *   time [n_rows]                               sum G: the expected time until the seeding or the clock (mmhn_order_times' unit)
+ *   before [n_rows][n_mut]                      sum over y without j of G lambda_j: P(mutation j arises before the end);
+ *                                               NaN for a held mutation
+ *   with_seed [n_rows][n_mut]                   sum over y with j of G sigma: P(the seeding comes first and the seeding cell
+ *                                               carries j); NaN for a held mutation
+ *   n_before [n_rows][n_mut + 1]                sum over |y - genotype| = m of G sigma: P(the seeding comes first, after exactly
+ *                                               m new mutations); exactly 0 for m > f
+ *   status [n_rows]: low half MMHN_ORD_OK, MMHN_ORD_INVALID (high half MMHN_ORD_BAD_ENTRY: an entry other than 0 / 1) or
+ *   MMHN_ORD_TOO_LARGE (f > 30, or the row's workspace - 8 B x 2^f and, per 2^14 states, 3 f + 3 doubles of partials -
+ *   does not fit the workspace limit on its own); every output of a row is NaN where its status != 0.
+ * The call fails (return 1) for until = 0 when the seeding rate of the full genotype underflows to 0 (theta[n][n] of
+ * -1e10, as a fit without seeded samples leaves it): the full state would have no exit.  Mutation rates of 0 are fine.
+ * n_rows = 0 is valid.  No atomics: two calls return the same bytes, whatever the batching and the other rows.  Rows are
+ * cut into batches that fit mmhn_set_workspace_limit (allocated once per call).
+ */
+enum { MMHN_ORD_BAD_ENTRY = 8 };     /* mmhn_seeding_forecasts: a genotype entry other than 0 / 1 */
+int mmhn_seeding_forecasts(mmhn_handle h, const double* log_theta, const double* obs1, const int8_t* genotypes,
+                           int64_t n_rows, int until, double* p_seed, double* time, double* before, double* with_seed,
+                           double* n_before, int32_t* status);
+
 /* ---- measurement -------------------------------------------------------------------
  * mmhn_bench_kronvec: `batch` resident copies of a 2^k vector, `iters` back-to-back
  * launches of mmhn_kronvec_batched's launch (diag = 0: y = Q_off p into a NaN-filled y, every tile of every vector,
@@ -509,7 +542,7 @@ typedef struct {
   int32_t comm_rank;  /* this engine's rank in it (ncclCommUserRank), -1: none */
 } mmhn_counters;
 /* ABI version of this header: bumped whenever an exported signature or structure changes (4: mmhn_bench_kronvec has its
- * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions, mmhn_order_samples, mmhn_simulate_pairs, mmhn_order_times and mmhn_order_snapshots were added within version 8, purely additive changes).  A client built against another header must refuse to run:
+ * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions, mmhn_order_samples, mmhn_simulate_pairs, mmhn_order_times, mmhn_order_snapshots and mmhn_seeding_forecasts were added within version 8, purely additive changes).  A client built against another header must refuse to run:
  * mmhn_abi_version() != MMHN_ABI_VERSION (metmhn_amd/_lib.py checks it on load). */
 #define MMHN_ABI_VERSION 8
 int mmhn_abi_version(void);

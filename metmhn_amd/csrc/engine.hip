@@ -3,7 +3,7 @@
 // The rest of the host side lives in headers of this one translation unit: plan.h (the cohort planner, host-only:
 // batches, routes, work lists, offsets), host.h (errors, device arrays, MMHN_* knob readers), comm.h (RCCL),
 // prims.h / orders_host.h / orderpost_host.h (the batching of the order-posterior entry points, opr_rows) /
-// orderprec_host.h / orderpos_host.h / ordertime_host.h / ordersnap_host.h / ordersample_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
+// orderprec_host.h / orderpos_host.h / ordertime_host.h / ordersnap_host.h / ordersample_host.h / forecast_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
 //
 // Pipeline of one evaluation (reference call graph: regularized_optimization.py:163-267 ->
 // likelihood.py:_g_coupled_*, _grad_prim_obs, _grad_met_obs), run batch by batch with every
@@ -1257,6 +1257,7 @@ struct Engine : EngineBase {
 #include "ordertime_host.h"
 #include "ordersnap_host.h"
 #include "ordersample_host.h"
+#include "forecast_host.h"
 #include "sampler_host.h"
 #include "bench.h"
 
@@ -1851,6 +1852,21 @@ int mmhn_order_samples(mmhn_handle h, const double* log_theta, const double* obs
   REQUIRE(h->dtype == MMHN_F64, "order samples need an fp64 engine (MMHN_F64)");
   order_samples(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, first, n_samples, seed,
                 log_evidence, orders, log_prob, status);
+  API_END
+}
+
+// ---- seeding forecasts from a tumour's genotype: what comes before the seeding, how likely it is before the next look
+int mmhn_seeding_forecasts(mmhn_handle h, const double* log_theta, const double* obs1, const int8_t* genotypes, int64_t n_rows,
+                           int until, double* p_seed, double* time, double* before, double* with_seed, double* n_before,
+                           int32_t* status) {
+  API_BEGIN
+  GUARD(h);
+  REQUIRE(n_rows >= 0 && n_rows < ((int64_t)1 << 31), "n_rows out of range");
+  REQUIRE(log_theta && obs1, "null pointer");
+  REQUIRE((genotypes && p_seed && time && before && with_seed && n_before && status) || n_rows == 0, "null pointer");
+  REQUIRE(h->dtype == MMHN_F64, "seeding forecasts need an fp64 engine (MMHN_F64)");
+  seeding_forecasts(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, genotypes, n_rows, until, p_seed, time, before,
+                    with_seed, n_before, status);
   API_END
 }
 

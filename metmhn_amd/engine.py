@@ -603,6 +603,29 @@ class Engine:
                                                status.ctypes.data_as(_lib.i32p)))
         return le, orders, log_prob, status
 
+    # ---- seeding forecasts
+    def seeding_forecasts(self, log_theta, obs1, genotypes, until="seeding"):
+        """MetMHN.seeding_forecast of every row of int8 `genotypes` [R, n] (1 = held) in one call (mmhn_seeding_forecasts),
+        until "seeding" or "observation": float64 p_seed [R], time [R], before [R, n], with_seed [R, n] (NaN for a held
+        mutation), n_before [R, n+1] (0 past the row's free mutations), int32 status [R] (low half 0 ok, 2 an entry other than
+        0 / 1 - reason code 8 in status >> 16 -, 3 more than 30 free mutations or a lattice larger than the workspace; NaN
+        outputs wherever it is not 0)."""
+        if until not in ("seeding", "observation"):
+            raise ValueError("until must be 'seeding' or 'observation'")
+        lt, ltp = self._theta(log_theta); a, ap = self._rates(obs1, "obs1")
+        g = np.ascontiguousarray(np.asarray(genotypes).astype(np.int8))
+        if g.ndim != 2 or g.shape[1] != self.n:
+            raise ValueError(f"genotypes must be a 2-D array [R, {self.n}]")
+        R = g.shape[0]
+        p_seed, time = np.empty(R), np.empty(R)                 # (the library fills them with NaN first)
+        before, with_seed, n_before = np.empty((R, self.n)), np.empty((R, self.n)), np.empty((R, self.N))
+        status = np.zeros(R, dtype=np.int32)
+        _lib.check(self.lib.mmhn_seeding_forecasts(
+            self.h, ltp, ap, g.ctypes.data_as(i8p), R, 0 if until == "seeding" else 1, p_seed.ctypes.data_as(f64p),
+            time.ctypes.data_as(f64p), before.ctypes.data_as(f64p), with_seed.ctypes.data_as(f64p),
+            n_before.ctypes.data_as(f64p), status.ctypes.data_as(_lib.i32p)))
+        return p_seed, time, before, with_seed, n_before, status
+
     # ---- measurement
     def bench_kronvec(self, log_theta, state, batch, iters, transpose=False, jacobi=False, tiles=False):
         """ms per launch of mmhn_kronvec_batched's launch (or the fused Jacobi step); tiles=True also returns

@@ -321,6 +321,33 @@ class OrderSamples(SimpleNamespace):
         return out
 
 
+class SeedingForecast(SimpleNamespace):
+    """What lies ahead of a primary tumour that holds a genotype and has not seeded, until the seeding (or the model's own
+    clock of the first observation, whichever comes first): `p_seed` = P(the seeding comes before the clock), 1 until the
+    seeding; `time` = the expected time until then (order_time's unit); `before[j]` = P(mutation j arises before then);
+    `with_seed[j]` = P(the seeding comes first and the seeding cell carries j) - both [n], NaN for a mutation the genotype
+    holds; `n_before[m]` = P(the seeding comes first, after exactly m new mutations) [n+1]; `next[j]` = P(the next event is
+    mutation j), next[n] the seeding [n+1], NaN for a held mutation.  No reference counterpart."""
+
+    def __init__(self, p_seed, time, before, with_seed, n_before, next):
+        super().__init__(p_seed=p_seed, time=time, before=before, with_seed=with_seed, n_before=n_before, next=next)
+
+
+class SeedingForecasts(SeedingForecast):
+    """SeedingForecast of R genotypes: every field with a leading axis over the rows."""
+
+    def expected_new_events(self) -> np.ndarray:
+        """The expected number of new mutations before the seeding (or the clock) [R]: the sum of `before` over the free
+        mutations."""
+        return np.nansum(self.before, axis=1)
+
+
+_FORECAST_UNTIL = ("seeding", "observation")
+_FORECAST_HOST_MAX = 24          # free mutations the host definition takes on: f x 2^f doubles of rates
+_NO_SEEDING_EXIT = ("the seeding rate of the full genotype underflows to 0 (a theta[n, n] of -1e10, as a fit without seeded "
+                    "samples leaves it?): until='seeding' the full state would have no exit; use until='observation'")
+
+
 class MetMHN:
     """The metastasis MHN with its two observation-rate vectors (model.py:175-211)."""
 
@@ -688,6 +715,120 @@ class MetMHN:
             ("orders", "log_prob"), ((n_samples, 2 * self.n + 1), (n_samples,)), dat, backend,
             dtypes=(np.int8, np.float64), with_row=True)
         return OrderSamples(*out)
+
+    # ------------------------------------------------------------------ seeding forecasts
+    def _forecast_checks(self, genotypes, until: str) -> np.ndarray:
+        """The genotypes as an int array [R, n]; the errors of seeding_forecast / seeding_forecasts."""
+        if until not in _FORECAST_UNTIL:
+            raise ValueError("until must be 'seeding' or 'observation'")
+        g = np.asarray(genotypes)
+        if g.ndim != 2 or g.shape[1] != self.n:
+            raise ValueError(f"genotypes must have shape [R, {self.n}]")
+        bad = np.flatnonzero(~np.isin(g, (0, 1)).all(axis=1))
+        if bad.size:
+            raise ValueError(f"row {int(bad[0])}: a genotype entry is neither 0 nor 1")
+        th = self._pt_log_theta
+        if until == "seeding" and np.exp(th[self.n, self.n] + th[self.n, :self.n].sum()) == 0.0:
+            raise ValueError(_NO_SEEDING_EXIT)
+        return g.astype(np.int64)
+
+    def _forecast_next(self, g: np.ndarray, until: str) -> np.ndarray:
+        """next [R, n+1] of the genotypes g [R, n]: the rates out of the genotype over their sum with the clock."""
+        th, n = self._pt_log_theta, self.n
+        rate = np.exp(np.diag(th)[None, :] + g @ th[:, :n].T)                      # [R, n+1]: lambda_j(x), sigma(x)
+        rate[:, :n] = np.where(g == 1, 0.0, rate[:, :n])
+        kap = np.exp(g @ self.obs1[:n]) if until == "observation" else 0.0
+        out = rate / (rate.sum(axis=1) + kap)[:, None]
+        out[:, :n] = np.where(g == 1, np.nan, out[:, :n])
+        return out
+
+    def seeding_forecast(self, genotype, until: str = "seeding") -> "SeedingForecast":
+        """The forward question: a primary tumour holds the mutations of `genotype` (n entries 0 / 1) and has not seeded -
+        what happens until the seeding (until="seeding"), or until the seeding or the first observation on the model's own
+        clock, whichever comes first (until="observation")?  See SeedingForecast for the answers.
+
+        Exact: before the seeding the chain runs on the supersets y of the genotype, a lattice over the f mutations it does
+        not hold, with rates lambda_j(y) = exp(theta_jj + sum_{i in y} theta_ji) (j not in y), sigma(y) the same for the
+        seeding (the primary tumour's theta: theta[:n, n] is not read) and kappa(y) = exp(sum_{i in y} obs1_i) for the clock
+        (0 until the seeding); den = sum lambda + sigma + kappa.  F(genotype) = 1, F(y) = sum_b F(y - b) lambda_b(y - b) /
+        den(y - b) is the probability of reaching y, G = F / den the expected time spent there, and every answer is a sum of
+        G times a rate.  This is the host definition, level by level in NumPy (f <= 24); seeding_forecasts has the device."""
+        g = self._forecast_checks(np.asarray(genotype)[None, :] if np.ndim(genotype) == 1 else genotype, until)
+        if g.shape[0] != 1:
+            raise ValueError("seeding_forecast takes one genotype; seeding_forecasts takes many")
+        g = g[0]
+        th, n = self._pt_log_theta, self.n
+        held = [i for i in range(n) if g[i]]
+        free = [i for i in range(n) if not g[i]]
+        f = len(free)
+        if f > _FORECAST_HOST_MAX:
+            raise ValueError(f"{f} free mutations: the host definition stops at {_FORECAST_HOST_MAX} "
+                             f"(a lattice of 2^{f} states x {f} rates); use seeding_forecasts, backend='device'")
+        idx = np.arange(1 << f)
+        level = _subset_sums(np.ones(f)).astype(np.int64)
+        # rate of j in the state y (its own bit does not count: rows of j-free states are the only ones read)
+        lam = [np.exp(th[j, j] + th[j, held].sum() + _subset_sums(th[j, free])) for j in free]
+        sig = np.exp(th[n, n] + th[n, held].sum() + _subset_sums(th[n, free]))
+        kap = np.exp(self.obs1[held].sum() + _subset_sums(self.obs1[free])) if until == "observation" else np.zeros(1 << f)
+        out = [(idx >> a & 1) == 0 for a in range(f)]
+        den = np.zeros(1 << f)
+        for a in range(f):
+            den += np.where(out[a], lam[a], 0.0)
+        den = den + sig + kap
+        F, G = np.zeros(1 << f), np.zeros(1 << f)
+        F[0] = 1.0
+        for lev in range(f + 1):
+            ys = idx[level == lev]
+            for a in range(f if lev else 0):
+                to = ys[(ys >> a & 1) == 1]
+                frm = to ^ (1 << a)
+                F[to] += G[frm] * lam[a][frm]
+            G[ys] = F[ys] / den[ys]
+        gs = G * sig
+        before, with_seed = np.full(n, np.nan), np.full(n, np.nan)
+        for a, j in enumerate(free):
+            before[j] = float((G * lam[a])[out[a]].sum())
+            with_seed[j] = float(gs[~out[a]].sum())
+        n_before = np.zeros(n + 1)
+        for m in range(f + 1):
+            n_before[m] = float(gs[level == m].sum())
+        return SeedingForecast(float(gs.sum()), float(G.sum()), before, with_seed, n_before,
+                               self._forecast_next(g[None, :], until)[0])
+
+    def seeding_forecasts(self, genotypes, until: str = "seeding", backend: str = "device") -> "SeedingForecasts":
+        """seeding_forecast of every row of `genotypes` [R, n] (of a cohort `dat`: dat[:, 0:2*n:2], the primary tumours'
+        columns): arrays p_seed [R], time [R], before [R, n], with_seed [R, n], n_before [R, n+1], next [R, n+1].
+        Identical genotypes are solved once.
+
+        backend="device": every distinct genotype in one call of the HIP library (mmhn_seeding_forecasts), a lattice of
+        8 B x 2^f per row spread over the whole GPU, level by level.  A row that does not fit (more than 30 free mutations,
+        or a lattice larger than the workspace limit) raises a ValueError that names the row and the bytes it needs: there
+        is no host fallback, a host lattice of 2^28 states is none.  backend="host": seeding_forecast row by row.
+        An entry other than 0 / 1 raises ValueError("row i: ...")."""
+        if backend not in ("device", "host"):
+            raise ValueError("backend must be 'device' or 'host'")
+        g = self._forecast_checks(genotypes, until)
+        R, n = g.shape[0], self.n
+        uniq, first, inverse = np.unique(g, axis=0, return_index=True, return_inverse=True)
+        inverse = np.asarray(inverse).reshape(-1)
+        if backend == "host":
+            rows = [self.seeding_forecast(u, until) for u in uniq]
+            cols = [np.array([getattr(r, name) for r in rows], dtype=np.float64).reshape((len(rows),) + shape)
+                    for name, shape in (("p_seed", ()), ("time", ()), ("before", (n,)), ("with_seed", (n,)),
+                                        ("n_before", (n + 1,)))]
+        else:
+            from .jx import engine
+            *cols, status = engine(n).seeding_forecasts(self.log_theta, self.obs1, uniq.astype(np.int8), until)
+            bad = np.flatnonzero(status != 0)
+            if bad.size:
+                u = int(bad[0])
+                i, f = int(first[u]), int(n - uniq[u].sum())
+                if (int(status[u]) & 0xFFFF) == 2:
+                    raise ValueError(f"row {i}: a genotype entry is neither 0 nor 1")
+                raise ValueError(f"row {i}: {f} free mutations, a lattice of 2^{f} states that needs {8 << f} bytes "
+                                 "(at most 30 free mutations, and the lattice has to fit the workspace limit); "
+                                 "there is no host fallback")
+        return SeedingForecasts(*(c[inverse] for c in cols), self._forecast_next(g, until))
 
     def likelihood(self, order, met_status: str, first_obs: str = None) -> float:
         """model.py:295-376: probability of exactly this order of events being what is observed."""

@@ -435,6 +435,25 @@ def met_status_posterior(log_theta, log_d_p, log_d_m, dat):
     return out
 
 
+def seeding_forecast(log_theta, log_d_p, log_d_m, dat, until: str = "observation", backend: str = "device"):
+    """What lies ahead of the primary tumour of every row of `dat` that has one of its own (types 0, 1 and 4), given that it
+    has not seeded yet: (forecasts, seeded).  forecasts: MetMHN.seeding_forecasts of the rows' PT genotypes
+    dat[:, 0:2*n:2] with obs1 = log_d_p, a model.SeedingForecasts whose rows of types 2 and 3 are NaN throughout; seeded
+    [n_pat]: met_status_posterior's probability that the seeding has ALREADY happened - the forecast is conditional on
+    "not yet", so P(seeded by the next look) = seeded + (1 - seeded) p_seed."""
+    from .model import MetMHN, SeedingForecasts
+    arr = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
+    n = (arr.shape[1] - 3) // 2
+    pick = np.isin(arr[:, -1], (0, 1, 4))
+    shapes = {"p_seed": (), "time": (), "before": (n,), "with_seed": (n,), "n_before": (n + 1,), "next": (n + 1,)}
+    out = {name: np.full((arr.shape[0],) + shape, np.nan) for name, shape in shapes.items()}
+    if pick.any():
+        got = MetMHN(log_theta, log_d_p, log_d_m).seeding_forecasts(arr[pick][:, 0:2 * n:2], until, backend)
+        for name in shapes:
+            out[name][pick] = getattr(got, name)
+    return SeedingForecasts(**out), met_status_posterior(log_theta, log_d_p, log_d_m, dat)
+
+
 def _unpack(params, n_total):
     params = np.asarray(params, dtype=np.float64)
     return (params[0:n_total ** 2].reshape((n_total, n_total)), params[n_total ** 2:n_total * (n_total + 1)],
