@@ -75,7 +75,7 @@ double bench_kronvec(Engine<T>& E, const Desc& d0, long long batch, int iters, b
   HIPCHECK(hipMemsetAsync(b.p, 0xFF, (size_t)(batch * V) * sizeof(T), E.stream));   // y starts as NaNs: the launch writes all of it
   if (jacobi) {
     c.alloc((size_t)(batch * V)); r.alloc((size_t)(batch * V));
-    E.launch_diag(kb.dd.p, kb.map.p, kb.ntiles, nullptr, c.p, nullptr, KD_LIDG);
+    E.launch_diag(E.main, kb.dd.p, kb.map.p, kb.ntiles, nullptr, c.p, nullptr, KD_LIDG);
     HIPCHECK(hipMemcpyAsync(r.p, a.p, (size_t)(batch * V) * sizeof(T), hipMemcpyDeviceToDevice, E.stream));
   }
   // the timed launch is exactly the one mmhn_kronvec_batched issues (plain product), or the fused Jacobi step

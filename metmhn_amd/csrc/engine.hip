@@ -1,7 +1,9 @@
 // Host side of the metMHN engine: the engine's state, its kernel launches, the cohort evaluation and the
-// C ABI of include/metmhn_amd.h.  One engine = one GPU, one HIP stream.
+// C ABI of include/metmhn_amd.h.  One engine = one GPU; one main lane (host.h: Lane - a HIP stream with its cooperative flag
+// set and its fork / join events) and three side lanes that an evaluation forks off it.
 // The rest of the host side lives in headers of this one translation unit: plan.h (the cohort planner, host-only:
-// batches, routes, work lists, offsets), host.h (errors, device arrays, MMHN_* knob readers), comm.h (RCCL),
+// batches, routes, work lists, offsets), host.h (errors, device arrays, lanes, MMHN_* knob readers), comm.h (RCCL),
+// rowmix_host.h (row weights and row groups: their checks, device copies and the launches of the group kernels),
 // prims.h / orders_host.h / orderpost_host.h (the batching of the order-posterior entry points, opr_rows) /
 // orderprec_host.h / orderpos_host.h / ordertime_host.h / ordersnap_host.h / ordersample_host.h / forecast_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
 //
@@ -104,9 +106,14 @@ struct EngineBase {
   virtual ~EngineBase() = default;
   int dtype = 0;
   int device = 0;
-  hipStream_t stream = nullptr;
+  hipStream_t stream = nullptr;       // the main lane's (Engine::main.s): set when the engine is created, never reassigned
   Config cfg;
 };
+
+template <typename T> struct Engine;
+// rowmix_host.h: what the engine itself calls of it
+template <typename T> void clear_row_groups(Engine<T>& E);
+template <typename T> void launch_mix(Engine<T>& E, const Lane& L);
 
 // one list of problems with its tile maps (cl / dcl: its cooperative work lists, forward / transposed, or nullptr)
 template <typename T>
@@ -140,7 +147,9 @@ struct Engine : EngineBase {
   std::vector<int8_t> dat;
   long long n_pat = 0;
   int n_cols = 0;
-  double n_em = 0;
+  // the three counts of the objective: sum of w [seeding = 1], sum of w, sum of w [type 4], taken on the host in row order -
+  // plain: w = 1 (the integer counts), weighted: the row weights, grouped: the weights of the row groups
+  struct Counts { double em = 0, pat = 0, unknown = 0; } plain, weighted, grouped;
   std::vector<Batch> batches;
   std::vector<BatchDev> dev;
   // ---- workspace (sized for the largest batch)
@@ -157,11 +166,10 @@ struct Engine : EngineBase {
   DevArr<double> resp;                // [n_pat] by cohort row: P(seeded | genotype) of the rows of unknown status (dat type 4), written
                                       // where their score is formed; NaN everywhere else (filled once, when the cohort is set)
   long long n_unknown = 0;            // rows of dat type 4
-  // ---- row weights (mmhn_set_row_weights): by cohort row, empty = none; their three sums, taken on the host in row order
+  // ---- row weights (mmhn_set_row_weights, rowmix_host.h): by cohort row, empty = none
   std::vector<double> row_w;
-  double w_em = 0, w_pat = 0, w_unknown = 0;
-  // ---- row groups (mmhn_set_row_groups, rowmix.h): the group lists and weights as given (grp_ptr empty = none), the
-  // transposed lists and the per-evaluation arrays on the device, the three group-weighted counts
+  // ---- row groups (mmhn_set_row_groups, rowmix.h, rowmix_host.h): the group lists and weights as given (grp_ptr empty =
+  // none), the transposed lists and the per-evaluation arrays on the device
   std::vector<long long> grp_ptr;
   std::vector<int> grp_rows;
   std::vector<double> grp_w;
@@ -170,24 +178,19 @@ struct Engine : EngineBase {
     DevArr<int> grows, mgrp;
     DevArr<double> gw, lpc, lpg, omega, lambda, rho;
   } gd;
-  double g_em = 0, g_pat = 0, g_unknown = 0;
   bool want_rho = false;              // mmhn_group_posteriors: k_group_lse also writes rho
   DevArr<JLink<T>> links;
   double* h_abi = nullptr;            // pinned landing buffer of the result download
   double* h_abi_dev = nullptr;        // device view of it
-  // ---- streams / events
-  hipStream_t side[3] = {};               // side streams: [0], [1] of the small-space path, [2] of the staged own-problem patients
-  hipEvent_t ev_fork[3] = {}, ev_join[3] = {};
-  // small-space launches of an evaluation in flight on side[0] / side[1] (small_classes, small_join); fork_recorded: the
-  // point of the main stream they wait for was recorded ahead of time (small_fork)
-  bool small_forked[2] = {false, false}, fork_recorded[2] = {false, false};
+  // ---- lanes (host.h): main carries the joint path; side[0], side[1] the small-space launches (small_classes), side[2] the
+  // staged own-problem patients, whose cooperative launches use the second flag set
+  Lane main, side[3];
   // ---- cooperative launches (tsolve.h): queue heads + abort word, the flags of the tiles (value = epoch of the launch that
   // finished the tile), the pinned host copy of the abort word
   DevArr<CoopCtl> coop_ctl;
-  DevArr<unsigned> coop_flags[2];   // one set per lane: launches of two streams may be in flight together
+  DevArr<unsigned> coop_flags[2];   // one set per lane that issues such launches (Lane::flags): two may be in flight together
   unsigned coop_epoch = 0;
   int coop_slot = 0;
-  int cur_lane = 0;                 // lane of the launches being issued (1: a side stream)
   unsigned* h_abort = nullptr;
   unsigned* h_abort_dev = nullptr;
   bool coop_used = false;           // an evaluation issued a cooperative launch since the last check_abort
@@ -226,6 +229,8 @@ struct Engine : EngineBase {
     REQUIRE(n_mut >= 1 && n_mut < MAXN, "n_mut must be in [1, 31]");
     DevGuard guard(device);
     HIPCHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    main.s = stream;
+    main.flags = 0;
     d_par.alloc(NPSET);
     HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&h_par), NPSET * sizeof(Params<T>), hipHostMallocDefault));
     HIPCHECK(hipHostGetDevicePointer(&h_par_dev, h_par, 0));
@@ -271,19 +276,20 @@ struct Engine : EngineBase {
     HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&h_abort), 64, hipHostMallocDefault));
     HIPCHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h_abort_dev), h_abort, 0));
     *h_abort = 0u;
-    for (int i = 0; i < 3; ++i) {
-      HIPCHECK(hipStreamCreateWithFlags(&side[i], hipStreamNonBlocking));
-      HIPCHECK(hipEventCreateWithFlags(&ev_fork[i], hipEventDisableTiming));
-      HIPCHECK(hipEventCreateWithFlags(&ev_join[i], hipEventDisableTiming));
+    for (Lane& l : side) {
+      HIPCHECK(hipStreamCreateWithFlags(&l.s, hipStreamNonBlocking));
+      HIPCHECK(hipEventCreateWithFlags(&l.ev_fork, hipEventDisableTiming));
+      HIPCHECK(hipEventCreateWithFlags(&l.ev_join, hipEventDisableTiming));
     }
+    side[2].flags = 1;
   }
   ~Engine() override {                       // runs under the DevGuard of mmhn_destroy
     comm_destroy();
     for (auto& e : ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    for (int i = 0; i < 3; ++i) {
-      if (ev_join[i]) (void)hipEventDestroy(ev_join[i]);
-      if (ev_fork[i]) (void)hipEventDestroy(ev_fork[i]);
-      if (side[i]) (void)hipStreamDestroy(side[i]);
+    for (Lane& l : side) {
+      if (l.ev_join) (void)hipEventDestroy(l.ev_join);
+      if (l.ev_fork) (void)hipEventDestroy(l.ev_fork);
+      if (l.s) (void)hipStreamDestroy(l.s);
     }
     if (h_par) (void)hipHostFree(h_par);
     if (h_abi) (void)hipHostFree(h_abi);
@@ -335,48 +341,41 @@ struct Engine : EngineBase {
   // joint: a workgroup per table of a problem (three class tables + the rate tables, k_prep) when the launch is short
   // enough for its length to be one workgroup's chain; large cohorts keep one workgroup per problem
   // (tables of more than 2^13 entries - k = 25 - are also cut into parts of 2^13: grid.y = 4 * parts)
-  void prep(const Desc* descs, int nprob, T* tab, bool joint = false, int maxkc = 0) {
+  // plist (optional): the problems to prepare, nprob of them (k_prep)
+  void prep(const Lane& L, const Desc* descs, int nprob, T* tab, bool joint = false, int maxkc = 0, const int* plist = nullptr) {
     if (nprob == 0) return;
     // SPLIT: a table of more than 2^9 entries is dealt over several workgroups (the launch is the head of every evaluation
     // of a short cohort; at most 32 parts: the workgroups of the shorter tables of the launch exit at once, but they are launched)
     const int parts = maxkc > 9 ? 1 << std::min(maxkc - 9, 5) : 1;
-    if (joint && nprob <= cfg.plan.prep_split_max) hipLaunchKernelGGL((k_prep<T, true>), dim3(nprob, 4 * parts), dim3(BLOCK), prep_lds<T>(N), stream, descs, d_par.p, tab);
-    else if (nprob >= 256) hipLaunchKernelGGL((k_prep<T, false, 1024>), dim3(nprob), dim3(1024), prep_lds<T>(N), stream, descs, d_par.p, tab);
-    else hipLaunchKernelGGL((k_prep<T, false>), dim3(nprob), dim3(BLOCK), prep_lds<T>(N), stream, descs, d_par.p, tab);
+    if (joint && nprob <= cfg.plan.prep_split_max) hipLaunchKernelGGL((k_prep<T, true>), dim3(nprob, 4 * parts), dim3(BLOCK), prep_lds<T>(N), L.s, descs, d_par.p, tab, plist);
+    else if (nprob >= 256) hipLaunchKernelGGL((k_prep<T, false, 1024>), dim3(nprob), dim3(1024), prep_lds<T>(N), L.s, descs, d_par.p, tab, plist);
+    else hipLaunchKernelGGL((k_prep<T, false>), dim3(nprob), dim3(BLOCK), prep_lds<T>(N), L.s, descs, d_par.p, tab, plist);
     HIPCHECK(hipGetLastError());
   }
 
-  void launch_sweep(bool tr, const Desc* descs, const int2* map, int ntiles, int maxk, const T* p, T* y,
+  void launch_sweep(const Lane& L, bool tr, const Desc* descs, const int2* map, int ntiles, int maxk, const T* p, T* y,
                     const T* lidg, const T* rhs, int rhs_mode, const T* scal, double alg_bytes, const T* tab) {
     if (ntiles == 0) return;
     const size_t lds = sweep_lds(maxk);
     auto launch = [&]() {
-      if (tr)
-        hipLaunchKernelGGL((k_sweep<T, true>), dim3(ntiles), dim3(KSB), lds, stream, descs, map, d_par.p, p, y,
+      with_flags([&](auto tr_) {
+        hipLaunchKernelGGL((k_sweep<T, tr_()>), dim3(ntiles), dim3(KSB), lds, L.s, descs, map, d_par.p, p, y,
                            lidg, rhs, rhs_mode, scal, std::max(maxk, 1), tab);
-      else
-        hipLaunchKernelGGL((k_sweep<T, false>), dim3(ntiles), dim3(KSB), lds, stream, descs, map, d_par.p, p, y,
-                           lidg, rhs, rhs_mode, scal, std::max(maxk, 1), tab);
+      }, tr);
     };
-    if (alg_bytes > 0) { timed(MMHN_K_OTHER_SOLVE, alg_bytes, launch); return; }   // (a launch without algorithmic bytes is never timed)
+    if (alg_bytes > 0) { timed(L, MMHN_K_OTHER_SOLVE, alg_bytes, launch); return; }   // (a launch without algorithmic bytes is never timed)
     launch();
     HIPCHECK(hipGetLastError());
   }
   // plain product on full tiles of multi-tile spaces (k_kv); hxt from k_hx for the same map
   // zmap: see k_kv; lidg / rhs: fused Jacobi step y = lidg * (Q_off p + rhs) over the same tile list
-  void launch_kv(bool tr, const Desc* descs, const int2* map, int ntiles, int maxk, const T* p, T* y, const T* tab, const T* hxt,
+  void launch_kv(const Lane& L, bool tr, const Desc* descs, const int2* map, int ntiles, int maxk, const T* p, T* y, const T* tab, const T* hxt,
                  const int* zmap = nullptr, const T* lidg = nullptr, const T* rhs = nullptr) {
     if (ntiles == 0) return;
     const size_t lds = DESC_PAD + ((size_t)(1 << TB) + 2 * (size_t)maxk * 64 + 32) * sizeof(T);
-#define KV_ARGS dim3(ntiles), dim3(KSB), lds, stream, descs, map, ntiles, p, y, tab, hxt, maxk, zmap, lidg, rhs
-    if (lidg) {
-      if (tr) hipLaunchKernelGGL((k_kv<T, true, 1, true>), KV_ARGS);
-      else hipLaunchKernelGGL((k_kv<T, false, 1, true>), KV_ARGS);
-    } else {
-      if (tr) hipLaunchKernelGGL((k_kv<T, true, 1, false>), KV_ARGS);
-      else hipLaunchKernelGGL((k_kv<T, false, 1, false>), KV_ARGS);
-    }
-#undef KV_ARGS
+    with_flags([&](auto tr_, auto jac) {
+      hipLaunchKernelGGL((k_kv<T, tr_(), 1, jac()>), dim3(ntiles), dim3(KSB), lds, L.s, descs, map, ntiles, p, y, tab, hxt, maxk, zmap, lidg, rhs);
+    }, tr, lidg != nullptr);
     HIPCHECK(hipGetLastError());
   }
   void collect_events() {
@@ -393,21 +392,21 @@ struct Engine : EngineBase {
     ev_slot.clear();
   }
 
-  void launch_diag(const Desc* descs, const int2* map, int ntiles, const T* p, T* outp, const T* dvec, int what,
+  void launch_diag(const Lane& L, const Desc* descs, const int2* map, int ntiles, const T* p, T* outp, const T* dvec, int what,
                    int pbit = -1) {
     if (ntiles == 0) return;
     const size_t lds = DESC_PAD + ((size_t)4 * N * 64 + 256) * sizeof(T);
     if (ntiles >= 256)
-      hipLaunchKernelGGL((k_diag<T, 1024>), dim3(ntiles), dim3(1024), lds, stream, descs, map, d_par.p, p, outp, dvec, what, N, pbit);
+      hipLaunchKernelGGL((k_diag<T, 1024>), dim3(ntiles), dim3(1024), lds, L.s, descs, map, d_par.p, p, outp, dvec, what, N, pbit);
     else
-      hipLaunchKernelGGL((k_diag<T>), dim3(ntiles), dim3(BLOCK), lds, stream, descs, map, d_par.p, p, outp, dvec,
+      hipLaunchKernelGGL((k_diag<T>), dim3(ntiles), dim3(BLOCK), lds, L.s, descs, map, d_par.p, p, outp, dvec,
                          what, N, pbit);
     HIPCHECK(hipGetLastError());
   }
   // dj != nullptr (joint kinds): one extra row per problem with the observation-rate gradient
   // partial rows of the subset chunks are added up: G (and dj) must be zero on entry
   // kind < 0: the work list holds the three joint kinds (kind in bits 24+ of the chunk field), G matrices gstride apart
-  void launch_grad_rows(const Desc* descs, int nprob, int maxk, const T* A, const T* p, const T* q, T* G, int kind,
+  void launch_grad_rows(const Lane& L, const Desc* descs, int nprob, int maxk, const T* A, const T* p, const T* q, T* G, int kind,
                         const DevArr<int2>& chunks, T* dj = nullptr, long long gstride = 0) {
     if (nprob == 0 || chunks.n == 0) return;
     (void)maxk;
@@ -416,27 +415,28 @@ struct Engine : EngineBase {
       // long launches: one row (wave) per workgroup - no barrier, nothing shared but the class-bit list (measured on the bench cohort,
       // rows per workgroup 1 / 2 / 4 / 8 / 12: the step minus its big kernels 4.08 / 4.12 / 4.16 / 4.45 / 4.62 ms)
       const size_t lds1 = ((size_t)192 + 32) * sizeof(T);
-      hipLaunchKernelGGL((k_grad_rows<T, 1>), dim3((unsigned)chunks.n, rows), dim3(64), lds1, stream,
+      hipLaunchKernelGGL((k_grad_rows<T, 1>), dim3((unsigned)chunks.n, rows), dim3(64), lds1, L.s,
                          descs, d_par.p, A, p, q, G, kind, dj, chunks.p, nprob, gstride);
       HIPCHECK(hipGetLastError());
       return;
     }
     const size_t lds = ((size_t)WAVES * 192 + WAVES * 32) * sizeof(T);
-    hipLaunchKernelGGL((k_grad_rows<T>), dim3((unsigned)chunks.n, (rows + WAVES - 1) / WAVES), dim3(BLOCK), lds, stream,
+    hipLaunchKernelGGL((k_grad_rows<T>), dim3((unsigned)chunks.n, (rows + WAVES - 1) / WAVES), dim3(BLOCK), lds, L.s,
                        descs, d_par.p, A, p, q, G, kind, dj, chunks.p, nprob, gstride);
     HIPCHECK(hipGetLastError());
   }
-  void zero(T* p, long long count) {
-    if (count > 0) HIPCHECK(hipMemsetAsync(p, 0, (size_t)count * sizeof(T), stream));
+  void zero(const Lane& L, T* p, long long count) {
+    if (count > 0) HIPCHECK(hipMemsetAsync(p, 0, (size_t)count * sizeof(T), L.s));
   }
   // MMHN_POISON=1 (tests): the result buffers of the api_* paths start as NaNs, filled as soon as they are allocated and
   // before the path's own clearing, so an element that no launch (or memset) writes shows in the output
-  void poison_fill(T* p, long long count) {
-    if (cfg.poison && count > 0) HIPCHECK(hipMemsetAsync(p, 0xFF, (size_t)count * sizeof(T), stream));
+  void poison_fill(const Lane& L, T* p, long long count) {
+    if (cfg.poison && count > 0) HIPCHECK(hipMemsetAsync(p, 0xFF, (size_t)count * sizeof(T), L.s));
   }
-  // timed launch helper shared by the two solvers
+  // timed launch helper shared by the two solvers: the events are recorded on the lane of the launch (they are not
+  // created with hipEventDisableTiming - evaluate() keeps a timed batch on the main lane)
   template <typename F>
-  void timed(int slot, double alg_bytes, F&& launch) {
+  void timed(const Lane& L, int slot, double alg_bytes, F&& launch) {
     if (!time_kernels) {
       launch();
       HIPCHECK(hipGetLastError());
@@ -452,10 +452,10 @@ struct Engine : EngineBase {
     ++ev_used;
     ev_bytes.push_back(alg_bytes);
     ev_slot.push_back(slot);
-    HIPCHECK(hipEventRecord(e0, stream));
+    HIPCHECK(hipEventRecord(e0, L.s));
     launch();
     HIPCHECK(hipGetLastError());
-    HIPCHECK(hipEventRecord(e1, stream));
+    HIPCHECK(hipEventRecord(e1, L.s));
   }
 
   // k_psolve2 (one workgroup per patient, all-seeded-tile launches)
@@ -463,7 +463,7 @@ struct Engine : EngineBase {
     return DESC_PAD + ((size_t)(1 << TB) + (size_t)((1 << TB) / TSB) + 3 * (size_t)maxk * 64 + (size_t)maxk * maxk + maxk) * sizeof(T) + 400 * sizeof(uint32_t) + (size_t)TSB * sizeof(uint16_t);
   }
   // the joint solves of a batch, every problem on its route (Batch::route)
-  void psolve(bool tr, const Batch& b, T* y, int rhs_mode) {
+  void psolve(const Lane& L, bool tr, const Batch& b, T* y, int rhs_mode) {
     const int nJ = (int)b.dJ.size();
     if (nJ == 0) return;
     const BatchDev& db = dev[b.id];
@@ -473,11 +473,11 @@ struct Engine : EngineBase {
       double bytes = 0;
       for (const WDesc& w : b.wd) bytes += 0.5 * (double)(1ll << b.dJ[w.prob].k) * sizeof(T);
       T* yw = b.wdirect ? y : (tr ? qM.p : piM.p);
-      timed(tr ? MMHN_K_PSOLVE_ADJ : MMHN_K_PSOLVE_FWD, bytes, [&]() {
+      timed(L, tr ? MMHN_K_PSOLVE_ADJ : MMHN_K_PSOLVE_FWD, bytes, [&]() {
         const int nch = (int)b.wchains.size();
         const dim3 g((unsigned)std::min(nch, cfg.plan.wsolve_wgs > 0 ? cfg.plan.wsolve_wgs : cfg.plan.n_cu)), bk(WROWS);
         const size_t lds = wsolve_lds<T>();
-#define WS_ARGS g, bk, lds, stream, db.dJ.p, db.wd.p, db.wchains.p, nch, yw, tabJ.p, links.p, qS.p
+#define WS_ARGS g, bk, lds, L.s, db.dJ.p, db.wd.p, db.wchains.p, nch, yw, tabJ.p, links.p, qS.p
         // (a batch whose chains all have the same number of external bits - every k = 20 cohort: 5, k = 25: 9 - runs the instantiation
         // that knows it at compile time)
         if (b.wnx == WCfg<T>::NXT) { if (tr) hipLaunchKernelGGL((k_wsolve<T, true, WCfg<T>::NXT>), WS_ARGS); else hipLaunchKernelGGL((k_wsolve<T, false, WCfg<T>::NXT>), WS_ARGS); }
@@ -486,7 +486,7 @@ struct Engine : EngineBase {
 #undef WS_ARGS
       });
       if (!b.wdirect) {
-        hipLaunchKernelGGL((k_wconvert<T>), dim3(nW, 32), dim3(WROWS), 0, stream, db.dJ.p, db.wd.p, yw, y);
+        hipLaunchKernelGGL((k_wconvert<T>), dim3(nW, 32), dim3(WROWS), 0, L.s, db.dJ.p, db.wd.p, yw, y);
         HIPCHECK(hipGetLastError());
       }
     }
@@ -499,18 +499,18 @@ struct Engine : EngineBase {
       const double bytes = (double)b.ptiles.size() * (double)(1 << TB) * sizeof(T);
       const bool dlok = b.max_dl <= dl_cap;       // every patient's dP / dM tile slices fit the dl area: branch-free instantiation
       const int nold = (int)b.olist.size();
-      timed(tr ? MMHN_K_PSOLVE_ADJ : MMHN_K_PSOLVE_FWD, bytes, [&]() {
-#define PS2_ARGS dim3(nold), dim3(TSB), lds, stream, db.dJ.p, db.ptoff.p, db.ptiles.p, d_par.p, y, rhs_mode, d_perm.p, mk, tabJ.p, links.p, qS.p, dl_cap, db.olist.p
-        if (tr) { if (dlok) hipLaunchKernelGGL((k_psolve2<T, true, true>), PS2_ARGS); else hipLaunchKernelGGL((k_psolve2<T, true, false>), PS2_ARGS); }
-        else { if (dlok) hipLaunchKernelGGL((k_psolve2<T, false, true>), PS2_ARGS); else hipLaunchKernelGGL((k_psolve2<T, false, false>), PS2_ARGS); }
-#undef PS2_ARGS
+      timed(L, tr ? MMHN_K_PSOLVE_ADJ : MMHN_K_PSOLVE_FWD, bytes, [&]() {
+        with_flags([&](auto tr_, auto dl) {
+          hipLaunchKernelGGL((k_psolve2<T, tr_(), dl()>), dim3(nold), dim3(TSB), lds, L.s, db.dJ.p, db.ptoff.p, db.ptiles.p, d_par.p, y, rhs_mode,
+                             d_perm.p, mk, tabJ.p, links.p, qS.p, dl_cap, db.olist.p);
+        }, tr, dlok);
       });
     }
     if (!b.lmapT.empty()) {
       // everything else: all tiles in one cooperative launch (several workgroups per patient)
       const PList LT{db.dJ.p, nullptr, (int)b.lmapT.size(), b.maxkT, 0, db.lmapT.p, &b.lofT, tabJ.p, b.clJ, db.clJ,
                      tr ? MMHN_K_CSOLVE_ADJ : MMHN_K_CSOLVE_FWD};
-      solve(tr, LT, y, nullptr, nullptr, rhs_mode, nullptr);
+      solve(L, tr, LT, y, nullptr, nullptr, rhs_mode, nullptr);
     }
   }
 
@@ -518,30 +518,31 @@ struct Engine : EngineBase {
   //   default: tile-level substitution, ONE cooperative launch over the list's work list (k_csolve); a list of one level,
   //   lists without a work list (API calls) and MMHN_COOP=0: one launch per level of tile-index popcount (k_tsolve);
   //   MMHN_SOLVER=jacobi: k+1 in-place fused Jacobi sweeps from zero (the reference's iteration).
-  void solve(bool tr, const PList& L, T* y, const T* lidg, const T* rhs, int rhs_mode, const T* scal) {
-    if (L.ntiles == 0) return;
+  void solve(const Lane& L, bool tr, const PList& P, T* y, const T* lidg, const T* rhs, int rhs_mode, const T* scal) {
+    if (P.ntiles == 0) return;
     if (cfg.plan.use_jacobi) {
-      zero(y, L.vec);
-      const double bytes = 4.0 * (double)L.vec * sizeof(T);   // read y, lidg, rhs; write y (B_js)
-      for (int s = 0; s <= L.maxk; ++s)
-        launch_sweep(tr, L.d, L.map, L.ntiles, L.maxk, y, y, lidg, rhs, rhs_mode, scal, bytes, L.tab);
+      zero(L, y, P.vec);
+      const double bytes = 4.0 * (double)P.vec * sizeof(T);   // read y, lidg, rhs; write y (B_js)
+      for (int s = 0; s <= P.maxk; ++s)
+        launch_sweep(L, tr, P.d, P.map, P.ntiles, P.maxk, y, y, lidg, rhs, rhs_mode, scal, bytes, P.tab);
       return;
     }
-    const int nlev = (int)L.lof->size() - 1;
-    const size_t lds = sweep_lds(L.maxk);
-    const int mk = std::max(L.maxk, 1);
+    const int nlev = (int)P.lof->size() - 1;
+    const size_t lds = sweep_lds(P.maxk);
+    const int mk = std::max(P.maxk, 1);
     // compulsory traffic of a tile: write y (+ read dense rhs, + read the lidg vector when there is one)
-    const double per_tile = (double)((rhs_mode == 0 ? 2 : 1) + (lidg ? 1 : 0)) * (double)(1 << std::min(L.maxk, TB)) * sizeof(T);   // modes 1-3: rhs is not a 2^k vector
-    if (cfg.coop && L.cl && nlev > 1) {
-      const CList& cl = L.cl[tr ? 1 : 0];
-      const CListDev& dcl = L.dcl[tr ? 1 : 0];
+    const double per_tile = (double)((rhs_mode == 0 ? 2 : 1) + (lidg ? 1 : 0)) * (double)(1 << std::min(P.maxk, TB)) * sizeof(T);   // modes 1-3: rhs is not a 2^k vector
+    if (cfg.coop && P.cl && nlev > 1) {
+      const CList& cl = P.cl[tr ? 1 : 0];
+      const CListDev& dcl = P.dcl[tr ? 1 : 0];
       const int nitems = (int)cl.items.size();
-      REQUIRE(nitems == L.ntiles, "cooperative solve: work list and tile list differ");
-      DevArr<unsigned>& flags = coop_flags[cur_lane];
+      REQUIRE(nitems == P.ntiles, "cooperative solve: work list and tile list differ");
+      REQUIRE(L.flags >= 0, "cooperative solve: issued on a lane without a flag set");
+      DevArr<unsigned>& flags = coop_flags[L.flags];
       if (flags.n < (size_t)nitems) {
-        HIPCHECK(hipStreamSynchronize(stream));                // (a launch of this lane may still poll the old array)
+        HIPCHECK(hipStreamSynchronize(L.s));                // (a launch of this lane may still poll the old array)
         flags.alloc((size_t)nitems + 1024);
-        HIPCHECK(hipMemsetAsync(flags.p, 0, flags.n * sizeof(unsigned), stream));
+        HIPCHECK(hipMemsetAsync(flags.p, 0, flags.n * sizeof(unsigned), L.s));
       }
       if (++coop_epoch == 0u) {                                // (wrapped: no stale flag may equal a future epoch)
         HIPCHECK(hipDeviceSynchronize());
@@ -549,41 +550,31 @@ struct Engine : EngineBase {
         coop_epoch = 1u;
       }
       coop_slot = (coop_slot + 1) & 3;
-      const int slot = cur_lane * 4 + coop_slot;
+      const int slot = L.flags * 4 + coop_slot;
       coop_used = true;
-      timed(L.kslot, per_tile * nitems, [&]() {
+      timed(L, P.kslot, per_tile * nitems, [&]() {
         const dim3 g((unsigned)std::min(nitems, cfg.coop_wgs > 0 ? cfg.coop_wgs : cfg.plan.n_cu)), bk(TSB);
-#define CS_ARGS g, bk, lds, stream, L.d, dcl.items.p, dcl.deps.p, nitems, flags.p, coop_epoch, coop_ctl.p, slot, h_abort_dev, cfg.coop_fault ? 1 : 0, \
-                y, lidg, rhs, rhs_mode, scal, d_perm.p, mk, L.tab, links.p, qS.p
-        if (lidg) {
-          if (tr) hipLaunchKernelGGL((k_csolve<T, true, true>), CS_ARGS);
-          else hipLaunchKernelGGL((k_csolve<T, false, true>), CS_ARGS);
-        } else if (coop_alone) {                               // (nothing runs beside the joint solves of this batch: 93 registers)
-          if (tr) hipLaunchKernelGGL((k_csolve<T, true, false, 4>), CS_ARGS);
-          else hipLaunchKernelGGL((k_csolve<T, false, false, 4>), CS_ARGS);
-        } else {
-          if (tr) hipLaunchKernelGGL((k_csolve<T, true, false>), CS_ARGS);
-          else hipLaunchKernelGGL((k_csolve<T, false, false>), CS_ARGS);
-        }
+#define CS_ARGS g, bk, lds, L.s, P.d, dcl.items.p, dcl.deps.p, nitems, flags.p, coop_epoch, coop_ctl.p, slot, h_abort_dev, cfg.coop_fault ? 1 : 0, \
+                y, lidg, rhs, rhs_mode, scal, d_perm.p, mk, P.tab, links.p, qS.p
+        // (three of the four (lidg, coop_alone) variants exist: a list with a lidg vector never runs the 4-wave one)
+        with_flags([&](auto tr_) {
+          if (lidg) hipLaunchKernelGGL((k_csolve<T, tr_(), true>), CS_ARGS);
+          else if (coop_alone) hipLaunchKernelGGL((k_csolve<T, tr_(), false, 4>), CS_ARGS);   // (nothing runs beside the joint solves of this batch: 93 registers)
+          else hipLaunchKernelGGL((k_csolve<T, tr_(), false>), CS_ARGS);
+        }, tr);
 #undef CS_ARGS
       });
       return;
     }
     for (int s = 0; s < nlev; ++s) {
       const int lev = tr ? nlev - 1 - s : s;
-      const int beg = (*L.lof)[lev], cntl = (*L.lof)[lev + 1] - beg;
+      const int beg = (*P.lof)[lev], cntl = (*P.lof)[lev + 1] - beg;
       if (cntl == 0) continue;
-      timed(L.kslot, per_tile * cntl, [&]() {
-        const dim3 g(cntl), bk(TSB);
-#define TS_ARGS L.d, L.lmap + beg, d_par.p, y, lidg, rhs, rhs_mode, scal, d_perm.p, d_lvl.p, mk, L.tab, links.p, qS.p
-        if (lidg) {
-          if (tr) hipLaunchKernelGGL((k_tsolve<T, true, true>), g, bk, lds, stream, TS_ARGS);
-          else hipLaunchKernelGGL((k_tsolve<T, false, true>), g, bk, lds, stream, TS_ARGS);
-        } else {
-          if (tr) hipLaunchKernelGGL((k_tsolve<T, true, false>), g, bk, lds, stream, TS_ARGS);
-          else hipLaunchKernelGGL((k_tsolve<T, false, false>), g, bk, lds, stream, TS_ARGS);
-        }
-#undef TS_ARGS
+      timed(L, P.kslot, per_tile * cntl, [&]() {
+        with_flags([&](auto tr_, auto jac) {
+          hipLaunchKernelGGL((k_tsolve<T, tr_(), jac()>), dim3(cntl), dim3(TSB), lds, L.s, P.d, P.lmap + beg, d_par.p, y, lidg, rhs, rhs_mode, scal,
+                             d_perm.p, d_lvl.p, mk, P.tab, links.p, qS.p);
+        }, tr, lidg != nullptr);
       });
     }
   }
@@ -631,169 +622,27 @@ struct Engine : EngineBase {
     batches.clear();
     dev.clear();
     row_w.clear();                                          // (the weights belong to the rows they were set for)
-    clear_row_groups();                                     // (and so do the groups)
-    n_em = 0; n_unknown = 0;
+    clear_row_groups(*this);                                // (and so do the groups)
+    n_unknown = 0;
+    plain = Counts{0, (double)np, 0};
     // a cohort that is refused, or whose plan cannot be brought to the device, leaves the engine without one (no patient
     // count next to an empty or half-uploaded plan)
     try {
-      batches = plan_cohort<T>(cfg.plan, dat.data(), np, nc, n, n_em);
+      batches = plan_cohort<T>(cfg.plan, dat.data(), np, nc, n, plain.em);
       for (long long r = 0; r < np; ++r) n_unknown += dat[(size_t)r * nc + nc - 1] == 4;
+      plain.unknown = (double)n_unknown;
       place_cohort();
     } catch (...) {
       dat.clear(); batches.clear(); dev.clear();
-      n_pat = 0; n_em = 0; n_unknown = 0;
+      n_pat = 0; n_unknown = 0;
+      plain = Counts{};
       throw;
     }
   }
-  // the three counts of the objective: sum of w [seeding = 1], sum of w, sum of w [type 4] - the integer counts without weights
-  // (with row groups: the group-weighted ones)
   bool mixing() const { return !grp_ptr.empty(); }
-  double count_em() const { return mixing() ? g_em : row_w.empty() ? n_em : w_em; }
-  double count_pat() const { return mixing() ? g_pat : row_w.empty() ? (double)n_pat : w_pat; }
-  double count_unknown() const { return mixing() ? g_unknown : row_w.empty() ? (double)n_unknown : w_unknown; }
-  void row_weight_sums(double* out3) const { out3[0] = count_em(); out3[1] = count_pat(); out3[2] = count_unknown(); }
-  // one weight per cohort row (nullptr: none).  Everything an evaluation needs is brought to the device here, one array per
-  // batch in the batch's own order of patients (PatRec::row); an evaluation then only picks k_reduce_rows_w.
-  void set_row_weights(const double* w, long long nw) {
-    REQUIRE(!sums_pending, "mmhn_set_row_weights: an evaluation begun with mmhn_cohort_sums_begin has not been collected");
-    if (!w) {
-      row_w.clear();
-      for (BatchDev& d : dev) d.wrow.release();
-      return;
-    }
-    REQUIRE(!mixing(), "mmhn_set_row_weights: the engine holds row groups (group 0 of " + std::to_string(grp_w.size()) +
-                           "), whose weights take the role of row weights: remove them first");
-    const std::string rows = std::to_string(n_pat);
-    REQUIRE(n_pat > 0 && !batches.empty(), "mmhn_set_row_weights: the engine holds no cohort (row 0 does not exist)");
-    REQUIRE(nw == n_pat, "mmhn_set_row_weights: " + std::to_string(nw) + " weights for a cohort of " + rows + " rows (" +
-                             (nw < n_pat ? "row " + std::to_string(std::max<long long>(nw, 0)) + " has no weight"
-                                         : "row " + rows + " does not exist") + ")");
-    double s_em = 0, s_pat = 0, s_unknown = 0;
-    bool any = false;
-    for (long long r = 0; r < n_pat; ++r) {
-      const std::string at = "mmhn_set_row_weights: the weight of row " + std::to_string(r);
-      REQUIRE(std::isfinite(w[r]), at + " is not finite");
-      REQUIRE(w[r] >= 0, at + " is negative");
-      any = any || w[r] != 0;
-      const int8_t* row = dat.data() + (size_t)r * n_cols;
-      if (row[2 * n] == 1) s_em += w[r];
-      s_pat += w[r];
-      if (row[n_cols - 1] == 4) s_unknown += w[r];
-    }
-    REQUIRE(any, "mmhn_set_row_weights: every weight is 0 (row 0 is the first of " + rows + ")");
-    std::vector<DevArr<double>> fresh(batches.size());
-    std::vector<double> hw;
-    for (const Batch& b : batches) {
-      hw.resize(b.pats.size());
-      for (size_t i = 0; i < hw.size(); ++i) hw[i] = w[b.pats[i].row];
-      fresh[b.id].alloc(hw.size());
-      if (!hw.empty()) HIPCHECK(hipMemcpy(fresh[b.id].p, hw.data(), hw.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    for (const Batch& b : batches) dev[b.id].wrow = std::move(fresh[b.id]);
-    row_w.assign(w, w + n_pat);
-    w_em = s_em; w_pat = s_pat; w_unknown = s_unknown;
-  }
-  void clear_row_groups() {
-    grp_ptr.clear(); grp_rows.clear(); grp_w.clear();
-    gd = GroupsDev{};
-  }
-  // mmhn_set_row_groups: group g = rows[ptr[g] .. ptr[g+1]) of the current cohort with weight w[g].  Checked in full, then
-  // brought to the device in full, then swapped in: a refused call leaves what was held before.
-  void set_row_groups(const int64_t* ptr, long long ng, const int64_t* rows, const double* w) {
-    const std::string fn = "mmhn_set_row_groups: ";
-    REQUIRE(!sums_pending, fn + "an evaluation begun with mmhn_cohort_sums_begin has not been collected");
-    if (ng == 0 || !ptr || !rows || !w) {
-      REQUIRE(ng == 0 || (!ptr && !rows && !w), fn + "null pointer next to " + std::to_string(ng) + " groups (group 0)");
-      clear_row_groups();
-      return;
-    }
-    REQUIRE(ng > 0 && ng < (1ll << 31), fn + "the number of groups must be in 0 .. 2^31 - 1 (group " + std::to_string(ng) + ")");
-    REQUIRE(n_pat > 0 && !batches.empty(), fn + "the engine holds no cohort (row 0 of group 0 does not exist)");
-    REQUIRE(row_w.empty(), fn + "the engine holds row weights (row 0), and group weights take their role: remove them first");
-    REQUIRE(comm_size <= 1, fn + "the engine is rank " + std::to_string(comm_rank) + " of " + std::to_string(comm_size) +
-                                ": sharding cuts through groups (group 0), so row groups need a one-rank engine");
-    REQUIRE(ptr[0] == 0, fn + "ptr[0] must be 0 (group 0)");
-    for (long long g = 0; g < ng; ++g) {
-      const std::string at = fn + "group " + std::to_string(g);
-      REQUIRE(ptr[g + 1] >= ptr[g], at + ": ptr is decreasing");
-      REQUIRE(ptr[g + 1] > ptr[g], at + " is empty");
-    }
-    double s_em = 0, s_pat = 0, s_unknown = 0;
-    bool any = false;
-    auto cls = [&](long long r) { const int t = dat[(size_t)r * n_cols + n_cols - 1]; return t == 0 || t == 4 ? 1 : 0; };
-    auto unk = [&](long long r) { return dat[(size_t)r * n_cols + n_cols - 1] == 4; };
-    auto seeded = [&](long long r) { return dat[(size_t)r * n_cols + 2 * n] == 1; };
-    for (long long g = 0; g < ng; ++g) {
-      const std::string at = fn + "group " + std::to_string(g);
-      for (long long k = ptr[g]; k < ptr[g + 1]; ++k)
-        REQUIRE(rows[k] >= 0 && rows[k] < n_pat, at + " holds row " + std::to_string(rows[k]) + ", outside the cohort of " +
-                                                     std::to_string(n_pat) + " rows");
-      REQUIRE(std::isfinite(w[g]), "mmhn_set_row_groups: the weight of group " + std::to_string(g) + " is not finite");
-      REQUIRE(w[g] >= 0, "mmhn_set_row_groups: the weight of group " + std::to_string(g) + " is negative");
-      const long long r0 = rows[ptr[g]];
-      for (long long k = ptr[g] + 1; k < ptr[g + 1]; ++k) {
-        REQUIRE(cls(rows[k]) == cls(r0), at + " mixes the two blocks of the cohort sums: row " + std::to_string(r0) + " is " +
-                                             (cls(r0) ? "NM / type 4" : "EM") + ", row " + std::to_string(rows[k]) + " is not");
-        REQUIRE(unk(rows[k]) == unk(r0), at + " mixes rows of type 4 with others (rows " + std::to_string(r0) + " and " +
-                                             std::to_string(rows[k]) + ")");
-      }
-      any = any || w[g] != 0;
-      if (seeded(r0)) s_em += w[g];
-      s_pat += w[g];
-      if (unk(r0)) s_unknown += w[g];
-    }
-    REQUIRE(any, fn + "every weight is 0 (group 0 is the first of " + std::to_string(ng) + ")");
-    const long long nnz = ptr[ng];
-    // the transposed lists: the memberships of every cohort row, in group order
-    std::vector<long long> mptr((size_t)n_pat + 1, 0);
-    for (long long k = 0; k < nnz; ++k) ++mptr[(size_t)rows[k] + 1];
-    for (long long r = 0; r < n_pat; ++r) mptr[(size_t)r + 1] += mptr[(size_t)r];
-    std::vector<int> mgrp((size_t)nnz), hrows((size_t)nnz);
-    {
-      std::vector<long long> at(mptr.begin(), mptr.end() - 1);
-      for (long long g = 0; g < ng; ++g)
-        for (long long k = ptr[g]; k < ptr[g + 1]; ++k) { mgrp[(size_t)at[(size_t)rows[k]]++] = (int)g; hrows[(size_t)k] = (int)rows[k]; }
-    }
-    GroupsDev fresh;
-    auto upv = [](auto& d, const auto* src, size_t cnt) {
-      d.alloc(cnt);
-      if (cnt) HIPCHECK(hipMemcpy(d.p, src, cnt * sizeof(*src), hipMemcpyHostToDevice));
-    };
-    upv(fresh.gptr, ptr, (size_t)ng + 1);
-    upv(fresh.grows, hrows.data(), (size_t)nnz);
-    upv(fresh.gw, w, (size_t)ng);
-    upv(fresh.mptr, mptr.data(), mptr.size());
-    upv(fresh.mgrp, mgrp.data(), mgrp.size());
-    fresh.lpc.alloc((size_t)n_pat); fresh.omega.alloc((size_t)n_pat); fresh.lambda.alloc((size_t)n_pat);
-    fresh.lpg.alloc((size_t)ng); fresh.rho.alloc((size_t)nnz);
-    gd = std::move(fresh);
-    grp_ptr.assign(ptr, ptr + ng + 1);
-    grp_rows = std::move(hrows);
-    grp_w.assign(w, w + ng);
-    g_em = s_em; g_pat = s_pat; g_unknown = s_unknown;
-  }
-  MixDev mix_dev() const {
-    return MixDev{gd.gptr.p, gd.grows.p, gd.gw.p, (int)grp_w.size(), gd.mptr.p, gd.mgrp.p, (int)n_pat,
-                  gd.lpc.p, gd.lpg.p, gd.omega.p, gd.lambda.p};
-  }
-  // lp_g of every group, then omega / lambda of every row: after the last batch has written its rows of lpc
-  void launch_mix() {
-    const MixDev m = mix_dev();
-    hipLaunchKernelGGL(k_group_lse, dim3((m.n_groups + MIX_WAVES - 1) / MIX_WAVES), dim3(BLOCK), 0, stream, m, want_rho ? gd.rho.p : nullptr);
-    HIPCHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_mix_weights, dim3((m.n_rows + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, m);
-    HIPCHECK(hipGetLastError());
-  }
-  // score-only evaluation: lp_g [n_groups], rho [ptr[n_groups]] in the order of the group lists
-  void group_posteriors(const double* lt, const double* ldp, const double* ldm, double* lp_group, double* rho) {
-    REQUIRE(mixing(), "mmhn_group_posteriors: the engine holds no row groups (mmhn_set_row_groups)");
-    std::vector<double> s(2 * stride());
-    want_rho = true;
-    struct Unset { bool& f; ~Unset() { f = false; } } unset{want_rho};
-    evaluate(lt, ldp, ldm, false, s.data(), nullptr);
-    HIPCHECK(hipMemcpy(lp_group, gd.lpg.p, grp_w.size() * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHECK(hipMemcpy(rho, gd.rho.p, grp_rows.size() * sizeof(double), hipMemcpyDeviceToHost));
-  }
+  // the counts of the objective that hold for the next evaluation (with row groups: the group-weighted ones)
+  const Counts& counts() const { return mixing() ? grouped : row_w.empty() ? plain : weighted; }
+  void row_weight_sums(double* out3) const { out3[0] = counts().em; out3[1] = counts().pat; out3[2] = counts().unknown; }
   // device copies of the plan and the workspace
   void place_cohort() {
     dev.resize(batches.size());
@@ -831,50 +680,256 @@ struct Engine : EngineBase {
   // stage 4, the adjoint seeds, the single-tumour gradients and the <q, rhs> dots, one workgroup (or wave) per patient.
   // which = 0: the patients that are their own problem (launched first: nothing of the joint path feeds them), 1: the
   // paired ones (after k_gather_marg).  The size classes are independent of each other.
-  // Streams: the own-problem launches go to side[0], next to the joint path on the main stream, and are joined before the
-  // assembly; of the paired launches the 1024-thread class goes to side[1], the merged one stays on the main stream.
-  // small_fork: the point of the main stream the side launches of `which` wait for (recorded ahead of time when launches of the
-  // critical chain are to be issued first: the host needs ~25 us for a fork, the launches and the join record)
-  void small_fork(int which) {
-    HIPCHECK(hipEventRecord(ev_fork[which], stream));
-    fork_recorded[which] = true;
-  }
+  // Lanes: the own-problem launches go to side[0], next to the joint path on the main lane, and are joined before the
+  // assembly; of the paired launches the 1024-thread class goes to side[1], the merged one stays on the main lane.
+  // The point of the main lane that the side launches of which = 0 wait for is recorded ahead of time (Lane::record_fork: the
+  // launches of the critical chain are issued first).  The caller joins (Lane::join).
   void small_classes(const Batch& b, int which, bool grad) {
     const BatchDev& db = dev[b.id];
     const int n0 = (int)b.sp_list[which][0].size(), n1 = (int)b.sp_list[which][1].size(), n2 = (int)b.sp_list[which][2].size();
     const int np0 = which ? (int)b.sp_list[2][0].size() : 0, np1 = which ? (int)b.sp_list[2][1].size() : 0;
     const int mk0 = spatient_class_maxk(0), mk1 = which ? b.mk1p : spatient_class_maxk(1), mk2 = spatient_class_maxk(2);
     const bool on_side = which == 0 ? (n0 + n1 + n2 > 0) : n2 > 0;
-    hipStream_t sd = side[which];
-    if (on_side) {
-      if (!fork_recorded[which]) HIPCHECK(hipEventRecord(ev_fork[which], stream));
-      HIPCHECK(hipStreamWaitEvent(sd, ev_fork[which], 0));
-    }
-    fork_recorded[which] = false;
+    Lane& sd = side[which];
+    if (on_side) sd.begin(main);
+    else sd.reset();                                          // (a fork recorded ahead of time goes unused)
 #define SP_TAIL db.pats.p, db.dS.p, d_par.p, d_perm.p, d_lvl.p, db.dJ.p, db.wd.p, pi.p, links.p, pS.p, qS.p, GS.p, bmS.p, dots.p, lp.p, resp.p
-    auto big_class = [&]() {
-      if (!n2) return;
+    if (n2) {
       const size_t lds = (spatient_lds<T>(N, mk2) + 15) / 16 * 16;
-      hipLaunchKernelGGL((k_spatient<T, 1024, 1>), dim3(n2), dim3(1024), lds, sd, db.sp_list[which][2].p, n2, SP_TAIL, mk2, N, grad ? 1 : 0);
+      hipLaunchKernelGGL((k_spatient<T, 1024, 1>), dim3(n2), dim3(1024), lds, sd.s, db.sp_list[which][2].p, n2, SP_TAIL, mk2, N, grad ? 1 : 0);
       HIPCHECK(hipGetLastError());
-    };
-    big_class();
+    }
     if (n0 + n1 + np0 + np1) {
       const size_t s0 = (spatient_lds<T>(N, mk0) + 15) / 16 * 16, s1 = (spatient_lds<T>(N, mk1) + 15) / 16 * 16;
       const size_t lds = std::max(s0 * SP_PPB0, n1 + np1 ? s1 * (np1 ? 2 : 1) : 0) + 64;
       const int nblk = (n0 + SP_PPB0 - 1) / SP_PPB0 + n1 + (np0 + SP_PPB0 / 2 - 1) / (SP_PPB0 / 2) + np1;
-      hipLaunchKernelGGL((k_spatient2<T>), dim3(nblk), dim3(256), lds, which == 0 ? sd : stream,
+      hipLaunchKernelGGL((k_spatient2<T>), dim3(nblk), dim3(256), lds, which == 0 ? sd.s : main.s,
                          db.sp_list[which][0].p, n0, mk0, db.sp_list[which][1].p, n1, mk1,
                          db.sp_list[2][0].p, np0, db.sp_list[2][1].p, np1, SP_TAIL, N, grad ? 1 : 0);
       HIPCHECK(hipGetLastError());
     }
 #undef SP_TAIL
-    if (on_side) HIPCHECK(hipEventRecord(ev_join[which], sd));
-    small_forked[which] = on_side;                           // (the caller joins: small_join)
+    if (on_side) sd.end();
   }
-  void small_join(int which) {
-    if (small_forked[which]) HIPCHECK(hipStreamWaitEvent(stream, ev_join[which], 0));
-    small_forked[which] = false;
+
+  // ---- the stages of an evaluation, in the order evaluate() issues them
+  // The head: parameters up, cohort sums and - when it fits the same launch - the first batch's gradient work arrays
+  // cleared.  Returns whether that clear was done.
+  bool eval_head(const double* lt, const double* ldp, const double* ldm, bool grad) {
+    const int st = stride();
+    bool head_done = false;
+    if (cfg.zero_copy && !batches.empty()) {
+      build_params(lt, ldp, ldm, false);
+      const Batch& b0 = batches.front();
+      // (a large batch clears its ~GB of work arrays with the runtime's fill, which is faster at that size: +1.0 ms
+      // per evaluation on the 5 000-patient bench cohort when this kernel did it)
+      long long nz = grad && !b0.dJ.empty() ? zclear_elems(b0, N) * (long long)sizeof(T) / 16 : 0;
+      const bool fill_here = nz <= (32ll << 20) / 16;
+      if (!fill_here) nz = 0;
+      const int nw = (int)(NPSET * sizeof(Params<T>) / sizeof(uint4));
+      const long long need = std::max<long long>(std::max<long long>(nw, 2 * st), nz);
+      const int nblk = (int)std::min<long long>((need + 255) / 256, 4096);
+      hipLaunchKernelGGL(k_begin_eval, dim3(nblk), dim3(256), 0, main.s, static_cast<const uint4*>(h_par_dev),
+                         reinterpret_cast<uint4*>(d_par.p), nw, sums.p, 2 * st, reinterpret_cast<uint4*>(zarena.p), nz);
+      HIPCHECK(hipGetLastError());
+      head_done = fill_here;
+    } else {
+      build_params(lt, ldp, ldm);
+      HIPCHECK(hipMemsetAsync(sums.p, 0, 2 * st * sizeof(double), main.s));
+    }
+    if (mixing() && cfg.poison) HIPCHECK(hipMemsetAsync(gd.lpc.p, 0xFF, (size_t)n_pat * sizeof(double), main.s));
+    return head_done;
+  }
+  // What a batch decides for all its launches, the views into zarena, and the clear of its accumulators (cleared: the
+  // head of the evaluation did it)
+  void batch_prepare(const Batch& b, bool grad, bool cleared) {
+    const int nJ = (int)b.dJ.size();
+    coop_alone = b.stg[0].empty();                          // (no second cooperative launch on a side stream next to the joint solves)
+    time_kernels = cfg.force_timing || b.vecJ + b.vecS >= (1ll << 26);
+    GJ.p = zarena.p;
+    DJ.p = GJ.p + up4(3ll * nJ * N * N);
+    Abuf.p = DJ.p + up4(3ll * nJ * N);
+    if (grad && nJ && !cleared) zero(main, zarena.p, zclear_elems(b, N));
+    // (MMHN_POISON=1, tests: the arrays outside the memset start as NaNs - an entry that a consumer reads and no launch
+    // wrote shows in the gradient)
+    if (grad && nJ && cfg.poison) poison_fill(main, Abuf.p + b.aclr, b.asize - b.aclr);
+  }
+  // The tile solver skips dead tiles and its consumers read them: those parts of pi / q_J must hold zeros - the vectors
+  // of the tile route lie behind offT and are cleared once per batch.  The window and per-patient kernels never let a
+  // value of a dead tile into arithmetic (they are only ever loaded behind a per-state select): no clearing, which
+  // matters when a cohort takes several batches per evaluation; MMHN_POISON=1 (tests) NaN-fills their part.
+  void clear_dead_tiles(const Batch& b, bool grad) {
+    if (cfg.plan.use_jacobi || b.dJ.empty()) return;
+    if (pi_owner != b.id) { zero(main, pi.p + b.offT, b.vecJ - b.offT); pi_owner = b.id; }
+    if (grad && qJ_owner != b.id) { zero(main, qJ.p + b.offT, b.vecJ - b.offT); qJ_owner = b.id; }
+    if (cfg.poison && b.offT > 0) {
+      HIPCHECK(hipMemsetAsync(pi.p, 0xFF, (size_t)b.offT * sizeof(T), main.s));
+      if (grad) HIPCHECK(hipMemsetAsync(qJ.p, 0xFF, (size_t)b.offT * sizeof(T), main.s));
+    }
+  }
+  // every joint problem of a batch as one list (Jacobi solver only)
+  PList joint_list(const Batch& b) const {
+    const BatchDev& db = dev[b.id];
+    return PList{db.dJ.p, db.mapJ.p, (int)b.mapJ.size(), b.maxkJ, b.vecJ, db.lmapJ.p, &b.lofJ, tabJ.p};
+  }
+  // 1-2 joint forward
+  void joint_forward(const Batch& b) {
+    const BatchDev& db = dev[b.id];
+    if (cfg.plan.use_jacobi) {
+      launch_diag(main, db.dJ.p, db.mapJ.p, (int)b.mapJ.size(), nullptr, lidgJ.p, nullptr, KD_LIDG);
+      solve(main, false, joint_list(b), pi.p, lidgJ.p, nullptr, 2, nullptr);
+    } else {
+      psolve(main, false, b, pi.p, 2);
+    }
+  }
+  // 3-4 the staged kernels of one group of patients (Batch::stg[w]; 0: own-problem patients, 1: paired rows): forward part
+  // (tables, right-hand sides, 1/diag, forward solve, scores and adjoint seeds) and gradient part (adjoint solve, gradient
+  // rows, observation-rate marginals)
+  // (Jacobi / MMHN_SMALL=0: the group is every single-tumour problem, so that vec = every single-tumour vector)
+  PList staged_list(const Batch& b, int w) const {
+    const Staged& g = b.stg[w];
+    const StagedDev& dg = dev[b.id].stg[w];
+    return PList{dev[b.id].dS.p, dg.map.p, (int)g.map.size(), g.maxk, b.vecS, dg.lmap.p, &g.lof, tabS.p, g.cl, dg.cl};
+  }
+  void staged_fwd(const Lane& L, const Batch& b, int w, bool grad) {
+    const BatchDev& db = dev[b.id];
+    const Staged& g = b.stg[w];
+    const StagedDev& dg = db.stg[w];
+    if (g.empty()) return;
+    const int nG = (int)g.pats.size(), tG = (int)g.map.size();
+    // (the group's accumulators cleared, the e_0 right-hand sides written: before anything of the group runs)
+    hipLaunchKernelGGL((k_staged_init<T>), dim3(nG), dim3(BLOCK), 0, L.s, db.pats.p, db.dS.p, rhsS.p, GS.p, bmS.p, N, grad ? 1 : 0, dg.pats.p);
+    HIPCHECK(hipGetLastError());
+    prep(L, db.dS.p, (int)g.probs.size(), tabS.p, false, 0, dg.probs.p);
+    // marginal right-hand sides (the small-space kernels read pi themselves and write the links)
+    if (!g.paired.empty()) {
+      hipLaunchKernelGGL((k_gather_marg<T>), dim3((unsigned)g.paired.size(), 2, g.maxk > 10 ? 8 : 1), dim3(BLOCK), 0, L.s,
+                         db.pats.p, db.dJ.p, db.dS.p, d_par.p, pi.p, rhsS.p, links.p, dg.paired.p, db.wd.p);
+      HIPCHECK(hipGetLastError());
+    }
+    launch_diag(L, db.dS.p, dg.map.p, tG, nullptr, lidgS.p, nullptr, KD_LIDG);
+    solve(L, false, staged_list(b, w), pS.p, lidgS.p, rhsS.p, 0, nullptr);
+    hipLaunchKernelGGL((k_seeds<T>), dim3((nG + 255) / 256), dim3(256), 0, L.s, db.pats.p, nG, db.dS.p,
+                       d_par.p, pS.p, seedS.p, lp.p, resp.p, N, dg.pats.p);
+    HIPCHECK(hipGetLastError());
+  }
+  void staged_adj(const Lane& L, const Batch& b, int w) {
+    const BatchDev& db = dev[b.id];
+    const Staged& g = b.stg[w];
+    const StagedDev& dg = db.stg[w];
+    if (g.empty()) return;
+    solve(L, true, staged_list(b, w), qS.p, lidgS.p, nullptr, 1, seedS.p);
+    launch_grad_rows(L, db.dS.p, (int)g.probs.size(), g.maxk, nullptr, pS.p, qS.p, GS.p, GK_S, dg.grc);
+    if (g.kind2) {
+      hipLaunchKernelGGL((k_bit_marg<T>), dim3((unsigned)g.map.size()), dim3(BLOCK), 0, L.s, db.dS.p, dg.map.p, d_par.p, pS.p, qS.p, bmS.p);
+      HIPCHECK(hipGetLastError());
+    }
+  }
+  // 5 joint adjoint: right-hand side D_obs * scatter(q_S) formed on the fly inside the solve
+  void joint_adjoint(const Batch& b) {
+    const BatchDev& db = dev[b.id];
+    if (cfg.plan.use_jacobi) zero(main, rhsJ.p, b.vecJ);
+    for (int part = 0; part < 2 && !b.stg[1].paired.empty(); ++part) {
+      if (b.stg[1].paired.size() >= 256)
+        hipLaunchKernelGGL((k_scatter_marg<T, 1024>), dim3((unsigned)b.stg[1].paired.size()), dim3(1024), 0, main.s, db.pats.p, db.dJ.p,
+                           db.dS.p, d_par.p, qS.p, rhsS.p, cfg.plan.use_jacobi ? rhsJ.p : nullptr, dots.p, part, db.stg[1].paired.p);
+      else
+        hipLaunchKernelGGL((k_scatter_marg<T>), dim3((unsigned)b.stg[1].paired.size()), dim3(BLOCK), 0, main.s, db.pats.p, db.dJ.p,
+                           db.dS.p, d_par.p, qS.p, rhsS.p, cfg.plan.use_jacobi ? rhsJ.p : nullptr, dots.p, part, db.stg[1].paired.p);
+      HIPCHECK(hipGetLastError());
+    }
+    if (cfg.plan.use_jacobi) solve(main, true, joint_list(b), qJ.p, lidgJ.p, rhsJ.p, 0, nullptr);
+    else psolve(main, true, b, qJ.p, 3);
+  }
+  // 6 joint gradient (accumulators cleared at the start of the batch)
+  void joint_gradient(const Batch& b) {
+    const BatchDev& db = dev[b.id];
+    const int nJ = (int)b.dJ.size();
+    if (!cfg.plan.use_jacobi) {
+      // algorithmic bytes: the seeded halves of pi and q_J read once
+      const double mbytes = (double)b.vecJ * sizeof(T);
+      timed(main, MMHN_K_PCLASS, mbytes, [&]() {
+        if (b.wdirect) {                                                  // window-layout problems: both classes, two reads
+          const int nW = (int)b.wd.size();
+          hipLaunchKernelGGL((k_wclass<T>), dim3((unsigned)std::min(nW, cfg.plan.n_cu)), dim3(WROWS), wclass_lds<T>(), main.s, db.dJ.p, db.wd.p, nW, pi.p, qJ.p, Abuf.p);
+        }
+        // the problems in index order: work items (class passes of a problem cut into ranges + its eq block's flows)
+        // on short launches, one workgroup per problem on long ones
+        if (!b.pcl.empty())
+          hipLaunchKernelGGL((k_pclass<T, true>), dim3((unsigned)b.pcl.size()), dim3(CMB), PC_LDS_ELEMS * sizeof(T), main.s, db.dJ.p, db.wd.p, pi.p, qJ.p, Abuf.p, db.pcl.p);
+        else if ((int)b.wd.size() < nJ || !b.wdirect)
+          hipLaunchKernelGGL((k_pclass<T, false>), dim3(nJ), dim3(CMB), PC_LDS_ELEMS * sizeof(T), main.s, db.dJ.p, db.wd.p, pi.p, qJ.p, Abuf.p);
+      });
+      if (!b.mapX.empty())
+        hipLaunchKernelGGL((k_class_marg<T>), dim3((unsigned)b.mapX.size()), dim3(CMB), 2 * sizeof(T) << TB, main.s,
+                           db.dJ.p, db.mapX.p, pi.p, qJ.p, Abuf.p);
+    } else {
+      hipLaunchKernelGGL((k_class_marg<T>), dim3((unsigned)b.mapJ.size()), dim3(CMB), 2 * sizeof(T) << TB, main.s, db.dJ.p,
+                         db.mapJ.p, pi.p, qJ.p, Abuf.p);
+    }
+    HIPCHECK(hipGetLastError());
+    // (its own launch: folded into the workgroups of k_pclass it cost more than the launch - k_pclass 20.5 -> 21.9 ms
+    // on the bench cohort, the LUAD evaluation +25 us; short launches run it as work items of k_pclass)
+    if (b.pcl.empty()) {
+      hipLaunchKernelGGL((k_eq_flows<T>), dim3(nJ), dim3(BLOCK), 0, main.s, db.dJ.p, db.wd.p, pi.p, qJ.p, Abuf.p);
+      HIPCHECK(hipGetLastError());
+    }
+    launch_grad_rows(main, db.dJ.p, nJ, b.maxkcJ, Abuf.p, nullptr, nullptr, GJ.p, -1, db.grcJ, DJ.p, (long long)nJ * N * N);
+  }
+  // 7 per-patient assembly; gather: the rows' lp into lpc for the row groups (first sweep)
+  void finalize_batch(const Batch& b, bool grad, bool gather) {
+    const BatchDev& db = dev[b.id];
+    const int npat = (int)b.pats.size(), nJ = (int)b.dJ.size();
+    const AsmArgs<T> aa{db.pats.p, db.dJ.p, db.dS.p, d_par.p, GS.p, GJ.p, (long long)nJ * N * N, dots.p, DJ.p, (long long)nJ * N, bmS.p, lp.p, N,
+                        grad ? 1 : 0};
+    hipLaunchKernelGGL((k_finalize<T>), dim3(npat), dim3(BLOCK), 0, main.s, aa, out.p);
+    HIPCHECK(hipGetLastError());
+    if (gather) {
+      hipLaunchKernelGGL(k_mix_gather, dim3((npat + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, main.s, db.pats.p, npat, out.p, stride(), gd.lpc.p);
+      HIPCHECK(hipGetLastError());
+      if (batches.size() == 1) launch_mix(*this, main);
+    }
+  }
+  // cohort reduction of one batch (nelem elements of its rows) into sums; the last batch's also packs
+  void reduce_batch(const Batch& b, int nelem) {
+    const BatchDev& db = dev[b.id];
+    const int st = stride(), npat = (int)b.pats.size();
+    const int per = red_per(npat), nchunk = (npat + per - 1) / per;
+    const dim3 cols((nelem + BLOCK - 1) / BLOCK);
+    if (mixing())
+      hipLaunchKernelGGL(k_reduce_rows_mix, dim3(cols.x, nchunk), dim3(BLOCK), 0, main.s, db.pats.p, npat, per, out.p, st, nelem,
+                         gd.omega.p, gd.lambda.p, redbuf.p);
+    else if (row_w.empty())
+      hipLaunchKernelGGL(k_reduce_rows, dim3(cols.x, nchunk), dim3(BLOCK), 0, main.s, db.pats.p, npat, per, out.p, st, nelem, redbuf.p);
+    else
+      hipLaunchKernelGGL(k_reduce_rows_w, dim3(cols.x, nchunk), dim3(BLOCK), 0, main.s, db.pats.p, npat, per, out.p, st, nelem,
+                         db.wrow.p, redbuf.p);
+    HIPCHECK(hipGetLastError());
+    if (pack_mode && &b == &batches.back()) {
+      hipLaunchKernelGGL(k_reduce_parts_pack, dim3((st + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, main.s, redbuf.p, st, nelem, nchunk,
+                         sums.p, pack_mode, N, pack_a, pack_b, pack_dst);
+      packed_in_eval = true;
+    } else {
+      hipLaunchKernelGGL(k_reduce_parts, dim3(cols.x, 2), dim3(BLOCK), 0, main.s, redbuf.p, st, nelem, nchunk, sums.p);
+    }
+    HIPCHECK(hipGetLastError());
+  }
+  // the per-patient rows of a batch to their cohort rows of host_out (waits for the batch)
+  void download_rows(const Batch& b, double* host_out) {
+    const int st = stride(), npat = (int)b.pats.size();
+    std::vector<double> tmp((size_t)npat * st);
+    HIPCHECK(hipMemcpyAsync(tmp.data(), out.p, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, main.s));
+    HIPCHECK(hipStreamSynchronize(main.s));
+    check_abort();
+    for (int i = 0; i < npat; ++i)
+      std::memcpy(host_out + (size_t)b.pats[i].row * st, tmp.data() + (size_t)i * st, st * sizeof(double));
+  }
+  void download_sums(double* host_sums) {
+    std::vector<double> hs(2 * stride());
+    HIPCHECK(hipMemcpyAsync(hs.data(), sums.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost, main.s));
+    HIPCHECK(hipStreamSynchronize(main.s));
+    check_abort();
+    std::memcpy(host_sums, hs.data(), hs.size() * sizeof(double));
   }
 
   // host_out (optional): per-patient rows [n_pat][stride]; host_sums: [2][stride] (EM, NM)
@@ -888,253 +943,59 @@ struct Engine : EngineBase {
     const bool mix = mixing();
     const int nsweep = mix && want_grad && batches.size() > 1 ? 2 : 1;
     const bool reduce_behind = mix && !want_grad && batches.size() > 1;
-    bool grad = want_grad && nsweep == 1;                   // (of the first sweep: what the head clears for)
     auto t0 = std::chrono::steady_clock::now();
-    const int st = stride();
-    // (an evaluation that threw between a fork and its join must not leave its flags to the next one: the side stream
-    // would wait for the previous evaluation's event and start before this one's parameters are up)
-    small_forked[0] = small_forked[1] = fork_recorded[0] = fork_recorded[1] = false;
-    // the head of the evaluation: parameters up, cohort sums and the first batch's gradient work arrays cleared
-    bool head_done = false;
-    if (cfg.zero_copy && !batches.empty()) {
-      build_params(lt, ldp, ldm, false);
-      const Batch& b0 = batches.front();
-      // (a large batch clears its ~GB of work arrays with the runtime's fill, which is faster at that size: +1.0 ms
-      // per evaluation on the 5 000-patient bench cohort when this kernel did it)
-      long long nz = grad && !b0.dJ.empty() ? zclear_elems(b0, N) * (long long)sizeof(T) / 16 : 0;
-      const bool fill_here = nz <= (32ll << 20) / 16;
-      if (!fill_here) nz = 0;
-      const int nw = (int)(NPSET * sizeof(Params<T>) / sizeof(uint4));
-      const long long need = std::max<long long>(std::max<long long>(nw, 2 * st), nz);
-      const int nblk = (int)std::min<long long>((need + 255) / 256, 4096);
-      hipLaunchKernelGGL(k_begin_eval, dim3(nblk), dim3(256), 0, stream, static_cast<const uint4*>(h_par_dev),
-                         reinterpret_cast<uint4*>(d_par.p), nw, sums.p, 2 * st, reinterpret_cast<uint4*>(zarena.p), nz);
-      HIPCHECK(hipGetLastError());
-      head_done = fill_here;
-    } else {
-      build_params(lt, ldp, ldm);
-      HIPCHECK(hipMemsetAsync(sums.p, 0, 2 * st * sizeof(double), stream));
-    }
-    if (mix && cfg.poison) HIPCHECK(hipMemsetAsync(gd.lpc.p, 0xFF, (size_t)n_pat * sizeof(double), stream));
-    // cohort reduction of one batch (nelem elements of its rows) into sums; the last batch's also packs
-    auto reduce_batch = [&](const Batch& b, int nelem) {
-      const BatchDev& db = dev[b.id];
-      const int npat = (int)b.pats.size();
-      const int per = red_per(npat), nchunk = (npat + per - 1) / per;
-      const dim3 cols((nelem + BLOCK - 1) / BLOCK);
-      if (mix)
-        hipLaunchKernelGGL(k_reduce_rows_mix, dim3(cols.x, nchunk), dim3(BLOCK), 0, stream, db.pats.p, npat, per, out.p, st, nelem,
-                           gd.omega.p, gd.lambda.p, redbuf.p);
-      else if (row_w.empty())
-        hipLaunchKernelGGL(k_reduce_rows, dim3(cols.x, nchunk), dim3(BLOCK), 0, stream, db.pats.p, npat, per, out.p, st, nelem, redbuf.p);
-      else
-        hipLaunchKernelGGL(k_reduce_rows_w, dim3(cols.x, nchunk), dim3(BLOCK), 0, stream, db.pats.p, npat, per, out.p, st, nelem,
-                           db.wrow.p, redbuf.p);
-      HIPCHECK(hipGetLastError());
-      if (pack_mode && &b == &batches.back()) {
-        hipLaunchKernelGGL(k_reduce_parts_pack, dim3((st + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, redbuf.p, st, nelem, nchunk,
-                           sums.p, pack_mode, N, pack_a, pack_b, pack_dst);
-        packed_in_eval = true;
-      } else {
-        hipLaunchKernelGGL(k_reduce_parts, dim3(cols.x, 2), dim3(BLOCK), 0, stream, redbuf.p, st, nelem, nchunk, sums.p);
-      }
-      HIPCHECK(hipGetLastError());
-    };
+    for (Lane& l : side) l.reset();
+    bool head_done = eval_head(lt, ldp, ldm, want_grad && nsweep == 1);   // (the gradient of the first sweep: what the head clears for)
     for (int sweep = 0; sweep < nsweep; ++sweep) {
       const bool last_sweep = sweep == nsweep - 1;
-      grad = want_grad && last_sweep;
-      if (sweep > 0) { launch_mix(); head_done = false; }     // (lpc is whole; the head cleared nothing for a gradient)
+      const bool grad = want_grad && last_sweep;
+      if (sweep > 0) { launch_mix(*this, main); head_done = false; }     // (lpc is whole; the head cleared nothing for a gradient)
       for (const Batch& b : batches) {
         const BatchDev& db = dev[b.id];
-        const int npat = (int)b.pats.size(), nJ = (int)b.dJ.size(), nS = (int)b.dS.size();
-        const int tJ = (int)b.mapJ.size();
-        const PList LJ{db.dJ.p, db.mapJ.p, tJ, b.maxkJ, b.vecJ, db.lmapJ.p, &b.lofJ, tabJ.p};       // (Jacobi solver only)
-        const bool fused_small = b.has_small;
-        coop_alone = b.stg[0].empty();                          // (no second cooperative launch on a side stream next to the joint solves)
-        // the staged kernels of one group of patients (Batch::stg): forward part (tables, right-hand sides, 1/diag, forward solve,
-        // scores and adjoint seeds) and gradient part (adjoint solve, gradient rows, observation-rate marginals)
-        auto staged_fwd = [&](int w) {
-          const Staged& g = b.stg[w];
-          const StagedDev& dg = db.stg[w];
-          if (g.empty()) return;
-          const int nG = (int)g.pats.size(), tG = (int)g.map.size();
-          // (Jacobi / MMHN_SMALL=0: the group is every single-tumour problem, so that vec = every single-tumour vector)
-          const PList LG{db.dS.p, dg.map.p, tG, g.maxk, b.vecS, dg.lmap.p, &g.lof, tabS.p, g.cl, dg.cl};
-          // (the group's accumulators cleared, the e_0 right-hand sides written: before anything of the group runs)
-          hipLaunchKernelGGL((k_staged_init<T>), dim3(nG), dim3(BLOCK), 0, stream, db.pats.p, db.dS.p, rhsS.p, GS.p, bmS.p, N, grad ? 1 : 0, dg.pats.p);
-          HIPCHECK(hipGetLastError());
-          if (g.probs.size() >= 256)
-            hipLaunchKernelGGL((k_prep<T, false, 1024>), dim3((unsigned)g.probs.size()), dim3(1024), prep_lds<T>(N), stream, db.dS.p, d_par.p, tabS.p, dg.probs.p);
-          else
-            hipLaunchKernelGGL((k_prep<T, false>), dim3((unsigned)g.probs.size()), dim3(BLOCK), prep_lds<T>(N), stream, db.dS.p, d_par.p, tabS.p, dg.probs.p);
-          HIPCHECK(hipGetLastError());
-          // marginal right-hand sides (the small-space kernels read pi themselves and write the links)
-          if (!g.paired.empty()) {
-            hipLaunchKernelGGL((k_gather_marg<T>), dim3((unsigned)g.paired.size(), 2, g.maxk > 10 ? 8 : 1), dim3(BLOCK), 0, stream,
-                               db.pats.p, db.dJ.p, db.dS.p, d_par.p, pi.p, rhsS.p, links.p, dg.paired.p, db.wd.p);
-            HIPCHECK(hipGetLastError());
-          }
-          launch_diag(db.dS.p, dg.map.p, tG, nullptr, lidgS.p, nullptr, KD_LIDG);
-          solve(false, LG, pS.p, lidgS.p, rhsS.p, 0, nullptr);
-          hipLaunchKernelGGL((k_seeds<T>), dim3((nG + 255) / 256), dim3(256), 0, stream, db.pats.p, nG, db.dS.p,
-                             d_par.p, pS.p, seedS.p, lp.p, resp.p, N, dg.pats.p);
-          HIPCHECK(hipGetLastError());
-        };
-        auto staged_adj = [&](int w) {
-          const Staged& g = b.stg[w];
-          const StagedDev& dg = db.stg[w];
-          if (g.empty()) return;
-          const int tG = (int)g.map.size();
-          const PList LG{db.dS.p, dg.map.p, tG, g.maxk, b.vecS, dg.lmap.p, &g.lof, tabS.p, g.cl, dg.cl};
-          solve(true, LG, qS.p, lidgS.p, nullptr, 1, seedS.p);
-          launch_grad_rows(db.dS.p, (int)g.probs.size(), g.maxk, nullptr, pS.p, qS.p, GS.p, GK_S, dg.grc);
-          if (g.kind2) {
-            hipLaunchKernelGGL((k_bit_marg<T>), dim3(tG), dim3(BLOCK), 0, stream, db.dS.p, dg.map.p, d_par.p, pS.p, qS.p, bmS.p);
-            HIPCHECK(hipGetLastError());
-          }
-        };
-        time_kernels = cfg.force_timing || b.vecJ + b.vecS >= (1ll << 26);
-        const long long gjs = (long long)nJ * N * N;
-        GJ.p = zarena.p;
-        DJ.p = GJ.p + up4(3 * gjs);
-        Abuf.p = DJ.p + up4(3ll * nJ * N);
-        if (grad && nJ && !(head_done && &b == &batches.front())) zero(zarena.p, zclear_elems(b, N));
-        // (MMHN_POISON=1, tests: the arrays outside the memset start as NaNs - an entry that a consumer reads and no launch
-        // wrote shows in the gradient)
-        if (grad && nJ && cfg.poison) poison_fill(Abuf.p + b.aclr, b.asize - b.aclr);
-        prep(db.dJ.p, nJ, tabJ.p, true, b.maxkcJ);                    // (first: the head of the critical chain)
-        // staged patients that are their own problem: a side stream of their own from here to the assembly (a timed
-        // evaluation keeps them on the main stream - events are recorded there)
-        bool own_forked = false;
-        if (!b.stg[0].empty() && !time_kernels) {
-          HIPCHECK(hipEventRecord(ev_fork[2], stream));
-          HIPCHECK(hipStreamWaitEvent(side[2], ev_fork[2], 0));
-          hipStream_t keep = stream;
-          stream = side[2]; cur_lane = 1;
-          try {
-            staged_fwd(0);
-            if (grad) staged_adj(0);
-          } catch (...) { stream = keep; cur_lane = 0; throw; }
-          stream = keep; cur_lane = 0;
-          HIPCHECK(hipEventRecord(ev_join[2], side[2]));
-          own_forked = true;
+        const int nJ = (int)b.dJ.size();
+        batch_prepare(b, grad, head_done && &b == &batches.front());
+        prep(main, db.dJ.p, nJ, tabJ.p, true, b.maxkcJ);              // (first: the head of the critical chain)
+        // staged patients that are their own problem: a side lane of their own from here to the assembly, with its own
+        // flag set for their cooperative launches (a timed batch keeps them on the main lane, where its events are recorded)
+        Lane& own = time_kernels ? main : side[2];
+        const bool own_apart = &own != &main && !b.stg[0].empty();
+        if (own_apart) {
+          own.begin(main);
+          staged_fwd(own, b, 0, grad);
+          if (grad) staged_adj(own, b, 0);
+          own.end();
         }
         // patients that are their own single-tumour problem need nothing of the joint path: their small-space kernels
-        // run on a side stream from here on, next to the joint forward solve (whose launch is issued first - it is the
+        // run on a side lane from here on, next to the joint forward solve (whose launch is issued first - it is the
         // critical chain); the assembly waits for them
-        if (fused_small) small_fork(0);
-        // The tile solver skips dead tiles and its consumers read them: those parts of pi / q_J must hold zeros - the vectors
-        // of the tile route lie behind offT and are cleared once per batch.  The window and per-patient kernels never let a
-        // value of a dead tile into arithmetic (they are only ever loaded behind a per-state select): no clearing, which
-        // matters when a cohort takes several batches per evaluation; MMHN_POISON=1 (tests) NaN-fills their part.
-        if (!cfg.plan.use_jacobi && nJ) {
-          if (pi_owner != b.id) { zero(pi.p + b.offT, b.vecJ - b.offT); pi_owner = b.id; }
-          if (grad && qJ_owner != b.id) { zero(qJ.p + b.offT, b.vecJ - b.offT); qJ_owner = b.id; }
-          if (cfg.poison && b.offT > 0) {
-            HIPCHECK(hipMemsetAsync(pi.p, 0xFF, (size_t)b.offT * sizeof(T), stream));
-            if (grad) HIPCHECK(hipMemsetAsync(qJ.p, 0xFF, (size_t)b.offT * sizeof(T), stream));
-          }
-        }
-        // 1-2 joint forward
-        if (cfg.plan.use_jacobi) {
-          launch_diag(db.dJ.p, db.mapJ.p, tJ, nullptr, lidgJ.p, nullptr, KD_LIDG);
-          solve(false, LJ, pi.p, lidgJ.p, nullptr, 2, nullptr);
-        } else {
-          psolve(false, b, pi.p, 2);
-        }
-        if (fused_small) small_classes(b, 0, grad);
-        if (fused_small) small_classes(b, 1, grad);
+        if (b.has_small) side[0].record_fork(main);
+        clear_dead_tiles(b, grad);
+        joint_forward(b);
+        if (b.has_small) { small_classes(b, 0, grad); small_classes(b, 1, grad); }
         // 3-4 the staged single-tumour problems (the paired rows' after the joint forward solve)
-        if (!own_forked) staged_fwd(0);
-        staged_fwd(1);
+        if (!own_apart) staged_fwd(main, b, 0, grad);
+        staged_fwd(main, b, 1, grad);
         if (grad) {
-          if (!own_forked) staged_adj(0);
-          staged_adj(1);
-          // (the 1024-thread class of the paired small-space launches ran on its side stream next to the staged kernels above:
+          if (!own_apart) staged_adj(main, b, 0);
+          staged_adj(main, b, 1);
+          // (the 1024-thread class of the paired small-space launches ran on its side lane next to the staged kernels above:
           // the joint adjoint is the first consumer of what it wrote)
-          small_join(1);
-          if (nJ) {
-            // 5 joint adjoint: right-hand side D_obs * scatter(q_S) formed on the fly inside the solve
-            if (cfg.plan.use_jacobi) zero(rhsJ.p, b.vecJ);
-            for (int part = 0; part < 2 && !b.stg[1].paired.empty(); ++part) {
-              if (b.stg[1].paired.size() >= 256)
-                hipLaunchKernelGGL((k_scatter_marg<T, 1024>), dim3((unsigned)b.stg[1].paired.size()), dim3(1024), 0, stream, db.pats.p, db.dJ.p,
-                                   db.dS.p, d_par.p, qS.p, rhsS.p, cfg.plan.use_jacobi ? rhsJ.p : nullptr, dots.p, part, db.stg[1].paired.p);
-              else
-              hipLaunchKernelGGL((k_scatter_marg<T>), dim3((unsigned)b.stg[1].paired.size()), dim3(BLOCK), 0, stream, db.pats.p, db.dJ.p,
-                                 db.dS.p, d_par.p, qS.p, rhsS.p, cfg.plan.use_jacobi ? rhsJ.p : nullptr, dots.p, part, db.stg[1].paired.p);
-              HIPCHECK(hipGetLastError());
-            }
-            if (cfg.plan.use_jacobi) solve(true, LJ, qJ.p, lidgJ.p, rhsJ.p, 0, nullptr);
-            else psolve(true, b, qJ.p, 3);
-            // 6 joint gradient (accumulators cleared at the start of the batch)
-            if (!cfg.plan.use_jacobi) {
-              // algorithmic bytes: the seeded halves of pi and q_J read once
-              const double mbytes = (double)b.vecJ * sizeof(T);
-              timed(MMHN_K_PCLASS, mbytes, [&]() {
-                if (b.wdirect) {                                                  // window-layout problems: both classes, two reads
-                  const int nW = (int)b.wd.size();
-                  hipLaunchKernelGGL((k_wclass<T>), dim3((unsigned)std::min(nW, cfg.plan.n_cu)), dim3(WROWS), wclass_lds<T>(), stream, db.dJ.p, db.wd.p, nW, pi.p, qJ.p, Abuf.p);
-                }
-                // the problems in index order: work items (class passes of a problem cut into ranges + its eq block's flows)
-                // on short launches, one workgroup per problem on long ones
-                if (!b.pcl.empty())
-                  hipLaunchKernelGGL((k_pclass<T, true>), dim3((unsigned)b.pcl.size()), dim3(CMB), PC_LDS_ELEMS * sizeof(T), stream, db.dJ.p, db.wd.p, pi.p, qJ.p, Abuf.p, db.pcl.p);
-                else if ((int)b.wd.size() < nJ || !b.wdirect)
-                  hipLaunchKernelGGL((k_pclass<T, false>), dim3(nJ), dim3(CMB), PC_LDS_ELEMS * sizeof(T), stream, db.dJ.p, db.wd.p, pi.p, qJ.p, Abuf.p);
-              });
-              if (!b.mapX.empty())
-                hipLaunchKernelGGL((k_class_marg<T>), dim3((unsigned)b.mapX.size()), dim3(CMB), 2 * sizeof(T) << TB, stream,
-                                   db.dJ.p, db.mapX.p, pi.p, qJ.p, Abuf.p);
-            } else {
-              hipLaunchKernelGGL((k_class_marg<T>), dim3(tJ), dim3(CMB), 2 * sizeof(T) << TB, stream, db.dJ.p,
-                                 db.mapJ.p, pi.p, qJ.p, Abuf.p);
-            }
-            HIPCHECK(hipGetLastError());
-            // (its own launch: folded into the workgroups of k_pclass it cost more than the launch - k_pclass 20.5 -> 21.9 ms
-            // on the bench cohort, the LUAD evaluation +25 us; short launches run it as work items of k_pclass)
-            if (b.pcl.empty()) {
-              hipLaunchKernelGGL((k_eq_flows<T>), dim3(nJ), dim3(BLOCK), 0, stream, db.dJ.p, db.wd.p, pi.p, qJ.p, Abuf.p);
-              HIPCHECK(hipGetLastError());
-            }
-            launch_grad_rows(db.dJ.p, nJ, b.maxkcJ, Abuf.p, nullptr, nullptr, GJ.p, -1, db.grcJ, DJ.p, gjs);
-          }
-          // 7 assembly
+          side[1].join(main);
+          if (nJ) { joint_adjoint(b); joint_gradient(b); }
         }
-        if (fused_small) { small_join(0); small_join(1); }
-        if (own_forked) HIPCHECK(hipStreamWaitEvent(stream, ev_join[2], 0));
-        const AsmArgs<T> aa{db.pats.p, db.dJ.p, db.dS.p, d_par.p, GS.p, GJ.p, gjs, dots.p, DJ.p, (long long)nJ * N, bmS.p, lp.p, N,
-                            grad ? 1 : 0};
-        const int nelem = grad ? st : 1;
-        hipLaunchKernelGGL((k_finalize<T>), dim3(npat), dim3(BLOCK), 0, stream, aa, out.p);
-        HIPCHECK(hipGetLastError());
-        if (mix && sweep == 0) {
-          hipLaunchKernelGGL(k_mix_gather, dim3((npat + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, db.pats.p, npat, out.p, st, gd.lpc.p);
-          HIPCHECK(hipGetLastError());
-          if (batches.size() == 1) launch_mix();
-        }
-        if (last_sweep && !reduce_behind) reduce_batch(b, nelem);
-        if (host_out && last_sweep) {
-          std::vector<double> tmp((size_t)npat * st);
-          HIPCHECK(hipMemcpyAsync(tmp.data(), out.p, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-          HIPCHECK(hipStreamSynchronize(stream));
-          check_abort();
-          for (int i = 0; i < npat; ++i)
-            std::memcpy(host_out + (size_t)b.pats[i].row * st, tmp.data() + (size_t)i * st, st * sizeof(double));
-        }
+        for (Lane& l : side) l.join(main);
+        finalize_batch(b, grad, mix && sweep == 0);
+        if (last_sweep && !reduce_behind) reduce_batch(b, grad ? stride() : 1);
+        if (host_out && last_sweep) download_rows(b, host_out);
       }
     }
     if (reduce_behind) {
-      launch_mix();
+      launch_mix(*this, main);
       for (const Batch& b : batches) reduce_batch(b, 1);
     }
     time_kernels = true;
     if (host_sums) {
-      std::vector<double> hs(2 * st);
-      HIPCHECK(hipMemcpyAsync(hs.data(), sums.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-      HIPCHECK(hipStreamSynchronize(stream));
-      check_abort();
-      std::memcpy(host_sums, hs.data(), hs.size() * sizeof(double));
+      download_sums(host_sums);
       finish_eval(t0);
     }
   }
@@ -1183,13 +1044,13 @@ struct Engine : EngineBase {
     double flag = 0.0;
     if (w_combined) { flag = reduce_flag; reduce_flag = 0.0; }
     pack_mode = w_combined ? 2 : 1;
-    pack_a = w_combined ? *w_combined : count_em(); pack_b = w_combined ? flag : count_pat(); pack_dst = packed;
+    pack_a = w_combined ? *w_combined : counts().em; pack_b = w_combined ? flag : counts().pat; pack_dst = packed;
     packed_in_eval = false;
     struct Unset { int& m; ~Unset() { m = 0; } } unset{pack_mode};
     evaluate(lt, ldp, ldm, grad, nullptr, nullptr);
     if (!packed_in_eval) {                                 // (no batch: an empty cohort)
       if (w_combined) hipLaunchKernelGGL(k_pack_wsums, dim3(2), dim3(256), 0, stream, sums.p, N, *w_combined, packed, flag);
-      else hipLaunchKernelGGL(k_pack_sums, dim3(2), dim3(256), 0, stream, sums.p, N, count_em(), count_pat(), packed);
+      else hipLaunchKernelGGL(k_pack_sums, dim3(2), dim3(256), 0, stream, sums.p, N, counts().em, counts().pat, packed);
       HIPCHECK(hipGetLastError());
     }
     const int moved = total + (w_combined ? 1 : 0);            // (the reduce flag rides behind the pre-combined buffer)
@@ -1249,6 +1110,7 @@ struct Engine : EngineBase {
 }  // namespace mmhn
 
 // what is not the cohort evaluation: free functions over an engine's launch helpers
+#include "rowmix_host.h"
 #include "prims.h"
 #include "orders_host.h"
 #include "orderpost_host.h"
@@ -1361,7 +1223,7 @@ static long long unknown_rows(mmhn_handle h) {
 int mmhn_set_row_weights(mmhn_handle h, const double* w, int64_t n) {
   API_BEGIN
   GUARD(h);
-  DISPATCH(h, set_row_weights(w, n));
+  DISPATCH_FN(h, set_row_weights, w, n);
   API_END
 }
 
@@ -1376,7 +1238,7 @@ int mmhn_get_row_weight_sums(mmhn_handle h, double* out3) {
 int mmhn_set_row_groups(mmhn_handle h, const int64_t* ptr, int64_t n_groups, const int64_t* rows, const double* w) {
   API_BEGIN
   GUARD(h);
-  DISPATCH(h, set_row_groups(ptr, n_groups, rows, w));
+  DISPATCH_FN(h, set_row_groups, ptr, n_groups, rows, w);
   API_END
 }
 
@@ -1384,7 +1246,7 @@ int mmhn_group_posteriors(mmhn_handle h, const double* lt, const double* ldp, co
   API_BEGIN
   GUARD(h);
   REQUIRE(lt && ldp && ldm && lp_group && rho, "null pointer");
-  DISPATCH(h, group_posteriors(lt, ldp, ldm, lp_group, rho));
+  DISPATCH_FN(h, group_posteriors, lt, ldp, ldm, lp_group, rho);
   API_END
 }
 

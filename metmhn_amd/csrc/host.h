@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 
 namespace mmhn {
 
@@ -64,6 +65,51 @@ struct DevGuard {
   DevGuard(const DevGuard&) = delete;
   DevGuard& operator=(const DevGuard&) = delete;
 };
+
+// A stream of the engine with what belongs to it.  Every launch helper takes the lane it issues on, so the stream, the flag
+// set of a cooperative launch and the events a stage waits for cannot come apart.
+// flags: index of the engine's coop_flags[] set its cooperative launches use, which also picks their CoopCtl slots
+// (flags * 4 + ...); -1: the lane carries none.  Launches of two lanes may be in flight together, so two lanes that both
+// issue cooperative launches never share a set.
+// fork / join: a side lane waits for a point of the main lane (begin), and the main lane later for the side lane's last
+// launch (end on the side lane, join on the main one).  The host needs ~25 us for a fork, the launches and the join
+// record, so the point to wait for may be recorded ahead of time (record_fork) and launches of the critical chain be issued
+// before those of the side lane.
+struct Lane {
+  hipStream_t s = nullptr;
+  int flags = -1;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;     // (created once, hipEventDisableTiming)
+  bool forked = false;                                 // launches of an evaluation in flight that the main lane has not joined
+  bool fork_recorded = false;                          // ev_fork was recorded ahead of time
+  void record_fork(const Lane& main) {
+    HIPCHECK(hipEventRecord(ev_fork, main.s));
+    fork_recorded = true;
+  }
+  void begin(const Lane& main) {
+    if (!fork_recorded) HIPCHECK(hipEventRecord(ev_fork, main.s));
+    fork_recorded = false;
+    HIPCHECK(hipStreamWaitEvent(s, ev_fork, 0));
+    forked = true;
+  }
+  void end() { HIPCHECK(hipEventRecord(ev_join, s)); }
+  void join(const Lane& main) {
+    if (forked) HIPCHECK(hipStreamWaitEvent(main.s, ev_join, 0));
+    forked = false;
+  }
+  // (an evaluation that threw between a fork and its join must not leave its flags to the next one: the side stream
+  // would wait for the previous evaluation's event and start before this one's parameters are up)
+  void reset() { forked = fork_recorded = false; }
+};
+
+// Run-time booleans as compile-time arguments of a generic lambda, to pick a template instantiation:
+//   with_flags([&](auto tr, auto jac) { launch k<T, tr(), jac()> }, transposed, lidg != nullptr);
+template <typename F>
+void with_flags(F&& f) { f(); }
+template <typename F, typename... Bs>
+void with_flags(F&& f, bool b, Bs... rest) {
+  if (b) with_flags([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+  else with_flags([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
 
 // MMHN_* environment knobs: an integer (fallback when unset), a switch (any value but 0 turns it on), a keyword
 inline bool env_set(const char* name) { return std::getenv(name) != nullptr; }

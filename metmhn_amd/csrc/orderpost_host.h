@@ -124,7 +124,7 @@ void opr_rows(Engine<T>& E, const double* lt, const double* obs1, const double* 
       dd.alloc(descs.size()); dmap.alloc(map.size());
       HIPCHECK(hipMemcpyAsync(dd.p, descs.data(), descs.size() * sizeof(Desc), hipMemcpyHostToDevice, E.stream));
       HIPCHECK(hipMemcpyAsync(dmap.p, map.data(), map.size() * sizeof(int2), hipMemcpyHostToDevice, E.stream));
-      E.launch_diag(dd.p, dmap.p, (int)map.size(), nullptr, tab.p, nullptr, KD_DQ);
+      E.launch_diag(E.main, dd.p, dmap.p, (int)map.size(), nullptr, tab.p, nullptr, KD_DQ);
     }
     if (boff) d_bytes.alloc((size_t)boff);
     if (!small.empty()) {

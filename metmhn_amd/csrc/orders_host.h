@@ -101,7 +101,7 @@ void likeliest_orders(Engine<T>& E, const double* lt, const double* obs1, const 
       B.dd.alloc(descs.size()); B.map.alloc(map.size());
       HIPCHECK(hipMemcpyAsync(B.dd.p, descs.data(), descs.size() * sizeof(Desc), hipMemcpyHostToDevice, E.stream));
       HIPCHECK(hipMemcpyAsync(B.map.p, map.data(), map.size() * sizeof(int2), hipMemcpyHostToDevice, E.stream));
-      E.launch_diag(B.dd.p, B.map.p, (int)map.size(), nullptr, B.tab.p, nullptr, KD_DQ);
+      E.launch_diag(E.main, B.dd.p, B.map.p, (int)map.size(), nullptr, B.tab.p, nullptr, KD_DQ);
     }
     const double* g_lt = B.par.p;
 #define ORD_ARGS E.stream, B.rows.p + off, g_lt, g_lt + E.N * E.N, g_lt + E.N * E.N + E.N, E.N, cap, B.tab.p, B.fvec.p, B.fbp.p, \

@@ -38,7 +38,7 @@ void mini_setup(Engine<T>& E, Mini<T>& m, const Desc& d) {
   HIPCHECK(hipMemcpyAsync(m.dd.p, &m.d, sizeof(Desc), hipMemcpyHostToDevice, E.stream));
   HIPCHECK(hipMemcpyAsync(m.map.p, mp.data(), mp.size() * sizeof(int2), hipMemcpyHostToDevice, E.stream));
   m.tab.alloc((size_t)std::max<long long>(table_size(m.d), 1));
-  E.prep(m.dd.p, 1, m.tab.p);
+  E.prep(E.main, m.dd.p, 1, m.tab.p);
   HIPCHECK(hipStreamSynchronize(E.stream));
 }
 template <typename T>
@@ -62,7 +62,7 @@ void api_kronvec(Engine<T>& E, const Desc& d, const double* p, double* y, bool d
   const size_t V = (size_t)1 << d.k;
   up(E, m.a, p, V);
   m.b.alloc(V);
-  E.poison_fill(m.b.p, (long long)V);
+  E.poison_fill(E.main, m.b.p, (long long)V);
   if (d.k > TB) {
     std::vector<int2> live;
     for (int tl = 0; tl < m.ntiles; ++tl) if (!dead_tile(m.d, (uint32_t)tl)) live.push_back(make_int2(0, tl));
@@ -74,12 +74,12 @@ void api_kronvec(Engine<T>& E, const Desc& d, const double* p, double* y, bool d
     HIPCHECK(hipMemsetAsync(m.b.p, 0, V * sizeof(T), E.stream));      // structurally zero tiles are not launched
     hipLaunchKernelGGL((k_hx<T>), dim3((unsigned)live.size()), dim3(64), 0, E.stream, m.dd.p, dlive.p, m.tab.p, hxt.p, d.k);
     HIPCHECK(hipGetLastError());
-    E.launch_kv(tr, m.dd.p, dlive.p, (int)live.size(), d.k, m.a.p, m.b.p, m.tab.p, hxt.p);
+    E.launch_kv(E.main, tr, m.dd.p, dlive.p, (int)live.size(), d.k, m.a.p, m.b.p, m.tab.p, hxt.p);
     HIPCHECK(hipStreamSynchronize(E.stream));
   } else {
-    E.launch_sweep(tr, m.dd.p, m.map.p, m.ntiles, d.k, m.a.p, m.b.p, nullptr, nullptr, 0, nullptr, 0, m.tab.p);
+    E.launch_sweep(E.main, tr, m.dd.p, m.map.p, m.ntiles, d.k, m.a.p, m.b.p, nullptr, nullptr, 0, nullptr, 0, m.tab.p);
   }
-  if (diag) E.launch_diag(m.dd.p, m.map.p, m.ntiles, m.a.p, m.b.p, nullptr, KD_ADDQP);
+  if (diag) E.launch_diag(E.main, m.dd.p, m.map.p, m.ntiles, m.a.p, m.b.p, nullptr, KD_ADDQP);
   down(E, y, m.b.p, V);
 }
 // ---- batched product (kronvec.py:499-539 applied to `batch` vectors of one restricted space): ONE launch over every
@@ -132,7 +132,7 @@ void kv_setup(Engine<T>& E, KvBatch<T>& kb, const Desc& d0, long long batch) {
   HIPCHECK(hipMemcpyAsync(kb.dd.p, ds.data(), ds.size() * sizeof(Desc), hipMemcpyHostToDevice, E.stream));
   HIPCHECK(hipMemcpyAsync(kb.map.p, mp.data(), mp.size() * sizeof(int2), hipMemcpyHostToDevice, E.stream));
   kb.tab.alloc((size_t)std::max<long long>(table_size(d0), 1));
-  E.prep(kb.dd.p, 1, kb.tab.p);                    // one table: every vector lives in the same space
+  E.prep(E.main, kb.dd.p, 1, kb.tab.p);                    // one table: every vector lives in the same space
   kb.use_kv = d0.k > TB;
   if (kb.use_kv) {
     kb.hxl.alloc(lv.size() * (size_t)d0.k);
@@ -145,8 +145,8 @@ void kv_setup(Engine<T>& E, KvBatch<T>& kb, const Desc& d0, long long batch) {
 // fused Jacobi step): all of y is written by one launch
 template <typename T>
 void kv_launch(Engine<T>& E, const KvBatch<T>& kb, bool tr, const T* p, T* y, const T* lidg = nullptr, const T* rhs = nullptr) {
-  if (kb.use_kv) E.launch_kv(tr, kb.dd.p, kb.live.p, kb.nlive, kb.d.k, p, y, kb.tab.p, kb.hxl.p, kb.zmap.p, lidg, rhs);
-  else E.launch_sweep(tr, kb.dd.p, kb.map.p, kb.ntiles, kb.d.k, p, y, lidg, rhs, 0, nullptr, 0, kb.tab.p);
+  if (kb.use_kv) E.launch_kv(E.main, tr, kb.dd.p, kb.live.p, kb.nlive, kb.d.k, p, y, kb.tab.p, kb.hxl.p, kb.zmap.p, lidg, rhs);
+  else E.launch_sweep(E.main, tr, kb.dd.p, kb.map.p, kb.ntiles, kb.d.k, p, y, lidg, rhs, 0, nullptr, 0, kb.tab.p);
 }
 template <typename T>
 void api_kronvec_batched(Engine<T>& E, const Desc& d, long long batch, const double* p, double* y, bool diag, bool tr) {
@@ -157,7 +157,7 @@ void api_kronvec_batched(Engine<T>& E, const Desc& d, long long batch, const dou
   b.alloc(tot);
   HIPCHECK(hipMemsetAsync(b.p, 0xFF, tot * sizeof(T), E.stream));   // NaN pattern: every element must be written by the launch
   kv_launch(E, kb, tr, a.p, b.p);
-  if (diag) E.launch_diag(kb.dd.p, kb.map.p, kb.ntiles, a.p, b.p, nullptr, KD_ADDQP);
+  if (diag) E.launch_diag(E.main, kb.dd.p, kb.map.p, kb.ntiles, a.p, b.p, nullptr, KD_ADDQP);
   down(E, y, b.p, tot);
 }
 // one fused Jacobi step of R_i_inv_vec (likelihood.py:253-255) for `batch` vectors of one space:
@@ -171,8 +171,8 @@ void api_jacobi_step_batched(Engine<T>& E, const Desc& d, long long batch, const
   up(E, a, p, tot);
   up(E, r, rhs, tot);
   b.alloc(tot); c.alloc(tot);
-  E.poison_fill(c.p, (long long)tot);
-  E.launch_diag(kb.dd.p, kb.map.p, kb.ntiles, nullptr, c.p, nullptr, KD_LIDG);
+  E.poison_fill(E.main, c.p, (long long)tot);
+  E.launch_diag(E.main, kb.dd.p, kb.map.p, kb.ntiles, nullptr, c.p, nullptr, KD_LIDG);
   HIPCHECK(hipMemsetAsync(b.p, 0xFF, tot * sizeof(T), E.stream));
   kv_launch(E, kb, tr, a.p, b.p, c.p, r.p);
   down(E, y, b.p, tot);
@@ -183,8 +183,8 @@ void api_diag(Engine<T>& E, const Desc& d, const double* p, double* outp, int wh
   const size_t V = (size_t)1 << d.k;
   if (p) up(E, m.a, p, V);
   m.b.alloc(V);
-  E.poison_fill(m.b.p, (long long)V);
-  E.launch_diag(m.dd.p, m.map.p, m.ntiles, m.a.p, m.b.p, nullptr, what, pbit);
+  E.poison_fill(E.main, m.b.p, (long long)V);
+  E.launch_diag(E.main, m.dd.p, m.map.p, m.ntiles, m.a.p, m.b.p, nullptr, what, pbit);
   down(E, outp, m.b.p, V);
 }
 // vanilla.x_partial_D_y (vanilla.py:190-203): weighted bit marginals of x * y under the two parts of scal_d_pt
@@ -195,8 +195,8 @@ void api_xDy_single(Engine<T>& E, const Desc& d0, const double* x, const double*
   up(E, m.a, y, V);
   up(E, m.b, x, V);
   m.e.alloc(64);
-  E.poison_fill(m.e.p, 64);
-  E.zero(m.e.p, 64);
+  E.poison_fill(E.main, m.e.p, 64);
+  E.zero(E.main, m.e.p, 64);
   hipLaunchKernelGGL((k_bit_marg<T>), dim3(m.ntiles), dim3(BLOCK), 0, E.stream, m.dd.p, m.map.p, E.d_par.p, m.a.p,
                      m.b.p, m.e.p);
   HIPCHECK(hipGetLastError());
@@ -216,10 +216,10 @@ void api_resolvent(Engine<T>& E, Desc d, const double* dvec, const double* x, do
   up(E, m.a, x, V);
   if (dvec) up(E, m.e, dvec, V);
   m.b.alloc(V); m.c.alloc(V);
-  E.poison_fill(m.b.p, (long long)V);
-  E.poison_fill(m.c.p, (long long)V);
-  E.launch_diag(m.dd.p, m.map.p, m.ntiles, nullptr, m.c.p, m.e.p, KD_LIDG);
-  E.solve(tr, m.plist((long long)V), m.b.p, m.c.p, m.a.p, 0, nullptr);
+  E.poison_fill(E.main, m.b.p, (long long)V);
+  E.poison_fill(E.main, m.c.p, (long long)V);
+  E.launch_diag(E.main, m.dd.p, m.map.p, m.ntiles, nullptr, m.c.p, m.e.p, KD_LIDG);
+  E.solve(E.main, tr, m.plist((long long)V), m.b.p, m.c.p, m.a.p, 0, nullptr);
   down(E, y, m.b.p, V);
 }
 template <typename T>
@@ -230,10 +230,10 @@ void api_xQy_joint(Engine<T>& E, const Desc& d0, const double* x, const double* 
   up(E, m.b, x, V);   // q (left vector)
   m.c.alloc((size_t)a_size(m.d));
   m.e.alloc((size_t)3 * E.N * E.N);
-  E.poison_fill(m.c.p, a_size(m.d));
-  E.poison_fill(m.e.p, 3ll * E.N * E.N);
-  E.zero(m.e.p, 3ll * E.N * E.N);
-  E.zero(m.c.p, a_size(m.d));
+  E.poison_fill(E.main, m.c.p, a_size(m.d));
+  E.poison_fill(E.main, m.e.p, 3ll * E.N * E.N);
+  E.zero(E.main, m.e.p, 3ll * E.N * E.N);
+  E.zero(E.main, m.c.p, a_size(m.d));
   hipLaunchKernelGGL((k_class_marg<T>), dim3(m.ntiles), dim3(CMB), 2 * sizeof(T) << TB, E.stream, m.dd.p, m.map.p,
                      m.a.p, m.b.p, m.c.p);
   HIPCHECK(hipGetLastError());
@@ -243,7 +243,7 @@ void api_xQy_joint(Engine<T>& E, const Desc& d0, const double* x, const double* 
     std::vector<int2> gc = grad_chunks(std::vector<Desc>{m.d}, kd);
     DevArr<int2> dgc; dgc.alloc(gc.size());
     HIPCHECK(hipMemcpy(dgc.p, gc.data(), gc.size() * sizeof(int2), hipMemcpyHostToDevice));
-    E.launch_grad_rows(m.dd.p, 1, d0.k, m.c.p, nullptr, nullptr, m.e.p + kd * E.N * E.N, kd, dgc);
+    E.launch_grad_rows(E.main, m.dd.p, 1, d0.k, m.c.p, nullptr, nullptr, m.e.p + kd * E.N * E.N, kd, dgc);
     HIPCHECK(hipStreamSynchronize(E.stream));
   }
   std::vector<double> g(3 * E.N * E.N);
@@ -257,13 +257,13 @@ void api_xQy_single(Engine<T>& E, const Desc& d0, const double* x, const double*
   up(E, m.a, y, V);
   up(E, m.b, x, V);
   m.e.alloc((size_t)E.N * E.N);
-  E.poison_fill(m.e.p, (long long)E.N * E.N);
-  E.zero(m.e.p, (long long)E.N * E.N);
+  E.poison_fill(E.main, m.e.p, (long long)E.N * E.N);
+  E.zero(E.main, m.e.p, (long long)E.N * E.N);
   {
     std::vector<int2> gc = grad_chunks(std::vector<Desc>{m.d}, GK_S);
     DevArr<int2> dgc; dgc.alloc(gc.size());
     HIPCHECK(hipMemcpy(dgc.p, gc.data(), gc.size() * sizeof(int2), hipMemcpyHostToDevice));
-    E.launch_grad_rows(m.dd.p, 1, d0.k, nullptr, m.a.p, m.b.p, m.e.p, GK_S, dgc);
+    E.launch_grad_rows(E.main, m.dd.p, 1, d0.k, nullptr, m.a.p, m.b.p, m.e.p, GK_S, dgc);
     HIPCHECK(hipStreamSynchronize(E.stream));
   }
   down(E, G, m.e.p, (size_t)E.N * E.N);
@@ -281,8 +281,8 @@ void api_xDy_joint(Engine<T>& E, const Desc& d0, const double* x, const double* 
   up(E, m.a, y, V);
   up(E, m.b, x, V);
   m.e.alloc(64);
-  E.poison_fill(m.e.p, 64);
-  E.zero(m.e.p, 64);
+  E.poison_fill(E.main, m.e.p, 64);
+  E.zero(E.main, m.e.p, 64);
   hipLaunchKernelGGL((k_bit_marg<T>), dim3(m.ntiles), dim3(BLOCK), 0, E.stream, m.dd.p, m.map.p, E.d_par.p, m.a.p,
                      m.b.p, m.e.p);
   HIPCHECK(hipGetLastError());

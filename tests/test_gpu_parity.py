@@ -789,16 +789,16 @@ def test_luad_reduced_anchor(golden):
     np.testing.assert_allclose(gr, g["indep_reg_grad"], rtol=1e-7, atol=1e-10)
 
 
-def test_every_route_in_one_batch(monkeypatch):
-    """Per-problem dispatch (round 5): ONE batch in which all three joint routes and both single-tumour paths are active at
-    once - window-shaped paired rows (k = 15 .. 17; route RT_W once the thresholds are lowered), multi-tile rows outside the window
-    shapes (RT_P), rows with the seeding bit inside the tile and a few deep ones left over (RT_T, the cooperative launch), paired
-    rows whose marginal space exceeds a tile and unpaired rows of 13 - 15 bits (staged kernels, both groups) next to small ones
-    (small-space path).  Random slots, every order, every type; per-patient log-probabilities and gradients against
-    oracle/metmhn_ref.c (reference pass structure) - with the default thresholds (everything on the tile route), with the
-    thresholds at 8 (all routes), and with level-by-level launches."""
+_EVERY_ROUTE = {}
+
+
+def _every_route_case():
+    """The cohort of test_every_route_in_one_batch (n = 16, 78 rows) with its parameters and the per-patient values of
+    oracle/metmhn_ref.c, built once: (n, lt, dp, dm, dat, (lp, d_theta, d_dp, d_dm))."""
+    if _EVERY_ROUTE:
+        return _EVERY_ROUTE["case"]
     from oracle import cref
-    from metmhn_amd import Engine, synthetic
+    from metmhn_amd import synthetic
     n = 16
     rng = np.random.default_rng(516)
     lt, dp, dm = synthetic.random_params(n)
@@ -828,7 +828,23 @@ def test_every_route_in_one_batch(monkeypatch):
         rows.append(r)
     dat = np.array(rows, dtype=np.int8)
     rng.shuffle(dat, axis=0)
-    lp, g, a, b = cref.patients(lt, dp, dm, dat)
+    ref = cref.patients(lt, dp, dm, dat)
+    for x in (lt, dp, dm, dat) + tuple(ref):
+        x.setflags(write=False)
+    _EVERY_ROUTE["case"] = (n, lt, dp, dm, dat, ref)
+    return _EVERY_ROUTE["case"]
+
+
+def test_every_route_in_one_batch(monkeypatch):
+    """Per-problem dispatch (round 5): ONE batch in which all three joint routes and both single-tumour paths are active at
+    once - window-shaped paired rows (k = 15 .. 17; route RT_W once the thresholds are lowered), multi-tile rows outside the window
+    shapes (RT_P), rows with the seeding bit inside the tile and a few deep ones left over (RT_T, the cooperative launch), paired
+    rows whose marginal space exceeds a tile and unpaired rows of 13 - 15 bits (staged kernels, both groups) next to small ones
+    (small-space path).  Random slots, every order, every type; per-patient log-probabilities and gradients against
+    oracle/metmhn_ref.c (reference pass structure) - with the default thresholds (everything on the tile route), with the
+    thresholds at 8 (all routes), and with level-by-level launches."""
+    from metmhn_amd import Engine
+    n, lt, dp, dm, dat, (lp, g, a, b) = _every_route_case()
     for env in ({}, {"MMHN_PSOLVE_MIN": "8", "MMHN_WSOLVE_MIN": "8", "MMHN_POISON": "1"}, {"MMHN_COOP": "0", "MMHN_PSOLVE_MIN": "8"}):
         for k_, v_ in env.items():
             monkeypatch.setenv(k_, v_)
@@ -842,6 +858,51 @@ def test_every_route_in_one_batch(monkeypatch):
         np.testing.assert_allclose(r[3], b, rtol=1e-7, atol=1e-10, err_msg=str(env))
         for k_ in env:
             monkeypatch.delenv(k_)
+
+
+def test_forked_and_unforked_issue_agree(monkeypatch):
+    """The same evaluation issued both ways the engine knows: at defaults the staged own-problem group runs on its side lane
+    (second flag set of the cooperative launches) and the small-space classes are forked; with MMHN_TIME_KERNELS=1 every
+    launch of the batch goes to the main lane.  The cohort of test_every_route_in_one_batch with the thresholds at 8, so
+    that every route issues; each engine evaluates three times in a row and every evaluation is compared.  fp64 against
+    oracle/metmhn_ref.c at the tolerances of that test; fp32 against the fp64 engine at the tolerances of
+    test_fp32_engine_close_to_fp64.  A lane passed wrongly picks the wrong flag set or waits for the wrong event.
+    (The gradient kernels add with atomics: no bitwise comparison of gradients.  The lp vectors of one engine's three runs
+    are identical.)"""
+    from metmhn_amd import Engine
+    n, lt, dp, dm, dat, ref = _every_route_case()
+    monkeypatch.setenv("MMHN_PSOLVE_MIN", "8")
+    monkeypatch.setenv("MMHN_WSOLVE_MIN", "8")
+    runs = {}
+    for dt in ("f64", "f32"):
+        for timed in (False, True):
+            if timed:
+                monkeypatch.setenv("MMHN_TIME_KERNELS", "1")
+            else:
+                monkeypatch.delenv("MMHN_TIME_KERNELS", raising=False)
+            e = Engine(n, dtype=dt)
+            e.set_cohort(dat)
+            e.reset_counters()
+            runs[dt, timed] = [e.patient_grads(lt, dp, dm) for _ in range(3)]
+            c = e.counters()
+            e.close()
+            # (launches are counted where they are timed: the cohort is far below the size that is timed unasked, so the
+            # two engines did issue differently)
+            counted = sum(c[k]["launches"] for k in ("psolve_fwd", "psolve_adj", "csolve_fwd", "csolve_adj", "other_solve"))
+            assert (counted > 0) == timed, (dt, timed, c)
+    for (dt, timed), evals in runs.items():
+        tag = f"{dt} {'main lane only' if timed else 'forked'}"
+        for i, r in enumerate(evals):
+            np.testing.assert_array_equal(r[0], evals[0][0], err_msg=f"{tag}: lp of evaluation {i} against evaluation 0")
+            if dt == "f64":
+                np.testing.assert_allclose(r[0], ref[0], rtol=1e-9, atol=1e-12, err_msg=f"{tag} #{i} lp")
+                for x, y, nm in zip(r[1:], ref[1:], ("d_theta", "d_dp", "d_dm")):
+                    np.testing.assert_allclose(x, y, rtol=1e-7, atol=1e-10, err_msg=f"{tag} #{i} {nm}")
+            else:
+                r64 = runs["f64", timed][i]
+                np.testing.assert_allclose(r[0], r64[0], rtol=2e-5, err_msg=f"{tag} #{i} lp")
+                for x, y, nm in zip(r[1:], r64[1:], ("d_theta", "d_dp", "d_dm")):
+                    np.testing.assert_allclose(x, y, rtol=2e-3, atol=2e-5, err_msg=f"{tag} #{i} {nm}")
 
 
 def test_reference_name_mirrors_one_event_and_all_zero(golden):
