@@ -512,6 +512,30 @@ int mmhn_seeding_forecasts(mmhn_handle h, const double* log_theta, const double*
                            int64_t n_rows, int until, double* p_seed, double* time, double* before, double* with_seed,
                            double* n_before, int32_t* status);
 
+/* ---- seeding landscape: the forecast scalars of every genotype ------------------------------
+ * mmhn_seeding_landscape: ONE backward sweep over all 2^n_mut genotypes of the model gives every genotype's scalar answers of
+ * mmhn_seeding_forecasts.  x is a genotype code, bit j = mutation j held (the order of genotypes[r][j]); with the rates of
+ * mmhn_seeding_forecasts and j over the mutations x does not hold
+ *   p_seed(x)      = (sigma(x) + sum_j lambda_j(x) p_seed(x + j)) / den(x)
+ *   time(x)        = (1        + sum_j lambda_j(x) time(x + j)) / den(x)
+ *   new_events(x)  = (           sum_j lambda_j(x) (1 + new_events(x + j))) / den(x)                  = the sum of `before`
+ *   seed_events(x) = (           sum_j lambda_j(x) (p_seed(x + j) + seed_events(x + j))) / den(x)     = the sum of `with_seed`
+ * from the full genotype down (metmhn_amd/csrc/landscape.h: tiles of 2^10 codes finished in LDS, one launch per popcount of
+ * the tile number).  No reference counterpart.  fp64 engines only; independent of mmhn_set_cohort.
+ *   genotypes [n_rows][n_mut]                   int8 queries, 1 = held, 0 = not; n_rows = 0 is valid
+ *   values [n_rows][4]                          p_seed, time, new_events, seed_events of every query
+ *   status [n_rows]                             MMHN_ORD_OK, or MMHN_ORD_INVALID with MMHN_ORD_BAD_ENTRY in the high half for
+ *                                               an entry other than 0 / 1: that row's values are NaN, the others unaffected
+ *   full                                        null, or [4][2^n_mut]: the four values of every genotype by code
+ * The call fails (return 1, mmhn_last_error names the bytes needed) when 32 B x 2^n_mut, the rate tables and the tile list
+ * (4 B per 2^10 codes) exceed mmhn_set_workspace_limit: there is no partial landscape and nothing is launched.  It fails
+ * for until = 0 when the seeding rate of the full genotype underflows to 0, as mmhn_seeding_forecasts does.  Mutation rates
+ * of 0 are fine and give exact zeros.  Every shape depends on n_mut alone and there are no atomics: a genotype's four
+ * values do not depend on the queries or on an earlier call.
+ */
+int mmhn_seeding_landscape(mmhn_handle h, const double* log_theta, const double* obs1, int until, const int8_t* genotypes,
+                           int64_t n_rows, double* values, int32_t* status, double* full);
+
 /* ---- measurement -------------------------------------------------------------------
  * mmhn_bench_kronvec: `batch` resident copies of a 2^k vector, `iters` back-to-back
  * launches of mmhn_kronvec_batched's launch (diag = 0: y = Q_off p into a NaN-filled y, every tile of every vector,
@@ -542,7 +566,7 @@ typedef struct {
   int32_t comm_rank;  /* this engine's rank in it (ncclCommUserRank), -1: none */
 } mmhn_counters;
 /* ABI version of this header: bumped whenever an exported signature or structure changes (4: mmhn_bench_kronvec has its
- * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions, mmhn_order_samples, mmhn_simulate_pairs, mmhn_order_times, mmhn_order_snapshots and mmhn_seeding_forecasts were added within version 8, purely additive changes).  A client built against another header must refuse to run:
+ * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions, mmhn_order_samples, mmhn_simulate_pairs, mmhn_order_times, mmhn_order_snapshots, mmhn_seeding_forecasts and mmhn_seeding_landscape were added within version 8, purely additive changes).  A client built against another header must refuse to run:
  * mmhn_abi_version() != MMHN_ABI_VERSION (metmhn_amd/_lib.py checks it on load). */
 #define MMHN_ABI_VERSION 8
 int mmhn_abi_version(void);

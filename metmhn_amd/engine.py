@@ -626,6 +626,29 @@ class Engine:
             n_before.ctypes.data_as(f64p), status.ctypes.data_as(_lib.i32p)))
         return p_seed, time, before, with_seed, n_before, status
 
+    # ---- seeding landscape
+    def seeding_landscape(self, log_theta, obs1, genotypes, until="seeding", full=False):
+        """The four forecast scalars of every genotype of the model from one backward sweep over all 2^n genotype codes
+        (mmhn_seeding_landscape), until "seeding" or "observation", read at the rows of int8 `genotypes` [R, n] (1 = held; R
+        may be 0): float64 values [R, 4] = p_seed, time, new_events, seed_events, int32 status [R] (0 ok, 2 with reason code
+        8 in status >> 16 for an entry other than 0 / 1, whose values are NaN), and with full=True the whole landscape
+        [4, 2^n] by code (bit j = mutation j), else None.  Raises when 32 B x 2^n and the tile list exceed the workspace
+        limit."""
+        if until not in ("seeding", "observation"):
+            raise ValueError("until must be 'seeding' or 'observation'")
+        lt, ltp = self._theta(log_theta); a, ap = self._rates(obs1, "obs1")
+        g = np.ascontiguousarray(np.asarray(genotypes).astype(np.int8))
+        if g.ndim != 2 or g.shape[1] != self.n:
+            raise ValueError(f"genotypes must be a 2-D array [R, {self.n}]")
+        R = g.shape[0]
+        values = np.empty((R, 4))                                # (the library fills it with NaN first)
+        status = np.zeros(R, dtype=np.int32)
+        whole = np.empty((4, 1 << self.n)) if full else None
+        _lib.check(self.lib.mmhn_seeding_landscape(
+            self.h, ltp, ap, 0 if until == "seeding" else 1, g.ctypes.data_as(i8p), R, values.ctypes.data_as(f64p),
+            status.ctypes.data_as(_lib.i32p), whole.ctypes.data_as(f64p) if full else None))
+        return values, status, whole
+
     # ---- measurement
     def bench_kronvec(self, log_theta, state, batch, iters, transpose=False, jacobi=False, tiles=False):
         """ms per launch of mmhn_kronvec_batched's launch (or the fused Jacobi step); tiles=True also returns

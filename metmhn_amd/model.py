@@ -342,8 +342,41 @@ class SeedingForecasts(SeedingForecast):
         return np.nansum(self.before, axis=1)
 
 
+class SeedingLandscape(SimpleNamespace):
+    """The four forecast scalars of many genotypes of one model, arrays over the genotypes `codes` (bit j of a code =
+    mutation j held): `p_seed`, `time` as SeedingForecast has them, `new_events` = the expected number of new mutations before
+    the seeding or the clock (SeedingForecasts.expected_new_events()), `seed_events` = the expected number of new mutations
+    the seeding cell carries where the seeding comes first (the sum of with_seed).  MetMHN.seeding_landscape returns every
+    genotype, codes = 0 .. 2^n - 1; seeding_landscape_at the rows it was given.  No reference counterpart."""
+
+    FIELDS = ("p_seed", "time", "new_events", "seed_events")
+
+    def __init__(self, p_seed, time, new_events, seed_events, codes):
+        super().__init__(p_seed=p_seed, time=time, new_events=new_events, seed_events=seed_events, codes=codes)
+
+    def neighbours(self, genotype) -> np.ndarray:
+        """[n + 1, 4]: the four values of `genotype` (n entries 0 / 1) in row 0 and, in row 1 + j, of the genotype one
+        mutation j further - NaN where the genotype holds j already.  A lookup on a full landscape."""
+        size = len(self.codes)
+        n = size.bit_length() - 1
+        if size != 1 << n or not np.array_equal(self.codes, np.arange(size)):
+            raise ValueError("neighbours needs a full landscape (MetMHN.seeding_landscape)")
+        g = np.asarray(genotype)
+        if g.shape != (n,) or not np.isin(g, (0, 1)).all():
+            raise ValueError(f"genotype must have {n} entries 0 / 1")
+        x = int(sum(1 << j for j in range(n) if g[j]))
+        at = lambda code: [float(getattr(self, name)[code]) for name in self.FIELDS]
+        out = np.full((n + 1, 4), np.nan)
+        out[0] = at(x)
+        for j in range(n):
+            if not g[j]:
+                out[1 + j] = at(x | 1 << j)
+        return out
+
+
 _FORECAST_UNTIL = ("seeding", "observation")
 _FORECAST_HOST_MAX = 24          # free mutations the host definition takes on: f x 2^f doubles of rates
+_LANDSCAPE_HOST_MAX = 24         # mutations the host landscape takes on: n x 2^n doubles of rates
 _NO_SEEDING_EXIT = ("the seeding rate of the full genotype underflows to 0 (a theta[n, n] of -1e10, as a fit without seeded "
                     "samples leaves it?): until='seeding' the full state would have no exit; use until='observation'")
 
@@ -829,6 +862,92 @@ class MetMHN:
                                  "(at most 30 free mutations, and the lattice has to fit the workspace limit); "
                                  "there is no host fallback")
         return SeedingForecasts(*(c[inverse] for c in cols), self._forecast_next(g, until))
+
+    # ------------------------------------------------------------------ seeding landscape
+    def _landscape_host(self, until: str) -> np.ndarray:
+        """[4, 2^n]: the definition of the landscape, level by level over the popcount of the code, descending."""
+        th, n = self._pt_log_theta, self.n
+        if n > _LANDSCAPE_HOST_MAX:
+            raise ValueError(f"{n} mutations: the host landscape stops at {_LANDSCAPE_HOST_MAX} ({n} x 2^{n} doubles of "
+                             "rates); use backend='device'")
+        size = 1 << n
+        idx = np.arange(size)
+        level = _subset_sums(np.ones(n)).astype(np.int64)
+        lam = [np.exp(th[j, j] + _subset_sums(np.where(np.arange(n) == j, 0.0, th[j, :n]))) for j in range(n)]
+        sig = np.exp(th[n, n] + _subset_sums(th[n, :n]))
+        kap = np.exp(_subset_sums(self.obs1[:n])) if until == "observation" else np.zeros(size)
+        p, t, e, s = (np.zeros(size) for _ in range(4))
+        for lev in range(n, -1, -1):
+            xs = idx[level == lev]
+            n0, n1, n2, n3, den = (np.zeros(len(xs)) for _ in range(5))
+            for j in range(n):
+                m = (xs >> j & 1) == 0
+                x = xs[m]
+                y = x | 1 << j
+                r = lam[j][x]
+                n0[m] += r * p[y]
+                n1[m] += r * t[y]
+                n2[m] += r * (1.0 + e[y])
+                n3[m] += r * (p[y] + s[y])
+                den[m] += r
+            den = den + sig[xs] + kap[xs]
+            p[xs] = (sig[xs] + n0) / den
+            t[xs] = (1.0 + n1) / den
+            e[xs] = n2 / den
+            s[xs] = n3 / den
+        return np.stack((p, t, e, s))
+
+    def seeding_landscape(self, until: str = "seeding", backend: str = "device", max_bytes: int = 2 ** 31) -> "SeedingLandscape":
+        """seeding_forecast's p_seed, time, sum of before and sum of with_seed of EVERY genotype of the model: arrays over
+        the 2^n genotype codes (bit j of a code = mutation j held), from one backward pass over the lattice of all genotypes
+        instead of a forward pass per genotype.  With the rates of seeding_forecast and j over the mutations x does not hold:
+            p_seed(x)      = (sigma(x) + sum_j lambda_j(x) p_seed(x + j)) / den(x)
+            time(x)        = (1 + sum_j lambda_j(x) time(x + j)) / den(x)
+            new_events(x)  = sum_j lambda_j(x) (1 + new_events(x + j)) / den(x)
+            seed_events(x) = sum_j lambda_j(x) (p_seed(x + j) + seed_events(x + j)) / den(x)
+        starting at the full genotype, which has no j.
+
+        backend="device": one call of the HIP library (mmhn_seeding_landscape), 32 B x 2^n of workspace and as much here for
+        the result; a ValueError names the bytes when that exceeds `max_bytes` (2 GiB: n <= 26).  backend="host": the
+        definition in NumPy, level by level, n <= 24."""
+        if until not in _FORECAST_UNTIL:
+            raise ValueError("until must be 'seeding' or 'observation'")
+        if backend not in ("device", "host"):
+            raise ValueError("backend must be 'device' or 'host'")
+        th, n = self._pt_log_theta, self.n
+        if until == "seeding" and np.exp(th[n, n] + th[n, :n].sum()) == 0.0:
+            raise ValueError(_NO_SEEDING_EXIT)
+        if backend == "host" and n > _LANDSCAPE_HOST_MAX:
+            self._landscape_host(until)             # (raises: the message points to the device)
+        if 32 << n > max_bytes:
+            raise ValueError(f"{n} mutations: a landscape of 2^{n} genotypes needs {32 << n} bytes, more than max_bytes = "
+                             f"{int(max_bytes)}; seeding_landscape_at reads single genotypes off the device's landscape")
+        if backend == "host":
+            whole = self._landscape_host(until)
+        else:
+            from .jx import engine
+            _, _, whole = engine(n).seeding_landscape(self.log_theta, self.obs1, np.zeros((0, n), dtype=np.int8), until, full=True)
+        return SeedingLandscape(*whole, np.arange(1 << n))
+
+    def seeding_landscape_at(self, genotypes, until: str = "seeding", backend: str = "device") -> "SeedingLandscape":
+        """The four values of seeding_landscape at the rows of `genotypes` [R, n] (0 / 1), [R] each, with the rows' codes:
+        the whole landscape is swept on the device (32 B x 2^n of its workspace, any n the engine takes) and only the rows
+        come back - what a cohort of many rows needs, whatever its size.  backend="host": the NumPy landscape, n <= 24.
+        An entry other than 0 / 1 raises ValueError("row i: ...") as seeding_forecasts does."""
+        if backend not in ("device", "host"):
+            raise ValueError("backend must be 'device' or 'host'")
+        g = self._forecast_checks(genotypes, until)
+        n = self.n
+        codes = g @ (1 << np.arange(n, dtype=np.int64))
+        if backend == "host":
+            values = self._landscape_host(until)[:, codes].T
+        else:
+            from .jx import engine
+            values, status, _ = engine(n).seeding_landscape(self.log_theta, self.obs1, g.astype(np.int8), until)
+            bad = np.flatnonzero(status != 0)
+            if bad.size:
+                raise ValueError(f"row {int(bad[0])}: a genotype entry is neither 0 nor 1")
+        return SeedingLandscape(*(np.ascontiguousarray(values[:, k]) for k in range(4)), codes)
 
     def likelihood(self, order, met_status: str, first_obs: str = None) -> float:
         """model.py:295-376: probability of exactly this order of events being what is observed."""

@@ -454,6 +454,27 @@ def seeding_forecast(log_theta, log_d_p, log_d_m, dat, until: str = "observation
     return SeedingForecasts(**out), met_status_posterior(log_theta, log_d_p, log_d_m, dat)
 
 
+def seeding_risk(log_theta, log_d_p, log_d_m, dat, until: str = "observation", backend: str = "device"):
+    """The scalar answers of seeding_forecast for every row of `dat` with a primary tumour of its own (types 0, 1 and 4),
+    from ONE backward sweep over all genotypes of the model instead of a lattice per distinct genotype: (risk, seeded).
+    risk: a model.SeedingLandscape over the rows - p_seed, time, new_events, seed_events [n_pat] of the rows' PT genotypes
+    dat[:, 0:2*n:2] with obs1 = log_d_p (MetMHN.seeding_landscape_at), NaN and code -1 for the rows of types 2 and 3;
+    seeded [n_pat]: met_status_posterior's probability that the seeding has already happened, as seeding_forecast returns
+    it."""
+    from .model import MetMHN, SeedingLandscape
+    arr = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
+    n = (arr.shape[1] - 3) // 2
+    pick = np.isin(arr[:, -1], (0, 1, 4))
+    out = {name: np.full(arr.shape[0], np.nan) for name in SeedingLandscape.FIELDS}
+    codes = np.full(arr.shape[0], -1, dtype=np.int64)
+    if pick.any():
+        got = MetMHN(log_theta, log_d_p, log_d_m).seeding_landscape_at(arr[pick][:, 0:2 * n:2], until, backend)
+        for name in SeedingLandscape.FIELDS:
+            out[name][pick] = getattr(got, name)
+        codes[pick] = got.codes
+    return SeedingLandscape(**out, codes=codes), met_status_posterior(log_theta, log_d_p, log_d_m, dat)
+
+
 def _unpack(params, n_total):
     params = np.asarray(params, dtype=np.float64)
     return (params[0:n_total ** 2].reshape((n_total, n_total)), params[n_total ** 2:n_total * (n_total + 1)],
