@@ -536,6 +536,34 @@ int mmhn_seeding_forecasts(mmhn_handle h, const double* log_theta, const double*
 int mmhn_seeding_landscape(mmhn_handle h, const double* log_theta, const double* obs1, int until, const int8_t* genotypes,
                            int64_t n_rows, double* values, int32_t* status, double* full);
 
+/* ---- genotype distribution of the primary tumour ---------------------------------------------
+ * mmhn_genotype_distribution: ONE forward sweep over all 2^n_mut genotypes gives the probability that the primary tumour
+ * is observed with genotype x and has not seeded (U), or has seeded by then (S).  The primary tumour is an autonomous chain
+ * on (genotype, seeded or not): theta[i][n], i < n, is not read.  With the rates of the seeding forecasts, j over the
+ * mutations x does not hold and b over the ones it holds
+ *   kappa0(x) = exp(sum over i in x of obs1[i]),  kappa1(x) = kappa0(x) exp(obs1[n]),  L(x) = sum_j lambda_j(x)
+ *   F0(empty) = 1,  F0(y) = sum_b G0(y - b) lambda_b(y - b),                    G0 = F0 / (L + sigma + kappa0)
+ *                   F1(y) = G0(y) sigma(y) + sum_b G1(y - b) lambda_b(y - b),   G1 = F1 / (L + kappa1)
+ *   U = kappa0 G0 = exp(lp) of the cohort row of type 0 with that genotype,  S = kappa1 G1 = the same of type 1
+ * from the empty genotype up (metmhn_amd/csrc/genodist.h: the tiles of the seeding landscape, one launch per popcount of the
+ * tile number, ascending).  fp64 engines only; independent of the loaded cohort.
+ *   genotypes [n_rows][n_mut]                   int8 queries, 1 = held, 0 = not; n_rows = 0 is valid
+ *   values [n_rows][2]                          U, S of every query
+ *   status [n_rows]                             MMHN_ORD_OK, or MMHN_ORD_INVALID with MMHN_ORD_BAD_ENTRY in the high half for
+ *                                               an entry other than 0 / 1: that row's values are NaN, the others unaffected
+ *   summary                                     null, or [2][1 + n_mut * n_mut + n_mut + 1], per plane s (0: U, 1: S):
+ *                                               mass = sum_x P_s(x), pairs [n_mut][n_mut] = sum_x P_s(x) x_i x_j (the
+ *                                               marginals on the diagonal), burden [n_mut + 1] = sum over |x| = m of P_s(x)
+ *   full                                        null, or [2][2^n_mut]: U and S of every genotype by code (bit j = mutation j)
+ * The call fails (return 1, the last error names the bytes needed) when 16 B x 2^n_mut, the rate tables, the tile list
+ * (4 B per 2^10 codes) and, with a summary, the tiles' partial sums (1 072 B per 2^10 codes) exceed the workspace limit:
+ * there is no partial distribution and nothing is launched.  Mutation rates of 0 give exact zeros on every genotype that
+ * holds the mutation; a seeding rate of 0 gives S = 0 throughout and is no failure.  Every shape depends on n_mut alone and
+ * there are no atomics: no byte of an output depends on the queries or on an earlier call.
+ */
+int mmhn_genotype_distribution(mmhn_handle h, const double* log_theta, const double* obs1, const int8_t* genotypes,
+                               int64_t n_rows, double* values, int32_t* status, double* summary, double* full);
+
 /* ---- measurement -------------------------------------------------------------------
  * mmhn_bench_kronvec: `batch` resident copies of a 2^k vector, `iters` back-to-back
  * launches of mmhn_kronvec_batched's launch (diag = 0: y = Q_off p into a NaN-filled y, every tile of every vector,
@@ -566,7 +594,7 @@ typedef struct {
   int32_t comm_rank;  /* this engine's rank in it (ncclCommUserRank), -1: none */
 } mmhn_counters;
 /* ABI version of this header: bumped whenever an exported signature or structure changes (4: mmhn_bench_kronvec has its
- * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions, mmhn_order_samples, mmhn_simulate_pairs, mmhn_order_times, mmhn_order_snapshots, mmhn_seeding_forecasts and mmhn_seeding_landscape were added within version 8, purely additive changes).  A client built against another header must refuse to run:
+ * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions, mmhn_order_samples, mmhn_simulate_pairs, mmhn_order_times, mmhn_order_snapshots, mmhn_seeding_forecasts, mmhn_seeding_landscape and mmhn_genotype_distribution were added within version 8, purely additive changes).  A client built against another header must refuse to run:
  * mmhn_abi_version() != MMHN_ABI_VERSION (metmhn_amd/_lib.py checks it on load). */
 #define MMHN_ABI_VERSION 8
 int mmhn_abi_version(void);

@@ -21,6 +21,38 @@ inline long long ls_bytes(int n) {
   return (32ll << n) + (long long)sizeof(LsTables) + (4ll << (n - ls_tile_bits(n)));
 }
 
+// the query genotypes gen [R][n] (1 = held) as codes: the status of every row, the codes of the valid rows and the rows they
+// came from (shared with genodist_host.h)
+inline void ls_decode_queries(const int8_t* gen, long long R, int n, int32_t* status, std::vector<uint32_t>& codes,
+                              std::vector<long long>& src) {
+  for (long long i = 0; i < R; ++i) {
+    const int8_t* g = gen + i * n;
+    uint32_t x = 0;
+    bool bad = false;
+    for (int j = 0; j < n && !bad; ++j) {
+      if (g[j] == 1) x |= 1u << j;
+      else if (g[j] != 0) bad = true;
+    }
+    if (bad) { status[i] = MMHN_ORD_INVALID | (MMHN_ORD_BAD_ENTRY << 16); continue; }
+    status[i] = MMHN_ORD_OK;
+    codes.push_back(x);
+    src.push_back(i);
+  }
+}
+
+// the 2^hb tile numbers in levels by popcount - level l holds the tiles of popcount hb - l (descending) or l -, ascending
+// within a level; first[l]: where level l starts, first[hb + 1] the number of tiles (shared with genodist_host.h)
+inline void ls_tile_levels(int hb, bool descending, std::vector<uint32_t>& tiles, std::vector<size_t>& first) {
+  const size_t nt = (size_t)1 << hb;
+  auto level = [&](size_t t) { const int pc = __builtin_popcountll(t); return descending ? hb - pc : pc; };
+  first.assign(hb + 2, 0);
+  for (size_t t = 0; t < nt; ++t) ++first[level(t) + 1];
+  for (int l = 0; l <= hb; ++l) first[l + 1] += first[l];
+  tiles.resize(nt);
+  std::vector<size_t> at(first.begin(), first.end() - 1);
+  for (size_t t = 0; t < nt; ++t) tiles[at[level(t)]++] = (uint32_t)t;
+}
+
 // gen [R][n]: 1 = held (R may be 0).  until: 0 the seeding, 1 the seeding or the clock of the first observation.
 // values [R][4]: p_seed, time, new_events, seed_events of every query; full: nullptr or [4][2^n], every genotype by code.
 template <typename T>
@@ -43,30 +75,13 @@ void seeding_landscape(Engine<T>& E, const double* lt, const double* obs1, int u
                std::to_string(limit) + " bytes; there is no partial landscape"};
   std::vector<uint32_t> codes;
   std::vector<long long> src;
-  for (long long i = 0; i < R; ++i) {
-    const int8_t* g = gen + i * n;
-    uint32_t x = 0;
-    bool bad = false;
-    for (int j = 0; j < n && !bad; ++j) {
-      if (g[j] == 1) x |= 1u << j;
-      else if (g[j] != 0) bad = true;
-    }
-    if (bad) { status[i] = MMHN_ORD_INVALID | (MMHN_ORD_BAD_ENTRY << 16); continue; }
-    status[i] = MMHN_ORD_OK;
-    codes.push_back(x);
-    src.push_back(i);
-  }
-  // the tiles by the popcount of their number, descending; ascending within a popcount
+  ls_decode_queries(gen, R, n, status, codes, src);
+  // the tiles by the popcount of their number, descending
   const int hb = n - c;
   const size_t nt = (size_t)1 << hb;
-  std::vector<size_t> first(hb + 2, 0);                // first[l]: where the tiles of popcount hb - l start
-  for (size_t t = 0; t < nt; ++t) ++first[hb - __builtin_popcountll(t) + 1];
-  for (int l = 0; l <= hb; ++l) first[l + 1] += first[l];
-  std::vector<uint32_t> tiles(nt);
-  {
-    std::vector<size_t> at(first.begin(), first.end() - 1);
-    for (size_t t = 0; t < nt; ++t) tiles[at[hb - __builtin_popcountll(t)]++] = (uint32_t)t;
-  }
+  std::vector<uint32_t> tiles;
+  std::vector<size_t> first;                           // first[l]: where the tiles of popcount hb - l start
+  ls_tile_levels(hb, true, tiles, first);
   DevArr<double> par, V, d_out;
   DevArr<LsTables> tabs;
   DevArr<uint32_t> d_tiles, d_codes;

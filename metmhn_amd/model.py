@@ -374,7 +374,112 @@ class SeedingLandscape(SimpleNamespace):
         return out
 
 
+GENOTYPE_STRATA = ("NM", "EM-PT", "unknown")     # cohort row types 0, 1 and 4: what is known of the seeding when a PT is observed
+
+
+class GenotypeSummary:
+    """Exact sums over the genotype distribution of the primary tumour, per plane s (0: observed unseeded, 1: observed
+    seeded): mass [2] = sum_x P_s(x), pairs [2, n, n] = sum_x P_s(x) x_i x_j with the marginals on the diagonal, burden
+    [2, n+1] = sum over |x| = m of P_s(x).  The interface of simulations.PairSummary restricted to the primary tumour -
+    what simulate_pairs estimates from samples, without the sampling error.  Strata (GENOTYPE_STRATA): "NM" plane 0 over
+    mass[0], "EM-PT" plane 1 over mass[1], "unknown" the sum of both planes (over mass[0] + mass[1] = 1)."""
+
+    def __init__(self, mass, pairs, burden):
+        self.mass = np.asarray(mass, dtype=np.float64).reshape(2)
+        self.burden = np.asarray(burden, dtype=np.float64)
+        self.n_mut = n = self.burden.shape[-1] - 1
+        self.burden = self.burden.reshape(2, n + 1)
+        self.pairs = np.asarray(pairs, dtype=np.float64).reshape(2, n, n)
+
+    def __repr__(self):
+        return f"GenotypeSummary(n_mut={self.n_mut}, mass={self.mass.tolist()})"
+
+    def _stratum(self, stratum):
+        """(pair sums [n, n], burden sums [n+1], mass) of a stratum."""
+        if stratum not in GENOTYPE_STRATA:
+            raise ValueError(f"stratum must be one of {GENOTYPE_STRATA}, got {stratum!r}")
+        if stratum == "unknown":
+            return self.pairs[0] + self.pairs[1], self.burden[0] + self.burden[1], self.mass[0] + self.mass[1]
+        s = GENOTYPE_STRATA.index(stratum)
+        return self.pairs[s], self.burden[s], self.mass[s]
+
+    def frequencies(self, stratum) -> np.ndarray:
+        """pairs / mass of the stratum, float64 [n, n]: joint frequencies of two mutations, marginal ones on the diagonal
+        (NaN everywhere if the stratum has no mass)."""
+        pairs, _, mass = self._stratum(stratum)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return pairs / np.float64(mass)
+
+    def log_odds(self, stratum) -> np.ndarray:
+        """Log odds ratio of every two mutations from the stratum's 2x2 table: log(p11 p00 / (p10 p01)) with p11 the pair
+        frequency and the other cells from the marginal ones; NaN where a cell is not positive (the diagonal included)."""
+        f = self.frequencies(stratum)
+        m = np.diag(f)
+        p10, p01 = m[:, None] - f, m[None, :] - f
+        p00 = 1.0 - m[:, None] - m[None, :] + f
+        cells = np.stack((f, p10, p01, p00))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            lo = np.log(f) + np.log(p00) - np.log(p10) - np.log(p01)
+        lo[~(cells > 0).all(axis=0)] = np.nan
+        return lo
+
+    def burden_pmf(self, stratum) -> np.ndarray:
+        """burden / mass of the stratum [n+1]: the distribution of the primary tumour's mutation count."""
+        _, burden, mass = self._stratum(stratum)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return burden / np.float64(mass)
+
+    def compare(self, dat) -> dict:
+        """The check of a cohort `dat` [n_pat, 2 n_mut + 3] (reference format, type in the last column) against the exact
+        frequencies: per row type present among 0, 1 and 4 {stratum: residuals [n, n]}, the standardised residuals
+        (obs - n p) / sqrt(n p (1 - p)) of the observed PT pair counts of the type's rows against n = rows of the type and
+        p = frequencies(stratum) - simulations.PairSummary.compare's formula; NaN where p is not inside (0, 1).  Type 4 is
+        counted from `dat` directly (Utilityfunctions.pair_counts ignores it)."""
+        from .Utilityfunctions import pair_counts
+        dat = np.asarray(dat)
+        n = self.n_mut
+        if dat.ndim != 2 or dat.shape[1] != 2 * n + 3:
+            raise ValueError(f"dat must have shape (n_pat, {2 * n + 3}), got {dat.shape}")
+        n_type, obs = pair_counts(dat)
+        g4 = dat[dat[:, -1] == 4][:, 0:2 * n:2].astype(np.int64)
+        seen = {"NM": (int(n_type[0]), obs[0][0::2, 0::2]), "EM-PT": (int(n_type[1]), obs[1][0::2, 0::2]),
+                "unknown": (g4.shape[0], g4.T @ g4)}
+        out = {}
+        for stratum in GENOTYPE_STRATA:
+            rows, counts = seen[stratum]
+            if rows == 0:
+                continue
+            p = self.frequencies(stratum)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                r = (counts - rows * p) / np.sqrt(rows * p * (1.0 - p))
+            r[~((p > 0.0) & (p < 1.0))] = np.nan
+            out[stratum] = r
+        return out
+
+
+class GenotypeDistribution(SimpleNamespace):
+    """The probability that the primary tumour is observed with a genotype and has not seeded (`unseeded`, the likelihood
+    of the cohort row of type 0) or has seeded by then (`seeded`, type 1), arrays over the genotypes `codes` (bit j of a
+    code = mutation j held), with `summary`, the GenotypeSummary of the WHOLE lattice.  MetMHN.genotype_distribution
+    returns every genotype, codes = 0 .. 2^n - 1; genotype_distribution_at the rows it was given."""
+
+    def __init__(self, unseeded, seeded, codes, summary):
+        super().__init__(unseeded=unseeded, seeded=seeded, codes=codes, summary=summary)
+
+    @property
+    def total(self) -> np.ndarray:
+        """unseeded + seeded: the likelihood of the row of unknown status (type 4)."""
+        return self.unseeded + self.seeded
+
+    @property
+    def p_seeded(self) -> np.ndarray:
+        """seeded / total: P(seeded | genotype), met_status_posterior's value (NaN where total is 0)."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.seeded / self.total
+
+
 _FORECAST_UNTIL = ("seeding", "observation")
+_GENODIST_HOST_MAX = 24          # mutations the host distribution takes on: n x 2^n doubles of rates
 _FORECAST_HOST_MAX = 24          # free mutations the host definition takes on: f x 2^f doubles of rates
 _LANDSCAPE_HOST_MAX = 24         # mutations the host landscape takes on: n x 2^n doubles of rates
 _NO_SEEDING_EXIT = ("the seeding rate of the full genotype underflows to 0 (a theta[n, n] of -1e10, as a fit without seeded "
@@ -948,6 +1053,112 @@ class MetMHN:
             if bad.size:
                 raise ValueError(f"row {int(bad[0])}: a genotype entry is neither 0 nor 1")
         return SeedingLandscape(*(np.ascontiguousarray(values[:, k]) for k in range(4)), codes)
+
+    # ------------------------------------------------------------------ genotype distribution of the primary tumour
+    def _genodist_host(self) -> np.ndarray:
+        """[2, 2^n]: the definition of the genotype distribution (U, S), level by level over the popcount, ascending."""
+        th, n = self._pt_log_theta, self.n
+        if n > _GENODIST_HOST_MAX:
+            raise ValueError(f"{n} mutations: the host distribution stops at {_GENODIST_HOST_MAX} ({n} x 2^{n} doubles of "
+                             "rates); use backend='device'")
+        size = 1 << n
+        idx = np.arange(size)
+        level = _subset_sums(np.ones(n)).astype(np.int64)
+        lam = [np.exp(th[j, j] + _subset_sums(np.where(np.arange(n) == j, 0.0, th[j, :n]))) for j in range(n)]
+        sig = np.exp(th[n, n] + _subset_sums(th[n, :n]))
+        kap0 = np.exp(_subset_sums(self.obs1[:n]))
+        kap1 = kap0 * np.exp(self.obs1[n])
+        L = np.zeros(size)
+        for j in range(n):
+            L += np.where((idx >> j & 1) == 0, lam[j], 0.0)
+        den0, den1 = L + sig + kap0, L + kap1
+        F0, F1, G0, G1 = (np.zeros(size) for _ in range(4))
+        F0[0] = 1.0
+        for lev in range(n + 1):
+            ys = idx[level == lev]
+            for b in range(n if lev else 0):
+                to = ys[(ys >> b & 1) == 1]
+                frm = to ^ (1 << b)
+                r = lam[b][frm]
+                F0[to] += G0[frm] * r
+                F1[to] += G1[frm] * r
+            G0[ys] = F0[ys] / den0[ys]
+            F1[ys] = G0[ys] * sig[ys] + F1[ys]
+            G1[ys] = F1[ys] / den1[ys]
+        return np.stack((kap0 * G0, kap1 * G1))
+
+    @staticmethod
+    def _genodist_summary_host(P: np.ndarray) -> "GenotypeSummary":
+        """The GenotypeSummary of the two planes P [2, 2^n], by its definition."""
+        n = P.shape[1].bit_length() - 1
+        level = _subset_sums(np.ones(n)).astype(np.int64)
+        pairs, burden = np.zeros((2, n, n)), np.zeros((2, n + 1))
+        for s in range(2):
+            burden[s] = np.bincount(level, weights=P[s], minlength=n + 1)
+            cube = P[s].reshape((2,) * n)                    # axis n - 1 - j is bit j
+            for j in range(n):
+                held = cube.take(1, axis=n - 1 - j)          # (bit i < j is axis n - 2 - i of what remains)
+                pairs[s, j, j] = held.sum()
+                for i in range(j):
+                    pairs[s, i, j] = pairs[s, j, i] = held.take(1, axis=n - 2 - i).sum()
+        return GenotypeSummary(P.sum(axis=1), pairs, burden)
+
+    def genotype_distribution(self, backend: str = "device", max_bytes: int = 2 ** 31) -> "GenotypeDistribution":
+        """The model's distribution over ALL genotypes of the primary tumour at its observation, split by whether the
+        seeding has happened by then: arrays over the 2^n genotype codes (bit j of a code = mutation j held), from one forward
+        pass over the lattice of all genotypes.  The primary tumour is an autonomous chain on (genotype, seeded or not) -
+        theta[:n, n] is not read, the metastasis never acts on it.  With lambda_j(x) = exp(theta_jj + sum_{i in x}
+        theta_ji), sigma(x) the same for the seeding, kappa0(x) = exp(sum_{i in x} obs1_i), kappa1 = kappa0 exp(obs1_n),
+        L(x) the sum of lambda_j over the mutations x does not hold, b over the ones it holds:
+            F0(empty) = 1,  F0(y) = sum_b G0(y - b) lambda_b(y - b),                    G0 = F0 / (L + sigma + kappa0)
+                            F1(y) = G0(y) sigma(y) + sum_b G1(y - b) lambda_b(y - b),   G1 = F1 / (L + kappa1)
+            unseeded = kappa0 G0 (exp(lp) of the type-0 row),  seeded = kappa1 G1 (exp(lp) of the type-1 row)
+        `total` is the type-4 likelihood and sums to 1 over the genotypes, `p_seeded` is met_status_posterior's value and
+        `summary` the exact marginal and pairwise frequencies and burden distributions of both planes (GenotypeSummary).  The
+        reference's sibling package calls the one-plane form generate_pTh.
+
+        backend="device": one call of the HIP library (mmhn_genotype_distribution), 16 B x 2^n of workspace and as much here
+        for the result; a ValueError names the bytes when that exceeds `max_bytes` (2 GiB: n <= 27).  backend="host": the
+        definition in NumPy, level by level, n <= 24."""
+        if backend not in ("device", "host"):
+            raise ValueError("backend must be 'device' or 'host'")
+        n = self.n
+        if backend == "host" and n > _GENODIST_HOST_MAX:
+            self._genodist_host()                   # (raises: the message points to the device)
+        if 16 << n > max_bytes:
+            raise ValueError(f"{n} mutations: a distribution over 2^{n} genotypes needs {16 << n} bytes, more than max_bytes = "
+                             f"{int(max_bytes)}; genotype_distribution_at reads single genotypes off the device's distribution")
+        if backend == "host":
+            whole = self._genodist_host()
+            summary = self._genodist_summary_host(whole)
+        else:
+            from .jx import engine
+            _, _, sums, whole = engine(n).genotype_distribution(self.log_theta, self.obs1, np.zeros((0, n), dtype=np.int8),
+                                                                summary=True, full=True)
+            summary = GenotypeSummary(*sums)
+        return GenotypeDistribution(whole[0], whole[1], np.arange(1 << n), summary)
+
+    def genotype_distribution_at(self, genotypes, backend: str = "device") -> "GenotypeDistribution":
+        """genotype_distribution's two values at the rows of `genotypes` [R, n] (0 / 1), [R] each, with the rows' codes and
+        the summary of the WHOLE lattice: the distribution is swept on the device (16 B x 2^n of its workspace, any n the
+        engine takes) and only the rows and the summary come back.  backend="host": the NumPy definition, n <= 24.
+        An entry other than 0 / 1 raises ValueError("row i: ...") as seeding_forecasts does."""
+        if backend not in ("device", "host"):
+            raise ValueError("backend must be 'device' or 'host'")
+        g = self._forecast_checks(genotypes, "observation")
+        n = self.n
+        codes = g @ (1 << np.arange(n, dtype=np.int64))
+        if backend == "host":
+            whole = self._genodist_host()
+            values, summary = whole[:, codes].T, self._genodist_summary_host(whole)
+        else:
+            from .jx import engine
+            values, status, sums, _ = engine(n).genotype_distribution(self.log_theta, self.obs1, g.astype(np.int8), summary=True)
+            bad = np.flatnonzero(status != 0)
+            if bad.size:
+                raise ValueError(f"row {int(bad[0])}: a genotype entry is neither 0 nor 1")
+            summary = GenotypeSummary(*sums)
+        return GenotypeDistribution(np.ascontiguousarray(values[:, 0]), np.ascontiguousarray(values[:, 1]), codes, summary)
 
     def likelihood(self, order, met_status: str, first_obs: str = None) -> float:
         """model.py:295-376: probability of exactly this order of events being what is observed."""

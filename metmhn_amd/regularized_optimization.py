@@ -475,6 +475,38 @@ def seeding_risk(log_theta, log_d_p, log_d_m, dat, until: str = "observation", b
     return SeedingLandscape(**out, codes=codes), met_status_posterior(log_theta, log_d_p, log_d_m, dat)
 
 
+def genotype_fit(log_theta, log_d_p, log_d_m, dat, backend: str = "device"):
+    """How well the model's exact genotype distribution of the primary tumour fits the PT genotypes of `dat`, from ONE
+    forward sweep over all genotypes (MetMHN.genotype_distribution_at with obs1 = log_d_p).  A namespace of
+    prob [n_pat]: the probability of the row's PT genotype dat[:, 0:2*n:2] within its stratum - unseeded / mass[0] for a row
+        of type 0 ("NM"), seeded / mass[1] for type 1 ("EM-PT"), unseeded + seeded for type 4 ("unknown"); NaN for types 2, 3;
+    codes [n_pat]: the rows' genotype codes, -1 for types 2 and 3;
+    table: {stratum: (codes, observed, expected)} for the strata with rows - the distinct genotype codes of the stratum's
+        rows, ascending, how many rows carry each, and rows of the stratum x the genotype's probability within it;
+    summary: the model.GenotypeSummary of the whole lattice;  residuals: summary.compare(dat)."""
+    from types import SimpleNamespace
+    from .model import GENOTYPE_STRATA, MetMHN
+    arr = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
+    n = (arr.shape[1] - 3) // 2
+    typ = arr[:, -1]
+    pick = np.isin(typ, (0, 1, 4))
+    got = MetMHN(log_theta, log_d_p, log_d_m).genotype_distribution_at(arr[pick][:, 0:2 * n:2], backend)
+    mass = got.summary.mass
+    within = {0: got.unseeded / mass[0], 1: got.seeded / mass[1], 4: got.total}
+    prob = np.full(arr.shape[0], np.nan)
+    codes = np.full(arr.shape[0], -1, dtype=np.int64)
+    codes[pick] = got.codes
+    t = typ[pick]
+    prob[pick] = np.select([t == 0, t == 1], [within[0], within[1]], within[4])
+    table = {}
+    for stratum, ty in zip(GENOTYPE_STRATA, (0, 1, 4)):
+        rows = typ == ty
+        if rows.any():
+            uniq, first, counts = np.unique(codes[rows], return_index=True, return_counts=True)
+            table[stratum] = (uniq, counts.astype(np.int64), int(rows.sum()) * prob[rows][first])
+    return SimpleNamespace(prob=prob, codes=codes, table=table, summary=got.summary, residuals=got.summary.compare(arr))
+
+
 def _unpack(params, n_total):
     params = np.asarray(params, dtype=np.float64)
     return (params[0:n_total ** 2].reshape((n_total, n_total)), params[n_total ** 2:n_total * (n_total + 1)],
