@@ -564,6 +564,38 @@ int mmhn_seeding_landscape(mmhn_handle h, const double* log_theta, const double*
 int mmhn_genotype_distribution(mmhn_handle h, const double* log_theta, const double* obs1, const int8_t* genotypes,
                                int64_t n_rows, double* values, int32_t* status, double* summary, double* full);
 
+/* ---- genotype distribution of the metastasis and its founder ---------------------------------
+ * mmhn_metastasis_distribution: ONE forward sweep over all 2^n_mut genotypes gives the probability that the seeding happens
+ * before the primary tumour's observation and the seeding cell (the founder) holds exactly y (Z), the probability that the
+ * metastasis is observed with genotype z (M), and M weighted by the number of z's mutations the founder held (C).  The
+ * metastasis is an autonomous chain: the common lineage until the seeding, then its own rates, which carry the seeding's
+ * effect theta[j][n], until its own clock obs2; nothing the primary tumour does afterwards reaches it.  With the notation of
+ * mmhn_genotype_distribution, j over the mutations a code does not hold and b over the ones it holds
+ *   mu_j(z) = lambda_j(z) exp(theta[j][n]),  Lm(z) = sum_j mu_j(z),  kappam(z) = exp(obs2[n] + sum over i in z of obs2[i])
+ *   F0(empty) = 1,  F0(y) = sum_b G0(y - b) lambda_b(y - b),                      G0 = F0 / (L + sigma + kappa0)
+ *                   FM(y) = G0(y) sigma(y)     + sum_b GM(y - b) mu_b(y - b),     GM = FM / (Lm + kappam)
+ *                   FC(y) = G0(y) sigma(y) |y| + sum_b GC(y - b) mu_b(y - b),     GC = FC / (Lm + kappam)
+ *   Z = sigma G0,  M = kappam GM = exp(lp) of the cohort row of type 2 with that MT genotype,  C = kappam GC
+ * from the empty genotype up (metmhn_amd/csrc/metdist.h, on the tiles of mmhn_genotype_distribution).  sum Z = sum M = the
+ * mass[1] of mmhn_genotype_distribution; C / M is the expected number of z's mutations that were already in the founder,
+ * 0 <= C <= |z| M.  fp64 engines only; independent of the loaded cohort.
+ *   genotypes [n_rows][n_mut]                   int8 queries, 1 = held, 0 = not; n_rows = 0 is valid
+ *   values [n_rows][3]                          Z, M, C of every query
+ *   status [n_rows]                             as for mmhn_genotype_distribution: MMHN_ORD_OK, or MMHN_ORD_INVALID with
+ *                                               MMHN_ORD_BAD_ENTRY in the high half (that row's values are NaN)
+ *   summary                                     null, or [2][1 + n_mut * n_mut + n_mut + 1]: mass, pairs [n_mut][n_mut],
+ *                                               burden [n_mut + 1] of the founder plane Z and then of the metastasis plane M
+ *   full                                        null, or [3][2^n_mut]: Z, M and C of every genotype by code
+ * The call fails (return 1, the last error names the bytes needed) when 24 B x 2^n_mut, the two sets of rate tables, the
+ * tile list and, with a summary, the tiles' partial sums exceed the workspace limit: there is no partial distribution and
+ * nothing is launched.  A mutation rate of 0 gives exact zeros on every genotype that holds the mutation; a seeding rate of
+ * 0 gives all three planes 0 and is no failure.  Every shape depends on n_mut alone and there are no atomics: no byte of an
+ * output depends on the queries or on an earlier call.
+ */
+int mmhn_metastasis_distribution(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2,
+                                 const int8_t* genotypes, int64_t n_rows, double* values, int32_t* status, double* summary,
+                                 double* full);
+
 /* ---- measurement -------------------------------------------------------------------
  * mmhn_bench_kronvec: `batch` resident copies of a 2^k vector, `iters` back-to-back
  * launches of mmhn_kronvec_batched's launch (diag = 0: y = Q_off p into a NaN-filled y, every tile of every vector,
@@ -594,7 +626,7 @@ typedef struct {
   int32_t comm_rank;  /* this engine's rank in it (ncclCommUserRank), -1: none */
 } mmhn_counters;
 /* ABI version of this header: bumped whenever an exported signature or structure changes (4: mmhn_bench_kronvec has its
- * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions, mmhn_order_samples, mmhn_simulate_pairs, mmhn_order_times, mmhn_order_snapshots, mmhn_seeding_forecasts, mmhn_seeding_landscape and mmhn_genotype_distribution were added within version 8, purely additive changes).  A client built against another header must refuse to run:
+ * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions, mmhn_order_samples, mmhn_simulate_pairs, mmhn_order_times, mmhn_order_snapshots, mmhn_seeding_forecasts, mmhn_seeding_landscape, mmhn_genotype_distribution and mmhn_metastasis_distribution were added within version 8, purely additive changes).  A client built against another header must refuse to run:
  * mmhn_abi_version() != MMHN_ABI_VERSION (metmhn_amd/_lib.py checks it on load). */
 #define MMHN_ABI_VERSION 8
 int mmhn_abi_version(void);

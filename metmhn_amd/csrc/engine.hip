@@ -5,7 +5,7 @@
 // batches, routes, work lists, offsets), host.h (errors, device arrays, lanes, MMHN_* knob readers), comm.h (RCCL),
 // rowmix_host.h (row weights and row groups: their checks, device copies and the launches of the group kernels),
 // prims.h / orders_host.h / orderpost_host.h (the batching of the order-posterior entry points, opr_rows) /
-// orderprec_host.h / orderpos_host.h / ordertime_host.h / ordersnap_host.h / ordersample_host.h / forecast_host.h / landscape_host.h / genodist_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
+// orderprec_host.h / orderpos_host.h / ordertime_host.h / ordersnap_host.h / ordersample_host.h / forecast_host.h / landscape_host.h / genodist_host.h / metdist_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
 //
 // Pipeline of one evaluation (reference call graph: regularized_optimization.py:163-267 ->
 // likelihood.py:_g_coupled_*, _grad_prim_obs, _grad_met_obs), run batch by batch with every
@@ -1122,6 +1122,7 @@ struct Engine : EngineBase {
 #include "forecast_host.h"
 #include "landscape_host.h"
 #include "genodist_host.h"
+#include "metdist_host.h"
 #include "sampler_host.h"
 #include "bench.h"
 
@@ -1757,6 +1758,21 @@ int mmhn_genotype_distribution(mmhn_handle h, const double* log_theta, const dou
   REQUIRE((genotypes && values && status) || n_rows == 0, "null pointer");
   REQUIRE(h->dtype == MMHN_F64, "the genotype distribution needs an fp64 engine (MMHN_F64)");
   genotype_distribution(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, genotypes, n_rows, values, status, summary, full);
+  API_END
+}
+
+// ---- genotype distribution of the metastasis and its founder: every genotype's Z, M, C from one forward sweep
+int mmhn_metastasis_distribution(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2,
+                                 const int8_t* genotypes, int64_t n_rows, double* values, int32_t* status, double* summary,
+                                 double* full) {
+  API_BEGIN
+  GUARD(h);
+  REQUIRE(n_rows >= 0 && n_rows < ((int64_t)1 << 31), "n_rows out of range");
+  REQUIRE(log_theta && obs1 && obs2, "null pointer");
+  REQUIRE((genotypes && values && status) || n_rows == 0, "null pointer");
+  REQUIRE(h->dtype == MMHN_F64, "the metastasis distribution needs an fp64 engine (MMHN_F64)");
+  metastasis_distribution(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, genotypes, n_rows, values, status,
+                          summary, full);
   API_END
 }
 

@@ -39,7 +39,7 @@
 // Summary.  mass[s] = sum_x P_s(x), pairs[s][i][j] = sum_x P_s(x) x_i x_j (marginals on the diagonal),
 // burden[s][m] = sum over |x| = m of P_s(x).  k_genodist_tile (a workgroup per tile, every tile in one launch) forms per
 // plane the GD_FEAT = 67 sums of its tile: mass, the c low-bit marginals, the low-low pair sums, the histogram by low
-// popcount - a fold in LDS in three stages (the low 5 bits in pieces of 8 offsets, the four pieces, the next 5 bits), every
+// popcount - a fold in LDS (gd_tile_fold, which metdist.h's k_metdist_tile calls too) in three stages (the low 5 bits in pieces of 8 offsets, the four pieces, the next 5 bits), every
 // sum in ascending order.  k_genodist_summary (a workgroup per output) then adds the tiles' partials: a high bit of a tile
 // is constant over the tile, so high-high = the sum over the tiles that hold both bits of the tile mass, high-low = the sum
 // over the tiles that hold the high bit of the low marginal, burden is shifted by the popcount of the tile number.  Thread
@@ -161,6 +161,90 @@ __global__ __launch_bounds__(LS_KB) void k_genodist_level(const LsTables* __rest
   }
 }
 
+// the GD_FEAT partial sums of a tile's two planes to part[(s * GD_FEAT + f) * nt + T]: u / w hold the planes' values at the
+// thread's offsets tid + s * LS_KB (0 past the tile); every thread of the workgroup calls it (k_genodist_tile and metdist.h's
+// k_metdist_tile share this one copy)
+__device__ __forceinline__ void gd_tile_fold(const double (&u)[LS_SPT], const double (&w)[LS_SPT], double* __restrict__ part,
+                                             long long nt, uint32_t T) {
+  const int tid = threadIdx.x;
+  __shared__ double P[2][(1 << LS_HALF) * GD_ROW];   // the tile's two planes, offset (hi, lo) at hi * GD_ROW + lo; 0 past the tile
+  __shared__ double Q[GD_S1][4][64];                 // stage 1: per piece of 8 offsets of a row
+  __shared__ double R[GD_S2][64];                    // stage 2: per row (plane, hi): all, bit i, pair (i, j), popcount a of the low 5 bits
+#pragma unroll
+  for (int s = 0; s < LS_SPT; ++s) {
+    const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
+    P[0][(p >> LS_HALF) * GD_ROW + (p & 31u)] = u[s];
+    P[1][(p >> LS_HALF) * GD_ROW + (p & 31u)] = w[s];
+  }
+  __syncthreads();
+  {
+    const int row = tid & 63, piece = tid >> 6;
+    const double* x = &P[row >> 5][(row & 31) * GD_ROW + piece * 8];
+    double b = 0.0, m0 = 0.0, m1 = 0.0, m2 = 0.0, m01 = 0.0, m02 = 0.0, m12 = 0.0, c0 = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0;
+#pragma unroll
+    for (int l = 0; l < 8; ++l) {
+      const double t = x[l];
+      b += t;
+      if (l & 1) m0 += t;
+      if (l & 2) m1 += t;
+      if (l & 4) m2 += t;
+      if ((l & 3) == 3) m01 += t;
+      if ((l & 5) == 5) m02 += t;
+      if ((l & 6) == 6) m12 += t;
+      const int pc = (l & 1) + ((l >> 1) & 1) + ((l >> 2) & 1);
+      if (pc == 0) c0 += t; else if (pc == 1) c1 += t; else if (pc == 2) c2 += t; else c3 += t;
+    }
+    Q[0][piece][row] = b; Q[1][piece][row] = m0; Q[2][piece][row] = m1; Q[3][piece][row] = m2;
+    Q[4][piece][row] = m01; Q[5][piece][row] = m02; Q[6][piece][row] = m12;
+    Q[7][piece][row] = c0; Q[8][piece][row] = c1; Q[9][piece][row] = c2; Q[10][piece][row] = c3;
+  }
+  __syncthreads();
+  // stage 2: the four pieces of a row, ascending.  The piece number is the bits 3, 4 of the offset.
+  for (int it = tid; it < GD_S2 * 64; it += LS_KB) {
+    const int k = it >> 6, row = it & 63;
+    double r = 0.0;
+    if (k < 1 + LS_HALF + LS_HALF * (LS_HALF - 1) / 2) {
+      uint32_t bits = 0u;
+      if (k >= 1 + LS_HALF) { int i, j; gd_pair_of(k - 1 - LS_HALF, i, j); bits = (1u << i) | (1u << j); }
+      else if (k >= 1) bits = 1u << (k - 1);
+      const uint32_t sl = bits & 7u, sh = bits >> 3;
+      const int qi = sl == 0u ? 0 : sl == 1u ? 1 : sl == 2u ? 2 : sl == 4u ? 3 : sl == 3u ? 4 : sl == 5u ? 5 : 6;
+      for (uint32_t piece = 0; piece < 4; ++piece)
+        if ((piece & sh) == sh) r += Q[qi][piece][row];
+    } else {
+      const int a = k - (1 + LS_HALF + LS_HALF * (LS_HALF - 1) / 2);
+      for (int piece = 0; piece < 4; ++piece) {
+        const int d = a - __builtin_popcount(piece);
+        if (d >= 0 && d <= 3) r += Q[7 + d][piece][row];
+      }
+    }
+    R[k][row] = r;
+  }
+  __syncthreads();
+  // stage 3: the 32 rows of a plane, ascending
+  if (tid < 2 * GD_FEAT) {
+    const int s = tid / GD_FEAT, f = tid % GD_FEAT;
+    double r = 0.0;
+    if (f < GD_F_HIST) {
+      uint32_t bits = 0u;
+      if (f >= GD_F_PAIR) { int i, j; gd_pair_of(f - GD_F_PAIR, i, j); bits = (1u << i) | (1u << j); }
+      else if (f >= GD_F_MARG) bits = 1u << (f - GD_F_MARG);
+      const uint32_t sl = bits & 31u, sh = bits >> LS_HALF;
+      const int pc = __builtin_popcount(sl);
+      const int k = pc == 0 ? 0 : pc == 1 ? 1 + __builtin_ctz(sl) : 1 + LS_HALF + gd_pair_index(__builtin_ctz(sl), 31 - __builtin_clz(sl));
+      for (uint32_t hi = 0; hi < 32u; ++hi)
+        if ((hi & sh) == sh) r += R[k][s * 32 + hi];
+    } else {
+      const int m = f - GD_F_HIST;
+      for (int hi = 0; hi < 32; ++hi) {
+        const int d = m - __builtin_popcount(hi);
+        if (d >= 0 && d <= LS_HALF) r += R[1 + LS_HALF + LS_HALF * (LS_HALF - 1) / 2 + d][s * 32 + hi];
+      }
+    }
+    part[((long long)s * GD_FEAT + f) * nt + T] = r;
+  }
+}
+
 // every tile once all levels are finished (workgroup = tile number): G to U = kappa0 G0 and S = kappa1 G1 in place and,
 // with SUMS, the GD_FEAT partial sums of the tile and plane at part[(s * GD_FEAT + f) * nt + T]
 template <bool SUMS>
@@ -189,84 +273,7 @@ __global__ __launch_bounds__(LS_KB) void k_genodist_tile(const LsTables* __restr
       o[0] = u[s]; o[plane] = w[s];
     }
   }
-  if constexpr (SUMS) {
-    __shared__ double P[2][(1 << LS_HALF) * GD_ROW];   // the tile's two planes, offset (hi, lo) at hi * GD_ROW + lo; 0 past the tile
-    __shared__ double Q[GD_S1][4][64];                 // stage 1: per piece of 8 offsets of a row
-    __shared__ double R[GD_S2][64];                    // stage 2: per row (plane, hi): all, bit i, pair (i, j), popcount a of the low 5 bits
-#pragma unroll
-    for (int s = 0; s < LS_SPT; ++s) {
-      const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
-      P[0][(p >> LS_HALF) * GD_ROW + (p & 31u)] = u[s];
-      P[1][(p >> LS_HALF) * GD_ROW + (p & 31u)] = w[s];
-    }
-    __syncthreads();
-    {
-      const int row = tid & 63, piece = tid >> 6;
-      const double* x = &P[row >> 5][(row & 31) * GD_ROW + piece * 8];
-      double b = 0.0, m0 = 0.0, m1 = 0.0, m2 = 0.0, m01 = 0.0, m02 = 0.0, m12 = 0.0, c0 = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0;
-#pragma unroll
-      for (int l = 0; l < 8; ++l) {
-        const double t = x[l];
-        b += t;
-        if (l & 1) m0 += t;
-        if (l & 2) m1 += t;
-        if (l & 4) m2 += t;
-        if ((l & 3) == 3) m01 += t;
-        if ((l & 5) == 5) m02 += t;
-        if ((l & 6) == 6) m12 += t;
-        const int pc = (l & 1) + ((l >> 1) & 1) + ((l >> 2) & 1);
-        if (pc == 0) c0 += t; else if (pc == 1) c1 += t; else if (pc == 2) c2 += t; else c3 += t;
-      }
-      Q[0][piece][row] = b; Q[1][piece][row] = m0; Q[2][piece][row] = m1; Q[3][piece][row] = m2;
-      Q[4][piece][row] = m01; Q[5][piece][row] = m02; Q[6][piece][row] = m12;
-      Q[7][piece][row] = c0; Q[8][piece][row] = c1; Q[9][piece][row] = c2; Q[10][piece][row] = c3;
-    }
-    __syncthreads();
-    // stage 2: the four pieces of a row, ascending.  The piece number is the bits 3, 4 of the offset.
-    for (int it = tid; it < GD_S2 * 64; it += LS_KB) {
-      const int k = it >> 6, row = it & 63;
-      double r = 0.0;
-      if (k < 1 + LS_HALF + LS_HALF * (LS_HALF - 1) / 2) {
-        uint32_t bits = 0u;
-        if (k >= 1 + LS_HALF) { int i, j; gd_pair_of(k - 1 - LS_HALF, i, j); bits = (1u << i) | (1u << j); }
-        else if (k >= 1) bits = 1u << (k - 1);
-        const uint32_t sl = bits & 7u, sh = bits >> 3;
-        const int qi = sl == 0u ? 0 : sl == 1u ? 1 : sl == 2u ? 2 : sl == 4u ? 3 : sl == 3u ? 4 : sl == 5u ? 5 : 6;
-        for (uint32_t piece = 0; piece < 4; ++piece)
-          if ((piece & sh) == sh) r += Q[qi][piece][row];
-      } else {
-        const int a = k - (1 + LS_HALF + LS_HALF * (LS_HALF - 1) / 2);
-        for (int piece = 0; piece < 4; ++piece) {
-          const int d = a - __builtin_popcount(piece);
-          if (d >= 0 && d <= 3) r += Q[7 + d][piece][row];
-        }
-      }
-      R[k][row] = r;
-    }
-    __syncthreads();
-    // stage 3: the 32 rows of a plane, ascending
-    if (tid < 2 * GD_FEAT) {
-      const int s = tid / GD_FEAT, f = tid % GD_FEAT;
-      double r = 0.0;
-      if (f < GD_F_HIST) {
-        uint32_t bits = 0u;
-        if (f >= GD_F_PAIR) { int i, j; gd_pair_of(f - GD_F_PAIR, i, j); bits = (1u << i) | (1u << j); }
-        else if (f >= GD_F_MARG) bits = 1u << (f - GD_F_MARG);
-        const uint32_t sl = bits & 31u, sh = bits >> LS_HALF;
-        const int pc = __builtin_popcount(sl);
-        const int k = pc == 0 ? 0 : pc == 1 ? 1 + __builtin_ctz(sl) : 1 + LS_HALF + gd_pair_index(__builtin_ctz(sl), 31 - __builtin_clz(sl));
-        for (uint32_t hi = 0; hi < 32u; ++hi)
-          if ((hi & sh) == sh) r += R[k][s * 32 + hi];
-      } else {
-        const int m = f - GD_F_HIST;
-        for (int hi = 0; hi < 32; ++hi) {
-          const int d = m - __builtin_popcount(hi);
-          if (d >= 0 && d <= LS_HALF) r += R[1 + LS_HALF + LS_HALF * (LS_HALF - 1) / 2 + d][s * 32 + hi];
-        }
-      }
-      part[((long long)s * GD_FEAT + f) * nt + T] = r;
-    }
-  }
+  if constexpr (SUMS) gd_tile_fold(u, w, part, nt, T);
 }
 
 // outputs of a plane's summary that k_genodist_summary forms: mass, the pairs i <= j, burden

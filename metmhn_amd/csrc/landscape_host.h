@@ -22,7 +22,7 @@ inline long long ls_bytes(int n) {
 }
 
 // the query genotypes gen [R][n] (1 = held) as codes: the status of every row, the codes of the valid rows and the rows they
-// came from (shared with genodist_host.h)
+// came from (shared with genodist_host.h and metdist_host.h)
 inline void ls_decode_queries(const int8_t* gen, long long R, int n, int32_t* status, std::vector<uint32_t>& codes,
                               std::vector<long long>& src) {
   for (long long i = 0; i < R; ++i) {
@@ -41,7 +41,7 @@ inline void ls_decode_queries(const int8_t* gen, long long R, int n, int32_t* st
 }
 
 // the 2^hb tile numbers in levels by popcount - level l holds the tiles of popcount hb - l (descending) or l -, ascending
-// within a level; first[l]: where level l starts, first[hb + 1] the number of tiles (shared with genodist_host.h)
+// within a level; first[l]: where level l starts, first[hb + 1] the number of tiles (shared with genodist_host.h and metdist_host.h)
 inline void ls_tile_levels(int hb, bool descending, std::vector<uint32_t>& tiles, std::vector<size_t>& first) {
   const size_t nt = (size_t)1 << hb;
   auto level = [&](size_t t) { const int pc = __builtin_popcountll(t); return descending ? hb - pc : pc; };

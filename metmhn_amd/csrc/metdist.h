@@ -1,0 +1,217 @@
+// Genotype distribution of the metastasis and of its founder: the probability of EVERY genotype to be the one the seeding
+// cell holds (Z), to be the metastasis' observed one (M), and M weighted by how many of its mutations the founder already
+// held (C), in one forward sweep over the full lattice - genodist.h's sweep with a third plane and the metastasis' own
+// rates behind the seeding (metmhn_amd/model.py MetMHN.metastasis_distribution has the definition on the host).
+//
+// The metastasis is an autonomous chain: up to the seeding it is the common lineage, which leaves by seeding or by the
+// primary tumour's first clock; from the seeding on it runs with its own rates, which carry the seeding's effect
+// theta[j][n], until its own clock obs2.  x, y, z are genotype codes, j over the mutations a code does not hold, b over the
+// ones it holds; lambda, sigma, kappa0, L as in genodist.h and
+//   mu_j(z) = lambda_j(z) exp(theta[j][n]),  Lm(z) = sum_j mu_j(z),  kappam(z) = exp(obs2[n] + sum over i in z of obs2[i])
+//   F0(empty) = 1,  F0(y) = sum_b G0(y - b) lambda_b(y - b),                       G0 = F0 / (L + sigma + kappa0)
+//                   FM(y) = G0(y) sigma(y)      + sum_b GM(y - b) mu_b(y - b),     GM = FM / (Lm + kappam)
+//                   FC(y) = G0(y) sigma(y) |y|  + sum_b GC(y - b) mu_b(y - b),     GC = FC / (Lm + kappam)
+//   Z = sigma G0,  M = kappam GM (exp(lp) of the cohort row of type 2),  C = kappam GC  (C / M: the expected number of
+//   the metastasis' mutations that the founder held)
+//
+// Layout.  PLANAR: three vectors of 2^n doubles in the workspace, plane s of code x at V[s * 2^n + x], G0, GM, GC during
+// the sweep; k_metdist_tile turns them into Z, M, C in place once every level is finished - the layout of `full`.
+//
+// Shape.  k_genodist_level's: the tiles of landscape.h, a host-built list of tile numbers sorted by popcount, one launch of
+// k_metdist_level per popcount of the tile number, ASCENDING, ordered by stream order alone: no cooperative launch, no
+// flags, no atomics.  Inside a tile
+//   1. the high columns once: r = HF[j] TL[j] TH[j] is formed once per move, r exp(theta[j][n]) (the factor from a
+//      32-entry table in LDS) serves GM and GC; a held column pulls from the finished tile T - bit at the same offsets -
+//      consecutive lanes read consecutive addresses of all three planes - a free one adds to the partial L and Lm;
+//   2. the forward substitution over the low bits in LDS with orderpass.h's level walk; G0 of a state before its FM and
+//      FC, which take G0 sigma of the same state; |y| = popcount(T) + popcount(p); the tile is written out once.
+//
+// kappa0 is column n + 1 of the obs1 tables, as in genodist.h.  kappam needs the same column of obs2: the host launches
+// landscape.h's k_landscape_tables a SECOND time with obs2 in place of obs1 and a tile copies ONLY the clock column of
+// that second set (2 x 32 doubles) into LDS - no table kernel of its own; the second set's rate columns equal the first's
+// and are not read.
+//
+// LDS of a workgroup of k_metdist_level: 5 x 8 KiB (F0, FM, FC, the partial L and Lm of 2^10 states) + 16.5 KiB of rate
+// tables + 2 KiB of patterns + the tile's factors, exp(theta[j][n]) and the obs2 clock column: the landscape's footprint,
+// two workgroups a CU.  256 threads, 4 states per thread in step 1: 20 accumulators.
+//
+// Summary.  k_metdist_tile<SUMS> forms the GD_FEAT = 67 partial sums of the planes Z and M per tile with genodist.h's
+// three-stage fold (gd_tile_fold, the one copy both kernels call); k_genodist_summary then adds the tiles' partials,
+// unchanged: summary plane 0 is the founder, plane 1 the metastasis.
+//
+// Every shape depends on n alone: no byte of an output depends on the queries, the grid or an earlier call.  fp64 only.
+//
+// RESOURCES (gfx950, -O3, -Rpass-analysis=kernel-resource-usage): k_metdist_level 96 VGPRs, 0 AGPRs, 53 SGPRs, scratch 0,
+// LDS 61 024 B, 2 waves / SIMD (two workgroups a CU, by LDS; the registers would allow 5); k_metdist_tile<true> 40 VGPRs,
+// 54 SGPRs, scratch 0, LDS 51 712 B, three workgroups a CU; k_metdist_tile<false> 26 VGPRs, scratch 0, LDS 1 024 B;
+// k_metdist_gather 14 VGPRs, scratch 0.  (k_genodist_tile<true>, the other caller of gd_tile_fold: 36 VGPRs, 50 SGPRs,
+// scratch 0, LDS 51 200 B - the 512 B between the two are the sigma tables.)
+#pragma once
+#include "genodist.h"
+
+namespace mmhn {
+
+// one level of tiles: workgroup b finishes the tile tiles[b]; every tile tiles[b] - bit is finished (earlier launches).
+// tabs: the tables of (theta, obs1); tabm: the tables of (theta, obs2), of which only the clock column is read
+__global__ __launch_bounds__(LS_KB) void k_metdist_level(const LsTables* __restrict__ tabs, const LsTables* __restrict__ tabm,
+                                                         const uint32_t* __restrict__ tiles, const double* __restrict__ g_lt,
+                                                         const double* __restrict__ g_o1, const double* __restrict__ g_o2,
+                                                         int N, int c, double* V) {
+  __shared__ LsTables S;
+  __shared__ double HF[LS_COLS];                // column j: exp(diagonal + the effects of the tile's high bits)
+  __shared__ double EM[ORD_MAXN + 1];           // exp(theta[j][n]): mu_j = lambda_j EM[j]
+  __shared__ double ML[1 << LS_HALF], MH[1 << LS_HALF];   // the clock column of the obs2 tables
+  __shared__ double KM;                         // exp(obs2[n] + the obs2 of the tile's high bits)
+  __shared__ double W[5][1 << LS_TILE_BITS];    // 0 / 1 / 2: F0 / FM / FC of the tile's states (partial until a state is finished, then G), 3 / 4: its partial L / Lm
+  const int tid = threadIdx.x, n = N - 1, cols = N + 1;
+  const uint32_t T = tiles[blockIdx.x];
+  const uint32_t Vt = 1u << c;
+  const long long plane = 1ll << n, base = (long long)T << c;
+  for (int i = tid; i < (int)(sizeof(LsTables) / 4); i += LS_KB)
+    reinterpret_cast<uint32_t*>(&S)[i] = reinterpret_cast<const uint32_t*>(tabs)[i];
+  if (tid < cols) {
+    const int j = tid;
+    double v = j <= n ? g_lt[j * N + j] : 0.0;
+    for (uint32_t m = T; m; m &= m - 1) v += ls_eff(g_lt, g_o1, N, j, c + __builtin_ctz(m));
+    HF[j] = exp(v);
+  }
+  if (tid < (1 << LS_HALF)) {
+    ML[tid] = tabm->TL[n + 1][tid]; MH[tid] = tabm->TH[n + 1][tid];
+    EM[tid] = tid < n ? exp(g_lt[tid * N + n]) : 0.0;
+  }
+  if (tid == LS_KB - 1) {
+    double v = g_o2[n];
+    for (uint32_t m = T; m; m &= m - 1) v += g_o2[c + __builtin_ctz(m)];
+    KM = exp(v);
+  }
+  __syncthreads();
+
+  // 1. the columns of the high bits: a held one is the move pulled from the tile T - bit, a free one a term of L and Lm
+  {
+    double a0[LS_SPT], a1[LS_SPT], a2[LS_SPT], dn[LS_SPT], dm[LS_SPT];
+#pragma unroll
+    for (int s = 0; s < LS_SPT; ++s) a0[s] = a1[s] = a2[s] = dn[s] = dm[s] = 0.0;
+    for (int j = c; j < n; ++j) {
+      const bool held = (T >> (j - c)) & 1u;
+      const double hf = HF[j], em = EM[j];
+      const double* q = held ? V + base - (1ll << j) : V;
+#pragma unroll
+      for (int s = 0; s < LS_SPT; ++s) {
+        const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
+        if (p < Vt) {
+          const double r = hf * S.TL[j][p & 31u] * S.TH[j][p >> LS_HALF];
+          const double rm = r * em;
+          if (held) {
+            a0[s] += r * q[p];
+            a1[s] += rm * q[plane + p];
+            a2[s] += rm * q[2 * plane + p];
+          } else {
+            dn[s] += r;
+            dm[s] += rm;
+          }
+        }
+      }
+    }
+    if (T == 0u && tid == 0) a0[0] = 1.0;         // F0 of the empty genotype
+#pragma unroll
+    for (int s = 0; s < LS_SPT; ++s) {
+      const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
+      if (p < Vt) { W[0][p] = a0[s]; W[1][p] = a1[s]; W[2][p] = a2[s]; W[3][p] = dn[s]; W[4][p] = dm[s]; }
+    }
+  }
+  __syncthreads();
+
+  // 2. the forward substitution over the low bits
+  const uint32_t chunks = Vt >> S.L.c;
+  const int pcT = __builtin_popcount(T);
+  const double km = KM;
+  for (int lev = 0; lev <= c; ++lev) {
+    opo_level<LS_KB>(S.L, 0u, chunks, lev, [&](uint32_t p) {
+      const uint32_t lo = p & 31u, hi = p >> LS_HALF;
+      double f0 = W[0][p], fm = W[1][p], fc = W[2][p], L = W[3][p], Lm = W[4][p];
+#pragma unroll
+      for (int j = 0; j < LS_TILE_BITS; ++j) {
+        if (j < c) {
+          const double r = HF[j] * S.TL[j][lo] * S.TH[j][hi];
+          const double rm = r * EM[j];
+          if ((p >> j) & 1u) {
+            const uint32_t y = p ^ (1u << j);
+            f0 += r * W[0][y];
+            fm += rm * W[1][y];
+            fc += rm * W[2][y];
+          } else {
+            L += r;
+            Lm += rm;
+          }
+        }
+      }
+      const double sig = HF[n] * S.TL[n][lo] * S.TH[n][hi];
+      const double kap = HF[n + 1] * S.TL[n + 1][lo] * S.TH[n + 1][hi];
+      const double g0 = f0 / (L + sig + kap);
+      const double seeded = g0 * sig;
+      const double denm = Lm + km * ML[lo] * MH[hi];
+      W[0][p] = g0;
+      W[1][p] = (seeded + fm) / denm;
+      W[2][p] = (seeded * (double)(pcT + __builtin_popcount(p)) + fc) / denm;
+    });
+    __syncthreads();
+  }
+  for (uint32_t p = tid; p < Vt; p += LS_KB) {
+    double* o = V + base + p;
+    o[0] = W[0][p]; o[plane] = W[1][p]; o[2 * plane] = W[2][p];
+  }
+}
+
+// every tile once all levels are finished (workgroup = tile number): G to Z = sigma G0, M = kappam GM, C = kappam GC in
+// place and, with SUMS, the GD_FEAT partial sums of the tile's Z and M at part[(s * GD_FEAT + f) * nt + T]
+template <bool SUMS>
+__global__ __launch_bounds__(LS_KB) void k_metdist_tile(const LsTables* __restrict__ tabs, const LsTables* __restrict__ tabm,
+                                                        const double* __restrict__ g_lt, const double* __restrict__ g_o2,
+                                                        int N, int c, double* V, double* __restrict__ part, long long nt) {
+  __shared__ double SL[1 << LS_HALF], SH[1 << LS_HALF], ML[1 << LS_HALF], MH[1 << LS_HALF];
+  const int tid = threadIdx.x, n = N - 1;
+  const uint32_t T = blockIdx.x;
+  const uint32_t Vt = 1u << c;
+  const long long plane = 1ll << n, base = (long long)T << c;
+  if (tid < (1 << LS_HALF)) {
+    SL[tid] = tabs->TL[n][tid]; SH[tid] = tabs->TH[n][tid];
+    ML[tid] = tabm->TL[n + 1][tid]; MH[tid] = tabm->TH[n + 1][tid];
+  }
+  double vs = g_lt[n * N + n], vm = g_o2[n];    // (k_metdist_level's HF[n] and KM)
+  for (uint32_t m = T; m; m &= m - 1) {
+    const int i = c + __builtin_ctz(m);
+    vs += g_lt[n * N + i];
+    vm += g_o2[i];
+  }
+  const double sf = exp(vs), km = exp(vm);
+  __syncthreads();
+  double u[LS_SPT], w[LS_SPT];
+#pragma unroll
+  for (int s = 0; s < LS_SPT; ++s) {
+    const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
+    u[s] = w[s] = 0.0;
+    if (p < Vt) {
+      const uint32_t lo = p & 31u, hi = p >> LS_HALF;
+      const double sig = sf * SL[lo] * SH[hi];
+      const double kap = km * ML[lo] * MH[hi];
+      double* o = V + base + p;
+      u[s] = sig * o[0];
+      w[s] = kap * o[plane];
+      o[0] = u[s]; o[plane] = w[s];
+      o[2 * plane] = kap * o[2 * plane];
+    }
+  }
+  if constexpr (SUMS) gd_tile_fold(u, w, part, nt, T);
+}
+
+// the three values at the queried codes: out[i][s] = V[s][codes[i]]
+__global__ __launch_bounds__(LS_KB) void k_metdist_gather(const uint32_t* __restrict__ codes, long long R,
+                                                          const double* __restrict__ V, int n, double* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * LS_KB + threadIdx.x;
+  if (i >= R) return;
+  const long long plane = 1ll << n, x = codes[i];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out[3 * i + k] = V[k * plane + x];
+}
+
+}  // namespace mmhn

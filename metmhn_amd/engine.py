@@ -675,6 +675,33 @@ class Engine:
                     np.ascontiguousarray(sums[:, 1 + n * n:]))
         return values, status, sums, whole
 
+    # ---- metastasis distribution
+    def metastasis_distribution(self, log_theta, obs1, obs2, genotypes, summary=True, full=False):
+        """The probability of every genotype to be the founder's (Z: the seeding happens before the PT's observation and the
+        seeding cell holds exactly that genotype), the metastasis' observed one (M, exp(lp) of the type-2 row) and M weighted
+        by the number of its mutations the founder held (C), from one forward sweep over all 2^n genotype codes
+        (mmhn_metastasis_distribution), read at the rows of int8 `genotypes` [R, n] (1 = held; R may be 0): float64 values
+        [R, 3] = Z, M, C, int32 status [R] (0 ok, 2 with reason code 8 in status >> 16 for an entry other than 0 / 1, whose
+        values are NaN), with summary=True (mass [2], pairs [2, n, n], burden [2, n+1]) of the planes Z and M, else None, and
+        with full=True the three planes [3, 2^n] by code (bit j = mutation j), else None.  Raises when 24 B x 2^n, the tables,
+        the tile list and the tiles' partial sums exceed the workspace limit."""
+        lt, ltp = self._theta(log_theta); a, ap = self._rates(obs1, "obs1"); b, bp = self._rates(obs2, "obs2")
+        g = np.ascontiguousarray(np.asarray(genotypes).astype(np.int8))
+        if g.ndim != 2 or g.shape[1] != self.n:
+            raise ValueError(f"genotypes must be a 2-D array [R, {self.n}]")
+        R, n = g.shape[0], self.n
+        values = np.empty((R, 3))                                # (the library fills it with NaN first)
+        status = np.zeros(R, dtype=np.int32)
+        sums = np.empty((2, 1 + n * n + n + 1)) if summary else None
+        whole = np.empty((3, 1 << n)) if full else None
+        _lib.check(self.lib.mmhn_metastasis_distribution(
+            self.h, ltp, ap, bp, g.ctypes.data_as(i8p), R, values.ctypes.data_as(f64p), status.ctypes.data_as(_lib.i32p),
+            sums.ctypes.data_as(f64p) if summary else None, whole.ctypes.data_as(f64p) if full else None))
+        if summary:
+            sums = (np.ascontiguousarray(sums[:, 0]), np.ascontiguousarray(sums[:, 1:1 + n * n]).reshape(2, n, n),
+                    np.ascontiguousarray(sums[:, 1 + n * n:]))
+        return values, status, sums, whole
+
     # ---- measurement
     def bench_kronvec(self, log_theta, state, batch, iters, transpose=False, jacobi=False, tiles=False):
         """ms per launch of mmhn_kronvec_batched's launch (or the fused Jacobi step); tiles=True also returns

@@ -478,8 +478,83 @@ class GenotypeDistribution(SimpleNamespace):
             return self.seeded / self.total
 
 
+METASTASIS_STRATA = ("founder", "MT")           # the planes of the metastasis distribution's summary
+
+
+class MetastasisSummary(GenotypeSummary):
+    """Exact sums over the genotype distribution of the metastasis' founder (plane 0: the genotype of the cell that seeds,
+    Z) and of the metastasis at its observation (plane 1, M), GenotypeSummary's arrays: mass [2] (the two are equal, the
+    probability that the seeding happens before the primary tumour's observation), pairs [2, n, n], burden [2, n+1].  Strata
+    (METASTASIS_STRATA): "founder" plane 0 over mass[0], "MT" plane 1 over mass[1]; frequencies, log_odds and burden_pmf are
+    GenotypeSummary's."""
+
+    def __repr__(self):
+        return f"MetastasisSummary(n_mut={self.n_mut}, mass={self.mass.tolist()})"
+
+    def _stratum(self, stratum):
+        if stratum not in METASTASIS_STRATA:
+            raise ValueError(f"stratum must be one of {METASTASIS_STRATA}, got {stratum!r}")
+        s = METASTASIS_STRATA.index(stratum)
+        return self.pairs[s], self.burden[s], self.mass[s]
+
+    def acquired(self) -> np.ndarray:
+        """[n]: the probability that the metastasis gained mutation j after the seeding - the marginal frequency of j in
+        the metastasis minus the one in its founder (the founder's mutations all stay)."""
+        return np.diag(self.frequencies("MT")) - np.diag(self.frequencies("founder"))
+
+    def expected_founder_events(self) -> float:
+        """The expected number of mutations the seeding cell holds: sum_m m burden_pmf("founder")[m]."""
+        return float(np.arange(self.n_mut + 1) @ self.burden_pmf("founder"))
+
+    def compare(self, dat) -> dict:
+        """The check of a cohort `dat` [n_pat, 2 n_mut + 3] against the exact frequencies of the metastasis: per row type
+        present among 2 (key "EM-MT") and 3 (key "paired") the standardised residuals [n, n]
+        (obs - rows p) / sqrt(rows p (1 - p)) of the observed MT-block pair counts of the type's rows
+        (Utilityfunctions.pair_counts(dat)[1][t][1::2, 1::2]) against p = frequencies("MT") - simulations.PairSummary.compare's
+        formula; NaN where p is not inside (0, 1)."""
+        from .Utilityfunctions import pair_counts
+        dat = np.asarray(dat)
+        n = self.n_mut
+        if dat.ndim != 2 or dat.shape[1] != 2 * n + 3:
+            raise ValueError(f"dat must have shape (n_pat, {2 * n + 3}), got {dat.shape}")
+        n_type, obs = pair_counts(dat)
+        p = self.frequencies("MT")
+        out = {}
+        for key, t in (("EM-MT", 2), ("paired", 3)):
+            rows = int(n_type[t])
+            if rows == 0:
+                continue
+            with np.errstate(divide="ignore", invalid="ignore"):
+                r = (obs[t][1::2, 1::2] - rows * p) / np.sqrt(rows * p * (1.0 - p))
+            r[~((p > 0.0) & (p < 1.0))] = np.nan
+            out[key] = r
+        return out
+
+
+class MetastasisDistribution(SimpleNamespace):
+    """The probability that the seeding happens before the primary tumour's observation and the seeding cell holds exactly
+    a genotype (`founder`, Z), that the metastasis is observed with it (`metastasis`, M, the likelihood of the cohort row of
+    type 2) and M weighted by how many of the genotype's mutations the founder held (`founder_weighted`, C), arrays over
+    the genotypes `codes` (bit j of a code = mutation j held), with `summary`, the MetastasisSummary of the WHOLE lattice.
+    MetMHN.metastasis_distribution returns every genotype, codes = 0 .. 2^n - 1; metastasis_distribution_at the rows it
+    was given."""
+
+    def __init__(self, founder, metastasis, founder_weighted, codes, summary):
+        super().__init__(founder=founder, metastasis=metastasis, founder_weighted=founder_weighted, codes=codes,
+                         summary=summary)
+
+    @property
+    def founder_events(self) -> np.ndarray:
+        """founder_weighted / metastasis: the expected number of the metastasis' mutations that were already in the
+        founder, given only the MT genotype (NaN where metastasis is 0)."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out = self.founder_weighted / self.metastasis
+        return np.where(self.metastasis == 0, np.nan, out)
+
+
 _FORECAST_UNTIL = ("seeding", "observation")
 _GENODIST_HOST_MAX = 24          # mutations the host distribution takes on: n x 2^n doubles of rates
+_METDIST_HOST_MAX = 24           # the same of the metastasis distribution
 _FORECAST_HOST_MAX = 24          # free mutations the host definition takes on: f x 2^f doubles of rates
 _LANDSCAPE_HOST_MAX = 24         # mutations the host landscape takes on: n x 2^n doubles of rates
 _NO_SEEDING_EXIT = ("the seeding rate of the full genotype underflows to 0 (a theta[n, n] of -1e10, as a fit without seeded "
@@ -1159,6 +1234,112 @@ class MetMHN:
                 raise ValueError(f"row {int(bad[0])}: a genotype entry is neither 0 nor 1")
             summary = GenotypeSummary(*sums)
         return GenotypeDistribution(np.ascontiguousarray(values[:, 0]), np.ascontiguousarray(values[:, 1]), codes, summary)
+
+    # ------------------------------------------------------------------ genotype distribution of the metastasis and its founder
+    def _metdist_host(self) -> np.ndarray:
+        """[3, 2^n]: the definition of the metastasis distribution (Z, M, C), level by level over the popcount, ascending."""
+        th, n = self._pt_log_theta, self.n
+        if n > _METDIST_HOST_MAX:
+            raise ValueError(f"{n} mutations: the host distribution stops at {_METDIST_HOST_MAX} ({n} x 2^{n} doubles of "
+                             "rates); use backend='device'")
+        size = 1 << n
+        idx = np.arange(size)
+        level = _subset_sums(np.ones(n)).astype(np.int64)
+        lam = [np.exp(th[j, j] + _subset_sums(np.where(np.arange(n) == j, 0.0, th[j, :n]))) for j in range(n)]
+        mu = [lam[j] * np.exp(self.log_theta[j, n]) for j in range(n)]
+        sig = np.exp(th[n, n] + _subset_sums(th[n, :n]))
+        kap0 = np.exp(_subset_sums(self.obs1[:n]))
+        kapm = np.exp(self.obs2[n] + _subset_sums(self.obs2[:n]))
+        L, Lm = np.zeros(size), np.zeros(size)
+        for j in range(n):
+            free = (idx >> j & 1) == 0
+            L += np.where(free, lam[j], 0.0)
+            Lm += np.where(free, mu[j], 0.0)
+        den0, denm = L + sig + kap0, Lm + kapm
+        F0, FM, FC, G0, GM, GC = (np.zeros(size) for _ in range(6))
+        F0[0] = 1.0
+        for lev in range(n + 1):
+            ys = idx[level == lev]
+            for b in range(n if lev else 0):
+                to = ys[(ys >> b & 1) == 1]
+                frm = to ^ (1 << b)
+                F0[to] += G0[frm] * lam[b][frm]
+                FM[to] += GM[frm] * mu[b][frm]
+                FC[to] += GC[frm] * mu[b][frm]
+            G0[ys] = F0[ys] / den0[ys]
+            seeded = G0[ys] * sig[ys]
+            FM[ys] = seeded + FM[ys]
+            FC[ys] = seeded * lev + FC[ys]
+            GM[ys] = FM[ys] / denm[ys]
+            GC[ys] = FC[ys] / denm[ys]
+        return np.stack((sig * G0, kapm * GM, kapm * GC))
+
+    @staticmethod
+    def _metdist_summary_host(P: np.ndarray) -> "MetastasisSummary":
+        """The MetastasisSummary of the planes P [3, 2^n] (Z and M are summed), by its definition."""
+        s = MetMHN._genodist_summary_host(P[:2])
+        return MetastasisSummary(s.mass, s.pairs, s.burden)
+
+    def metastasis_distribution(self, backend: str = "device", max_bytes: int = 2 ** 31) -> "MetastasisDistribution":
+        """The model's distribution over ALL genotypes of the metastasis at its observation and of its founder, the cell
+        that seeds: arrays over the 2^n genotype codes (bit j of a code = mutation j held), from one forward pass over the
+        lattice of all genotypes.  The metastasis is an autonomous chain: the common lineage until the seeding (which the
+        primary tumour's first observation can forestall), then its own rates, which carry the seeding's effect
+        theta[:n, n], until its own clock obs2.  With genotype_distribution's lambda, sigma, kappa0, L and
+        mu_j(z) = lambda_j(z) exp(theta_jn), Lm(z) the sum of mu_j over the mutations z does not hold,
+        kappam(z) = exp(obs2_n + sum_{i in z} obs2_i), b over the mutations a genotype holds:
+            F0(empty) = 1,  F0(y) = sum_b G0(y - b) lambda_b(y - b),                     G0 = F0 / (L + sigma + kappa0)
+                            FM(y) = G0(y) sigma(y)     + sum_b GM(y - b) mu_b(y - b),    GM = FM / (Lm + kappam)
+                            FC(y) = G0(y) sigma(y) |y| + sum_b GC(y - b) mu_b(y - b),    GC = FC / (Lm + kappam)
+            founder = sigma G0,  metastasis = kappam GM (exp(lp) of the type-2 row),  founder_weighted = kappam GC
+        `founder` and `metastasis` both sum to genotype_distribution's mass[1]; `founder_events` = founder_weighted /
+        metastasis is the expected number of the metastasis' mutations that were already in the founder; `summary` holds the
+        exact marginal and pairwise frequencies and burden distributions of the founder and the metastasis
+        (MetastasisSummary).
+
+        backend="device": one call of the HIP library (mmhn_metastasis_distribution), 24 B x 2^n of workspace and as much
+        here for the result; a ValueError names the bytes when that exceeds `max_bytes` (2 GiB: n <= 26).  backend="host": the
+        definition in NumPy, level by level, n <= 24."""
+        if backend not in ("device", "host"):
+            raise ValueError("backend must be 'device' or 'host'")
+        n = self.n
+        if backend == "host" and n > _METDIST_HOST_MAX:
+            self._metdist_host()                    # (raises: the message points to the device)
+        if 24 << n > max_bytes:
+            raise ValueError(f"{n} mutations: a distribution over 2^{n} genotypes needs {24 << n} bytes, more than max_bytes = "
+                             f"{int(max_bytes)}; metastasis_distribution_at reads single genotypes off the device's distribution")
+        if backend == "host":
+            whole = self._metdist_host()
+            summary = self._metdist_summary_host(whole)
+        else:
+            from .jx import engine
+            _, _, sums, whole = engine(n).metastasis_distribution(self.log_theta, self.obs1, self.obs2,
+                                                                  np.zeros((0, n), dtype=np.int8), summary=True, full=True)
+            summary = MetastasisSummary(*sums)
+        return MetastasisDistribution(whole[0], whole[1], whole[2], np.arange(1 << n), summary)
+
+    def metastasis_distribution_at(self, genotypes, backend: str = "device") -> "MetastasisDistribution":
+        """metastasis_distribution's three values at the rows of `genotypes` [R, n] (0 / 1), [R] each, with the rows' codes
+        and the summary of the WHOLE lattice: the distribution is swept on the device (24 B x 2^n of its workspace, any n the
+        engine takes) and only the rows and the summary come back.  backend="host": the NumPy definition, n <= 24.
+        An entry other than 0 / 1 raises ValueError("row i: ...") as seeding_forecasts does."""
+        if backend not in ("device", "host"):
+            raise ValueError("backend must be 'device' or 'host'")
+        g = self._forecast_checks(genotypes, "observation")
+        n = self.n
+        codes = g @ (1 << np.arange(n, dtype=np.int64))
+        if backend == "host":
+            whole = self._metdist_host()
+            values, summary = whole[:, codes].T, self._metdist_summary_host(whole)
+        else:
+            from .jx import engine
+            values, status, sums, _ = engine(n).metastasis_distribution(self.log_theta, self.obs1, self.obs2, g.astype(np.int8),
+                                                                        summary=True)
+            bad = np.flatnonzero(status != 0)
+            if bad.size:
+                raise ValueError(f"row {int(bad[0])}: a genotype entry is neither 0 nor 1")
+            summary = MetastasisSummary(*sums)
+        return MetastasisDistribution(*(np.ascontiguousarray(values[:, k]) for k in range(3)), codes, summary)
 
     def likelihood(self, order, met_status: str, first_obs: str = None) -> float:
         """model.py:295-376: probability of exactly this order of events being what is observed."""

@@ -507,6 +507,40 @@ def genotype_fit(log_theta, log_d_p, log_d_m, dat, backend: str = "device"):
     return SimpleNamespace(prob=prob, codes=codes, table=table, summary=got.summary, residuals=got.summary.compare(arr))
 
 
+def metastasis_fit(log_theta, log_d_p, log_d_m, dat, backend: str = "device"):
+    """How well the model's exact genotype distribution of the metastasis fits the MT genotypes of `dat`, from ONE forward
+    sweep over all genotypes (MetMHN.metastasis_distribution_at with obs1 = log_d_p, obs2 = log_d_m) - genotype_fit's
+    counterpart for the rows of types 2 ("EM-MT") and 3 ("paired").  A namespace of
+    prob [n_pat]: metastasis / mass[1] at the row's MT genotype dat[:, 1:2*n:2], its probability among the metastases; NaN
+        for the other types;
+    founder_events [n_pat]: the expected number of the MT genotype's mutations the founder held; NaN for the other types;
+    codes [n_pat]: the rows' MT genotype codes, -1 for the other types;
+    table: {stratum: (codes, observed, expected)} for the strata with rows - the distinct genotype codes of the stratum's
+        rows, ascending, how many rows carry each, and rows of the stratum x the genotype's probability;
+    summary: the model.MetastasisSummary of the whole lattice;  residuals: summary.compare(dat)."""
+    from types import SimpleNamespace
+    from .model import MetMHN
+    arr = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
+    n = (arr.shape[1] - 3) // 2
+    typ = arr[:, -1]
+    pick = np.isin(typ, (2, 3))
+    got = MetMHN(log_theta, log_d_p, log_d_m).metastasis_distribution_at(arr[pick][:, 1:2 * n:2], backend)
+    prob = np.full(arr.shape[0], np.nan)
+    founder_events = np.full(arr.shape[0], np.nan)
+    codes = np.full(arr.shape[0], -1, dtype=np.int64)
+    codes[pick] = got.codes
+    prob[pick] = got.metastasis / got.summary.mass[1]
+    founder_events[pick] = got.founder_events
+    table = {}
+    for stratum, ty in (("EM-MT", 2), ("paired", 3)):
+        rows = typ == ty
+        if rows.any():
+            uniq, first, counts = np.unique(codes[rows], return_index=True, return_counts=True)
+            table[stratum] = (uniq, counts.astype(np.int64), int(rows.sum()) * prob[rows][first])
+    return SimpleNamespace(prob=prob, founder_events=founder_events, codes=codes, table=table, summary=got.summary,
+                           residuals=got.summary.compare(arr))
+
+
 def _unpack(params, n_total):
     params = np.asarray(params, dtype=np.float64)
     return (params[0:n_total ** 2].reshape((n_total, n_total)), params[n_total ** 2:n_total * (n_total + 1)],
