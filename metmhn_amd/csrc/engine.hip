@@ -5,7 +5,7 @@
 // batches, routes, work lists, offsets), host.h (errors, device arrays, lanes, MMHN_* knob readers), comm.h (RCCL),
 // rowmix_host.h (row weights and row groups: their checks, device copies and the launches of the group kernels),
 // prims.h / orders_host.h / orderpost_host.h (the batching of the order-posterior entry points, opr_rows) /
-// orderprec_host.h / orderpos_host.h / ordertime_host.h / ordersnap_host.h / ordersample_host.h / forecast_host.h / landscape_host.h / genodist_host.h / metdist_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
+// orderprec_host.h / orderpos_host.h / ordertime_host.h / ordersnap_host.h / ordersample_host.h / forecast_host.h / lattice_host.h / landscape_host.h / genodist_host.h / metdist_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
 //
 // Pipeline of one evaluation (reference call graph: regularized_optimization.py:163-267 ->
 // likelihood.py:_g_coupled_*, _grad_prim_obs, _grad_met_obs), run batch by batch with every

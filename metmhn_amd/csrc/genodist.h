@@ -1,5 +1,5 @@
 // Genotype distribution of the primary tumour: the probability of EVERY genotype to be the one observed, unseeded (U) and
-// seeded by then (S), in one forward sweep over the full lattice - the forward counterpart of landscape.h on the same
+// seeded by then (S), in one forward sweep over the full lattice - the forward counterpart of landscape.h on lattice.h's
 // tiling (metmhn_amd/model.py MetMHN.genotype_distribution has the definition on the host).
 //
 // x is a genotype code (bit j = mutation j held), the primary tumour's theta, j over the mutations x does not hold, b over
@@ -14,7 +14,7 @@
 // the planes hold G (what a successor pulls); k_genodist_tile turns them into U and S in place once every level is
 // finished - the layout of the entry point's `full` output, so that is one copy - and folds the tile's sums on the way.
 //
-// Shape.  The tiles of landscape.h (the low c = min(n, LS_TILE_BITS) bits in LDS, the high bits name the tile, a
+// Shape.  The tiles of lattice.h (the low c = min(n, LS_TILE_BITS) bits in LDS, the high bits name the tile, a
 // host-built list of tile numbers sorted by popcount), one launch of k_genodist_level per popcount of the tile number,
 // ASCENDING: tile T needs the tiles T - bit and itself.  Stream order alone orders the levels: no cooperative launch, no
 // flags, no atomics.  Inside a tile
@@ -49,12 +49,12 @@
 //
 // Every shape depends on n alone: no byte of an output depends on the queries, the grid or an earlier call.  fp64 only.
 //
-// RESOURCES (gfx950, -O3): k_genodist_level 68 VGPRs, 0 AGPRs, 51 SGPRs, scratch 0, LDS 43 848 B, 3 waves / SIMD (three
-// workgroups a CU, by LDS; the registers would allow 7); k_genodist_tile<true> 36 VGPRs, 50 SGPRs, scratch 0, LDS 51 200 B,
-// three workgroups a CU; k_genodist_tile<false> 18 VGPRs, scratch 0, LDS 512 B; k_genodist_summary 12 VGPRs, scratch 0,
-// LDS 2 048 B; k_genodist_gather 10 VGPRs, scratch 0.
+// RESOURCES (gfx950, -O3, -Rpass-analysis=kernel-resource-usage): k_genodist_level 68 VGPRs, 0 AGPRs, 51 SGPRs, scratch 0,
+// LDS 43 848 B, 3 waves / SIMD (three workgroups a CU, by LDS; the registers would allow 7); k_genodist_tile<true> 36 VGPRs,
+// 50 SGPRs, scratch 0, LDS 51 200 B, 3 waves / SIMD; k_genodist_tile<false> 18 VGPRs, 46 SGPRs, scratch 0, LDS 512 B;
+// k_genodist_summary 12 VGPRs, 32 SGPRs, scratch 0, LDS 2 048 B.  lattice.h has the tables' and the gather's.
 #pragma once
-#include "landscape.h"
+#include "lattice.h"
 
 namespace mmhn {
 
@@ -81,18 +81,11 @@ __global__ __launch_bounds__(LS_KB) void k_genodist_level(const LsTables* __rest
   __shared__ LsTables S;
   __shared__ double HF[LS_COLS];                // column j: exp(diagonal + the effects of the tile's high bits)
   __shared__ double W[3][1 << LS_TILE_BITS];    // 0 / 1: F0 / F1 of the tile's states (partial until a state is finished, then G), 2: its partial L
-  const int tid = threadIdx.x, n = N - 1, cols = N + 1;
+  const int tid = threadIdx.x, n = N - 1;
   const uint32_t T = tiles[blockIdx.x];
   const uint32_t Vt = 1u << c;
   const long long plane = 1ll << n, base = (long long)T << c;
-  for (int i = tid; i < (int)(sizeof(LsTables) / 4); i += LS_KB)
-    reinterpret_cast<uint32_t*>(&S)[i] = reinterpret_cast<const uint32_t*>(tabs)[i];
-  if (tid < cols) {
-    const int j = tid;
-    double v = j <= n ? g_lt[j * N + j] : 0.0;
-    for (uint32_t m = T; m; m &= m - 1) v += ls_eff(g_lt, g_o1, N, j, c + __builtin_ctz(m));
-    HF[j] = exp(v);
-  }
+  ls_tile_prologue(S, HF, tabs, g_lt, g_o1, N, c, T);
   const double e1 = exp(g_o1[n]);               // kappa1 = kappa0 e1
   __syncthreads();
 
@@ -109,7 +102,7 @@ __global__ __launch_bounds__(LS_KB) void k_genodist_level(const LsTables* __rest
       for (int s = 0; s < LS_SPT; ++s) {
         const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
         if (p < Vt) {
-          const double r = hf * S.TL[j][p & 31u] * S.TH[j][p >> LS_HALF];
+          const double r = ls_rate(S, hf, j, p & 31u, p >> LS_HALF);
           if (held) {
             a0[s] += r * q[p];
             a1[s] += r * q[plane + p];
@@ -137,7 +130,7 @@ __global__ __launch_bounds__(LS_KB) void k_genodist_level(const LsTables* __rest
 #pragma unroll
       for (int j = 0; j < LS_TILE_BITS; ++j) {
         if (j < c) {
-          const double r = HF[j] * S.TL[j][lo] * S.TH[j][hi];
+          const double r = ls_rate(S, HF[j], j, lo, hi);
           if ((p >> j) & 1u) {
             const uint32_t y = p ^ (1u << j);
             f0 += r * W[0][y];
@@ -147,18 +140,15 @@ __global__ __launch_bounds__(LS_KB) void k_genodist_level(const LsTables* __rest
           }
         }
       }
-      const double sig = HF[n] * S.TL[n][lo] * S.TH[n][hi];
-      const double kap = HF[n + 1] * S.TL[n + 1][lo] * S.TH[n + 1][hi];
+      const double sig = ls_rate(S, HF[n], n, lo, hi);
+      const double kap = ls_rate(S, HF[n + 1], n + 1, lo, hi);
       const double g0 = f0 / (L + sig + kap);
       W[0][p] = g0;
       W[1][p] = (g0 * sig + f1) / (L + kap * e1);
     });
     __syncthreads();
   }
-  for (uint32_t p = tid; p < Vt; p += LS_KB) {
-    double* o = V + base + p;
-    o[0] = W[0][p]; o[plane] = W[1][p];
-  }
+  ls_write_tile<2>(W, Vt, V, base, plane);
 }
 
 // the GD_FEAT partial sums of a tile's two planes to part[(s * GD_FEAT + f) * nt + T]: u / w hold the planes' values at the
@@ -324,16 +314,6 @@ __global__ __launch_bounds__(LS_KB) void k_genodist_summary(const double* __rest
     else if (oi >= 0) { o[1 + oi * n + oj] = red[0]; o[1 + oj * n + oi] = red[0]; }
     else o[1 + n * n + (q - 1 - n * (n + 1) / 2)] = red[0];
   }
-}
-
-// the two values at the queried codes: out[i][s] = V[s][codes[i]]
-__global__ __launch_bounds__(LS_KB) void k_genodist_gather(const uint32_t* __restrict__ codes, long long R,
-                                                           const double* __restrict__ V, int n, double* __restrict__ out) {
-  const long long i = (long long)blockIdx.x * LS_KB + threadIdx.x;
-  if (i >= R) return;
-  const long long plane = 1ll << n, x = codes[i];
-  out[2 * i] = V[x];
-  out[2 * i + 1] = V[plane + x];
 }
 
 }  // namespace mmhn

@@ -1,34 +1,13 @@
-// Host side of the genotype distribution (genodist.h: k_genodist_level, k_genodist_tile, k_genodist_summary,
-// k_genodist_gather; the tables are landscape.h's k_landscape_tables): the query genotypes decoded to codes and checked,
-// the workspace - two planes of 2^n doubles, the model's tables, the tile list and, for the summary, the tiles' partial
-// sums - refused as a whole when it does not fit the workspace limit (there is no partial distribution), the tiles sorted
-// by the popcount of their number, one launch per popcount, ascending, on the engine's stream, one launch over every tile
-// that turns the planes into probabilities and folds the tiles' sums, the summary, the queried codes gathered on the device
-// and, on request, the two planes copied out.
+// Host side of the genotype distribution (genodist.h: k_genodist_level, k_genodist_tile, k_genodist_summary):
+// lattice_host.h's sweep with two planes, one set of tables, the levels ascending and, behind them, one launch over every
+// tile that turns the planes into probabilities and folds the tiles' sums, and the summary.
 #pragma once
-#include <algorithm>
-#include <cmath>
-#include <string>
-#include <vector>
-
 #include "genodist.h"
-#include "host.h"
-#include "landscape_host.h"                     // ls_decode_queries, ls_tile_levels
+#include "lattice_host.h"
 
 namespace mmhn {
 
 // (engine.hip includes this file behind the definition of Engine<T>)
-
-// doubles of the summary: per plane mass, pairs [n][n], burden [n + 1]
-inline long long gd_summary_doubles(int n) { return 2ll * (1 + (long long)n * n + n + 1); }
-
-// bytes of workspace a distribution over n mutations takes: 16 B a genotype, the tables, 4 B a tile and, with the summary,
-// 2 GD_FEAT doubles a tile and the summary itself
-inline long long gd_bytes(int n, bool summary) {
-  const long long nt = 1ll << (n - ls_tile_bits(n));
-  return (16ll << n) + (long long)sizeof(LsTables) + 4 * nt +
-         (summary ? (long long)sizeof(double) * (2 * GD_FEAT * nt + gd_summary_doubles(n)) : 0);
-}
 
 // gen [R][n]: 1 = held (R may be 0).  values [R][2]: U, S of every query; summary: nullptr or [2][1 + n * n + n + 1];
 // full: nullptr or [2][2^n], every genotype by code.
@@ -36,69 +15,19 @@ template <typename T>
 void genotype_distribution(Engine<T>& E, const double* lt, const double* obs1, const int8_t* gen, long long R,
                            double* values, int32_t* status, double* summary, double* full) {
   REQUIRE(E.N <= ORD_MAXN, "too many events for the genotype distribution kernels (n_mut <= 31)");
-  const int n = E.n, N = E.N, c = ls_tile_bits(n);
-  std::fill(values, values + 2 * R, std::nan(""));
-  const long long need = gd_bytes(n, summary != nullptr), limit = (long long)E.cfg.plan.ws_limit;
-  if (need > limit)
-    throw Fail{"genotype distribution: " + std::to_string(n) + " mutations need " + std::to_string(need) +
-               " bytes of workspace (16 B x 2^n_mut, the rate tables, the tile list and the tiles' partial sums), the "
-               "workspace limit is " + std::to_string(limit) + " bytes; there is no partial distribution"};
-  std::vector<uint32_t> codes;
-  std::vector<long long> src;
-  ls_decode_queries(gen, R, n, status, codes, src);
-  // the tiles by the popcount of their number, ascending
-  const int hb = n - c;
-  const size_t nt = (size_t)1 << hb;
-  std::vector<uint32_t> tiles;
-  std::vector<size_t> first;                           // first[l]: where the tiles of popcount l start
-  ls_tile_levels(hb, false, tiles, first);
-  DevArr<double> par, V, part, d_sum, d_out;
-  DevArr<LsTables> tabs;
-  DevArr<uint32_t> d_tiles, d_codes;
-  par.alloc((size_t)N * N + N);
-  V.alloc((size_t)2 << n);
-  tabs.alloc(1);
-  d_tiles.alloc(nt);
-  HIPCHECK(hipMemcpyAsync(par.p, lt, sizeof(double) * N * N, hipMemcpyHostToDevice, E.stream));
-  HIPCHECK(hipMemcpyAsync(par.p + N * N, obs1, sizeof(double) * N, hipMemcpyHostToDevice, E.stream));
-  HIPCHECK(hipMemcpyAsync(d_tiles.p, tiles.data(), nt * sizeof(uint32_t), hipMemcpyHostToDevice, E.stream));
-  hipLaunchKernelGGL(k_landscape_tables, dim3(1), dim3(LS_KB), 0, E.stream, par.p, par.p + N * N, N, c, tabs.p);
-  HIPCHECK(hipGetLastError());
-  for (int l = 0; l <= hb; ++l) {
-    hipLaunchKernelGGL(k_genodist_level, dim3((unsigned)(first[l + 1] - first[l])), dim3(LS_KB), 0, E.stream, tabs.p,
-                       d_tiles.p + first[l], par.p, par.p + N * N, N, c, V.p);
-    HIPCHECK(hipGetLastError());
-  }
-  if (summary) {
-    part.alloc((size_t)2 * GD_FEAT * nt);
-    d_sum.alloc((size_t)gd_summary_doubles(n));
-    hipLaunchKernelGGL(k_genodist_tile<true>, dim3((unsigned)nt), dim3(LS_KB), 0, E.stream, tabs.p, par.p + N * N, N, c, V.p,
-                       part.p, (long long)nt);
-    HIPCHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_genodist_summary, dim3((unsigned)(2 * gd_summary_items(n))), dim3(LS_KB), 0, E.stream, part.p,
-                       (long long)nt, n, c, d_sum.p);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpyAsync(summary, d_sum.p, sizeof(double) * gd_summary_doubles(n), hipMemcpyDeviceToHost, E.stream));
-  } else {
-    hipLaunchKernelGGL(k_genodist_tile<false>, dim3((unsigned)nt), dim3(LS_KB), 0, E.stream, tabs.p, par.p + N * N, N, c, V.p,
-                       (double*)nullptr, (long long)nt);
-    HIPCHECK(hipGetLastError());
-  }
-  std::vector<double> out(2 * codes.size());
-  if (!codes.empty()) {
-    d_codes.alloc(codes.size()); d_out.alloc(out.size());
-    HIPCHECK(hipMemcpyAsync(d_codes.p, codes.data(), codes.size() * sizeof(uint32_t), hipMemcpyHostToDevice, E.stream));
-    hipLaunchKernelGGL(k_genodist_gather, dim3((unsigned)((codes.size() + LS_KB - 1) / LS_KB)), dim3(LS_KB), 0, E.stream,
-                       d_codes.p, (long long)codes.size(), V.p, n, d_out.p);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpyAsync(out.data(), d_out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, E.stream));
-  }
-  if (full) HIPCHECK(hipMemcpyAsync(full, V.p, sizeof(double) * ((size_t)2 << n), hipMemcpyDeviceToHost, E.stream));
-  HIPCHECK(hipStreamSynchronize(E.stream));
-  for (size_t j = 0; j < codes.size(); ++j) {
-    values[2 * src[j]] = out[2 * j];
-    values[2 * src[j] + 1] = out[2 * j + 1];
-  }
+  static const LatticeSpec spec{"genotype distribution", ", the rate tables, the tile list and the tiles' partial sums",
+                                "distribution", 1, false};
+  lattice_sweep<2>(
+      E, spec, lt, obs1, nullptr, summary != nullptr, gen, R, values, status, full,
+      [](const LatticeRun& X, unsigned blocks, const uint32_t* tiles) {
+        hipLaunchKernelGGL(k_genodist_level, dim3(blocks), dim3(LS_KB), 0, X.stream, X.tabs, tiles, X.lt, X.obs1, X.N, X.c, X.V);
+      },
+      [&](LatticeRun& X) {
+        lattice_summary(X, summary, [&](auto sums, double* part) {
+          hipLaunchKernelGGL(k_genodist_tile<decltype(sums)::value>, dim3((unsigned)X.nt), dim3(LS_KB), 0, X.stream, X.tabs,
+                             X.obs1, X.N, X.c, X.V, part, (long long)X.nt);
+        });
+      });
 }
 
 }  // namespace mmhn

@@ -17,7 +17,7 @@
 // Layout.  PLANAR: three vectors of 2^n doubles in the workspace, plane s of code x at V[s * 2^n + x], G0, GM, GC during
 // the sweep; k_metdist_tile turns them into Z, M, C in place once every level is finished - the layout of `full`.
 //
-// Shape.  k_genodist_level's: the tiles of landscape.h, a host-built list of tile numbers sorted by popcount, one launch of
+// Shape.  k_genodist_level's: the tiles of lattice.h, a host-built list of tile numbers sorted by popcount, one launch of
 // k_metdist_level per popcount of the tile number, ASCENDING, ordered by stream order alone: no cooperative launch, no
 // flags, no atomics.  Inside a tile
 //   1. the high columns once: r = HF[j] TL[j] TH[j] is formed once per move, r exp(theta[j][n]) (the factor from a
@@ -27,7 +27,7 @@
 //      FC, which take G0 sigma of the same state; |y| = popcount(T) + popcount(p); the tile is written out once.
 //
 // kappa0 is column n + 1 of the obs1 tables, as in genodist.h.  kappam needs the same column of obs2: the host launches
-// landscape.h's k_landscape_tables a SECOND time with obs2 in place of obs1 and a tile copies ONLY the clock column of
+// lattice.h's k_landscape_tables a SECOND time with obs2 in place of obs1 and a tile copies ONLY the clock column of
 // that second set (2 x 32 doubles) into LDS - no table kernel of its own; the second set's rate columns equal the first's
 // and are not read.
 //
@@ -43,9 +43,9 @@
 //
 // RESOURCES (gfx950, -O3, -Rpass-analysis=kernel-resource-usage): k_metdist_level 96 VGPRs, 0 AGPRs, 53 SGPRs, scratch 0,
 // LDS 61 024 B, 2 waves / SIMD (two workgroups a CU, by LDS; the registers would allow 5); k_metdist_tile<true> 40 VGPRs,
-// 54 SGPRs, scratch 0, LDS 51 712 B, three workgroups a CU; k_metdist_tile<false> 26 VGPRs, scratch 0, LDS 1 024 B;
-// k_metdist_gather 14 VGPRs, scratch 0.  (k_genodist_tile<true>, the other caller of gd_tile_fold: 36 VGPRs, 50 SGPRs,
-// scratch 0, LDS 51 200 B - the 512 B between the two are the sigma tables.)
+// 54 SGPRs, scratch 0, LDS 51 712 B, 3 waves / SIMD; k_metdist_tile<false> 26 VGPRs, 48 SGPRs, scratch 0, LDS 1 024 B.
+// (k_genodist_tile<true>, the other caller of gd_tile_fold: 36 VGPRs, 50 SGPRs, scratch 0, LDS 51 200 B - the 512 B between
+// the two are the sigma tables.)  lattice.h has the tables' and the gather's.
 #pragma once
 #include "genodist.h"
 
@@ -63,18 +63,11 @@ __global__ __launch_bounds__(LS_KB) void k_metdist_level(const LsTables* __restr
   __shared__ double ML[1 << LS_HALF], MH[1 << LS_HALF];   // the clock column of the obs2 tables
   __shared__ double KM;                         // exp(obs2[n] + the obs2 of the tile's high bits)
   __shared__ double W[5][1 << LS_TILE_BITS];    // 0 / 1 / 2: F0 / FM / FC of the tile's states (partial until a state is finished, then G), 3 / 4: its partial L / Lm
-  const int tid = threadIdx.x, n = N - 1, cols = N + 1;
+  const int tid = threadIdx.x, n = N - 1;
   const uint32_t T = tiles[blockIdx.x];
   const uint32_t Vt = 1u << c;
   const long long plane = 1ll << n, base = (long long)T << c;
-  for (int i = tid; i < (int)(sizeof(LsTables) / 4); i += LS_KB)
-    reinterpret_cast<uint32_t*>(&S)[i] = reinterpret_cast<const uint32_t*>(tabs)[i];
-  if (tid < cols) {
-    const int j = tid;
-    double v = j <= n ? g_lt[j * N + j] : 0.0;
-    for (uint32_t m = T; m; m &= m - 1) v += ls_eff(g_lt, g_o1, N, j, c + __builtin_ctz(m));
-    HF[j] = exp(v);
-  }
+  ls_tile_prologue(S, HF, tabs, g_lt, g_o1, N, c, T);
   if (tid < (1 << LS_HALF)) {
     ML[tid] = tabm->TL[n + 1][tid]; MH[tid] = tabm->TH[n + 1][tid];
     EM[tid] = tid < n ? exp(g_lt[tid * N + n]) : 0.0;
@@ -99,7 +92,7 @@ __global__ __launch_bounds__(LS_KB) void k_metdist_level(const LsTables* __restr
       for (int s = 0; s < LS_SPT; ++s) {
         const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
         if (p < Vt) {
-          const double r = hf * S.TL[j][p & 31u] * S.TH[j][p >> LS_HALF];
+          const double r = ls_rate(S, hf, j, p & 31u, p >> LS_HALF);
           const double rm = r * em;
           if (held) {
             a0[s] += r * q[p];
@@ -132,7 +125,7 @@ __global__ __launch_bounds__(LS_KB) void k_metdist_level(const LsTables* __restr
 #pragma unroll
       for (int j = 0; j < LS_TILE_BITS; ++j) {
         if (j < c) {
-          const double r = HF[j] * S.TL[j][lo] * S.TH[j][hi];
+          const double r = ls_rate(S, HF[j], j, lo, hi);
           const double rm = r * EM[j];
           if ((p >> j) & 1u) {
             const uint32_t y = p ^ (1u << j);
@@ -145,8 +138,8 @@ __global__ __launch_bounds__(LS_KB) void k_metdist_level(const LsTables* __restr
           }
         }
       }
-      const double sig = HF[n] * S.TL[n][lo] * S.TH[n][hi];
-      const double kap = HF[n + 1] * S.TL[n + 1][lo] * S.TH[n + 1][hi];
+      const double sig = ls_rate(S, HF[n], n, lo, hi);
+      const double kap = ls_rate(S, HF[n + 1], n + 1, lo, hi);
       const double g0 = f0 / (L + sig + kap);
       const double seeded = g0 * sig;
       const double denm = Lm + km * ML[lo] * MH[hi];
@@ -156,10 +149,7 @@ __global__ __launch_bounds__(LS_KB) void k_metdist_level(const LsTables* __restr
     });
     __syncthreads();
   }
-  for (uint32_t p = tid; p < Vt; p += LS_KB) {
-    double* o = V + base + p;
-    o[0] = W[0][p]; o[plane] = W[1][p]; o[2 * plane] = W[2][p];
-  }
+  ls_write_tile<3>(W, Vt, V, base, plane);
 }
 
 // every tile once all levels are finished (workgroup = tile number): G to Z = sigma G0, M = kappam GM, C = kappam GC in
@@ -202,16 +192,6 @@ __global__ __launch_bounds__(LS_KB) void k_metdist_tile(const LsTables* __restri
     }
   }
   if constexpr (SUMS) gd_tile_fold(u, w, part, nt, T);
-}
-
-// the three values at the queried codes: out[i][s] = V[s][codes[i]]
-__global__ __launch_bounds__(LS_KB) void k_metdist_gather(const uint32_t* __restrict__ codes, long long R,
-                                                          const double* __restrict__ V, int n, double* __restrict__ out) {
-  const long long i = (long long)blockIdx.x * LS_KB + threadIdx.x;
-  if (i >= R) return;
-  const long long plane = 1ll << n, x = codes[i];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) out[3 * i + k] = V[k * plane + x];
 }
 
 }  // namespace mmhn

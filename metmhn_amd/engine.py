@@ -626,6 +626,27 @@ class Engine:
             n_before.ctypes.data_as(f64p), status.ctypes.data_as(_lib.i32p)))
         return p_seed, time, before, with_seed, n_before, status
 
+    # ---- sweeps over all 2^n genotypes
+    def _lattice_call(self, genotypes, planes, summary, full, call):
+        """What the three whole-lattice calls share: the check of int8 `genotypes` [R, n], the buffers values [R, planes],
+        status [R], sums (with `summary`) and whole [planes, 2^n] (with `full`), the library call - call(genotypes, R,
+        values, status, sums or None, whole or None), all pointers - and the summary split into (mass [2], pairs [2, n, n],
+        burden [2, n+1]).  Returns values, status, sums, whole."""
+        g = np.ascontiguousarray(np.asarray(genotypes).astype(np.int8))
+        if g.ndim != 2 or g.shape[1] != self.n:
+            raise ValueError(f"genotypes must be a 2-D array [R, {self.n}]")
+        R, n = g.shape[0], self.n
+        values = np.empty((R, planes))                           # (the library fills it with NaN first)
+        status = np.zeros(R, dtype=np.int32)
+        sums = np.empty((2, 1 + n * n + n + 1)) if summary else None
+        whole = np.empty((planes, 1 << n)) if full else None
+        _lib.check(call(g.ctypes.data_as(i8p), R, values.ctypes.data_as(f64p), status.ctypes.data_as(_lib.i32p),
+                        sums.ctypes.data_as(f64p) if summary else None, whole.ctypes.data_as(f64p) if full else None))
+        if summary:
+            sums = (np.ascontiguousarray(sums[:, 0]), np.ascontiguousarray(sums[:, 1:1 + n * n]).reshape(2, n, n),
+                    np.ascontiguousarray(sums[:, 1 + n * n:]))
+        return values, status, sums, whole
+
     # ---- seeding landscape
     def seeding_landscape(self, log_theta, obs1, genotypes, until="seeding", full=False):
         """The four forecast scalars of every genotype of the model from one backward sweep over all 2^n genotype codes
@@ -637,16 +658,9 @@ class Engine:
         if until not in ("seeding", "observation"):
             raise ValueError("until must be 'seeding' or 'observation'")
         lt, ltp = self._theta(log_theta); a, ap = self._rates(obs1, "obs1")
-        g = np.ascontiguousarray(np.asarray(genotypes).astype(np.int8))
-        if g.ndim != 2 or g.shape[1] != self.n:
-            raise ValueError(f"genotypes must be a 2-D array [R, {self.n}]")
-        R = g.shape[0]
-        values = np.empty((R, 4))                                # (the library fills it with NaN first)
-        status = np.zeros(R, dtype=np.int32)
-        whole = np.empty((4, 1 << self.n)) if full else None
-        _lib.check(self.lib.mmhn_seeding_landscape(
-            self.h, ltp, ap, 0 if until == "seeding" else 1, g.ctypes.data_as(i8p), R, values.ctypes.data_as(f64p),
-            status.ctypes.data_as(_lib.i32p), whole.ctypes.data_as(f64p) if full else None))
+        values, status, _, whole = self._lattice_call(
+            genotypes, 4, False, full, lambda gp, R, vp, sp, _, wp: self.lib.mmhn_seeding_landscape(
+                self.h, ltp, ap, 0 if until == "seeding" else 1, gp, R, vp, sp, wp))
         return values, status, whole
 
     # ---- genotype distribution
@@ -659,21 +673,8 @@ class Engine:
         mutation j), else None.  Raises when 16 B x 2^n, the tile list and the tiles' partial sums exceed the workspace
         limit."""
         lt, ltp = self._theta(log_theta); a, ap = self._rates(obs1, "obs1")
-        g = np.ascontiguousarray(np.asarray(genotypes).astype(np.int8))
-        if g.ndim != 2 or g.shape[1] != self.n:
-            raise ValueError(f"genotypes must be a 2-D array [R, {self.n}]")
-        R, n = g.shape[0], self.n
-        values = np.empty((R, 2))                                # (the library fills it with NaN first)
-        status = np.zeros(R, dtype=np.int32)
-        sums = np.empty((2, 1 + n * n + n + 1)) if summary else None
-        whole = np.empty((2, 1 << n)) if full else None
-        _lib.check(self.lib.mmhn_genotype_distribution(
-            self.h, ltp, ap, g.ctypes.data_as(i8p), R, values.ctypes.data_as(f64p), status.ctypes.data_as(_lib.i32p),
-            sums.ctypes.data_as(f64p) if summary else None, whole.ctypes.data_as(f64p) if full else None))
-        if summary:
-            sums = (np.ascontiguousarray(sums[:, 0]), np.ascontiguousarray(sums[:, 1:1 + n * n]).reshape(2, n, n),
-                    np.ascontiguousarray(sums[:, 1 + n * n:]))
-        return values, status, sums, whole
+        return self._lattice_call(genotypes, 2, summary, full,
+                                  lambda *buffers: self.lib.mmhn_genotype_distribution(self.h, ltp, ap, *buffers))
 
     # ---- metastasis distribution
     def metastasis_distribution(self, log_theta, obs1, obs2, genotypes, summary=True, full=False):
@@ -686,21 +687,8 @@ class Engine:
         with full=True the three planes [3, 2^n] by code (bit j = mutation j), else None.  Raises when 24 B x 2^n, the tables,
         the tile list and the tiles' partial sums exceed the workspace limit."""
         lt, ltp = self._theta(log_theta); a, ap = self._rates(obs1, "obs1"); b, bp = self._rates(obs2, "obs2")
-        g = np.ascontiguousarray(np.asarray(genotypes).astype(np.int8))
-        if g.ndim != 2 or g.shape[1] != self.n:
-            raise ValueError(f"genotypes must be a 2-D array [R, {self.n}]")
-        R, n = g.shape[0], self.n
-        values = np.empty((R, 3))                                # (the library fills it with NaN first)
-        status = np.zeros(R, dtype=np.int32)
-        sums = np.empty((2, 1 + n * n + n + 1)) if summary else None
-        whole = np.empty((3, 1 << n)) if full else None
-        _lib.check(self.lib.mmhn_metastasis_distribution(
-            self.h, ltp, ap, bp, g.ctypes.data_as(i8p), R, values.ctypes.data_as(f64p), status.ctypes.data_as(_lib.i32p),
-            sums.ctypes.data_as(f64p) if summary else None, whole.ctypes.data_as(f64p) if full else None))
-        if summary:
-            sums = (np.ascontiguousarray(sums[:, 0]), np.ascontiguousarray(sums[:, 1:1 + n * n]).reshape(2, n, n),
-                    np.ascontiguousarray(sums[:, 1 + n * n:]))
-        return values, status, sums, whole
+        return self._lattice_call(genotypes, 3, summary, full,
+                                  lambda *buffers: self.lib.mmhn_metastasis_distribution(self.h, ltp, ap, bp, *buffers))
 
     # ---- measurement
     def bench_kronvec(self, log_theta, state, batch, iters, transpose=False, jacobi=False, tiles=False):

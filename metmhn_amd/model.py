@@ -553,10 +553,8 @@ class MetastasisDistribution(SimpleNamespace):
 
 
 _FORECAST_UNTIL = ("seeding", "observation")
-_GENODIST_HOST_MAX = 24          # mutations the host distribution takes on: n x 2^n doubles of rates
-_METDIST_HOST_MAX = 24           # the same of the metastasis distribution
 _FORECAST_HOST_MAX = 24          # free mutations the host definition takes on: f x 2^f doubles of rates
-_LANDSCAPE_HOST_MAX = 24         # mutations the host landscape takes on: n x 2^n doubles of rates
+_LATTICE_HOST_MAX = 24           # mutations the host landscape and distributions take on: n x 2^n doubles of rates
 _NO_SEEDING_EXIT = ("the seeding rate of the full genotype underflows to 0 (a theta[n, n] of -1e10, as a fit without seeded "
                     "samples leaves it?): until='seeding' the full state would have no exit; use until='observation'")
 
@@ -1043,18 +1041,60 @@ class MetMHN:
                                  "there is no host fallback")
         return SeedingForecasts(*(c[inverse] for c in cols), self._forecast_next(g, until))
 
-    # ------------------------------------------------------------------ seeding landscape
-    def _landscape_host(self, until: str) -> np.ndarray:
-        """[4, 2^n]: the definition of the landscape, level by level over the popcount of the code, descending."""
+    # ------------------------------------------------------------------ sweeps over all 2^n genotypes: what the three share
+    def _lattice_host_rates(self, what: str):
+        """idx, level (the popcount), lam [n] and sig over the 2^n genotype codes for the host definition of the `what`."""
         th, n = self._pt_log_theta, self.n
-        if n > _LANDSCAPE_HOST_MAX:
-            raise ValueError(f"{n} mutations: the host landscape stops at {_LANDSCAPE_HOST_MAX} ({n} x 2^{n} doubles of "
+        if n > _LATTICE_HOST_MAX:
+            raise ValueError(f"{n} mutations: the host {what} stops at {_LATTICE_HOST_MAX} ({n} x 2^{n} doubles of "
                              "rates); use backend='device'")
-        size = 1 << n
-        idx = np.arange(size)
+        idx = np.arange(1 << n)
         level = _subset_sums(np.ones(n)).astype(np.int64)
         lam = [np.exp(th[j, j] + _subset_sums(np.where(np.arange(n) == j, 0.0, th[j, :n]))) for j in range(n)]
         sig = np.exp(th[n, n] + _subset_sums(th[n, :n]))
+        return idx, level, lam, sig
+
+    def _lattice_whole(self, backend, max_bytes, planes, noun, prep, at, host, device, result, summary_host=None, summary=None):
+        """The body of seeding_landscape, genotype_distribution and metastasis_distribution behind their own checks: every
+        genotype's `planes` values, from host() [planes, 2^n] (with summary_host of it) or from device(engine, genotypes,
+        full) -> values, status, sums, whole (with summary(*sums)).  `noun`, `prep` and `at` word the refusal of max_bytes."""
+        n = self.n
+        if backend == "host" and n > _LATTICE_HOST_MAX:
+            host()                                  # (raises: the message points to the device)
+        if 8 * planes << n > max_bytes:
+            raise ValueError(f"{n} mutations: a {noun} {prep} 2^{n} genotypes needs {8 * planes << n} bytes, more than max_bytes = "
+                             f"{int(max_bytes)}; {at} reads single genotypes off the device's {noun}")
+        if backend == "host":
+            whole = host()
+            sums = summary_host(whole) if summary_host else None
+        else:
+            from .jx import engine
+            _, _, sums, whole = device(engine(n), np.zeros((0, n), dtype=np.int8), True)
+            sums = summary(*sums) if summary else None
+        return result(*whole, np.arange(1 << n), *(() if sums is None else (sums,)))
+
+    def _lattice_at(self, genotypes, until, backend, planes, host, device, result, summary_host=None, summary=None):
+        """The body of the three _at methods behind the backend check: _lattice_whole's values at the rows of `genotypes`."""
+        g = self._forecast_checks(genotypes, until)
+        n = self.n
+        codes = g @ (1 << np.arange(n, dtype=np.int64))
+        if backend == "host":
+            whole = host()
+            values, sums = whole[:, codes].T, summary_host(whole) if summary_host else None
+        else:
+            from .jx import engine
+            values, status, sums, _ = device(engine(n), g.astype(np.int8), False)
+            bad = np.flatnonzero(status != 0)
+            if bad.size:
+                raise ValueError(f"row {int(bad[0])}: a genotype entry is neither 0 nor 1")
+            sums = summary(*sums) if summary else None
+        return result(*(np.ascontiguousarray(values[:, k]) for k in range(planes)), codes, *(() if sums is None else (sums,)))
+
+    # ------------------------------------------------------------------ seeding landscape
+    def _landscape_host(self, until: str) -> np.ndarray:
+        """[4, 2^n]: the definition of the landscape, level by level over the popcount of the code, descending."""
+        n, size = self.n, 1 << self.n
+        idx, level, lam, sig = self._lattice_host_rates("landscape")
         kap = np.exp(_subset_sums(self.obs1[:n])) if until == "observation" else np.zeros(size)
         p, t, e, s = (np.zeros(size) for _ in range(4))
         for lev in range(n, -1, -1):
@@ -1097,17 +1137,14 @@ class MetMHN:
         th, n = self._pt_log_theta, self.n
         if until == "seeding" and np.exp(th[n, n] + th[n, :n].sum()) == 0.0:
             raise ValueError(_NO_SEEDING_EXIT)
-        if backend == "host" and n > _LANDSCAPE_HOST_MAX:
-            self._landscape_host(until)             # (raises: the message points to the device)
-        if 32 << n > max_bytes:
-            raise ValueError(f"{n} mutations: a landscape of 2^{n} genotypes needs {32 << n} bytes, more than max_bytes = "
-                             f"{int(max_bytes)}; seeding_landscape_at reads single genotypes off the device's landscape")
-        if backend == "host":
-            whole = self._landscape_host(until)
-        else:
-            from .jx import engine
-            _, _, whole = engine(n).seeding_landscape(self.log_theta, self.obs1, np.zeros((0, n), dtype=np.int8), until, full=True)
-        return SeedingLandscape(*whole, np.arange(1 << n))
+        return self._lattice_whole(backend, max_bytes, 4, "landscape", "of", "seeding_landscape_at",
+                                   lambda: self._landscape_host(until), self._landscape_device(until), SeedingLandscape)
+
+    def _landscape_device(self, until: str):
+        def device(eng, g, full):
+            values, status, whole = eng.seeding_landscape(self.log_theta, self.obs1, g, until, full=full)
+            return values, status, None, whole
+        return device
 
     def seeding_landscape_at(self, genotypes, until: str = "seeding", backend: str = "device") -> "SeedingLandscape":
         """The four values of seeding_landscape at the rows of `genotypes` [R, n] (0 / 1), [R] each, with the rows' codes:
@@ -1116,31 +1153,14 @@ class MetMHN:
         An entry other than 0 / 1 raises ValueError("row i: ...") as seeding_forecasts does."""
         if backend not in ("device", "host"):
             raise ValueError("backend must be 'device' or 'host'")
-        g = self._forecast_checks(genotypes, until)
-        n = self.n
-        codes = g @ (1 << np.arange(n, dtype=np.int64))
-        if backend == "host":
-            values = self._landscape_host(until)[:, codes].T
-        else:
-            from .jx import engine
-            values, status, _ = engine(n).seeding_landscape(self.log_theta, self.obs1, g.astype(np.int8), until)
-            bad = np.flatnonzero(status != 0)
-            if bad.size:
-                raise ValueError(f"row {int(bad[0])}: a genotype entry is neither 0 nor 1")
-        return SeedingLandscape(*(np.ascontiguousarray(values[:, k]) for k in range(4)), codes)
+        return self._lattice_at(genotypes, until, backend, 4, lambda: self._landscape_host(until),
+                                self._landscape_device(until), SeedingLandscape)
 
     # ------------------------------------------------------------------ genotype distribution of the primary tumour
     def _genodist_host(self) -> np.ndarray:
         """[2, 2^n]: the definition of the genotype distribution (U, S), level by level over the popcount, ascending."""
-        th, n = self._pt_log_theta, self.n
-        if n > _GENODIST_HOST_MAX:
-            raise ValueError(f"{n} mutations: the host distribution stops at {_GENODIST_HOST_MAX} ({n} x 2^{n} doubles of "
-                             "rates); use backend='device'")
-        size = 1 << n
-        idx = np.arange(size)
-        level = _subset_sums(np.ones(n)).astype(np.int64)
-        lam = [np.exp(th[j, j] + _subset_sums(np.where(np.arange(n) == j, 0.0, th[j, :n]))) for j in range(n)]
-        sig = np.exp(th[n, n] + _subset_sums(th[n, :n]))
+        n, size = self.n, 1 << self.n
+        idx, level, lam, sig = self._lattice_host_rates("distribution")
         kap0 = np.exp(_subset_sums(self.obs1[:n]))
         kap1 = kap0 * np.exp(self.obs1[n])
         L = np.zeros(size)
@@ -1197,21 +1217,12 @@ class MetMHN:
         definition in NumPy, level by level, n <= 24."""
         if backend not in ("device", "host"):
             raise ValueError("backend must be 'device' or 'host'")
-        n = self.n
-        if backend == "host" and n > _GENODIST_HOST_MAX:
-            self._genodist_host()                   # (raises: the message points to the device)
-        if 16 << n > max_bytes:
-            raise ValueError(f"{n} mutations: a distribution over 2^{n} genotypes needs {16 << n} bytes, more than max_bytes = "
-                             f"{int(max_bytes)}; genotype_distribution_at reads single genotypes off the device's distribution")
-        if backend == "host":
-            whole = self._genodist_host()
-            summary = self._genodist_summary_host(whole)
-        else:
-            from .jx import engine
-            _, _, sums, whole = engine(n).genotype_distribution(self.log_theta, self.obs1, np.zeros((0, n), dtype=np.int8),
-                                                                summary=True, full=True)
-            summary = GenotypeSummary(*sums)
-        return GenotypeDistribution(whole[0], whole[1], np.arange(1 << n), summary)
+        return self._lattice_whole(backend, max_bytes, 2, "distribution", "over", "genotype_distribution_at",
+                                   self._genodist_host, self._genodist_device, GenotypeDistribution,
+                                   self._genodist_summary_host, GenotypeSummary)
+
+    def _genodist_device(self, eng, g, full):
+        return eng.genotype_distribution(self.log_theta, self.obs1, g, summary=True, full=full)
 
     def genotype_distribution_at(self, genotypes, backend: str = "device") -> "GenotypeDistribution":
         """genotype_distribution's two values at the rows of `genotypes` [R, n] (0 / 1), [R] each, with the rows' codes and
@@ -1220,34 +1231,15 @@ class MetMHN:
         An entry other than 0 / 1 raises ValueError("row i: ...") as seeding_forecasts does."""
         if backend not in ("device", "host"):
             raise ValueError("backend must be 'device' or 'host'")
-        g = self._forecast_checks(genotypes, "observation")
-        n = self.n
-        codes = g @ (1 << np.arange(n, dtype=np.int64))
-        if backend == "host":
-            whole = self._genodist_host()
-            values, summary = whole[:, codes].T, self._genodist_summary_host(whole)
-        else:
-            from .jx import engine
-            values, status, sums, _ = engine(n).genotype_distribution(self.log_theta, self.obs1, g.astype(np.int8), summary=True)
-            bad = np.flatnonzero(status != 0)
-            if bad.size:
-                raise ValueError(f"row {int(bad[0])}: a genotype entry is neither 0 nor 1")
-            summary = GenotypeSummary(*sums)
-        return GenotypeDistribution(np.ascontiguousarray(values[:, 0]), np.ascontiguousarray(values[:, 1]), codes, summary)
+        return self._lattice_at(genotypes, "observation", backend, 2, self._genodist_host, self._genodist_device,
+                                GenotypeDistribution, self._genodist_summary_host, GenotypeSummary)
 
     # ------------------------------------------------------------------ genotype distribution of the metastasis and its founder
     def _metdist_host(self) -> np.ndarray:
         """[3, 2^n]: the definition of the metastasis distribution (Z, M, C), level by level over the popcount, ascending."""
-        th, n = self._pt_log_theta, self.n
-        if n > _METDIST_HOST_MAX:
-            raise ValueError(f"{n} mutations: the host distribution stops at {_METDIST_HOST_MAX} ({n} x 2^{n} doubles of "
-                             "rates); use backend='device'")
-        size = 1 << n
-        idx = np.arange(size)
-        level = _subset_sums(np.ones(n)).astype(np.int64)
-        lam = [np.exp(th[j, j] + _subset_sums(np.where(np.arange(n) == j, 0.0, th[j, :n]))) for j in range(n)]
+        n, size = self.n, 1 << self.n
+        idx, level, lam, sig = self._lattice_host_rates("distribution")
         mu = [lam[j] * np.exp(self.log_theta[j, n]) for j in range(n)]
-        sig = np.exp(th[n, n] + _subset_sums(th[n, :n]))
         kap0 = np.exp(_subset_sums(self.obs1[:n]))
         kapm = np.exp(self.obs2[n] + _subset_sums(self.obs2[:n]))
         L, Lm = np.zeros(size), np.zeros(size)
@@ -1302,21 +1294,12 @@ class MetMHN:
         definition in NumPy, level by level, n <= 24."""
         if backend not in ("device", "host"):
             raise ValueError("backend must be 'device' or 'host'")
-        n = self.n
-        if backend == "host" and n > _METDIST_HOST_MAX:
-            self._metdist_host()                    # (raises: the message points to the device)
-        if 24 << n > max_bytes:
-            raise ValueError(f"{n} mutations: a distribution over 2^{n} genotypes needs {24 << n} bytes, more than max_bytes = "
-                             f"{int(max_bytes)}; metastasis_distribution_at reads single genotypes off the device's distribution")
-        if backend == "host":
-            whole = self._metdist_host()
-            summary = self._metdist_summary_host(whole)
-        else:
-            from .jx import engine
-            _, _, sums, whole = engine(n).metastasis_distribution(self.log_theta, self.obs1, self.obs2,
-                                                                  np.zeros((0, n), dtype=np.int8), summary=True, full=True)
-            summary = MetastasisSummary(*sums)
-        return MetastasisDistribution(whole[0], whole[1], whole[2], np.arange(1 << n), summary)
+        return self._lattice_whole(backend, max_bytes, 3, "distribution", "over", "metastasis_distribution_at",
+                                   self._metdist_host, self._metdist_device, MetastasisDistribution,
+                                   self._metdist_summary_host, MetastasisSummary)
+
+    def _metdist_device(self, eng, g, full):
+        return eng.metastasis_distribution(self.log_theta, self.obs1, self.obs2, g, summary=True, full=full)
 
     def metastasis_distribution_at(self, genotypes, backend: str = "device") -> "MetastasisDistribution":
         """metastasis_distribution's three values at the rows of `genotypes` [R, n] (0 / 1), [R] each, with the rows' codes
@@ -1325,21 +1308,8 @@ class MetMHN:
         An entry other than 0 / 1 raises ValueError("row i: ...") as seeding_forecasts does."""
         if backend not in ("device", "host"):
             raise ValueError("backend must be 'device' or 'host'")
-        g = self._forecast_checks(genotypes, "observation")
-        n = self.n
-        codes = g @ (1 << np.arange(n, dtype=np.int64))
-        if backend == "host":
-            whole = self._metdist_host()
-            values, summary = whole[:, codes].T, self._metdist_summary_host(whole)
-        else:
-            from .jx import engine
-            values, status, sums, _ = engine(n).metastasis_distribution(self.log_theta, self.obs1, self.obs2, g.astype(np.int8),
-                                                                        summary=True)
-            bad = np.flatnonzero(status != 0)
-            if bad.size:
-                raise ValueError(f"row {int(bad[0])}: a genotype entry is neither 0 nor 1")
-            summary = MetastasisSummary(*sums)
-        return MetastasisDistribution(*(np.ascontiguousarray(values[:, k]) for k in range(3)), codes, summary)
+        return self._lattice_at(genotypes, "observation", backend, 3, self._metdist_host, self._metdist_device,
+                                MetastasisDistribution, self._metdist_summary_host, MetastasisSummary)
 
     def likelihood(self, order, met_status: str, first_obs: str = None) -> float:
         """model.py:295-376: probability of exactly this order of events being what is observed."""

@@ -475,6 +475,17 @@ def seeding_risk(log_theta, log_d_p, log_d_m, dat, until: str = "observation", b
     return SeedingLandscape(**out, codes=codes), met_status_posterior(log_theta, log_d_p, log_d_m, dat)
 
 
+def _stratum_table(strata, typ, codes, prob) -> dict:
+    """{stratum: (codes, observed, expected)} of genotype_fit and metastasis_fit for the `strata` (name, row type) with rows."""
+    table = {}
+    for stratum, ty in strata:
+        rows = typ == ty
+        if rows.any():
+            uniq, first, counts = np.unique(codes[rows], return_index=True, return_counts=True)
+            table[stratum] = (uniq, counts.astype(np.int64), int(rows.sum()) * prob[rows][first])
+    return table
+
+
 def genotype_fit(log_theta, log_d_p, log_d_m, dat, backend: str = "device"):
     """How well the model's exact genotype distribution of the primary tumour fits the PT genotypes of `dat`, from ONE
     forward sweep over all genotypes (MetMHN.genotype_distribution_at with obs1 = log_d_p).  A namespace of
@@ -498,12 +509,7 @@ def genotype_fit(log_theta, log_d_p, log_d_m, dat, backend: str = "device"):
     codes[pick] = got.codes
     t = typ[pick]
     prob[pick] = np.select([t == 0, t == 1], [within[0], within[1]], within[4])
-    table = {}
-    for stratum, ty in zip(GENOTYPE_STRATA, (0, 1, 4)):
-        rows = typ == ty
-        if rows.any():
-            uniq, first, counts = np.unique(codes[rows], return_index=True, return_counts=True)
-            table[stratum] = (uniq, counts.astype(np.int64), int(rows.sum()) * prob[rows][first])
+    table = _stratum_table(zip(GENOTYPE_STRATA, (0, 1, 4)), typ, codes, prob)
     return SimpleNamespace(prob=prob, codes=codes, table=table, summary=got.summary, residuals=got.summary.compare(arr))
 
 
@@ -531,12 +537,7 @@ def metastasis_fit(log_theta, log_d_p, log_d_m, dat, backend: str = "device"):
     codes[pick] = got.codes
     prob[pick] = got.metastasis / got.summary.mass[1]
     founder_events[pick] = got.founder_events
-    table = {}
-    for stratum, ty in (("EM-MT", 2), ("paired", 3)):
-        rows = typ == ty
-        if rows.any():
-            uniq, first, counts = np.unique(codes[rows], return_index=True, return_counts=True)
-            table[stratum] = (uniq, counts.astype(np.int64), int(rows.sum()) * prob[rows][first])
+    table = _stratum_table((("EM-MT", 2), ("paired", 3)), typ, codes, prob)
     return SimpleNamespace(prob=prob, founder_events=founder_events, codes=codes, table=table, summary=got.summary,
                            residuals=got.summary.compare(arr))
 

@@ -30,7 +30,7 @@ dat = g["dat"]
 mod = MetMHN(g["fit_theta"], g["fit_dp"], g["fit_dm"])
 n = mod.n
 mts = np.unique(dat[np.isin(dat[:, -1], (2, 3))][:, 1:2 * n:2], axis=0).astype(np.int8)
-c = min(n, int(re.search(r"LS_TILE_BITS = (\d+);", open(os.path.join(ROOT, "metmhn_amd", "csrc", "landscape.h")).read()).group(1)))
+c = min(n, int(re.search(r"LS_TILE_BITS = (\d+);", open(os.path.join(ROOT, "metmhn_amd", "csrc", "lattice.h")).read()).group(1)))
 sweep_bytes = ((n - c) / 2 + 1) * 24 * 2 ** n + 48 * 2 ** n    # a tile reads (n - c) / 2 finished tiles on average and is written once; the planes are read and written once more on the way to probabilities
 genodist_bytes = ((n - c) / 2 + 1) * 16 * 2 ** n + 32 * 2 ** n
 

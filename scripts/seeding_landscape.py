@@ -29,7 +29,7 @@ dat = g["dat"]
 mod = MetMHN(g["fit_theta"], g["fit_dp"], g["fit_dm"])
 n = mod.n
 pts = np.unique(dat[np.isin(dat[:, -1], (0, 1, 3, 4))][:, 0:2 * n:2], axis=0).astype(np.int8)
-c = min(n, int(re.search(r"LS_TILE_BITS = (\d+);", open(os.path.join(ROOT, "metmhn_amd", "csrc", "landscape.h")).read()).group(1)))
+c = min(n, int(re.search(r"LS_TILE_BITS = (\d+);", open(os.path.join(ROOT, "metmhn_amd", "csrc", "lattice.h")).read()).group(1)))
 moves = n << (n - 1)                                   # pairs (x, j not in x)
 sweep_bytes = ((n - c) / 2 + 1) * 32 * 2 ** n          # a tile reads (n - c) / 2 finished tiles on average and is written once
 QS = (0, .05, .25, .5, .75, .95, 1)

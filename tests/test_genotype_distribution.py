@@ -8,7 +8,7 @@ relative), its identities, the recursion re-evaluated in long double, the host s
 double, rates of 0, compare / genotype_fit against their formulas, the refusals.
 
 GPU: the device against the host definition, against the engine's own cohort rows, against the backward sweep
-(landscape.h, which shares no line with the forward one), the reduction alone, the bytes whatever the queries.
+(landscape.h, whose recursion shares no line with the forward one), the reduction alone, the bytes whatever the queries.
 
 The bound of the device against the host.  Both sides are fp64 evaluations of non-negative sum-products, so relative
 errors add along a path and a sum takes the worst of its terms plus its additions.  With u = 2^-53,
@@ -34,7 +34,6 @@ CPU: the host definition against the dense oracle 2.0e-15 relative at the worst,
 1.1e-7 of its bar, the recursion's residual 3.6 u against 26 u, the host summary 0.14 of (n + 19) u.
 """
 import functools
-import os
 import re
 
 import numpy as np
@@ -43,28 +42,8 @@ import pytest
 import metmhn_amd.model as model_mod
 from metmhn_amd import regularized_optimization as ro
 from metmhn_amd.model import GenotypeDistribution, GenotypeSummary, MetMHN
-from order_common import mixed_cohort, model
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-U = 2.0 ** -53
-C = int(re.search(r"constexpr int LS_TILE_BITS = (\d+);",
-                  open(os.path.join(ROOT, "metmhn_amd", "csrc", "landscape.h")).read()).group(1))
-WORST = {}                         # test -> worst error / bound seen (printed)
-
-
-def bits(n, codes):
-    """[R, n] int8 genotypes of the codes."""
-    return (np.asarray(codes, dtype=np.int64)[:, None] >> np.arange(n) & 1).astype(np.int8)
-
-
-def rel(got, ref):
-    """Worst |got - ref| / |ref| over the entries; nothing may be NaN, an exact 0 must be met exactly."""
-    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    assert np.isfinite(got).all() and np.isfinite(ref).all(), "not finite"
-    zero = ref == 0
-    assert (got[zero] == 0).all(), "an exact zero of the reference is not met"
-    return float(np.max(np.abs(got[~zero] - ref[~zero]) / np.abs(ref[~zero]), initial=0.0))
+from lattice_common import C, U, bits, brute_summary, check_same_bytes, fit_cohort, ld_rel, note, red, rel, summary_rel, without
+from order_common import model
 
 
 def eps_of(mod):
@@ -82,22 +61,10 @@ def bound(mod):
     return b
 
 
-def red(n):
-    """Longest chain of additions of the device's reduction."""
-    return 52 + -(-(1 << max(n - C, 0)) // 256)
-
-
 def summary_bound(mod):
     b = bound(mod) + (red(mod.n) + mod.n + 19) * U
     assert b < 1e-9, (mod.n, b)
     return b
-
-
-def summary_rel(got, ref):
-    """Worst relative difference of the three arrays of two summaries (mass, pairs, burden as tuples or GenotypeSummary)."""
-    a = (got.mass, got.pairs, got.burden) if isinstance(got, GenotypeSummary) else got
-    b = (ref.mass, ref.pairs, ref.burden) if isinstance(ref, GenotypeSummary) else ref
-    return max(rel(x, y) for x, y in zip(a, b))
 
 
 @functools.lru_cache(maxsize=None)
@@ -117,32 +84,6 @@ def rows_of(n, codes, typ):
     dat[:, 0:2 * n:2] = bits(n, codes)
     dat[:, -3], dat[:, -2], dat[:, -1] = (1 if typ == 1 else 0), -99, typ
     return dat
-
-
-def brute_summary(P):
-    """(mass, pairs, burden) of the planes P [2, 2^n] in long double, over the bits of every code."""
-    ld = np.longdouble
-    n = P.shape[1].bit_length() - 1
-    g = bits(n, np.arange(1 << n)).astype(ld)
-    level = g.sum(axis=1).astype(np.int64)
-    mass, pairs, burden = np.zeros(2, dtype=ld), np.zeros((2, n, n), dtype=ld), np.zeros((2, n + 1), dtype=ld)
-    for s in range(2):
-        p = P[s].astype(ld)
-        mass[s] = p.sum()
-        for i in range(n):
-            for j in range(n):
-                pairs[s, i, j] = (p * g[:, i] * g[:, j]).sum()
-        for m in range(n + 1):
-            burden[s, m] = p[level == m].sum()
-    return mass, pairs, burden
-
-
-def ld_rel(got, ref):
-    """Worst relative difference of fp64 `got` against long double `ref`; exact zeros exact."""
-    got, ref = np.asarray(got), np.asarray(ref)
-    zero = ref == 0
-    assert (got[zero] == 0).all()
-    return float(np.max(np.abs(got[~zero].astype(np.longdouble) - ref[~zero]) / ref[~zero], initial=0.0))
 
 
 # ------------------------------------------------------------------------------------------------------------------ CPU
@@ -250,18 +191,6 @@ def test_host_summary_against_brute_force_in_long_double():
     assert worst <= 1.01
 
 
-def without(mod, j):
-    """(the model with theta_jj = -1e10, the model without mutation j, the codes without bit j, the same codes in the smaller
-    model)."""
-    n = mod.n
-    th = mod.log_theta.copy()
-    th[j, j] = -1e10
-    keep = [i for i in range(n + 1) if i != j]
-    codes = np.array([x for x in range(1 << n) if not x >> j & 1])
-    small = (codes & ((1 << j) - 1)) | (codes >> (j + 1) << j)
-    return MetMHN(th, mod.obs1, mod.obs2), MetMHN(th[np.ix_(keep, keep)], mod.obs1[keep], mod.obs2[keep]), codes, small
-
-
 def check_dead_mutation(a, b, codes, small, j, bar):
     """a: the distribution with mutation j of rate 0, b: the one of the model without it."""
     holds = np.setdiff1d(a.codes, codes)
@@ -296,12 +225,6 @@ def test_a_seeding_of_rate_zero():
     assert got.summary.mass[1] == 0.0 and not got.summary.pairs[1].any() and not got.summary.burden[1].any()
     assert np.isfinite(got.summary.mass).all() and abs(got.summary.mass[0] - 1.0) <= 1e-12
     assert (got.p_seeded == 0.0).all() and np.array_equal(got.total, got.unseeded)
-
-
-def fit_cohort(n=5):
-    import unknown_common as UC
-    extra = [UC.unknown_row(n, e) for e in ([0, 3], [], [1, 2, 4], [0, 3])]
-    return np.vstack((mixed_cohort(n), mixed_cohort(n)[:3], extra)).astype(np.int8)
 
 
 def check_fit(fit, mod, dat, whole, summary, bar):
@@ -398,12 +321,6 @@ def test_refusals(monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU
-def note(tag, worst):
-    WORST[tag] = max(WORST.get(tag, 0.0), worst)
-    print(f"{tag}: worst error / bound {worst:.3e}")
-    assert worst <= 1.0, (tag, worst)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("n", (1, 3, C, C + 1, C + 3))
 def test_device_against_the_host_definition(n):
@@ -485,34 +402,10 @@ def test_the_reduction_alone():
 @pytest.mark.gpu
 def test_same_bytes_whatever_the_queries():
     from metmhn_amd.jx import engine
-    n, seed = C + 1, 41 + C
-    mod = model(n, seed=seed)
-    eng = engine(n)
-    args = (mod.log_theta, mod.obs1)
-    codes = np.arange(1 << n)
-    G = bits(n, codes)
-    same = lambda a, b: all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
-    values, status, sums, whole = eng.genotype_distribution(*args, G, full=True)
-    assert (status == 0).all() and values.tobytes() == np.ascontiguousarray(whole.T).tobytes()
-    again = eng.genotype_distribution(*args, G, full=True)
-    assert again[0].tobytes() == values.tobytes() and again[3].tobytes() == whole.tobytes() and same(again[2], sums)
-    perm = np.random.default_rng(7).permutation(len(G))[:300]
-    mixed, st, s2, none = eng.genotype_distribution(*args, G[perm])
-    assert none is None and (st == 0).all() and mixed.tobytes() == values[perm].tobytes() and same(s2, sums)
-    for x in (0, 1, (1 << C) - 1, 1 << C, (1 << n) - 1):
-        one, st, s2, _ = eng.genotype_distribution(*args, G[x:x + 1])
-        assert st.tolist() == [0] and one[0].tobytes() == values[x].tobytes() and same(s2, sums)
-    bad = np.vstack((G[5], G[6], G[(1 << n) - 7]))
-    bad[1, 2] = 3
-    out, st, s2, _ = eng.genotype_distribution(*args, bad)
-    assert st.tolist() == [0, 2 | 8 << 16, 0] and np.isnan(out[1]).all() and same(s2, sums)
-    assert out[[0, 2]].tobytes() == values[[5, (1 << n) - 7]].tobytes()
-    v0, s0, s2, only = eng.genotype_distribution(*args, np.zeros((0, n), dtype=np.int8), full=True)
-    assert v0.shape == (0, 2) and s0.shape == (0,) and only.tobytes() == whole.tobytes() and same(s2, sums)
-    v1, _, s3, o3 = eng.genotype_distribution(*args, G[:9], summary=False, full=True)
-    assert s3 is None and o3.tobytes() == whole.tobytes() and v1.tobytes() == values[:9].tobytes()
-    with pytest.raises(ValueError, match=r"^row 1: "):
-        mod.genotype_distribution_at(bad)
+    n = C + 1
+    mod = model(n, seed=41 + C)
+    check_same_bytes(lambda G, **kw: engine(n).genotype_distribution(mod.log_theta, mod.obs1, G, **kw), 2, n,
+                     mod.genotype_distribution_at)
 
 
 @pytest.mark.gpu

@@ -46,9 +46,9 @@ import pytest
 import metmhn_amd.model as model_mod
 from metmhn_amd import regularized_optimization as ro
 from metmhn_amd.model import GenotypeSummary, MetastasisDistribution, MetastasisSummary, MetMHN
+from lattice_common import C, U, bits, brute_summary, check_same_bytes, ld_rel, note, red, rel, summary_rel, without
+from lattice_common import fit_cohort as pt_fit_cohort
 from order_common import mixed_cohort, model
-from test_genotype_distribution import C, U, bits, brute_summary, ld_rel, note, red, rel, summary_rel, without
-import test_genotype_distribution as TG
 
 PLANES = ("founder", "metastasis", "founder_weighted")
 
@@ -72,6 +72,18 @@ def summary_bound(mod):
     b = bound(mod) + (red(mod.n) + mod.n + 19) * U
     assert b < 1e-9, (mod.n, b)
     return b
+
+
+def genodist_bounds(mod):
+    """(eps, bound, summary bound) of the primary tumour's sweep as tests/test_genotype_distribution.py derives them, for the
+    checks of this sweep against that one."""
+    th, n = mod._pt_log_theta, mod.n
+    A = max(abs(th[j, j]) + np.abs(np.delete(th[j, :n], j) if j < n else th[j, :n]).sum() for j in range(n + 1))
+    eps = 2 * (n + 2) * U * max(A, np.abs(mod.obs1).sum()) + 4 * U
+    b = (n + 2) * (4 * eps + (4 * n + 14) * U) + 2 * eps + 8 * U
+    sb = b + (red(n) + n + 19) * U
+    assert sb < 1e-9, (n, sb)
+    return eps, b, sb
 
 
 @functools.lru_cache(maxsize=None)
@@ -276,7 +288,7 @@ def test_rates_of_zero():
 
 
 def fit_cohort(n=5):
-    return np.vstack((mixed_cohort(n), mixed_cohort(n)[4:9], TG.fit_cohort(n)[-4:])).astype(np.int8)
+    return np.vstack((mixed_cohort(n), mixed_cohort(n)[4:9], pt_fit_cohort(n)[-4:])).astype(np.int8)
 
 
 def check_fit(fit, mod, dat, whole, summary, bar):
@@ -458,7 +470,7 @@ def test_coinciding_chains_against_the_device_seeded_plane():
     got = mod.metastasis_distribution()
     seeded = mod.genotype_distribution().seeded
     note(f"M against the device's seeded plane with coinciding chains, n = {n}",
-         rel(got.metastasis, seeded) / (bound(mod) + TG.bound(mod)))
+         rel(got.metastasis, seeded) / (bound(mod) + genodist_bounds(mod)[1]))
 
 
 @pytest.mark.gpu
@@ -472,11 +484,11 @@ def test_masses_against_the_other_sweeps(n):
     _, _, gsums, _ = engine(n).genotype_distribution(mod.log_theta, mod.obs1, np.zeros((0, n), dtype=np.int8))
     back, status, _ = engine(n).seeding_landscape(mod.log_theta, mod.obs1, np.zeros((1, n), dtype=np.int8), "observation")
     assert status.tolist() == [0]
-    landscape_bound = (n + 1) * (4 * TG.eps_of(mod) + (2 * n + 8) * U)
+    landscape_bound = (n + 1) * (4 * genodist_bounds(mod)[0] + (2 * n + 8) * U)
     assert landscape_bound < 1e-9
     for what, v in (("sum Z", whole[0].sum()), ("sum M", whole[1].sum()), ("mass[0]", sums[0][0]), ("mass[1]", sums[0][1])):
         note(f"{what} against genotype_distribution's mass[1], n = {n}",
-             rel(v, gsums[0][1]) / (summary_bound(mod) + TG.summary_bound(mod)))
+             rel(v, gsums[0][1]) / (summary_bound(mod) + genodist_bounds(mod)[2]))
         note(f"{what} against the landscape's p_seed of the empty genotype, n = {n}",
              rel(v, back[0, 0]) / (summary_bound(mod) + landscape_bound))
     want = (popcounts(n) * whole[0]).sum()
@@ -496,32 +508,9 @@ def test_the_reduction_alone():
 
 @pytest.mark.gpu
 def test_same_bytes_whatever_the_queries():
-    n, seed = C + 1, 41 + C
-    mod = model(n, seed=seed)
-    codes = np.arange(1 << n)
-    G = bits(n, codes)
-    same = lambda a, b: all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
-    values, status, sums, whole = device(mod, G, full=True)
-    assert (status == 0).all() and values.tobytes() == np.ascontiguousarray(whole.T).tobytes()
-    again = device(mod, G, full=True)
-    assert again[0].tobytes() == values.tobytes() and again[3].tobytes() == whole.tobytes() and same(again[2], sums)
-    perm = np.random.default_rng(7).permutation(len(G))[:300]
-    mixed, st, s2, none = device(mod, G[perm])
-    assert none is None and (st == 0).all() and mixed.tobytes() == values[perm].tobytes() and same(s2, sums)
-    for x in (0, 1, (1 << C) - 1, 1 << C, (1 << n) - 1):
-        one, st, s2, _ = device(mod, G[x:x + 1])
-        assert st.tolist() == [0] and one[0].tobytes() == values[x].tobytes() and same(s2, sums)
-    bad = np.vstack((G[5], G[6], G[(1 << n) - 7]))
-    bad[1, 2] = 3
-    out, st, s2, _ = device(mod, bad)
-    assert st.tolist() == [0, 2 | 8 << 16, 0] and np.isnan(out[1]).all() and same(s2, sums)
-    assert out[[0, 2]].tobytes() == values[[5, (1 << n) - 7]].tobytes()
-    v0, s0, s2, only = device(mod, full=True)
-    assert v0.shape == (0, 3) and s0.shape == (0,) and only.tobytes() == whole.tobytes() and same(s2, sums)
-    v1, _, s3, o3 = device(mod, G[:9], summary=False, full=True)
-    assert s3 is None and o3.tobytes() == whole.tobytes() and v1.tobytes() == values[:9].tobytes()
-    with pytest.raises(ValueError, match=r"^row 1: "):
-        mod.metastasis_distribution_at(bad)
+    n = C + 1
+    mod = model(n, seed=41 + C)
+    check_same_bytes(lambda G, **kw: device(mod, G, **kw), 3, n, mod.metastasis_distribution_at)
 
 
 @pytest.mark.gpu

@@ -21,7 +21,6 @@ n = c + 3), against the forward kernel 5.4e-4 (n = c + 6) and 2.1e-4 (n = 22), s
 seeding_forecast 1.4e-3.  The host definition against seeding_forecast of every genotype (CPU): 3.6e-15 relative at the worst.
 """
 import functools
-import os
 import re
 
 import numpy as np
@@ -30,16 +29,13 @@ import pytest
 import metmhn_amd.model as model_mod
 from metmhn_amd import regularized_optimization as ro
 from metmhn_amd.model import MetMHN, SeedingLandscape
+from lattice_common import C, U, bits, check_same_bytes, note
+from lattice_common import rel as lattice_rel
 from order_common import mixed_cohort, model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-U = 2.0 ** -53
 UNTIL = ("seeding", "observation")
 FIELDS = SeedingLandscape.FIELDS
-C = int(re.search(r"constexpr int LS_TILE_BITS = (\d+);",
-                  open(os.path.join(ROOT, "metmhn_amd", "csrc", "landscape.h")).read()).group(1))
 S_FORECAST = 655                   # forecast.h: the longest chain of additions behind an output of the forward kernel
-WORST = {}                         # test -> worst error / bound seen (printed)
 
 
 def genotype(n, held):
@@ -48,21 +44,9 @@ def genotype(n, held):
     return g
 
 
-def bits(n, codes):
-    """[R, n] int8 genotypes of the codes."""
-    return (np.asarray(codes, dtype=np.int64)[:, None] >> np.arange(n) & 1).astype(np.int8)
-
-
 def rel(got, ref):
-    """Worst |got - ref| / |ref| over the entries; NaN must sit where NaN sits, an exact 0 must be met exactly."""
-    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    assert (np.isnan(got) == np.isnan(ref)).all(), "NaN pattern"
-    ok = ~np.isnan(ref)
-    zero = ok & (ref == 0)
-    assert (got[zero] == 0).all(), "an exact zero of the reference is not met"
-    live = ok & ~zero
-    return float(np.max(np.abs(got[live] - ref[live]) / np.abs(ref[live]), initial=0.0))
+    """lattice_common.rel where NaN must sit where NaN sits."""
+    return lattice_rel(got, ref, nan=True)
 
 
 def eps_of(mod):
@@ -281,12 +265,6 @@ def test_seeding_risk_scatters_over_a_mixed_cohort(monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU
-def note(tag, worst):
-    WORST[tag] = max(WORST.get(tag, 0.0), worst)
-    print(f"{tag}: worst error / bound {worst:.3e}")
-    assert worst <= 1.0, (tag, worst)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("until", UNTIL)
 @pytest.mark.parametrize("n", (1, 3, C, C + 1, C + 3))
@@ -356,30 +334,13 @@ def test_a_landscape_that_does_not_fit_is_refused_with_its_bytes():
 @pytest.mark.gpu
 def test_same_bytes_whatever_the_queries():
     from metmhn_amd.jx import engine
-    n, seed = C + 1, 41 + C
-    mod = model(n, seed=seed)
-    eng = engine(n)
-    args = (mod.log_theta, mod.obs1)
-    codes = np.arange(1 << n)
-    G = bits(n, codes)
+    n = C + 1
+    mod = model(n, seed=41 + C)
     for until in UNTIL:
-        values, status, whole = eng.seeding_landscape(*args, G, until, full=True)
-        assert (status == 0).all() and values.tobytes() == np.ascontiguousarray(whole.T).tobytes()
-        again = eng.seeding_landscape(*args, G, until, full=True)
-        assert again[0].tobytes() == values.tobytes() and again[2].tobytes() == whole.tobytes()
-        perm = np.random.default_rng(7).permutation(len(G))[:300]
-        mixed, st, none = eng.seeding_landscape(*args, G[perm], until)
-        assert none is None and (st == 0).all() and mixed.tobytes() == values[perm].tobytes()
-        for x in (0, 1, (1 << C) - 1, 1 << C, (1 << n) - 1):
-            one, st, _ = eng.seeding_landscape(*args, G[x:x + 1], until)
-            assert st.tolist() == [0] and one[0].tobytes() == values[x].tobytes()
-        bad = np.vstack((G[5], G[6], G[(1 << n) - 7]))
-        bad[1, 2] = 3
-        out, st, _ = eng.seeding_landscape(*args, bad, until)
-        assert st.tolist() == [0, 2 | 8 << 16, 0] and np.isnan(out[1]).all()
-        assert out[[0, 2]].tobytes() == values[[5, (1 << n) - 7]].tobytes()
-        v0, s0, only = eng.seeding_landscape(*args, np.zeros((0, n), dtype=np.int8), until, full=True)
-        assert v0.shape == (0, 4) and s0.shape == (0,) and only.tobytes() == whole.tobytes()
+        def call(G, **kw):
+            values, status, whole = engine(n).seeding_landscape(mod.log_theta, mod.obs1, G, until, **kw)
+            return values, status, None, whole
+        check_same_bytes(call, 4, n)
 
 
 @pytest.mark.gpu
