@@ -596,6 +596,45 @@ int mmhn_metastasis_distribution(mmhn_handle h, const double* log_theta, const d
                                  const int8_t* genotypes, int64_t n_rows, double* values, int32_t* status, double* summary,
                                  double* full);
 
+/* ---- genotype distribution of one tumour given the other -------------------------------------
+ * mmhn_partner_distributions: for every query genotype q the joint probability of q in the GIVEN tumour - the primary tumour
+ * observed seeded (given = 0) or the metastasis (given = 1) - with EVERY genotype of the other tumour, the partner: one row or
+ * column of the (PT x MT) table, exp(lp) of the cohort row of type 3 with unknown order of observation for all 2^n_mut
+ * partners at once.  After the seeding the two tumours are independent chains, each stopped by its own clock, so the joint
+ * factorises through the founder z.  With the notation of the two distributions above, kappa1 = kappa0 exp(obs1[n]),
+ * den1 = L + kappa1, denm = Lm + kappam, and for given = 0 (given = 1 exchanges the chains: mu, kappam, denm behind the
+ * seeding for B and lambda, kappa1, den1 for F)
+ *   G0(z), z a subset of q:  as in mmhn_genotype_distribution
+ *   B(q) = kappa1(q) / den1(q),  B(z) = sum over j in q - z of lambda_j(z) B(z + j) / den1(z)    (L over ALL mutations z lacks)
+ *   W(z) = sigma(z) G0(z) B(z) on the subsets of q, 0 elsewhere     = P(founder z, the given tumour observed as q)
+ *   F(y) = W(y) + sum_b G(y - b) mu_b(y - b),  G = F / denm,  J(y) = kappam(y) G(y)     = P(PT = q seeded, MT = y)
+ * sum W = sum J = S(q) of mmhn_genotype_distribution (given = 0) or M(q) of mmhn_metastasis_distribution (given = 1), and
+ * J of q given as PT at y = J of y given as MT at q.  Per DISTINCT query: a backward pass and a forward pass over the
+ * 2^|q| subsets of q and one forward sweep of one plane over all 2^n_mut genotypes (metmhn_amd/csrc/partner.h).  The device
+ * returns joint probabilities; the conditionals are J / mass.  fp64 engines only; independent of the loaded cohort.
+ *   given                                       0: the queries are primary tumours, 1: metastases
+ *   genotypes [n_rows][n_mut]                   int8 queries, 1 = held, 0 = not; n_rows = 0 is valid
+ *   targets                                     null, or [n_rows][n_mut]: a partner genotype per row
+ *   values [n_rows][3]                          mass = sum J - the sum over the tiles (thread t of 256 the tiles t, t + 256, ...
+ *                                               ascending, then a tree) of the tile masses of the summary's fold, the bytes of
+ *                                               the summary's mass of the partner, formed with or without summaries -, W and J
+ *                                               at the row's target (NaN without targets)
+ *   status [n_rows]                             as for mmhn_genotype_distribution: MMHN_ORD_OK, or MMHN_ORD_INVALID with
+ *                                               MMHN_ORD_BAD_ENTRY in the high half for an entry of the query or the target
+ *                                               other than 0 / 1 (that row's values and summaries are NaN)
+ *   summaries                                   null, or [n_rows][2][1 + n_mut * n_mut + n_mut + 1]: mass, pairs, burden of
+ *                                               the founder plane W and then of the partner plane J of every row
+ *   full                                        null, or [2][2^n_mut]: W and J of every genotype by code; n_rows must be 1
+ * The call fails (return 1, the last error names the bytes needed) when 16 B x 2^n_mut, the two sets of rate tables, the
+ * two tile lists and the tiles' partial sums exceed the workspace limit, whatever the rows (the per-row buffers, 28 B per valid
+ * row for the target code and the values, fall outside the limit as the gather buffers of the sweeps above do): there is no partial distribution
+ * and nothing is launched.  A query that holds a mutation of rate 0 gives exact zeros; no byte of a row's outputs depends
+ * on the other rows or on an earlier call.
+ */
+int mmhn_partner_distributions(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, int given,
+                               const int8_t* genotypes, const int8_t* targets, int64_t n_rows, double* values,
+                               int32_t* status, double* summaries, double* full);
+
 /* ---- measurement -------------------------------------------------------------------
  * mmhn_bench_kronvec: `batch` resident copies of a 2^k vector, `iters` back-to-back
  * launches of mmhn_kronvec_batched's launch (diag = 0: y = Q_off p into a NaN-filled y, every tile of every vector,
@@ -626,7 +665,7 @@ typedef struct {
   int32_t comm_rank;  /* this engine's rank in it (ncclCommUserRank), -1: none */
 } mmhn_counters;
 /* ABI version of this header: bumped whenever an exported signature or structure changes (4: mmhn_bench_kronvec has its
- * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions, mmhn_order_samples, mmhn_simulate_pairs, mmhn_order_times, mmhn_order_snapshots, mmhn_seeding_forecasts, mmhn_seeding_landscape, mmhn_genotype_distribution and mmhn_metastasis_distribution were added within version 8, purely additive changes).  A client built against another header must refuse to run:
+ * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions, mmhn_order_samples, mmhn_simulate_pairs, mmhn_order_times, mmhn_order_snapshots, mmhn_seeding_forecasts, mmhn_seeding_landscape, mmhn_genotype_distribution, mmhn_metastasis_distribution and mmhn_partner_distributions were added within version 8, purely additive changes).  A client built against another header must refuse to run:
  * mmhn_abi_version() != MMHN_ABI_VERSION (metmhn_amd/_lib.py checks it on load). */
 #define MMHN_ABI_VERSION 8
 int mmhn_abi_version(void);

@@ -5,7 +5,7 @@
 // batches, routes, work lists, offsets), host.h (errors, device arrays, lanes, MMHN_* knob readers), comm.h (RCCL),
 // rowmix_host.h (row weights and row groups: their checks, device copies and the launches of the group kernels),
 // prims.h / orders_host.h / orderpost_host.h (the batching of the order-posterior entry points, opr_rows) /
-// orderprec_host.h / orderpos_host.h / ordertime_host.h / ordersnap_host.h / ordersample_host.h / forecast_host.h / lattice_host.h / landscape_host.h / genodist_host.h / metdist_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
+// orderprec_host.h / orderpos_host.h / ordertime_host.h / ordersnap_host.h / ordersample_host.h / forecast_host.h / lattice_host.h / landscape_host.h / genodist_host.h / metdist_host.h / partner_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
 //
 // Pipeline of one evaluation (reference call graph: regularized_optimization.py:163-267 ->
 // likelihood.py:_g_coupled_*, _grad_prim_obs, _grad_met_obs), run batch by batch with every
@@ -1123,6 +1123,7 @@ struct Engine : EngineBase {
 #include "landscape_host.h"
 #include "genodist_host.h"
 #include "metdist_host.h"
+#include "partner_host.h"
 #include "sampler_host.h"
 #include "bench.h"
 
@@ -1773,6 +1774,21 @@ int mmhn_metastasis_distribution(mmhn_handle h, const double* log_theta, const d
   REQUIRE(h->dtype == MMHN_F64, "the metastasis distribution needs an fp64 engine (MMHN_F64)");
   metastasis_distribution(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, genotypes, n_rows, values, status,
                           summary, full);
+  API_END
+}
+
+// ---- genotype distribution of one tumour given the other: a row or column of the (PT x MT) table per query genotype
+int mmhn_partner_distributions(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, int given,
+                               const int8_t* genotypes, const int8_t* targets, int64_t n_rows, double* values,
+                               int32_t* status, double* summaries, double* full) {
+  API_BEGIN
+  GUARD(h);
+  REQUIRE(n_rows >= 0 && n_rows < ((int64_t)1 << 31), "n_rows out of range");
+  REQUIRE(log_theta && obs1 && obs2, "null pointer");
+  REQUIRE((genotypes && values && status) || n_rows == 0, "null pointer");
+  REQUIRE(h->dtype == MMHN_F64, "the partner distribution needs an fp64 engine (MMHN_F64)");
+  partner_distributions(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, given, genotypes, targets, n_rows,
+                        values, status, summaries, full);
   API_END
 }
 

@@ -4,6 +4,8 @@
 // (there is no partial sweep), sorts the tiles by the popcount of their number, launches the sweep's level kernel once
 // per popcount on the engine's stream, runs the sweep's finishing step, gathers the queried codes on the device and, on
 // request, copies the K planes out.  lattice_summary is the finishing step of the sweeps that have a summary.
+// partner_host.h loops over queries on one workspace and calls the pieces itself: ls_check_workspace, ls_decode_queries,
+// ls_tile_levels, ls_upload_model and, for the tiles under a query's high bits, ls_tile_levels_under.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -82,6 +84,40 @@ inline void ls_tile_levels(int hb, bool descending, std::vector<uint32_t>& tiles
   for (size_t t = 0; t < nt; ++t) tiles[at[level(t)]++] = (uint32_t)t;
 }
 
+// the refusal of a sweep of K planes whose `need` bytes of workspace exceed the limit
+inline void ls_check_workspace(const LatticeSpec& spec, int n, int K, long long need, long long limit) {
+  if (need > limit)
+    throw Fail{std::string(spec.name) + ": " + std::to_string(n) + " mutations need " + std::to_string(need) +
+               " bytes of workspace (" + std::to_string(8 * K) + " B x 2^n_mut" + spec.holds + "), the workspace limit is " +
+               std::to_string(limit) + " bytes; there is no partial " + spec.whole};
+}
+
+// the model and the tile list to the device - par: theta [N][N], then `sets` obs vectors [N] - and the sets of tables
+inline void ls_upload_model(hipStream_t stream, int N, int c, int sets, const double* lt, const double* const* obs,
+                            const std::vector<uint32_t>& tiles, double* par, uint32_t* d_tiles, LsTables* tabs) {
+  HIPCHECK(hipMemcpyAsync(par, lt, sizeof(double) * N * N, hipMemcpyHostToDevice, stream));
+  for (int s = 0; s < sets; ++s)
+    HIPCHECK(hipMemcpyAsync(par + N * N + s * N, obs[s], sizeof(double) * N, hipMemcpyHostToDevice, stream));
+  HIPCHECK(hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  for (int s = 0; s < sets; ++s) {
+    hipLaunchKernelGGL(k_landscape_tables, dim3(1), dim3(LS_KB), 0, stream, par, par + N * N + s * N, N, c, tabs + s);
+    HIPCHECK(hipGetLastError());
+  }
+}
+
+// the tile numbers that are subsets of `mask` in levels by popcount, ascending within a level: level l holds the subsets
+// of popcount l, first[l] where it starts, first[popcount(mask) + 1] their number (partner_host.h's restricted list)
+inline void ls_tile_levels_under(uint32_t mask, std::vector<uint32_t>& tiles, std::vector<size_t>& first) {
+  const int k = __builtin_popcount(mask);
+  first.assign(k + 2, 0);
+  tiles.resize((size_t)1 << k);
+  uint32_t t = 0;
+  do { ++first[__builtin_popcount(t) + 1]; t = (t - mask) & mask; } while (t);
+  for (int l = 0; l <= k; ++l) first[l + 1] += first[l];
+  std::vector<size_t> at(first.begin(), first.end() - 1);
+  do { tiles[at[__builtin_popcount(t)]++] = t; t = (t - mask) & mask; } while (t);
+}
+
 // One sweep of K planes.  gen [R][n]: 1 = held (R may be 0); values [R][K] of every query (NaN for a row that is not
 // valid); full: nullptr or [K][2^n], every genotype by code; summary: whether the workspace holds lattice_summary's.
 // level(X, blocks, tiles) launches the level kernel over the `blocks` tile numbers at `tiles` (on the device);
@@ -92,11 +128,7 @@ void lattice_sweep(Engine<T>& E, const LatticeSpec& spec, const double* lt, cons
                    Finish finish) {
   const int n = E.n, N = E.N, c = ls_tile_bits(n);
   std::fill(values, values + K * R, std::nan(""));
-  const long long need = lattice_bytes(n, K, spec.sets, summary), limit = (long long)E.cfg.plan.ws_limit;
-  if (need > limit)
-    throw Fail{std::string(spec.name) + ": " + std::to_string(n) + " mutations need " + std::to_string(need) +
-               " bytes of workspace (" + std::to_string(8 * K) + " B x 2^n_mut" + spec.holds + "), the workspace limit is " +
-               std::to_string(limit) + " bytes; there is no partial " + spec.whole};
+  ls_check_workspace(spec, n, K, lattice_bytes(n, K, spec.sets, summary), (long long)E.cfg.plan.ws_limit);
   std::vector<uint32_t> codes;
   std::vector<long long> src;
   ls_decode_queries(gen, R, n, status, codes, src);
@@ -113,14 +145,7 @@ void lattice_sweep(Engine<T>& E, const LatticeSpec& spec, const double* lt, cons
   tabs.alloc(spec.sets);
   d_tiles.alloc(nt);
   const double* obs[2] = {obs1, obs2};
-  HIPCHECK(hipMemcpyAsync(par.p, lt, sizeof(double) * N * N, hipMemcpyHostToDevice, E.stream));
-  for (int s = 0; s < spec.sets; ++s)
-    HIPCHECK(hipMemcpyAsync(par.p + N * N + s * N, obs[s], sizeof(double) * N, hipMemcpyHostToDevice, E.stream));
-  HIPCHECK(hipMemcpyAsync(d_tiles.p, tiles.data(), nt * sizeof(uint32_t), hipMemcpyHostToDevice, E.stream));
-  for (int s = 0; s < spec.sets; ++s) {
-    hipLaunchKernelGGL(k_landscape_tables, dim3(1), dim3(LS_KB), 0, E.stream, par.p, par.p + N * N + s * N, N, c, tabs.p + s);
-    HIPCHECK(hipGetLastError());
-  }
+  ls_upload_model(E.stream, N, c, spec.sets, lt, obs, tiles, par.p, d_tiles.p, tabs.p);
   LatticeRun X{n, N, c, nt, E.stream, par.p, par.p + N * N, spec.sets > 1 ? par.p + N * N + N : nullptr, tabs.p, V.p, {}, {}};
   for (int l = 0; l <= hb; ++l) {
     level(X, (unsigned)(first[l + 1] - first[l]), d_tiles.p + first[l]);

@@ -690,6 +690,46 @@ class Engine:
         return self._lattice_call(genotypes, 3, summary, full,
                                   lambda *buffers: self.lib.mmhn_metastasis_distribution(self.h, ltp, ap, bp, *buffers))
 
+    # ---- partner distributions
+    def partner_distributions(self, log_theta, obs1, obs2, genotypes, given="PT", targets=None, summary=True, full=False):
+        """For every row of int8 `genotypes` [R, n] (1 = held; R may be 0), taken as the primary tumour observed seeded
+        (given="PT") or as the metastasis (given="MT"), the joint probability with every genotype of the other tumour and
+        with every founder (mmhn_partner_distributions; a backward pass over the subsets of the row and one forward sweep
+        over all 2^n codes per DISTINCT row): float64 values [R, 3] = mass (the sum of the joint), founder W and joint J at
+        the row of `targets` [R, n] (NaN without targets), int32 status [R] (0 ok, 2 with reason code 8 in status >> 16 for
+        an entry of the row or its target other than 0 / 1, whose outputs are NaN), with summary=True (mass [R, 2], pairs
+        [R, 2, n, n], burden [R, 2, n+1]) of the founder and the partner plane of every row, else None, and with full=True,
+        which needs R == 1, the two planes [2, 2^n] by code, else None.  Raises when 16 B x 2^n, the tables, the tile
+        lists and the tiles' partial sums exceed the workspace limit."""
+        if given not in ("PT", "MT"):
+            raise ValueError("given must be 'PT' or 'MT'")
+        lt, ltp = self._theta(log_theta); a, ap = self._rates(obs1, "obs1"); b, bp = self._rates(obs2, "obs2")
+        n = self.n
+        g = np.ascontiguousarray(np.asarray(genotypes).astype(np.int8))
+        if g.ndim != 2 or g.shape[1] != n:
+            raise ValueError(f"genotypes must be a 2-D array [R, {n}]")
+        R = g.shape[0]
+        t = None
+        if targets is not None:
+            t = np.ascontiguousarray(np.asarray(targets).astype(np.int8))
+            if t.shape != g.shape:
+                raise ValueError(f"targets must be a 2-D array [R, {n}] with a row per genotype")
+        if full and R != 1:
+            raise ValueError(f"full=True returns the planes of one query: genotypes must have one row, got {R}")
+        values = np.empty((R, 3))                                # (the library fills it with NaN first)
+        status = np.zeros(R, dtype=np.int32)
+        sums = np.empty((R, 2, 1 + n * n + n + 1)) if summary else None
+        whole = np.empty((2, 1 << n)) if full else None
+        _lib.check(self.lib.mmhn_partner_distributions(
+            self.h, ltp, ap, bp, 0 if given == "PT" else 1, g.ctypes.data_as(i8p),
+            t.ctypes.data_as(i8p) if t is not None else None, R, values.ctypes.data_as(f64p),
+            status.ctypes.data_as(_lib.i32p), sums.ctypes.data_as(f64p) if summary else None,
+            whole.ctypes.data_as(f64p) if full else None))
+        if summary:
+            sums = (np.ascontiguousarray(sums[:, :, 0]), np.ascontiguousarray(sums[:, :, 1:1 + n * n]).reshape(R, 2, n, n),
+                    np.ascontiguousarray(sums[:, :, 1 + n * n:]))
+        return values, status, sums, whole
+
     # ---- measurement
     def bench_kronvec(self, log_theta, state, batch, iters, transpose=False, jacobi=False, tiles=False):
         """ms per launch of mmhn_kronvec_batched's launch (or the fused Jacobi step); tiles=True also returns

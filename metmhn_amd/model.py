@@ -552,6 +552,77 @@ class MetastasisDistribution(SimpleNamespace):
         return np.where(self.metastasis == 0, np.nan, out)
 
 
+PARTNER_STRATA = ("founder", "partner")         # the planes of a partner distribution's summary
+_PARTNER_GIVEN = ("PT", "MT")
+
+
+class PartnerSummary(GenotypeSummary):
+    """Exact sums over the joint distribution of one observed tumour with the founder (plane 0, W) and with the tumour
+    that was not sequenced, the partner (plane 1, J), GenotypeSummary's arrays: mass [2] (the two are equal, the
+    probability of the observed tumour's genotype), pairs [2, n, n], burden [2, n+1] - unnormalised, as in the siblings.
+    Strata (PARTNER_STRATA): "founder" plane 0 over mass[0], "partner" plane 1 over mass[1]; frequencies, log_odds and
+    burden_pmf are GenotypeSummary's and divide by the stratum's mass, so they are conditional on the observed tumour."""
+
+    def __repr__(self):
+        return f"PartnerSummary(n_mut={self.n_mut}, mass={self.mass.tolist()})"
+
+    def _stratum(self, stratum):
+        if stratum not in PARTNER_STRATA:
+            raise ValueError(f"stratum must be one of {PARTNER_STRATA}, got {stratum!r}")
+        s = PARTNER_STRATA.index(stratum)
+        return self.pairs[s], self.burden[s], self.mass[s]
+
+    def conditional_frequencies(self, stratum="partner") -> np.ndarray:
+        """[n]: the probability that the stratum's genotype holds mutation j given the observed tumour - the marginal sums
+        over the stratum's mass (NaN throughout if the mass is 0)."""
+        pairs, _, mass = self._stratum(stratum)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.diag(pairs) / np.float64(mass)
+
+    def expected_burden(self, stratum="partner") -> float:
+        """The expected number of mutations of the stratum's genotype given the observed tumour."""
+        return float(np.arange(self.n_mut + 1) @ self.burden_pmf(stratum))
+
+    def _held(self, genotype):
+        g = np.asarray(genotype)
+        if g.shape != (self.n_mut,) or not np.isin(g, (0, 1)).all():
+            raise ValueError(f"genotype must be {self.n_mut} entries of 0 / 1")
+        return g.astype(bool)
+
+    def gained(self, genotype) -> np.ndarray:
+        """[n]: the conditional probability that the partner holds mutation j, for the mutations the observed `genotype`
+        lacks (NaN for the ones it holds)."""
+        return np.where(self._held(genotype), np.nan, self.conditional_frequencies("partner"))
+
+    def lost(self, genotype) -> np.ndarray:
+        """[n]: the conditional probability that the partner lacks mutation j, for the mutations the observed `genotype`
+        holds (NaN for the ones it lacks)."""
+        return np.where(self._held(genotype), 1.0 - self.conditional_frequencies("partner"), np.nan)
+
+
+class PartnerDistribution(SimpleNamespace):
+    """The joint probability of one observed tumour - the primary tumour seeded (`given` "PT") or the metastasis ("MT")
+    with the genotype `genotype` (a code) - with every founder genotype (`founder`, W) and with every genotype of the
+    other tumour (`partner`, J: exp(lp) of the paired row of unknown order), arrays over the genotypes `codes`; `mass`
+    their common sum, the probability of the observed tumour; `summary` the PartnerSummary."""
+
+    def __init__(self, founder, partner, codes, mass, summary, given, genotype):
+        super().__init__(founder=founder, partner=partner, codes=codes, mass=mass, summary=summary, given=given,
+                         genotype=genotype)
+
+    @property
+    def conditional(self) -> np.ndarray:
+        """partner / mass: the distribution of the other tumour's genotype given the observed one (NaN if mass is 0)."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.partner / np.float64(self.mass)
+
+    @property
+    def founder_conditional(self) -> np.ndarray:
+        """founder / mass: the distribution of the founder's genotype given the observed tumour (NaN if mass is 0)."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.founder / np.float64(self.mass)
+
+
 _FORECAST_UNTIL = ("seeding", "observation")
 _FORECAST_HOST_MAX = 24          # free mutations the host definition takes on: f x 2^f doubles of rates
 _LATTICE_HOST_MAX = 24           # mutations the host landscape and distributions take on: n x 2^n doubles of rates
@@ -1061,9 +1132,7 @@ class MetMHN:
         n = self.n
         if backend == "host" and n > _LATTICE_HOST_MAX:
             host()                                  # (raises: the message points to the device)
-        if 8 * planes << n > max_bytes:
-            raise ValueError(f"{n} mutations: a {noun} {prep} 2^{n} genotypes needs {8 * planes << n} bytes, more than max_bytes = "
-                             f"{int(max_bytes)}; {at} reads single genotypes off the device's {noun}")
+        self._lattice_max_bytes(max_bytes, planes, noun, prep, at)
         if backend == "host":
             whole = host()
             sums = summary_host(whole) if summary_host else None
@@ -1310,6 +1379,161 @@ class MetMHN:
             raise ValueError("backend must be 'device' or 'host'")
         return self._lattice_at(genotypes, "observation", backend, 3, self._metdist_host, self._metdist_device,
                                 MetastasisDistribution, self._metdist_summary_host, MetastasisSummary)
+
+    # ------------------------------------------------------------------ genotype distribution of one tumour given the other
+    def _partner_rates(self):
+        """What _partner_host needs of the model, formed once for any number of queries."""
+        n, size = self.n, 1 << self.n
+        idx, level, lam, sig = self._lattice_host_rates("distribution")
+        mu = [lam[j] * np.exp(self.log_theta[j, n]) for j in range(n)]
+        kap0 = np.exp(_subset_sums(self.obs1[:n]))
+        kap1 = kap0 * np.exp(self.obs1[n])
+        kapm = np.exp(self.obs2[n] + _subset_sums(self.obs2[:n]))
+        L, Lm = np.zeros(size), np.zeros(size)
+        for j in range(n):
+            free = (idx >> j & 1) == 0
+            L += np.where(free, lam[j], 0.0)
+            Lm += np.where(free, mu[j], 0.0)
+        chains = {"PT": (lam, kap1, L + kap1), "MT": (mu, kapm, Lm + kapm)}
+        return idx, level, lam, sig, L + sig + kap0, chains
+
+    def _partner_host(self, q: int, given: str, rates=None) -> np.ndarray:
+        """[2, 2^n]: the definition of the partner distribution (W, J) of the query code q, level by level."""
+        n, size = self.n, 1 << self.n
+        idx, level, lam, sig, den0, chains = rates if rates is not None else self._partner_rates()
+        (rq, kq, dq), (rp, kp, dp) = chains[given], chains["MT" if given == "PT" else "PT"]
+        sub = (idx & ~q) == 0
+        top = bin(q).count("1")
+        F0, G0, B = (np.zeros(size) for _ in range(3))
+        F0[0] = 1.0
+        for lev in range(top + 1):                           # G0 on the subsets of q
+            ys = idx[(level == lev) & sub]
+            for b in range(n if lev else 0):
+                to = ys[(ys >> b & 1) == 1]
+                frm = to ^ (1 << b)
+                F0[to] += G0[frm] * lam[b][frm]
+            G0[ys] = F0[ys] / den0[ys]
+        B[q] = kq[q] / dq[q]
+        for lev in range(top - 1, -1, -1):                   # B: from a subset to q, then q's own clock
+            xs = idx[(level == lev) & sub]
+            num = np.zeros(len(xs))
+            for j in range(n):
+                if q >> j & 1:
+                    m = (xs >> j & 1) == 0
+                    x = xs[m]
+                    num[m] += rq[j][x] * B[x | 1 << j]
+            B[xs] = num / dq[xs]
+        W = np.where(sub, sig * G0 * B, 0.0)
+        F, G = W.copy(), np.zeros(size)
+        for lev in range(n + 1):                             # the partner's chain from every founder at once
+            ys = idx[level == lev]
+            for b in range(n if lev else 0):
+                to = ys[(ys >> b & 1) == 1]
+                frm = to ^ (1 << b)
+                F[to] += G[frm] * rp[b][frm]
+            G[ys] = F[ys] / dp[ys]
+        return np.stack((W, kp * G))
+
+    @staticmethod
+    def _partner_summary_host(P: np.ndarray) -> "PartnerSummary":
+        """The PartnerSummary of the planes P [2, 2^n], by its definition."""
+        s = MetMHN._genodist_summary_host(P)
+        return PartnerSummary(s.mass, s.pairs, s.burden)
+
+    def _lattice_max_bytes(self, max_bytes, planes, noun, prep, at):
+        """_lattice_whole's refusal of a result of `planes` values per genotype that exceeds max_bytes."""
+        n = self.n
+        if 8 * planes << n > max_bytes:
+            raise ValueError(f"{n} mutations: a {noun} {prep} 2^{n} genotypes needs {8 * planes << n} bytes, more than max_bytes = "
+                             f"{int(max_bytes)}; {at} reads single genotypes off the device's {noun}")
+
+    def _partner_checks(self, given, backend):
+        if given not in _PARTNER_GIVEN:
+            raise ValueError("given must be 'PT' or 'MT'")
+        if backend not in ("device", "host"):
+            raise ValueError("backend must be 'device' or 'host'")
+
+    def partner_distribution(self, genotype, given: str = "PT", backend: str = "device",
+                             max_bytes: int = 2 ** 31) -> "PartnerDistribution":
+        """The distribution of the tumour that was NOT sequenced: for a primary tumour that has seeded and is observed with
+        `genotype` [n] (0 / 1; given="PT") the joint probability with every genotype of its metastasis, for a metastasis
+        observed with `genotype` (given="MT") the joint probability with every genotype of the primary tumour - one row or
+        column of the (PT x MT) table, exp(lp) of the paired row (type 3) of unknown order for all 2^n partners at once.
+        After the seeding the two tumours are independent chains, each stopped by its own clock, so the joint factorises
+        through the founder z.  With metastasis_distribution's lambda, sigma, kappa0, mu, kappam, L, Lm, G0 and
+        kappa1 = kappa0 exp(obs1_n), den1 = L + kappa1, denm = Lm + kappam, for given="PT" and the query x:
+            B(x) = kappa1(x) / den1(x),  B(z) = sum_{j in x - z} lambda_j(z) B(z + j) / den1(z)    (z a subset of x; L in
+                                                                             den1 over ALL mutations z lacks)
+            W(z) = sigma(z) G0(z) B(z) on the subsets of x, 0 elsewhere      = P(founder z, PT observed seeded as x)
+            FM(y) = W(y) + sum_b GM(y - b) mu_b(y - b),  GM = FM / denm,  J(y) = kappam(y) GM(y) = P(PT = x seeded, MT = y)
+        and for given="MT" with the chains exchanged (B with mu, kappam, denm; the forward pass with lambda, kappa1, den1).
+        `founder` = W, `partner` = J, `mass` = sum J = sum W = genotype_distribution().seeded[x] or
+        metastasis_distribution().metastasis[y]; `conditional` and `founder_conditional` are the planes over `mass` (NaN
+        when it is 0, the joints then being exact zeros); `summary` the PartnerSummary.
+
+        backend="device": one call of the HIP library (mmhn_partner_distributions), 16 B x 2^n of workspace and as much here
+        for the result; a ValueError names the bytes when that exceeds `max_bytes` (2 GiB: n <= 27).  backend="host": the
+        definition in NumPy, level by level, n <= 24."""
+        self._partner_checks(given, backend)
+        n = self.n
+        g = np.asarray(genotype)
+        if g.ndim != 1:
+            raise ValueError(f"genotype must have shape [{n}]")
+        g = self._forecast_checks(g[None, :], "observation")
+        q = int(g[0] @ (1 << np.arange(n, dtype=np.int64)))
+        if backend == "host" and n > _LATTICE_HOST_MAX:
+            self._lattice_host_rates("distribution")         # (raises: the message points to the device)
+        self._lattice_max_bytes(max_bytes, 2, "distribution", "over", "partner_distributions")
+        if backend == "host":
+            whole = self._partner_host(q, given)
+            summary, mass = self._partner_summary_host(whole), whole[1].sum()
+        else:
+            from .jx import engine
+            values, _, sums, whole = engine(n).partner_distributions(self.log_theta, self.obs1, self.obs2, g.astype(np.int8),
+                                                                     given, summary=True, full=True)
+            summary, mass = PartnerSummary(*(s[0] for s in sums)), values[0, 0]
+        return PartnerDistribution(whole[0], whole[1], np.arange(1 << n), float(mass), summary, given, q)
+
+    def partner_distributions(self, genotypes, given: str = "PT", targets=None, backend: str = "device") -> SimpleNamespace:
+        """partner_distribution of every row of `genotypes` [R, n] (0 / 1) without the planes: `mass` [R], `summaries` (a
+        list of R PartnerSummary), `codes` [R] and, with `targets` [R, n], the joint `at_target` [R] with that genotype of
+        the other tumour - exp(lp) of the paired row of unknown order - and `founder_at_target` [R], the joint with that
+        founder (both NaN without targets).  Distinct genotypes are solved once.  backend="device": one call of the HIP
+        library, 16 B x 2^n of its workspace, any n the engine takes; backend="host": the NumPy definition, n <= 24.  An
+        entry other than 0 / 1 raises ValueError("row i: ...") as seeding_forecasts does."""
+        self._partner_checks(given, backend)
+        n = self.n
+        g = self._forecast_checks(genotypes, "observation")
+        t = None
+        if targets is not None:
+            if np.asarray(targets).shape != g.shape:
+                raise ValueError(f"targets must have shape [R, {n}], a row per genotype")
+            t = self._forecast_checks(targets, "observation")
+        pw = 1 << np.arange(n, dtype=np.int64)
+        codes = g @ pw
+        R = len(codes)
+        if backend == "host":
+            rates = self._partner_rates()
+            mass, at, fat, summaries = np.empty(R), np.full(R, np.nan), np.full(R, np.nan), [None] * R
+            uniq, inverse = np.unique(codes, return_inverse=True)
+            for k, q in enumerate(uniq):
+                whole = self._partner_host(int(q), given, rates)
+                summary = self._partner_summary_host(whole)
+                for i in np.flatnonzero(inverse == k):
+                    mass[i], summaries[i] = whole[1].sum(), summary
+                    if t is not None:
+                        fat[i], at[i] = whole[:, int(t[i] @ pw)]
+        else:
+            from .jx import engine
+            values, status, sums, _ = engine(n).partner_distributions(
+                self.log_theta, self.obs1, self.obs2, g.astype(np.int8), given,
+                None if t is None else t.astype(np.int8), summary=True)
+            bad = np.flatnonzero(status != 0)
+            if bad.size:
+                raise ValueError(f"row {int(bad[0])}: a genotype entry is neither 0 nor 1")
+            mass, fat, at = (np.ascontiguousarray(values[:, k]) for k in range(3))
+            summaries = [PartnerSummary(sums[0][i], sums[1][i], sums[2][i]) for i in range(R)]
+        return SimpleNamespace(mass=mass, at_target=at, founder_at_target=fat, codes=codes, summaries=summaries, given=given)
 
     def likelihood(self, order, met_status: str, first_obs: str = None) -> float:
         """model.py:295-376: probability of exactly this order of events being what is observed."""

@@ -542,6 +542,45 @@ def metastasis_fit(log_theta, log_d_p, log_d_m, dat, backend: str = "device"):
                            residuals=got.summary.compare(arr))
 
 
+def partner_forecast(log_theta, log_d_p, log_d_m, dat, backend: str = "device"):
+    """What the model says of the tumour that was NOT sequenced, for every row of `dat` that holds one tumour of a
+    metastasised (or possibly metastasised) patient, from MetMHN.partner_distributions with obs1 = log_d_p, obs2 = log_d_m
+    (distinct genotypes are solved once).  A row of type 1 is taken as given PT (its PT genotype dat[:, 0:2*n:2]: what
+    will the metastasis carry?), of type 2 as given MT (its MT genotype dat[:, 1:2*n:2]: what did the primary tumour look
+    like?), of type 4 as given PT conditional on the seeding; rows of types 0 and 3 give NaN.  A namespace of
+    frequencies [n_pat, n]: the conditional probability that the other tumour holds mutation j
+        (PartnerSummary.conditional_frequencies);
+    burden [n_pat]: its expected number of mutations;
+    founder_burden [n_pat]: the founder's;
+    mass [n_pat]: the probability of the row's own genotype (seeded, for the given PT);
+    given [n_pat]: "PT", "MT" or "" per row;  codes [n_pat]: the genotype code the row was solved for, -1 for types 0 and 3;
+    seeded [n_pat]: met_status_posterior's column - what a type-4 row's forecast is conditional on."""
+    from types import SimpleNamespace
+    from .model import MetMHN
+    arr = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
+    n_pat, n = arr.shape[0], (arr.shape[1] - 3) // 2
+    typ = arr[:, -1]
+    mod = MetMHN(log_theta, log_d_p, log_d_m)
+    if backend == "host":                                    # the same number without the library
+        own = np.isin(typ, (0, 1, 4))
+        seeded = np.full(n_pat, np.nan)
+        seeded[own] = mod.genotype_distribution_at(arr[own][:, 0:2 * n:2], "host").p_seeded
+    else:
+        seeded = met_status_posterior(log_theta, log_d_p, log_d_m, dat)
+    out = SimpleNamespace(frequencies=np.full((n_pat, n), np.nan), burden=np.full(n_pat, np.nan),
+                          founder_burden=np.full(n_pat, np.nan), mass=np.full(n_pat, np.nan),
+                          given=np.full(n_pat, "", dtype="<U2"), codes=np.full(n_pat, -1, dtype=np.int64), seeded=seeded)
+    for given, pick, first in (("PT", np.isin(typ, (1, 4)), 0), ("MT", typ == 2, 1)):
+        if not pick.any():
+            continue
+        got = mod.partner_distributions(arr[pick][:, first:2 * n:2], given, backend=backend)
+        out.given[pick], out.codes[pick], out.mass[pick] = given, got.codes, got.mass
+        out.frequencies[pick] = [s.conditional_frequencies("partner") for s in got.summaries]
+        out.burden[pick] = [s.expected_burden("partner") for s in got.summaries]
+        out.founder_burden[pick] = [s.expected_burden("founder") for s in got.summaries]
+    return out
+
+
 def _unpack(params, n_total):
     params = np.asarray(params, dtype=np.float64)
     return (params[0:n_total ** 2].reshape((n_total, n_total)), params[n_total ** 2:n_total * (n_total + 1)],
