@@ -14,22 +14,16 @@
 // the planes hold G (what a successor pulls); k_genodist_tile turns them into U and S in place once every level is
 // finished - the layout of the entry point's `full` output, so that is one copy - and folds the tile's sums on the way.
 //
-// Shape.  The tiles of lattice.h (the low c = min(n, LS_TILE_BITS) bits in LDS, the high bits name the tile, a
-// host-built list of tile numbers sorted by popcount), one launch of k_genodist_level per popcount of the tile number,
-// ASCENDING: tile T needs the tiles T - bit and itself.  Stream order alone orders the levels: no cooperative launch, no
-// flags, no atomics.  Inside a tile
-//   1. the inflow along the high bits, ascending: thread t owns the low offsets t, t + 256, ... and pulls
-//      lambda_b(x - b) G(x - b) along every high bit b of T from the finished tile T - b at the same offset - consecutive
-//      lanes read consecutive addresses of both planes, the rate is computed once per move and shared by the two planes;
-//   2. the forward substitution over the low bits in LDS, by popcount of the low part, ascending, with orderpass.h's
-//      level walk; G0 of a state before its F1, which takes G0 sigma of the same state; the tile is written out once.
+// Shape.  lattice.h's tiling and its tile solve forwards, one launch of k_genodist_level per popcount of the tile number,
+// ASCENDING: tile T needs the tiles T - bit and itself.  This file's own is the recursion (GenodistRecursion): the rate of
+// a move is shared by the two planes; G0 of a state before its F1, which takes G0 sigma of the same state.
 //
 // den.  A state's den needs its OUTGOING rates, which are not the moves it pulls.  L(x) is FORMED IN THE TILE, not
 // carried: column b of the rate tables does not read bit b (ls_eff), so lambda_b(x - b) is the product HF[b] TL[b] TH[b]
 // at x's own offsets.  A state therefore takes the n column products at its own offsets once: a column it holds is the
-// rate of the move it pulls, a column it does not hold is a term of L.  n products per state from LDS, no memory traffic
-// for den and no third plane (carrying L would cost a plane of 8 B x 2^n written and read once per state, and the pushes
-// to n - |x| successors).  The high columns are taken in step 1 (partial L to LDS), the low ones in step 2.
+// rate of the move it pulls, a column it does not hold is a term of L (the forward rule of ls_tile_solve).  n products per
+// state from LDS, no memory traffic for den and no third plane (carrying L would cost a plane of 8 B x 2^n written and read
+// once per state, and the pushes to n - |x| successors).
 //
 // LDS of a workgroup of k_genodist_level: 3 x 8 KiB (the two values and the partial L of 2^10 states) + 16.5 KiB of rate
 // tables + 2 KiB of patterns + the tile's factors = 42.8 KiB: three workgroups share a CU's 160 KiB.  256 threads, 4 states
@@ -43,14 +37,14 @@
 // sum in ascending order.  k_genodist_summary (a workgroup per output) then adds the tiles' partials: a high bit of a tile
 // is constant over the tile, so high-high = the sum over the tiles that hold both bits of the tile mass, high-low = the sum
 // over the tiles that hold the high bit of the low marginal, burden is shifted by the popcount of the tile number.  Thread
-// t adds the tiles t, t + 256, ... ascending, a tree in LDS adds the 256 threads.  No atomics; the partials are indexed by
+// t adds the tiles t, t + 256, ... ascending, lattice.h's ls_block_sum adds the 256 threads.  No atomics; the partials are indexed by
 // the tile number, not by the place in the list.  Longest chain of additions behind an output: 8 + 4 + 32 in the tile,
 // ceil(tiles / 256) + 8 across tiles.
 //
 // Every shape depends on n alone: no byte of an output depends on the queries, the grid or an earlier call.  fp64 only.
 //
-// RESOURCES (gfx950, -O3, -Rpass-analysis=kernel-resource-usage): k_genodist_level 68 VGPRs, 0 AGPRs, 51 SGPRs, scratch 0,
-// LDS 43 848 B, 3 waves / SIMD (three workgroups a CU, by LDS; the registers would allow 7); k_genodist_tile<true> 36 VGPRs,
+// RESOURCES (gfx950, -O3, -Rpass-analysis=kernel-resource-usage): k_genodist_level 56 VGPRs, 0 AGPRs, 50 SGPRs, scratch 0,
+// LDS 43 848 B, 3 waves / SIMD (three workgroups a CU, by LDS; the registers would allow 8); k_genodist_tile<true> 36 VGPRs,
 // 50 SGPRs, scratch 0, LDS 51 200 B, 3 waves / SIMD; k_genodist_tile<false> 18 VGPRs, 46 SGPRs, scratch 0, LDS 512 B;
 // k_genodist_summary 12 VGPRs, 32 SGPRs, scratch 0, LDS 2 048 B.  lattice.h has the tables' and the gather's.
 #pragma once
@@ -74,6 +68,25 @@ __host__ __device__ inline void gd_pair_of(int idx, int& i, int& j) {
   i = idx - j * (j - 1) / 2;
 }
 
+// the recursion of F0 / F1: G0 of a state before its F1, which takes G0 sigma of the same state
+struct GenodistRecursion : LsRecursion {
+  const LsTables& S;
+  const double (&HF)[LS_COLS];
+  int n;
+  uint32_t T;
+  double e1;
+  __device__ __forceinline__ void source(uint32_t p, double (&f)[2]) const {
+    if (T == 0u && p == 0u) f[0] = 1.0;         // F0 of the empty genotype
+  }
+  __device__ __forceinline__ void finish(uint32_t, uint32_t lo, uint32_t hi, double (&f)[2], const double (&L)[1]) const {
+    const double sig = ls_rate(S, HF[n], n, lo, hi);
+    const double kap = ls_rate(S, HF[n + 1], n + 1, lo, hi);
+    const double g0 = f[0] / (L[0] + sig + kap);
+    f[0] = g0;
+    f[1] = (g0 * sig + f[1]) / (L[0] + kap * e1);
+  }
+};
+
 // one level of tiles: workgroup b finishes the tile tiles[b]; every tile tiles[b] - bit is finished (earlier launches)
 __global__ __launch_bounds__(LS_KB) void k_genodist_level(const LsTables* __restrict__ tabs, const uint32_t* __restrict__ tiles,
                                                           const double* __restrict__ g_lt, const double* __restrict__ g_o1,
@@ -81,74 +94,14 @@ __global__ __launch_bounds__(LS_KB) void k_genodist_level(const LsTables* __rest
   __shared__ LsTables S;
   __shared__ double HF[LS_COLS];                // column j: exp(diagonal + the effects of the tile's high bits)
   __shared__ double W[3][1 << LS_TILE_BITS];    // 0 / 1: F0 / F1 of the tile's states (partial until a state is finished, then G), 2: its partial L
-  const int tid = threadIdx.x, n = N - 1;
+  const int n = N - 1;
   const uint32_t T = tiles[blockIdx.x];
-  const uint32_t Vt = 1u << c;
-  const long long plane = 1ll << n, base = (long long)T << c;
+  const long long plane = 1ll << n;
   ls_tile_prologue(S, HF, tabs, g_lt, g_o1, N, c, T);
   const double e1 = exp(g_o1[n]);               // kappa1 = kappa0 e1
   __syncthreads();
-
-  // 1. the columns of the high bits: a held one is the move pulled from the tile T - bit, a free one a term of L
-  {
-    double a0[LS_SPT], a1[LS_SPT], dn[LS_SPT];
-#pragma unroll
-    for (int s = 0; s < LS_SPT; ++s) a0[s] = a1[s] = dn[s] = 0.0;
-    for (int j = c; j < n; ++j) {
-      const bool held = (T >> (j - c)) & 1u;
-      const double hf = HF[j];
-      const double* q = held ? V + base - (1ll << j) : V;
-#pragma unroll
-      for (int s = 0; s < LS_SPT; ++s) {
-        const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
-        if (p < Vt) {
-          const double r = ls_rate(S, hf, j, p & 31u, p >> LS_HALF);
-          if (held) {
-            a0[s] += r * q[p];
-            a1[s] += r * q[plane + p];
-          } else {
-            dn[s] += r;
-          }
-        }
-      }
-    }
-    if (T == 0u && tid == 0) a0[0] = 1.0;         // F0 of the empty genotype
-#pragma unroll
-    for (int s = 0; s < LS_SPT; ++s) {
-      const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
-      if (p < Vt) { W[0][p] = a0[s]; W[1][p] = a1[s]; W[2][p] = dn[s]; }
-    }
-  }
-  __syncthreads();
-
-  // 2. the forward substitution over the low bits
-  const uint32_t chunks = Vt >> S.L.c;
-  for (int lev = 0; lev <= c; ++lev) {
-    opo_level<LS_KB>(S.L, 0u, chunks, lev, [&](uint32_t p) {
-      const uint32_t lo = p & 31u, hi = p >> LS_HALF;
-      double f0 = W[0][p], f1 = W[1][p], L = W[2][p];
-#pragma unroll
-      for (int j = 0; j < LS_TILE_BITS; ++j) {
-        if (j < c) {
-          const double r = ls_rate(S, HF[j], j, lo, hi);
-          if ((p >> j) & 1u) {
-            const uint32_t y = p ^ (1u << j);
-            f0 += r * W[0][y];
-            f1 += r * W[1][y];
-          } else {
-            L += r;
-          }
-        }
-      }
-      const double sig = ls_rate(S, HF[n], n, lo, hi);
-      const double kap = ls_rate(S, HF[n + 1], n + 1, lo, hi);
-      const double g0 = f0 / (L + sig + kap);
-      W[0][p] = g0;
-      W[1][p] = (g0 * sig + f1) / (L + kap * e1);
-    });
-    __syncthreads();
-  }
-  ls_write_tile<2>(W, Vt, V, base, plane);
+  ls_tile_solve<2, 1, true>(GenodistRecursion{{}, S, HF, n, T, e1}, S, HF, W, n, c, T, V, plane);
+  ls_write_tile<2>(W, 1u << c, V, (long long)T << c, plane);
 }
 
 // the GD_FEAT partial sums of a tile's two planes to part[(s * GD_FEAT + f) * nt + T]: u / w hold the planes' values at the
@@ -241,14 +194,13 @@ template <bool SUMS>
 __global__ __launch_bounds__(LS_KB) void k_genodist_tile(const LsTables* __restrict__ tabs, const double* __restrict__ g_o1,
                                                          int N, int c, double* V, double* __restrict__ part, long long nt) {
   __shared__ double KL[1 << LS_HALF], KH[1 << LS_HALF];
+  const LsColumn KC{KL, KH};                    // the clock
   const int tid = threadIdx.x, n = N - 1;
   const uint32_t T = blockIdx.x;
   const uint32_t Vt = 1u << c;
   const long long plane = 1ll << n, base = (long long)T << c;
-  if (tid < (1 << LS_HALF)) { KL[tid] = tabs->TL[n + 1][tid]; KH[tid] = tabs->TH[n + 1][tid]; }
-  double v = 0.0;
-  for (uint32_t m = T; m; m &= m - 1) v += g_o1[c + __builtin_ctz(m)];
-  const double k0 = exp(v), e1 = exp(g_o1[n]);  // (k_genodist_level's HF[n + 1] and e1)
+  KC.load(tabs, n + 1);
+  const double k0 = LsColumn::factor(g_o1, 0.0, c, T), e1 = exp(g_o1[n]);
   __syncthreads();
   double u[LS_SPT], w[LS_SPT];
 #pragma unroll
@@ -256,7 +208,7 @@ __global__ __launch_bounds__(LS_KB) void k_genodist_tile(const LsTables* __restr
     const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
     u[s] = w[s] = 0.0;
     if (p < Vt) {
-      const double kap = k0 * KL[p & 31u] * KH[p >> LS_HALF];
+      const double kap = KC.at(k0, p & 31u, p >> LS_HALF);
       double* o = V + base + p;
       u[s] = kap * o[0];
       w[s] = (kap * e1) * o[plane];
@@ -302,17 +254,12 @@ __global__ __launch_bounds__(LS_KB) void k_genodist_summary(const double* __rest
       if (d >= 0 && d <= c) acc += ps[(long long)(GD_F_HIST + d) * nt + T];
     }
   }
-  red[tid] = acc;
-  __syncthreads();
-  for (int d = LS_KB / 2; d; d >>= 1) {
-    if (tid < d) red[tid] += red[tid + d];
-    __syncthreads();
-  }
+  const double sum = ls_block_sum(red, acc);
   if (tid == 0) {
     double* o = out + (long long)s * len;
-    if (q == 0) o[0] = red[0];
-    else if (oi >= 0) { o[1 + oi * n + oj] = red[0]; o[1 + oj * n + oi] = red[0]; }
-    else o[1 + n * n + (q - 1 - n * (n + 1) / 2)] = red[0];
+    if (q == 0) o[0] = sum;
+    else if (oi >= 0) { o[1 + oi * n + oj] = sum; o[1 + oj * n + oi] = sum; }
+    else o[1 + n * n + (q - 1 - n * (n + 1) / 2)] = sum;
   }
 }
 

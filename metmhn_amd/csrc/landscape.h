@@ -21,7 +21,9 @@
 //   2. the backward substitution over the low bits in LDS, by popcount of the low part, descending, the low moves added in
 //      ascending bit.
 // So a state's sums run over the high bits ascending, then the low bits ascending.  A rate is computed once per move and
-// shared by the four values.
+// shared by the four values.  This is lattice.h's ls_tile_solve<4, 1, false> WRITTEN OUT: on the shared solve the kernel gave
+// the same bytes and the same instruction counts but 20.1 against 19.9 ms per LUAD-28 sweep in three rounds of three, more
+// than the parent's spread of 0.1 ms, so the one sweep that is bound by its stream keeps its own copy of the skeleton.
 //
 // LDS of a workgroup: 5 x 8 KiB (four values and the partial den of 2^10 states) + 16.5 KiB of rate tables + 2 KiB of
 // patterns + the tile's factors = 58.8 KiB, so two workgroups share a CU's 160 KiB and one streams its neighbour tiles

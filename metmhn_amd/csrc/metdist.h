@@ -17,19 +17,16 @@
 // Layout.  PLANAR: three vectors of 2^n doubles in the workspace, plane s of code x at V[s * 2^n + x], G0, GM, GC during
 // the sweep; k_metdist_tile turns them into Z, M, C in place once every level is finished - the layout of `full`.
 //
-// Shape.  k_genodist_level's: the tiles of lattice.h, a host-built list of tile numbers sorted by popcount, one launch of
-// k_metdist_level per popcount of the tile number, ASCENDING, ordered by stream order alone: no cooperative launch, no
-// flags, no atomics.  Inside a tile
-//   1. the high columns once: r = HF[j] TL[j] TH[j] is formed once per move, r exp(theta[j][n]) (the factor from a
-//      32-entry table in LDS) serves GM and GC; a held column pulls from the finished tile T - bit at the same offsets -
-//      consecutive lanes read consecutive addresses of all three planes - a free one adds to the partial L and Lm;
-//   2. the forward substitution over the low bits in LDS with orderpass.h's level walk; G0 of a state before its FM and
-//      FC, which take G0 sigma of the same state; |y| = popcount(T) + popcount(p); the tile is written out once.
+// Shape.  k_genodist_level's: lattice.h's tiling and its tile solve forwards, one launch of k_metdist_level per popcount
+// of the tile number, ASCENDING.  This file's own is the recursion (MetdistRecursion), with TWO rates per move: r = HF[j]
+// TL[j] TH[j] is formed once, r exp(theta[j][n]) (the factor from lattice.h's ls_seeded_factors, a 33-entry table in LDS)
+// serves GM, GC and Lm; G0 of a state before its FM and FC, which take G0 sigma of the same state; |y| = popcount(T) +
+// popcount(p).
 //
 // kappa0 is column n + 1 of the obs1 tables, as in genodist.h.  kappam needs the same column of obs2: the host launches
 // lattice.h's k_landscape_tables a SECOND time with obs2 in place of obs1 and a tile copies ONLY the clock column of
-// that second set (2 x 32 doubles) into LDS - no table kernel of its own; the second set's rate columns equal the first's
-// and are not read.
+// that second set (an LsColumn, 2 x 32 doubles) into LDS - no table kernel of its own; the second set's rate columns equal
+// the first's and are not read.
 //
 // LDS of a workgroup of k_metdist_level: 5 x 8 KiB (F0, FM, FC, the partial L and Lm of 2^10 states) + 16.5 KiB of rate
 // tables + 2 KiB of patterns + the tile's factors, exp(theta[j][n]) and the obs2 clock column: the landscape's footprint,
@@ -41,7 +38,7 @@
 //
 // Every shape depends on n alone: no byte of an output depends on the queries, the grid or an earlier call.  fp64 only.
 //
-// RESOURCES (gfx950, -O3, -Rpass-analysis=kernel-resource-usage): k_metdist_level 96 VGPRs, 0 AGPRs, 53 SGPRs, scratch 0,
+// RESOURCES (gfx950, -O3, -Rpass-analysis=kernel-resource-usage): k_metdist_level 82 VGPRs, 0 AGPRs, 52 SGPRs, scratch 0,
 // LDS 61 024 B, 2 waves / SIMD (two workgroups a CU, by LDS; the registers would allow 5); k_metdist_tile<true> 40 VGPRs,
 // 54 SGPRs, scratch 0, LDS 51 712 B, 3 waves / SIMD; k_metdist_tile<false> 26 VGPRs, 48 SGPRs, scratch 0, LDS 1 024 B.
 // (k_genodist_tile<true>, the other caller of gd_tile_fold: 36 VGPRs, 50 SGPRs, scratch 0, LDS 51 200 B - the 512 B between
@@ -50,6 +47,39 @@
 #include "genodist.h"
 
 namespace mmhn {
+
+// the recursion of F0 / FM / FC: two rates per move, lambda_j for F0 and L, mu_j for FM, FC and Lm; G0 of a state before its
+// FM and FC, which take G0 sigma of the same state; |y| = popcount(T) + popcount(p)
+struct MetdistRecursion : LsRecursion {
+  const LsTables& S;
+  const double (&HF)[LS_COLS];
+  const double (&EM)[ORD_MAXN + 1];
+  LsColumn MC;
+  int n;
+  uint32_t T;
+  int pcT;
+  double km;
+  __device__ __forceinline__ double column(int j) const { return EM[j]; }
+  __device__ __forceinline__ void rates(double r, double em, double (&rt)[2]) const { rt[0] = r; rt[1] = r * em; }
+  __device__ __forceinline__ void move(double (&f)[3], const double (&rt)[2], const double (&v)[3]) const {
+    f[0] += rt[0] * v[0];
+    f[1] += rt[1] * v[1];
+    f[2] += rt[1] * v[2];
+  }
+  __device__ __forceinline__ void source(uint32_t p, double (&f)[3]) const {
+    if (T == 0u && p == 0u) f[0] = 1.0;         // F0 of the empty genotype
+  }
+  __device__ __forceinline__ void finish(uint32_t p, uint32_t lo, uint32_t hi, double (&f)[3], const double (&L)[2]) const {
+    const double sig = ls_rate(S, HF[n], n, lo, hi);
+    const double kap = ls_rate(S, HF[n + 1], n + 1, lo, hi);
+    const double g0 = f[0] / (L[0] + sig + kap);
+    const double seeded = g0 * sig;
+    const double denm = L[1] + MC.at(km, lo, hi);
+    f[0] = g0;
+    f[1] = (seeded + f[1]) / denm;
+    f[2] = (seeded * (double)(pcT + __builtin_popcount(p)) + f[2]) / denm;
+  }
+};
 
 // one level of tiles: workgroup b finishes the tile tiles[b]; every tile tiles[b] - bit is finished (earlier launches).
 // tabs: the tables of (theta, obs1); tabm: the tables of (theta, obs2), of which only the clock column is read
@@ -60,96 +90,20 @@ __global__ __launch_bounds__(LS_KB) void k_metdist_level(const LsTables* __restr
   __shared__ LsTables S;
   __shared__ double HF[LS_COLS];                // column j: exp(diagonal + the effects of the tile's high bits)
   __shared__ double EM[ORD_MAXN + 1];           // exp(theta[j][n]): mu_j = lambda_j EM[j]
-  __shared__ double ML[1 << LS_HALF], MH[1 << LS_HALF];   // the clock column of the obs2 tables
-  __shared__ double KM;                         // exp(obs2[n] + the obs2 of the tile's high bits)
+  __shared__ double ML[1 << LS_HALF], MH[1 << LS_HALF];
+  const LsColumn MC{ML, MH};                    // the clock column of the obs2 tables
+  __shared__ double KM;                         // its factor of the tile, with exp(obs2[n])
   __shared__ double W[5][1 << LS_TILE_BITS];    // 0 / 1 / 2: F0 / FM / FC of the tile's states (partial until a state is finished, then G), 3 / 4: its partial L / Lm
   const int tid = threadIdx.x, n = N - 1;
   const uint32_t T = tiles[blockIdx.x];
-  const uint32_t Vt = 1u << c;
-  const long long plane = 1ll << n, base = (long long)T << c;
+  const long long plane = 1ll << n;
   ls_tile_prologue(S, HF, tabs, g_lt, g_o1, N, c, T);
-  if (tid < (1 << LS_HALF)) {
-    ML[tid] = tabm->TL[n + 1][tid]; MH[tid] = tabm->TH[n + 1][tid];
-    EM[tid] = tid < n ? exp(g_lt[tid * N + n]) : 0.0;
-  }
-  if (tid == LS_KB - 1) {
-    double v = g_o2[n];
-    for (uint32_t m = T; m; m &= m - 1) v += g_o2[c + __builtin_ctz(m)];
-    KM = exp(v);
-  }
+  ls_seeded_factors(EM, g_lt, N, true);
+  MC.load(tabm, n + 1);
+  if (tid == LS_KB - 1) KM = LsColumn::factor(g_o2, g_o2[n], c, T);
   __syncthreads();
-
-  // 1. the columns of the high bits: a held one is the move pulled from the tile T - bit, a free one a term of L and Lm
-  {
-    double a0[LS_SPT], a1[LS_SPT], a2[LS_SPT], dn[LS_SPT], dm[LS_SPT];
-#pragma unroll
-    for (int s = 0; s < LS_SPT; ++s) a0[s] = a1[s] = a2[s] = dn[s] = dm[s] = 0.0;
-    for (int j = c; j < n; ++j) {
-      const bool held = (T >> (j - c)) & 1u;
-      const double hf = HF[j], em = EM[j];
-      const double* q = held ? V + base - (1ll << j) : V;
-#pragma unroll
-      for (int s = 0; s < LS_SPT; ++s) {
-        const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
-        if (p < Vt) {
-          const double r = ls_rate(S, hf, j, p & 31u, p >> LS_HALF);
-          const double rm = r * em;
-          if (held) {
-            a0[s] += r * q[p];
-            a1[s] += rm * q[plane + p];
-            a2[s] += rm * q[2 * plane + p];
-          } else {
-            dn[s] += r;
-            dm[s] += rm;
-          }
-        }
-      }
-    }
-    if (T == 0u && tid == 0) a0[0] = 1.0;         // F0 of the empty genotype
-#pragma unroll
-    for (int s = 0; s < LS_SPT; ++s) {
-      const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
-      if (p < Vt) { W[0][p] = a0[s]; W[1][p] = a1[s]; W[2][p] = a2[s]; W[3][p] = dn[s]; W[4][p] = dm[s]; }
-    }
-  }
-  __syncthreads();
-
-  // 2. the forward substitution over the low bits
-  const uint32_t chunks = Vt >> S.L.c;
-  const int pcT = __builtin_popcount(T);
-  const double km = KM;
-  for (int lev = 0; lev <= c; ++lev) {
-    opo_level<LS_KB>(S.L, 0u, chunks, lev, [&](uint32_t p) {
-      const uint32_t lo = p & 31u, hi = p >> LS_HALF;
-      double f0 = W[0][p], fm = W[1][p], fc = W[2][p], L = W[3][p], Lm = W[4][p];
-#pragma unroll
-      for (int j = 0; j < LS_TILE_BITS; ++j) {
-        if (j < c) {
-          const double r = ls_rate(S, HF[j], j, lo, hi);
-          const double rm = r * EM[j];
-          if ((p >> j) & 1u) {
-            const uint32_t y = p ^ (1u << j);
-            f0 += r * W[0][y];
-            fm += rm * W[1][y];
-            fc += rm * W[2][y];
-          } else {
-            L += r;
-            Lm += rm;
-          }
-        }
-      }
-      const double sig = ls_rate(S, HF[n], n, lo, hi);
-      const double kap = ls_rate(S, HF[n + 1], n + 1, lo, hi);
-      const double g0 = f0 / (L + sig + kap);
-      const double seeded = g0 * sig;
-      const double denm = Lm + km * ML[lo] * MH[hi];
-      W[0][p] = g0;
-      W[1][p] = (seeded + fm) / denm;
-      W[2][p] = (seeded * (double)(pcT + __builtin_popcount(p)) + fc) / denm;
-    });
-    __syncthreads();
-  }
-  ls_write_tile<3>(W, Vt, V, base, plane);
+  ls_tile_solve<3, 2, true>(MetdistRecursion{{}, S, HF, EM, MC, n, T, __builtin_popcount(T), KM}, S, HF, W, n, c, T, V, plane);
+  ls_write_tile<3>(W, 1u << c, V, (long long)T << c, plane);
 }
 
 // every tile once all levels are finished (workgroup = tile number): G to Z = sigma G0, M = kappam GM, C = kappam GC in
@@ -159,21 +113,14 @@ __global__ __launch_bounds__(LS_KB) void k_metdist_tile(const LsTables* __restri
                                                         const double* __restrict__ g_lt, const double* __restrict__ g_o2,
                                                         int N, int c, double* V, double* __restrict__ part, long long nt) {
   __shared__ double SL[1 << LS_HALF], SH[1 << LS_HALF], ML[1 << LS_HALF], MH[1 << LS_HALF];
+  const LsColumn SC{SL, SH}, MC{ML, MH};        // sigma; the clock column of the obs2 tables
   const int tid = threadIdx.x, n = N - 1;
   const uint32_t T = blockIdx.x;
   const uint32_t Vt = 1u << c;
   const long long plane = 1ll << n, base = (long long)T << c;
-  if (tid < (1 << LS_HALF)) {
-    SL[tid] = tabs->TL[n][tid]; SH[tid] = tabs->TH[n][tid];
-    ML[tid] = tabm->TL[n + 1][tid]; MH[tid] = tabm->TH[n + 1][tid];
-  }
-  double vs = g_lt[n * N + n], vm = g_o2[n];    // (k_metdist_level's HF[n] and KM)
-  for (uint32_t m = T; m; m &= m - 1) {
-    const int i = c + __builtin_ctz(m);
-    vs += g_lt[n * N + i];
-    vm += g_o2[i];
-  }
-  const double sf = exp(vs), km = exp(vm);
+  SC.load(tabs, n);
+  MC.load(tabm, n + 1);
+  const double sf = LsColumn::factor(g_lt + n * N, g_lt[n * N + n], c, T), km = LsColumn::factor(g_o2, g_o2[n], c, T);
   __syncthreads();
   double u[LS_SPT], w[LS_SPT];
 #pragma unroll
@@ -182,8 +129,8 @@ __global__ __launch_bounds__(LS_KB) void k_metdist_tile(const LsTables* __restri
     u[s] = w[s] = 0.0;
     if (p < Vt) {
       const uint32_t lo = p & 31u, hi = p >> LS_HALF;
-      const double sig = sf * SL[lo] * SH[hi];
-      const double kap = km * ML[lo] * MH[hi];
+      const double sig = SC.at(sf, lo, hi);
+      const double kap = MC.at(km, lo, hi);
       double* o = V + base + p;
       u[s] = sig * o[0];
       w[s] = kap * o[plane];

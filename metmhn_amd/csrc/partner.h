@@ -21,22 +21,22 @@
 // Shape, per query, on lattice.h's tiling and by stream order alone (no cooperative launch, no flags, no atomics).  ql /
 // qh are the low c and the high bits of q; the RESTRICTED tiles are the 2^popcount(qh) tile numbers that are subsets of
 // qh, a host-built list sorted by popcount that the first two passes walk in opposite directions.
-//   1. k_partner_back, restricted tiles, levels DESCENDING: B into plane 0 - landscape.h's shape with one value.  A tile adds
-//      the moves along the free high bits (all of them to den, the ones q holds pulled from the finished tile T | bit at the
-//      same offsets), then substitutes backwards over the low bits; states whose low bits are not a subset of ql are 0.
-//   2. k_partner_seed, restricted tiles, levels ASCENDING: genodist.h's F0 / G0 on the subsets of q, G0 to plane 1, and
-//      plane 0 from B to W = sigma G0 B in place.
-//   3. k_partner_level, EVERY tile, levels ascending: metdist.h's FM recursion alone with the partner chain's rates and
-//      clock into plane 1.  The source W is read only where tile and state are subsets of q - the masks are tested before
-//      the load, so plane 0 outside the sub-lattice is never read - and a tile overwrites the G0 it may hold only after its
-//      own pulls, which read finished tiles of F.
+// The three level kernels are lattice.h's tile solve with a recursion each.
+//   1. k_partner_back, restricted tiles, levels DESCENDING: B into plane 0.  Every free bit is a term of den, only the ones
+//      q holds are pulled (from the finished tile T | bit); states whose low bits are not a subset of ql are 0.
+//   2. k_partner_seed, restricted tiles, levels ASCENDING: F0 / G0 on the subsets of q, pulled from and written to plane 1,
+//      and plane 0 from B to W = sigma G0 B in place.
+//   3. k_partner_level, EVERY tile, levels ascending: F / G with the partner chain's rates and clock into plane 1.  The
+//      source W is read only where tile and state are subsets of q - the masks are tested before the load, so plane 0
+//      outside the sub-lattice is never read - and a tile overwrites the G0 it may hold only after its own pulls, which
+//      read finished tiles of F.
 //   4. k_partner_tile, every tile: plane 1 times the partner's clock in place, and the GD_FEAT partial sums of founder and
 //      partner with genodist.h's gd_tile_fold.  The founder outside the sub-lattice is SUBSTITUTED BY MASK, not memset:
 //      the kernel folds an exact 0 there without reading plane 0 and, for the `full` output only (ZERO), stores the 0.
 //   5. k_genodist_summary, unchanged, when summaries are asked for; k_partner_values: `mass` = the sum over the tiles, in
-//      k_genodist_summary's order (thread t the tiles t, t + 256, ... ascending, a tree over the 256 threads), of the fold's
-//      tile masses of the partner plane - the same reduction and bytes as the summary's mass[1], formed whether or not
-//      summaries are asked for - and the two planes at the row's target.
+//      k_genodist_summary's order (thread t the tiles t, t + 256, ... ascending, then the one ls_block_sum both call), of the
+//      fold's tile masses of the partner plane - the summary's mass[1] by construction, formed whether or not summaries are
+//      asked for - and the two planes at the row's target.
 // The chain is a kernel parameter (PartnerChain), not a second copy: its tables (the rate columns are the same in both
 // sets, the clock column is obs1's or obs2's), its obs vector and whether a rate takes the factor exp(theta[j][n]).
 // Every rate comes in O(1) from the tile's factor and the two 32-entry tables.
@@ -49,7 +49,7 @@
 //
 // RESOURCES (gfx950, -O3, -Rpass-analysis=kernel-resource-usage): k_partner_back 64 VGPRs, 0 AGPRs, 76 SGPRs, scratch 0, LDS
 // 35 928 B, 4 waves / SIMD (four workgroups a CU, by LDS); k_partner_seed 46 VGPRs, 57 SGPRs, scratch 0, LDS 35 656 B, 4 waves
-// / SIMD; k_partner_level 66 VGPRs, 0 AGPRs, 50 SGPRs, scratch 0, LDS 35 928 B, 4 waves / SIMD; k_partner_tile<true> / <false>
+// / SIMD; k_partner_level 66 VGPRs, 0 AGPRs, 48 SGPRs, scratch 0, LDS 35 928 B, 4 waves / SIMD; k_partner_tile<true> / <false>
 // 34 VGPRs, 52 SGPRs, scratch 0, LDS 51 200 B, 3 waves / SIMD; k_partner_values 12 VGPRs, 26 SGPRs, scratch 0, LDS 2 048 B,
 // 8 waves / SIMD.  genodist.h has k_genodist_summary's, lattice.h the tables'.
 #pragma once
@@ -65,12 +65,37 @@ struct PartnerChain {
 };
 
 // what the kernels of a chain add to ls_tile_prologue, every thread: EM[j] the factor of rate j.  Returns exp(obs[n]).
-__device__ __forceinline__ double pt_chain_prologue(double (&EM)[ORD_MAXN + 1], const PartnerChain& ch,
-                                                    const double* __restrict__ g_lt, int N) {
-  const int tid = threadIdx.x, n = N - 1;
-  if (tid <= ORD_MAXN) EM[tid] = (tid < n && ch.met) ? exp(g_lt[tid * N + n]) : 1.0;
-  return exp(ch.obs[n]);
+__device__ __forceinline__ double pt_chain_prologue(LsTables& S, double (&HF)[LS_COLS], double (&EM)[ORD_MAXN + 1],
+                                                    const PartnerChain& ch, const double* __restrict__ g_lt, int N, int c,
+                                                    uint32_t T) {
+  ls_tile_prologue(S, HF, ch.tabs, g_lt, ch.obs, N, c, T);
+  ls_seeded_factors(EM, g_lt, N, ch.met != 0);
+  return exp(ch.obs[N - 1]);
 }
+
+// what the two recursions of a chain share: the one rate of a move is the chain's, its clock is column n + 1 times ek
+struct PartnerChainRecursion : LsRecursion {
+  const LsTables& S;
+  const double (&HF)[LS_COLS];
+  const double (&EM)[ORD_MAXN + 1];
+  int n;
+  double ek;
+  __device__ __forceinline__ double column(int j) const { return EM[j]; }
+  __device__ __forceinline__ void rates(double r, double em, double (&rt)[1]) const { rt[0] = r * em; }
+  __device__ __forceinline__ double clock(uint32_t lo, uint32_t hi) const { return ls_rate(S, HF[n + 1], n + 1, lo, hi) * ek; }
+};
+
+// B of the given chain: every free bit a term of den, the ones q holds pulled; 0 outside the subsets of q, the clock at q
+struct PartnerBackRecursion : PartnerChainRecursion {
+  uint32_t q, ql;
+  bool top;                                     // the tile of q
+  __device__ __forceinline__ bool pulls(int j) const { return (q >> j) & 1u; }
+  __device__ __forceinline__ bool live(uint32_t p) const { return !(p & ~ql); }
+  __device__ __forceinline__ void finish(uint32_t p, uint32_t lo, uint32_t hi, double (&f)[1], const double (&L)[1]) const {
+    const double kap = clock(lo, hi);
+    f[0] = ((top && p == ql) ? kap : f[0]) / (L[0] + kap);
+  }
+};
 
 // 1. one level of restricted tiles, descending: workgroup b finishes B of the tile tiles[b] (a subset of q's high bits);
 // every tile tiles[b] | bit with the bit in q is finished (earlier launches)
@@ -80,66 +105,29 @@ __global__ __launch_bounds__(LS_KB) void k_partner_back(PartnerChain ch, const u
   __shared__ double HF[LS_COLS];
   __shared__ double EM[ORD_MAXN + 1];
   __shared__ double W[2][1 << LS_TILE_BITS];    // 0: B of the tile's states (partial sums until a state is finished), 1: its partial den
-  const int tid = threadIdx.x, n = N - 1;
+  const int n = N - 1;
   const uint32_t T = tiles[blockIdx.x];
-  const uint32_t Vt = 1u << c, ql = q & (Vt - 1u), qh = q >> c;
-  const long long base = (long long)T << c;
-  ls_tile_prologue(S, HF, ch.tabs, g_lt, ch.obs, N, c, T);
-  const double ek = pt_chain_prologue(EM, ch, g_lt, N);
+  const uint32_t Vt = 1u << c, ql = q & (Vt - 1u);
+  const double ek = pt_chain_prologue(S, HF, EM, ch, g_lt, N, c, T);
   __syncthreads();
-
-  // 1. the moves along the free high bits: every one a term of den, the ones q holds pulled from the tile T | bit
-  {
-    double a[LS_SPT], dn[LS_SPT];
-#pragma unroll
-    for (int s = 0; s < LS_SPT; ++s) a[s] = dn[s] = 0.0;
-    for (int j = c; j < n; ++j) {
-      if ((T >> (j - c)) & 1u) continue;
-      const bool pull = (qh >> (j - c)) & 1u;
-      const double hf = HF[j], em = EM[j];
-      const double* v = V + base + (1ll << j);
-#pragma unroll
-      for (int s = 0; s < LS_SPT; ++s) {
-        const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
-        if (p < Vt) {
-          const double rm = ls_rate(S, hf, j, p & 31u, p >> LS_HALF) * em;
-          if (pull) a[s] += rm * v[p];
-          dn[s] += rm;
-        }
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < LS_SPT; ++s) {
-      const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
-      if (p < Vt) { W[0][p] = a[s]; W[1][p] = dn[s]; }
-    }
-  }
-  __syncthreads();
-
-  // 2. the backward substitution over the low bits; a state outside the sub-lattice is 0
-  const uint32_t chunks = Vt >> S.L.c;
-  const bool top = T == qh;
-  for (int lev = c; lev >= 0; --lev) {
-    opo_level<LS_KB>(S.L, 0u, chunks, lev, [&](uint32_t p) {
-      if (p & ~ql) { W[0][p] = 0.0; return; }
-      const uint32_t lo = p & 31u, hi = p >> LS_HALF;
-      double num = W[0][p], den = W[1][p];
-#pragma unroll
-      for (int j = 0; j < LS_TILE_BITS; ++j) {
-        if (j < c && !((p >> j) & 1u)) {
-          const double rm = ls_rate(S, HF[j], j, lo, hi) * EM[j];
-          if ((ql >> j) & 1u) num += rm * W[0][p | (1u << j)];
-          den += rm;
-        }
-      }
-      const double kap = ls_rate(S, HF[n + 1], n + 1, lo, hi) * ek;
-      den += kap;
-      W[0][p] = ((top && p == ql) ? kap : num) / den;
-    });
-    __syncthreads();
-  }
-  ls_write_tile<1>(W, Vt, V, base, 1ll << n);
+  ls_tile_solve<1, 1, false>(PartnerBackRecursion{{{}, S, HF, EM, n, ek}, q, ql, T == q >> c}, S, HF, W, n, c, T, V, 0);
+  ls_write_tile<1>(W, Vt, V, (long long)T << c, 1ll << n);
 }
+
+// F0 / G0 on the subsets of q
+struct PartnerSeedRecursion : LsRecursion {
+  const LsTables& S;
+  const double (&HF)[LS_COLS];
+  int n;
+  uint32_t T, ql;
+  __device__ __forceinline__ void source(uint32_t p, double (&f)[1]) const {
+    if (T == 0u && p == 0u) f[0] = 1.0;         // F0 of the empty genotype
+  }
+  __device__ __forceinline__ bool live(uint32_t p) const { return !(p & ~ql); }
+  __device__ __forceinline__ void finish(uint32_t, uint32_t lo, uint32_t hi, double (&f)[1], const double (&L)[1]) const {
+    f[0] = f[0] / (L[0] + ls_rate(S, HF[n], n, lo, hi) + ls_rate(S, HF[n + 1], n + 1, lo, hi));
+  }
+};
 
 // 2. one level of restricted tiles, ascending: G0 of the tile tiles[b] into plane 1 and plane 0 from B to W = sigma G0 B;
 // every tile tiles[b] - bit is finished (earlier launches).  tabs: the tables of (theta, obs1)
@@ -155,54 +143,7 @@ __global__ __launch_bounds__(LS_KB) void k_partner_seed(const LsTables* __restri
   const long long plane = 1ll << n, base = (long long)T << c;
   ls_tile_prologue(S, HF, tabs, g_lt, g_o1, N, c, T);
   __syncthreads();
-
-  // 1. the columns of the high bits: a held one is the move pulled from the tile T - bit, a free one a term of L
-  {
-    double a0[LS_SPT], dn[LS_SPT];
-#pragma unroll
-    for (int s = 0; s < LS_SPT; ++s) a0[s] = dn[s] = 0.0;
-    for (int j = c; j < n; ++j) {
-      const bool held = (T >> (j - c)) & 1u;
-      const double hf = HF[j];
-      const double* v = held ? V + plane + base - (1ll << j) : V;
-#pragma unroll
-      for (int s = 0; s < LS_SPT; ++s) {
-        const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
-        if (p < Vt) {
-          const double r = ls_rate(S, hf, j, p & 31u, p >> LS_HALF);
-          if (held) a0[s] += r * v[p];
-          else dn[s] += r;
-        }
-      }
-    }
-    if (T == 0u && tid == 0) a0[0] = 1.0;         // F0 of the empty genotype
-#pragma unroll
-    for (int s = 0; s < LS_SPT; ++s) {
-      const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
-      if (p < Vt) { W[0][p] = a0[s]; W[1][p] = dn[s]; }
-    }
-  }
-  __syncthreads();
-
-  // 2. the forward substitution over the low bits, on the subsets of ql
-  const uint32_t chunks = Vt >> S.L.c;
-  for (int lev = 0; lev <= c; ++lev) {
-    opo_level<LS_KB>(S.L, 0u, chunks, lev, [&](uint32_t p) {
-      if (p & ~ql) { W[0][p] = 0.0; return; }
-      const uint32_t lo = p & 31u, hi = p >> LS_HALF;
-      double f0 = W[0][p], L = W[1][p];
-#pragma unroll
-      for (int j = 0; j < LS_TILE_BITS; ++j) {
-        if (j < c) {
-          const double r = ls_rate(S, HF[j], j, lo, hi);
-          if ((p >> j) & 1u) f0 += r * W[0][p ^ (1u << j)];
-          else L += r;
-        }
-      }
-      W[0][p] = f0 / (L + ls_rate(S, HF[n], n, lo, hi) + ls_rate(S, HF[n + 1], n + 1, lo, hi));
-    });
-    __syncthreads();
-  }
+  ls_tile_solve<1, 1, true>(PartnerSeedRecursion{{}, S, HF, n, T, ql}, S, HF, W, n, c, T, V + plane, 0);   // G0 lives in plane 1
   for (uint32_t p = tid; p < Vt; p += LS_KB) {
     double* o = V + base + p;
     const double g0 = W[0][p];
@@ -210,6 +151,19 @@ __global__ __launch_bounds__(LS_KB) void k_partner_seed(const LsTables* __restri
     o[plane] = g0;
   }
 }
+
+// F / G of the partner chain; the source W is read only where tile and state are subsets of q, the masks tested before the load
+struct PartnerLevelRecursion : PartnerChainRecursion {
+  const double* src;                            // plane 0 of the tile
+  bool sub;                                     // the tile is a subset of q's high bits
+  uint32_t ql;
+  __device__ __forceinline__ void source(uint32_t p, double (&f)[1]) const {
+    if (sub && !(p & ~ql)) f[0] = src[p];
+  }
+  __device__ __forceinline__ void finish(uint32_t, uint32_t lo, uint32_t hi, double (&f)[1], const double (&L)[1]) const {
+    f[0] = f[0] / (L[0] + clock(lo, hi));
+  }
+};
 
 // 3. one level of ALL tiles, ascending: workgroup b finishes G = F / den of the partner chain in plane 1 of the tile tiles[b];
 // every tile tiles[b] - bit is finished (earlier launches).  The source W (plane 0) is read on the subsets of q only
@@ -219,64 +173,14 @@ __global__ __launch_bounds__(LS_KB) void k_partner_level(PartnerChain ch, const 
   __shared__ double HF[LS_COLS];
   __shared__ double EM[ORD_MAXN + 1];
   __shared__ double W[2][1 << LS_TILE_BITS];    // 0: F of the tile's states (partial until a state is finished, then G), 1: its partial L
-  const int tid = threadIdx.x, n = N - 1;
+  const int n = N - 1;
   const uint32_t T = tiles[blockIdx.x];
   const uint32_t Vt = 1u << c, ql = q & (Vt - 1u), qh = q >> c;
   const long long plane = 1ll << n, base = (long long)T << c;
-  ls_tile_prologue(S, HF, ch.tabs, g_lt, ch.obs, N, c, T);
-  const double ek = pt_chain_prologue(EM, ch, g_lt, N);
+  const double ek = pt_chain_prologue(S, HF, EM, ch, g_lt, N, c, T);
   __syncthreads();
-
-  // 1. the source, then the columns of the high bits: a held one pulled from the tile T - bit, a free one a term of L
-  {
-    const bool sub = (T & ~qh) == 0u;
-    double a[LS_SPT], dn[LS_SPT];
-#pragma unroll
-    for (int s = 0; s < LS_SPT; ++s) {
-      const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
-      dn[s] = 0.0;
-      a[s] = (sub && p < Vt && !(p & ~ql)) ? V[base + p] : 0.0;
-    }
-    for (int j = c; j < n; ++j) {
-      const bool held = (T >> (j - c)) & 1u;
-      const double hf = HF[j], em = EM[j];
-      const double* v = held ? V + plane + base - (1ll << j) : V;
-#pragma unroll
-      for (int s = 0; s < LS_SPT; ++s) {
-        const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
-        if (p < Vt) {
-          const double rm = ls_rate(S, hf, j, p & 31u, p >> LS_HALF) * em;
-          if (held) a[s] += rm * v[p];
-          else dn[s] += rm;
-        }
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < LS_SPT; ++s) {
-      const uint32_t p = (uint32_t)tid + (uint32_t)s * LS_KB;
-      if (p < Vt) { W[0][p] = a[s]; W[1][p] = dn[s]; }
-    }
-  }
-  __syncthreads();
-
-  // 2. the forward substitution over the low bits
-  const uint32_t chunks = Vt >> S.L.c;
-  for (int lev = 0; lev <= c; ++lev) {
-    opo_level<LS_KB>(S.L, 0u, chunks, lev, [&](uint32_t p) {
-      const uint32_t lo = p & 31u, hi = p >> LS_HALF;
-      double f = W[0][p], L = W[1][p];
-#pragma unroll
-      for (int j = 0; j < LS_TILE_BITS; ++j) {
-        if (j < c) {
-          const double rm = ls_rate(S, HF[j], j, lo, hi) * EM[j];
-          if ((p >> j) & 1u) f += rm * W[0][p ^ (1u << j)];
-          else L += rm;
-        }
-      }
-      W[0][p] = f / (L + ls_rate(S, HF[n + 1], n + 1, lo, hi) * ek);
-    });
-    __syncthreads();
-  }
+  ls_tile_solve<1, 1, true>(PartnerLevelRecursion{{{}, S, HF, EM, n, ek}, V + base, (T & ~qh) == 0u, ql}, S, HF, W, n, c, T,
+                            V + plane, 0);
   ls_write_tile<1>(W, Vt, V + plane, base, plane);
 }
 
@@ -287,14 +191,13 @@ template <bool ZERO>
 __global__ __launch_bounds__(LS_KB) void k_partner_tile(PartnerChain ch, int N, int c, uint32_t q, double* V,
                                                         double* __restrict__ part, long long nt) {
   __shared__ double KL[1 << LS_HALF], KH[1 << LS_HALF];
+  const LsColumn KC{KL, KH};                    // the chain's clock
   const int tid = threadIdx.x, n = N - 1;
   const uint32_t T = blockIdx.x;
   const uint32_t Vt = 1u << c, ql = q & (Vt - 1u), qh = q >> c;
   const long long plane = 1ll << n, base = (long long)T << c;
-  if (tid < (1 << LS_HALF)) { KL[tid] = ch.tabs->TL[n + 1][tid]; KH[tid] = ch.tabs->TH[n + 1][tid]; }
-  double v = 0.0;
-  for (uint32_t m = T; m; m &= m - 1) v += ch.obs[c + __builtin_ctz(m)];
-  const double k0 = exp(v), ek = exp(ch.obs[n]);  // (k_partner_level's HF[n + 1] and ek)
+  KC.load(ch.tabs, n + 1);
+  const double k0 = LsColumn::factor(ch.obs, 0.0, c, T), ek = exp(ch.obs[n]);
   const bool sub = (T & ~qh) == 0u;
   __syncthreads();
   double u[LS_SPT], w[LS_SPT];
@@ -306,7 +209,7 @@ __global__ __launch_bounds__(LS_KB) void k_partner_tile(PartnerChain ch, int N, 
       double* o = V + base + p;
       if (sub && !(p & ~ql)) u[s] = o[0];
       else if constexpr (ZERO) o[0] = 0.0;
-      w[s] = (k0 * KL[p & 31u] * KH[p >> LS_HALF] * ek) * o[plane];
+      w[s] = (KC.at(k0, p & 31u, p >> LS_HALF) * ek) * o[plane];
       o[plane] = w[s];
     }
   }
@@ -323,16 +226,11 @@ __global__ __launch_bounds__(LS_KB) void k_partner_values(const double* __restri
   const double* pc = part + (long long)GD_FEAT * nt;
   double acc = 0.0;
   for (long long T = tid; T < nt; T += LS_KB) acc += pc[T];
-  red[tid] = acc;
-  __syncthreads();
-  for (int d = LS_KB / 2; d; d >>= 1) {
-    if (tid < d) red[tid] += red[tid + d];
-    __syncthreads();
-  }
+  const double mass = ls_block_sum(red, acc);
   if (tid == 0) {
     const long long i = first + blockIdx.x;
     double* o = out + 3 * i;
-    o[0] = red[0];
+    o[0] = mass;
     o[1] = o[2] = __builtin_nan("");
     if (targets) {
       const uint32_t t = targets[i];

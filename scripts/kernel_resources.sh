@@ -9,7 +9,7 @@ cur=None;rows={}
 for l in sys.stdin:
     m=re.search(r'Function Name: (\S+)',l)
     if m: cur=m.group(1); rows[cur]={}; continue
-    m=re.search(r'remark: .*?\s+(VGPRs|AGPRs|SGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)',l)
+    m=re.search(r'remark: .*?\s+(?:Total)?(VGPRs|AGPRs|SGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)',l)
     if m and cur: rows[cur][m.group(1).split()[0]]=int(m.group(2))
 import subprocess
 for k,v in rows.items():
