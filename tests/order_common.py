@@ -584,3 +584,89 @@ def check_too_large_rows_get_the_host_value(e, monkeypatch):
         np.testing.assert_array_equal(getattr(got, name)[0], getattr(host, name))
         np.testing.assert_array_equal(getattr(got, name)[1:], getattr(ref, name)[1:])
     return mod, dat, ref, raw, host
+
+
+# ---------------------------------------------------------------------------------------------------- device against host
+# What the tests of one entry point and tests/test_limits.py (the same entry points at n = 31) both use.
+BAR = 1e-12                       # device against host (tests/test_order_posteriors.py derives it)
+MARGIN = 1e-9                     # a sample whose closest draw is nearer than this to a boundary is not compared
+MAX_EXCLUDED = 1e-3               # share of one test's samples that may be set aside
+
+
+def same_or_tie(mod, row, got, want, rel=1e-12):
+    """(order, probability) of the device against the host's: the same probability, and the same order or one as likely."""
+    (go, gp), (wo, wp) = got, want
+    assert abs(gp - wp) <= rel * wp, (row, gp, wp)
+    if go != wo:                                               # a tie: the device's order is as likely as the host's
+        _, status, first = Row(row, mod.n).call()
+        assert abs(mod.likelihood(go, status, first) - wp) <= rel * wp, (row, go, wo)
+
+
+def worst_entry(d):
+    """Largest entry of d, the NaN ones (NaN in both operands, which the callers assert first) left out."""
+    d = np.asarray(d, dtype=float)
+    return float(np.max(np.where(np.isnan(d), 0.0, d), initial=0.0))
+
+
+def last_observation(obs):
+    """The last observation time of rows of obs [..., 2]."""
+    return np.where(np.isnan(obs[..., 1]), obs[..., 0], obs[..., 1])
+
+
+def times_diff(got, want):
+    """order_times: (relative difference of the evidence, worst difference of time and obs over the last observation time,
+    absolute difference of pt_first - 0 where both are NaN); the NaN patterns are asserted equal."""
+    np.testing.assert_array_equal(np.isnan(got.time), np.isnan(want.time))
+    np.testing.assert_array_equal(np.isnan(got.obs), np.isnan(want.obs))
+    np.testing.assert_array_equal(np.isnan(got.pt_first), np.isnan(want.pt_first))
+    zg, zw = np.exp(got.log_evidence), np.exp(want.log_evidence)
+    last = last_observation(np.asarray(want.obs))
+    d_t = worst_entry(np.abs(np.asarray(got.time) - want.time) / last[..., None])
+    d_o = worst_entry(np.abs(np.asarray(got.obs) - want.obs) / last[..., None])
+    d_p = worst_entry(np.abs(np.asarray(got.pt_first, dtype=float) - want.pt_first))
+    return float(np.max(np.abs(zg - zw) / zw)), max(d_t, d_o), d_p
+
+
+def times_orderings(time, obs, dat, n):
+    """order_times: worst violation, over the last observation time, of: seeding <= first observation <= second observation;
+    a code of one tumour alone >= the seeding (paired rows); every time <= the last observation."""
+    worst = 0.0
+    for i, r in enumerate(dat):
+        w = Row(r, n)
+        last = last_observation(obs[i])
+        gaps = [t - last for t in time[i, w.codes]]
+        if r[2 * n]:
+            gaps.append(time[i, 2 * n] - obs[i, 0])
+        if w.typ == 3:
+            gaps.append(obs[i, 0] - obs[i, 1])
+            both = set(w.lineages["pt"]) & set(c - 1 for c in w.lineages["mt"])
+            gaps += [time[i, 2 * n] - time[i, c] for c in w.codes if c != 2 * n and c - c % 2 not in both]
+        worst = max([worst] + [g / last for g in gaps])
+    return worst
+
+
+def snapshots_diff(got, want):
+    """order_snapshots: (relative difference of the evidence, worst absolute difference of held, of late, of map_prob); the
+    NaN patterns, map_first and map_state are asserted equal."""
+    for name in ("held", "late", "map_prob"):
+        np.testing.assert_array_equal(np.isnan(getattr(got, name)), np.isnan(getattr(want, name)), err_msg=name)
+    np.testing.assert_array_equal(got.map_first, want.map_first)
+    np.testing.assert_array_equal(got.map_state, want.map_state)
+    zg, zw = np.exp(got.log_evidence), np.exp(want.log_evidence)
+    return (float(np.max(np.abs(zg - zw) / zw)),) + tuple(
+        worst_entry(np.abs(np.asarray(getattr(got, name), dtype=float) - getattr(want, name))) for name in ("held", "late", "map_prob"))
+
+
+def snapshots_patterns(run, dat, n):
+    """order_snapshots: the NaN / -1 patterns of a device result: codes carried, paired rows."""
+    paired_rows = dat[:, -1] == 3
+    carried = np.zeros((len(dat), 2 * n + 1), dtype=bool)
+    for i, r in enumerate(dat):
+        if paired_rows[i]:
+            carried[i, Row(r, n).codes] = True
+    np.testing.assert_array_equal(~np.isnan(run.held), np.repeat(carried[:, None], 2, axis=1))
+    np.testing.assert_array_equal(~np.isnan(run.late), np.broadcast_to(paired_rows[:, None, None], run.late.shape))
+    np.testing.assert_array_equal(run.map_state >= 0, carried)
+    np.testing.assert_array_equal(run.map_first >= 0, paired_rows)
+    np.testing.assert_array_equal(~np.isnan(run.map_prob), paired_rows)
+    assert np.all(np.isfinite(run.log_evidence)), "log_evidence is not finite"

@@ -2,11 +2,12 @@
 declares; host logic (sharding, all-reduce combination, penalties, synthetic generators)."""
 import os
 import re
-import socket
 import sys
 
 import numpy as np
 import pytest
+
+from eval_common import free_port
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -90,14 +91,6 @@ def test_shard_rows_partition():
         assert loads.max() <= loads.mean() + cost.max() + 1e-9          # LPT bound
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _worker(rank, world, port, q):
     sys.path.insert(0, ROOT)
     import torch.distributed as dist
@@ -121,7 +114,7 @@ def test_two_rank_gloo_allreduce_reproduces_full_cohort(golden):
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -176,7 +169,7 @@ def test_two_rank_precombined_payload_fixed_order(golden):
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker_wsums, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -231,7 +224,7 @@ def test_communicator_setup_is_decided_through_the_store(case):
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker_comm_setup, args=(r, 2, port, q, case)) for r in range(2)]
     for p in procs:
         p.start()
@@ -295,7 +288,7 @@ def test_fold_parallel_cross_val_two_ranks(golden):
     assert np.isfinite(ref).all() and len(np.unique(ref)) == ref.size
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_cv_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()

@@ -15,107 +15,17 @@ S_EM.)  Where S = 0 the bound is 0 and the comparison exact, as it is for the tw
 
 The bound presupposes that two patient_grads calls return the same bits; the GPU tests assert that first, and add the spread
 between the two calls, summed over the rows, to the bound (0 when the precondition holds)."""
-import math
 import os
 
 import numpy as np
 import pytest
 
-U = 2.0 ** -53
-RED_MAX_CHUNKS = 128            # csrc/assemble.h
+import reduction_common as RC
+from eval_common import engine_pool, free_port
+from reduction_common import (MULTI_BATCH, MULTI_BATCH_WS, PERC_MET, Reference, U, check_raw, check_wsums, raw_layout, raw_len, red_per, stride,
+                              wsums_layout)
+
 W = 0.37
-
-
-def red_per(npat):
-    """Rows per chunk of k_reduce_rows (csrc/assemble.h: red_per)."""
-    return max(32, (npat + RED_MAX_CHUNKS - 1) // RED_MAX_CHUNKS)
-
-
-def stride(N):
-    return 1 + N * N + 2 * N
-
-
-def raw_len(N):
-    return 4 + 2 * N * N + 3 * N
-
-
-# ---- the two layouts of include/metmhn_amd.h ---------------------------------------------------------------------------
-
-def raw_layout(em, nm, n_em, n_pat, N):
-    """[s_EM, s_NM, n_em, n_pat, G_EM, G_NM, p_EM, p_NM, m_EM] from two rows [lp, G, d_dp, d_dm] (mmhn_cohort_sums)."""
-    NN = N * N
-    return np.concatenate(([em[0], nm[0], n_em, n_pat], em[1:1 + NN], nm[1:1 + NN], em[1 + NN:1 + NN + N],
-                           nm[1 + NN:1 + NN + N], em[1 + NN + N:]))
-
-
-def wsums_layout(em, nm, w, N):
-    """[w s_EM + s_NM, w G_EM + G_NM, w p_EM + p_NM, w m_EM] (mmhn_cohort_wsums_begin / _end)."""
-    head = 1 + N * N + N
-    return np.concatenate((w * em[:head] + nm[:head], w * em[head:]))
-
-
-# ---- the reference and its bound -----------------------------------------------------------------------------------------
-
-def _colsum(a):
-    """Correctly rounded column sums of a [P, st] array."""
-    return np.array([math.fsum(c) for c in a.T]) if a.shape[0] else np.zeros(a.shape[1])
-
-
-class Reference:
-    """Exact per-class sums of the rows [P, st] of a cohort.  nm_rows: the rows of type 0 (all-zero rows among them);
-    n_seed: rows with the seeding event (sums[2]); spread (optional, [P, st]): |difference| of two downloads of the rows."""
-
-    def __init__(self, rows, nm_rows, n_seed, N, spread=None):
-        rows = np.asarray(rows, dtype=np.float64)
-        nm_rows = np.asarray(nm_rows, dtype=bool)
-        assert rows.shape == (nm_rows.shape[0], stride(N))
-        self.N, self.P, self.n_seed = N, rows.shape[0], float(n_seed)
-        self.p_em, self.p_nm = int((~nm_rows).sum()), int(nm_rows.sum())
-        self.em, self.nm = _colsum(rows[~nm_rows]), _colsum(rows[nm_rows])
-        self.abs_em, self.abs_nm = _colsum(np.abs(rows[~nm_rows])), _colsum(np.abs(rows[nm_rows]))
-        z = np.zeros(stride(N))
-        self.sp_em = z if spread is None else _colsum(spread[~nm_rows])
-        self.sp_nm = z if spread is None else _colsum(spread[nm_rows])
-
-    def raw(self):
-        """(reference, bound) of the mmhn_cohort_sums buffer; the bound of the two counts is 0."""
-        ref = raw_layout(self.em, self.nm, self.n_seed, float(self.P), self.N)
-        bound = raw_layout((self.p_em + 2) * U * self.abs_em + self.sp_em, (self.p_nm + 2) * U * self.abs_nm + self.sp_nm,
-                           0.0, 0.0, self.N)
-        return ref, bound
-
-    def wsums(self, w):
-        """(reference, bound) of the pre-combined buffer."""
-        ref = wsums_layout(self.em, self.nm, w, self.N)
-        bound = (self.P + 4) * U * wsums_layout(self.abs_em, self.abs_nm, abs(w), self.N) + \
-            wsums_layout(self.sp_em, self.sp_nm, abs(w), self.N)
-        return ref, bound
-
-
-def _within(got, ref, bound, what):
-    """Every element within its bound (exactly equal where the bound is 0, NaN never passes); the worst error / bound."""
-    got = np.asarray(got, dtype=np.float64)
-    assert got.shape == ref.shape, f"{what}: {got.shape} doubles, expected {ref.shape}"
-    err = np.abs(got - ref)
-    bad = np.flatnonzero(~(err <= bound))
-    assert bad.size == 0, (f"{what}: {bad.size} of {got.size} elements outside the bound, first at {bad[0]}: got {got[bad[0]]!r}, "
-                           f"reference {ref[bad[0]]!r}, error {err[bad[0]]:.3e}, bound {bound[bad[0]]:.3e}")
-    pos = bound > 0
-    return float((err[pos] / bound[pos]).max()) if pos.any() else 0.0
-
-
-def check_raw(got, reference, what="cohort_sums"):
-    return _within(got, *reference.raw(), what)
-
-
-def check_wsums(got_and_tail, reference, w, flag, what="cohort_wsums"):
-    """got_and_tail: the 1 + N^2 + 2N doubles and the slot behind them, which must hold the flag itself."""
-    got_and_tail = np.asarray(got_and_tail, dtype=np.float64)
-    st = stride(reference.N)
-    assert got_and_tail.shape == (st + 1,), f"{what}: {got_and_tail.shape}"
-    ratio = _within(got_and_tail[:st], *reference.wsums(w), what)
-    assert got_and_tail[st] == flag, f"{what}: the slot behind the buffer holds {got_and_tail[st]!r}, flag {flag!r}"
-    return ratio
 
 
 # ---- the kernels' order of additions, in float64 NumPy ------------------------------------------------------------------
@@ -175,8 +85,6 @@ def replay(rows, kinds, batches, N, mode, a, b, defect=None, before=None):
 SHAPES = [(4, P, "mixed") for P in (0, 1, 31, 32, 33, 4096, 4097)] + [(4, 33, "all_nm"), (4, 33, "all_em")] + \
          [(n, P, "mixed") for n in (14, 15) for P in (0, 33, 4097)]
 SHAPE_IDS = [f"n{n}-P{P}-{kind}" for n, P, kind in SHAPES]
-MULTI_BATCH = (4, 4097)                                       # in at least three batches
-MULTI_BATCH_WS = 1 << 20                                   # its workspace limit in bytes (test_multi_batch_reduction)
 
 
 def _random_rows(N, P, kind, seed):
@@ -246,118 +154,17 @@ def test_layouts_and_chunk_sizes():
 
 # ---- GPU: cohorts -----------------------------------------------------------------------------------------------------------
 
-PERC_MET = 0.3
-
-
-def _hand_rows(n):
-    """all-zero type 0; seeding-only rows of types 1, 2, 3 (diagnosis order 0); paired rows of orders 1 and 2 with one event each side."""
-    def row(pt, mt, seeding, order, typ):
-        r = np.zeros(2 * n + 3, dtype=np.int8)
-        r[[2 * j for j in pt]] = 1
-        r[[2 * j + 1 for j in mt]] = 1
-        r[2 * n], r[2 * n + 1], r[2 * n + 2] = seeding, order, typ
-        return r
-    return {"zero": row([], [], 0, -99, 0), "t1": row([], [], 1, -99, 1), "t2": row([], [], 1, -99, 2), "t3_o0": row([], [], 1, 0, 3),
-            "t3_o1": row([0], [1], 1, 1, 3), "t3_o2": row([1], [0, 2], 1, 2, 3)}
-
-
-MAX_PAIRED_EVENTS = 6
-
-
-def _few_events(dat):
-    """Paired rows keep their first MAX_PAIRED_EVENTS events: a joint space of up to 2^6 states beside the seeding bit is one
-    row of 64 states to k_pclass (csrc/classmarg.h), whose class-marginal entries one wave adds up.  With more, several
-    waves meet in the floating-point atomics of its flush and two evaluations of a row may differ in the last bit - the
-    reference rows would no longer be those of the evaluation under test."""
-    n = (dat.shape[1] - 3) // 2
-    for r in np.flatnonzero((dat[:, -1] == 3) & (dat[:, :2 * n].sum(axis=1) > MAX_PAIRED_EVENTS)):
-        dat[r, np.flatnonzero(dat[r, :2 * n])[MAX_PAIRED_EVENTS:]] = 0
-    return dat
-
-
-def _cohort(n, P, kind="mixed"):
-    """synthetic.mixed_cohort with few events per row (small spaces), the hand-written rows at its start, an order-1 paired row
-    as the last row of the first chunk and an all-zero row as the last row of the cohort."""
-    from metmhn_amd import synthetic
-    p_event = 0.25 if n <= 6 else 0.08
-    hand = _hand_rows(n)
-    if P == 0:
-        return np.zeros((0, 2 * n + 3), dtype=np.int8)
-    if P == 1:
-        return hand["t3_o1"][None, :].copy()
-    if kind != "mixed":
-        pool = synthetic.mixed_cohort(n, 40 * P, seed=P + n, p_event=p_event)
-        dat = _few_events(pool[(pool[:, -1] == 0) == (kind == "all_nm")][:P].copy())
-        assert dat.shape[0] == P
-        if kind == "all_nm":
-            dat[P - 1] = hand["zero"]
-        return dat
-    dat = _few_events(synthetic.mixed_cohort(n, P, seed=P + n, p_event=p_event))
-    for i, name in enumerate(("t1", "t2", "t3_o0", "t3_o2")):
-        dat[i] = hand[name]
-    dat[P - 1] = hand["zero"]
-    edge = min(red_per(P), P) - 1
-    dat[edge if edge < P - 1 else P - 2] = hand["t3_o1"]
-    assert (dat[:, -1] == 0).any() and all(((dat[:, -1] == 3) & (dat[:, -2] == o)).any() for o in (0, 1, 2))
-    return dat
-
-
-def _params(n):
-    from metmhn_amd import synthetic
-    return synthetic.random_params(n)
-
-
 @pytest.fixture(scope="module")
 def make_engine():
-    """Engines created under MMHN_POISON=1, kept for the module (at most four alive: the oldest is closed).  zerocopy=False:
-    MMHN_ZEROCOPY=0; comm=True: a one-rank communicator attached (the in-library all-reduce on a single GPU)."""
-    from metmhn_amd import Engine
-    from metmhn_amd.engine import unique_id
-    live = {}
-
-    def get(n, zerocopy=True, comm=False, dtype="f64", workspace=None, fresh=False):
-        key = (n, zerocopy, comm, dtype, workspace)
-        if fresh and key in live:
-            live.pop(key).close()
-        if key not in live:
-            while len(live) >= 4:
-                live.pop(next(iter(live))).close()
-            with pytest.MonkeyPatch.context() as mp:
-                mp.setenv("MMHN_POISON", "1")
-                if zerocopy:
-                    mp.delenv("MMHN_ZEROCOPY", raising=False)
-                else:
-                    mp.setenv("MMHN_ZEROCOPY", "0")
-                e = Engine(n, dtype=dtype, workspace_bytes=workspace)
-            if comm:
-                e.comm_init(unique_id(), 0, 1)
-            live[key] = e
-        live[key] = live.pop(key)                             # (most recently used last: a test's own engines are never the oldest)
-        return live[key]
-    yield get
-    for e in live.values():
-        e.close()
-
-
-def _rows_of(e, lt, dp, dm, with_grad=True):
-    """The engine's per-patient rows [P, st] = [lp, G, d_dp, d_dm] (with_grad=False: lp and zeros)."""
-    P, N = e.n_pat, e.N
-    if P == 0:
-        return np.zeros((0, stride(N)))
-    if not with_grad:
-        rows = np.zeros((P, stride(N)))
-        rows[:, 0] = e.patient_grads(lt, dp, dm, with_grad=False)
-        return rows
-    lp, g, gp, gm = e.patient_grads(lt, dp, dm)
-    return np.concatenate((lp[:, None], g.reshape(P, N * N), gp, gm), axis=1)
+    yield from engine_pool()
 
 
 def _references(e, dat, lt, dp, dm):
     """(reference of a gradient evaluation, reference of a score-only one, did two downloads agree bit for bit)."""
     nm_rows = dat[:, -1] == 0
     n_seed = float(dat[:, -3].sum())
-    r1, r2 = _rows_of(e, lt, dp, dm), _rows_of(e, lt, dp, dm)
-    s1, s2 = _rows_of(e, lt, dp, dm, False), _rows_of(e, lt, dp, dm, False)
+    r1, r2 = RC.rows_of(e, lt, dp, dm), RC.rows_of(e, lt, dp, dm)
+    s1, s2 = RC.rows_of(e, lt, dp, dm, False), RC.rows_of(e, lt, dp, dm, False)
     same = np.array_equal(r1, r2) and np.array_equal(s1, s2)
     assert np.isfinite(r1).all() and np.isfinite(s1).all()
     assert not r1[nm_rows][:, 1 + e.N * e.N + e.N:].any(), "a type-0 row has a d_dm entry: the raw layout has no slot for it"
@@ -409,12 +216,12 @@ def test_reduction_edges(make_engine, n, P, kind):
     MMHN_ZEROCOPY=0 and an attached one-rank communicator; the ABI's own combination against distributed.py's."""
     from metmhn_amd import distributed as D
     N = n + 1
-    lt, dp, dm = _params(n)
-    dat = _cohort(n, P, kind)
+    lt, dp, dm = RC.params(n)
+    dat = RC.cohort(n, P, kind)
     engines = {"default": make_engine(n), "zerocopy0": make_engine(n, zerocopy=False), "comm": make_engine(n, comm=True)}
     if P == 0:                                                # the handle held 33 rows and an evaluation of them before
         for e in engines.values():
-            e.set_cohort(_cohort(n, 33))
+            e.set_cohort(RC.cohort(n, 33))
             assert e.cohort_sums(lt, dp, dm)[3] == 33.0 and np.isfinite(_wsums(e, lt, dp, dm, W)).all()
     for e in engines.values():
         e.set_cohort(dat)
@@ -452,9 +259,9 @@ def test_reduction_edges(make_engine, n, P, kind):
 def test_empty_cohort_on_a_fresh_engine(make_engine):
     """k_pack_sums / k_pack_wsums on a handle that never held a row: zeros, zero counts, the flag behind the buffer."""
     n = 4
-    lt, dp, dm = _params(n)
+    lt, dp, dm = RC.params(n)
     e = make_engine(n, fresh=True)
-    e.set_cohort(_cohort(n, 0))
+    e.set_cohort(RC.cohort(n, 0))
     for grad in (True, False):
         assert not e.cohort_sums(lt, dp, dm, with_grad=grad).any()
         ws = _wsums(e, lt, dp, dm, W, with_grad=grad, flag=2.0)
@@ -470,8 +277,8 @@ def test_multi_batch_reduction(make_engine):
     rows before its footprint passes the limit, so the batches are at least the sum of these charges over the limit."""
     n, P = MULTI_BATCH
     N = n + 1
-    lt, dp, dm = _params(n)
-    dat = _cohort(n, P)
+    lt, dp, dm = RC.params(n)
+    dat = RC.cohort(n, P)
     all_zero = (dat[:, -1] == 0) & (dat[:, 0:2 * n + 1:2].sum(axis=1) == 0)
     charged = P * ((stride(N) + 1) * 8 + 2 * 8) + int((~all_zero).sum()) * ((N * N + 65) * 8 + 4 * 8)
     assert -(-charged // MULTI_BATCH_WS) >= 3
@@ -480,7 +287,7 @@ def test_multi_batch_reduction(make_engine):
     s, ws, _, _ = _evaluate_and_check(e, dat, lt, dp, dm, f"n={n} P={P} multi-batch")
     one = make_engine(n)                                      # one batch: another tree over the same rows
     one.set_cohort(dat)
-    ref = Reference(_rows_of(one, lt, dp, dm), dat[:, -1] == 0, float(dat[:, -3].sum()), n + 1)
+    ref = Reference(RC.rows_of(one, lt, dp, dm), dat[:, -1] == 0, float(dat[:, -3].sum()), n + 1)
     check_raw(s, ref, "multi-batch sums against the one-batch engine's rows")
     check_wsums(ws, ref, W, 0.0, "multi-batch wsums against the one-batch engine's rows")
 
@@ -490,8 +297,8 @@ def test_multi_batch_reduction(make_engine):
 def test_fp32_engine_reduction(make_engine, P):
     """The rows and the reduction are double in the fp32 engine too: the same bound against its own rows."""
     n = 4
-    lt, dp, dm = _params(n)
-    dat = _cohort(n, P)
+    lt, dp, dm = RC.params(n)
+    dat = RC.cohort(n, P)
     e = make_engine(n, dtype="f32")
     e.set_cohort(dat)
     _evaluate_and_check(e, dat, lt, dp, dm, f"n={n} P={P} fp32")
@@ -521,8 +328,8 @@ def _set_flag(e, value):
 def test_reduce_flag_rides_behind_the_weighted_buffer(make_engine, n, zerocopy, comm):
     """mmhn_set_reduce_flag / mmhn_get_reduce_flag: the value comes back from the weighted evaluation it was set for and from
     no other, leaves the buffer as it was, and a plain evaluation reads 0."""
-    lt, dp, dm = _params(n)
-    dat = _cohort(n, 33)
+    lt, dp, dm = RC.params(n)
+    dat = RC.cohort(n, 33)
     e = make_engine(n, zerocopy=zerocopy, comm=comm)
     e.set_cohort(dat)
     plain = _wsums(e, lt, dp, dm, W)
@@ -539,7 +346,7 @@ def test_reduce_flag_rides_behind_the_weighted_buffer(make_engine, n, zerocopy, 
     e.cohort_sums_begin(lt, dp, dm)
     e.cohort_sums_end()
     assert _get_flag(e) == 0.0                                # a plain evaluation has no flag
-    e.set_cohort(_cohort(n, 0))                               # k_pack_wsums
+    e.set_cohort(RC.cohort(n, 0))                               # k_pack_wsums
     empty = _wsums(e, lt, dp, dm, W, flag=4.0)
     assert empty[-1] == 4.0 and not empty[:-1].any()
     assert _wsums(e, lt, dp, dm, W)[-1] == 0.0
@@ -550,8 +357,8 @@ def test_reduce_flag_rides_behind_the_weighted_buffer(make_engine, n, zerocopy, 
 def test_reduce_flag_waits_for_the_next_weighted_evaluation(make_engine, n, zerocopy, comm):
     """include/metmhn_amd.h: the value "travels with the NEXT mmhn_cohort_wsums_begin" - a plain mmhn_cohort_sums and a
     mmhn_patient_grads in between, and a _begin refused while an evaluation is pending, leave it where it is."""
-    lt, dp, dm = _params(n)
-    dat = _cohort(n, 33)
+    lt, dp, dm = RC.params(n)
+    dat = RC.cohort(n, 33)
     e = make_engine(n, zerocopy=zerocopy, comm=comm)
     e.set_cohort(dat)
     plain = _wsums(e, lt, dp, dm, W)
@@ -653,11 +460,8 @@ def test_stale_cohort_on_one_of_two_ranks(stale_expected, reduce_mode, stale_ran
     """regularized_optimization._result with two ranks (gloo, both engines on device 0): the "edited in place" bit of one rank
     (or of both: the sum is 2) crosses in the evaluation's own all-reduce, both ranks rebuild their shard once and return
     the edited cohort's value."""
-    import socket
     import torch.multiprocessing as mp
-    with socket.socket() as sock:
-        sock.bind(("127.0.0.1", 0))
-        port = sock.getsockname()[1]
+    port = free_port()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     procs = [ctx.Process(target=_stale_worker, args=(r, 2, port, q, reduce_mode, stale_ranks)) for r in range(2)]

@@ -13,6 +13,9 @@ import warnings
 import numpy as np
 import pytest
 
+from eval_common import FP32_BAR, WINDOW_TOL, close, close_grads, close_to_largest, fp32_grads, paired, patient_grads, row, shape_rows, top_rows
+from order_common import BAR, MARGIN, MAX_EXCLUDED, same_or_tie, snapshots_diff, snapshots_patterns, times_diff, times_orderings
+
 N31 = 31
 BAD_N = "n_mut must be in [1, 31]"
 TOO_MANY = "too many active events for one patient"
@@ -20,44 +23,6 @@ TOO_MANY_SIM = "too many events for the sampler (n_mut <= 30: event and diagnosi
 
 
 # ---------------------------------------------------------------------------------------------------- helpers
-def _row(n, pt, mt, seed, order, typ):
-    r = np.zeros(2 * n + 3, dtype=np.int8)
-    for j in pt:
-        r[2 * j] = 1
-    for j in mt:
-        r[2 * j + 1] = 1
-    r[2 * n], r[2 * n + 1], r[2 * n + 2] = seed, order, typ
-    return r
-
-
-def _paired(n, pt, mt, order):
-    return _row(n, pt, mt, 1, order, 3)
-
-
-def _close(tag, got, ref, rtol, atol=0.0):
-    """numpy's assert_allclose bar |got - ref| <= atol + rtol |ref|, with the worst ratio to it printed first."""
-    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    assert got.shape == ref.shape, (tag, got.shape, ref.shape)
-    assert np.isfinite(got).all(), f"{tag}: {int((~np.isfinite(got)).sum())} non-finite entries"
-    bar = atol + rtol * np.abs(ref)
-    err = np.abs(got - ref)
-    ratio = np.where(err == 0.0, 0.0, err / np.where(bar > 0, bar, np.finfo(float).tiny))
-    i = np.unravel_index(int(np.argmax(ratio)), ratio.shape) if ratio.size else ()
-    print(f"[limits] {tag}: worst error / bar = {ratio.max(initial=0.0):.3g}" + (f" at {i}: {got[i]!r} against {ref[i]!r}" if ratio.size else ""))
-    assert (err <= bar).all(), f"{tag}: {int((err > bar).sum())} of {err.size} entries over the bar, worst ratio {ratio.max():.3g} at {i}"
-
-
-def _close_all(tag, got, ref, lp, grads):
-    """(lp, d_theta, d_dp, d_dm) against a reference: lp = (rtol, atol), grads = (rtol, atol)"""
-    for x, y, nm, bar in zip(got, ref, ("lp", "d_theta", "d_dp", "d_dm"), (lp, grads, grads, grads)):
-        _close(f"{tag} {nm}", x, y, *bar)
-
-
-def _fp32_close(tag, x32, x64):
-    """the componentwise fp32 bar of tests/test_gpu_parity.py (_fp32_report): 2e-3 |x| + 2e-5"""
-    _close(tag, x32, x64, 2e-3, 2e-5)
-
-
 def _fails_with(text):
     """the call raises with exactly this text of mmhn_last_error (the bindings put the package's name in front)"""
     return pytest.raises(RuntimeError, match="^" + re.escape("metmhn_amd: " + text) + "$")
@@ -65,44 +30,17 @@ def _fails_with(text):
 
 def _refused_rows():
     """(n, row, what): single-tumour spaces of more than MAXK = 30 bits, and a joint one"""
-    return [(31, _row(31, range(31), [], 0, -99, 0), "type 0, 31 PT events (k = 31)"),
-            (31, _row(31, range(31), [], 1, -99, 1), "type 1, 31 PT events and the seeding (k = 32)"),
-            (30, _row(30, [], range(30), 1, -99, 2), "type 2, 30 MT events and the seeding (k = 31)"),
-            (31, _paired(31, range(16), range(16, 31), 0), "paired, 16 PT and 15 MT events and the seeding (k = 32)")]
-
-
-def _top_rows(rng, count):
-    """rows of every type and order code at n = 31, the generator of test_gpu_parity.py:
-    test_random_patients_against_c_oracle with the slots biased to the events 27 .. 30 and k <= 12"""
-    n = N31
-    rows = []
-    while len(rows) < count:
-        dens = rng.choice([0.0, 0.15, 0.5, 0.85, 1.0])
-        prob = np.full(2 * n, 0.03 * (dens > 0))
-        prob[2 * 27:] = dens
-        bits = (rng.random(2 * n) < prob).astype(np.int8)
-        typ = len(rows) % 4
-        if typ == 0:
-            bits[1::2] = 0
-            r = np.concatenate((bits, [0, -99, 0]))
-        elif typ == 1:
-            bits[1::2] = 0
-            r = np.concatenate((bits, [1, -99, 1]))
-        elif typ == 2:
-            bits[0::2] = 0
-            r = np.concatenate((bits, [1, -99, 2]))
-        else:
-            r = np.concatenate((bits, [1, [0, 1, 2, -99, 3][(len(rows) // 4) % 5], 3]))
-        if int(r[:2 * n + 1].sum()) <= 12:
-            rows.append(r)
-    return rows
+    return [(31, row(31, range(31), [], 0, -99, 0), "type 0, 31 PT events (k = 31)"),
+            (31, row(31, range(31), [], 1, -99, 1), "type 1, 31 PT events and the seeding (k = 32)"),
+            (30, row(30, [], range(30), 1, -99, 2), "type 2, 30 MT events and the seeding (k = 31)"),
+            (31, paired(31, range(16), range(16, 31), 0), "paired, 16 PT and 15 MT events and the seeding (k = 32)")]
 
 
 def _fixed_rows():
     n = N31
-    rows = [_row(n, [], [], 0, -99, 0), _row(n, [], [], 1, -99, 1), _row(n, [], [], 1, -99, 2)]
+    rows = [row(n, [], [], 0, -99, 0), row(n, [], [], 1, -99, 1), row(n, [], [], 1, -99, 2)]
     for order in (0, 1, 2):
-        rows += [_paired(n, [], [], order), _paired(n, [30], [], order), _paired(n, [], [30], order), _paired(n, [30], [30], order)]
+        rows += [paired(n, [], [], order), paired(n, [30], [], order), paired(n, [], [30], order), paired(n, [30], [30], order)]
     return rows
 
 
@@ -123,13 +61,13 @@ def test_c_ports_at_n31_against_the_python_oracle():
         typ = i % 4
         if typ == 3:
             pt, mt = low[:1] + [29, 30][:1 + i // 4 % 2], low[1:] + [30, 29][:1 + i // 8]
-            rows.append(_paired(n, pt, mt, [0, 1, 2, -99][i // 4]))
+            rows.append(paired(n, pt, mt, [0, 1, 2, -99][i // 4]))
         elif typ == 2:
-            rows.append(_row(n, [], low + [29, 30], 1, -99, 2))
+            rows.append(row(n, [], low + [29, 30], 1, -99, 2))
         else:
-            rows.append(_row(n, low + [29, 30], [], typ, -99, typ))
-    rows += [_paired(n, [0, 29, 30], [29, 30], 0), _paired(n, [29, 30], [1, 29, 30], 1), _paired(n, [28, 29, 30], [30], 2),
-             _paired(n, [30], [28, 29], 2), _row(n, [], [], 0, -99, 0), _paired(n, [], [], 0)]
+            rows.append(row(n, low + [29, 30], [], typ, -99, typ))
+    rows += [paired(n, [0, 29, 30], [29, 30], 0), paired(n, [29, 30], [1, 29, 30], 1), paired(n, [28, 29, 30], [30], 2),
+             paired(n, [30], [28, 29], 2), row(n, [], [], 0, -99, 0), paired(n, [], [], 0)]
     dat = np.array(rows, dtype=np.int8)
     k = dat[:, :2 * n + 1].astype(int).sum(1)
     assert len(dat) >= 20 and k.max() <= 8
@@ -141,9 +79,9 @@ def test_c_ports_at_n31_against_the_python_oracle():
     print(f"[limits] Python oracle, {len(dat)} rows at n = 31: {time.perf_counter() - t0:.1f} s")
     assert ref[1].shape == (len(dat), n + 1, n + 1) and ref[2].shape == ref[3].shape == (len(dat), n + 1)
     bar = (1e-10, 1e-10)
-    _close_all("metmhn_ref.c at n = 31", cref.patients(lt, dp, dm, dat, with_grad=True), ref, bar, bar)
-    paired = dat[:, -1] == 3
-    _close_all("metmhn_fast.c at n = 31", cref.fast_patients(lt, dp, dm, dat[paired]), [r[paired] for r in ref], bar, bar)
+    close_grads("metmhn_ref.c at n = 31", cref.patients(lt, dp, dm, dat, with_grad=True), ref, bar, bar)
+    both = dat[:, -1] == 3
+    close_grads("metmhn_fast.c at n = 31", cref.fast_patients(lt, dp, dm, dat[both]), [r[both] for r in ref], bar, bar)
 
 
 # ---------------------------------------------------------------------------------------------------- GPU: n_mut = 31
@@ -157,7 +95,7 @@ def test_limits_are_refused_before_any_launch():
     from metmhn_amd import Engine, synthetic
     with _fails_with(BAD_N):
         Engine(32)
-    valid = {n: np.array([_paired(n, [0, n - 1], [n - 1], 0), _row(n, [n - 1], [], 1, -99, 1)], dtype=np.int8) for n in (30, 31)}
+    valid = {n: np.array([paired(n, [0, n - 1], [n - 1], 0), row(n, [n - 1], [], 1, -99, 1)], dtype=np.int8) for n in (30, 31)}
     for n, bad, what in _refused_rows():
         lt, dp, dm = synthetic.random_params(n, seed=n)
         want = cref.patients(lt, dp, dm, valid[n], with_grad=False)[0]
@@ -170,7 +108,7 @@ def test_limits_are_refused_before_any_launch():
                 sums = e.cohort_sums(lt, dp, dm, with_grad=False)     # (score of the EM rows, of the NM rows, n_em, n_pat, ...)
                 assert sums[2] == 0 and sums[3] == 0 and sums[0] == 0 and sums[1] == 0, (what, sums[:4])
             e.set_cohort(valid[n])
-            _close(f"after refusing {what}: lp", e.patient_grads(lt, dp, dm, with_grad=False), want, 1e-9, 1e-12)
+            close(f"after refusing {what}: lp", e.patient_grads(lt, dp, dm, with_grad=False), want, 1e-9, 1e-12)
     lt, dp, dm = synthetic.random_params(N31, seed=1)
     with Engine(N31) as e:
         for call in (lambda: e.simulate(lt, dp, dm, 16, seed=1), lambda: e.simulate_summary(lt, dp, dm, 16, seed=1),
@@ -189,7 +127,7 @@ def top_cohort():
     from oracle import cref
     from metmhn_amd import synthetic
     lt, dp, dm = synthetic.random_params(N31, seed=131)
-    dat = np.array(_top_rows(np.random.default_rng(20240831), 60) + _fixed_rows(), dtype=np.int8)
+    dat = np.array(top_rows(np.random.default_rng(20240831), 60) + _fixed_rows(), dtype=np.int8)
     k = dat[:, :2 * N31 + 1].astype(int).sum(1)
     assert k.max() <= 12 and k.max() >= 9 and set(dat[:, -1]) == {0, 1, 2, 3} and set(dat[dat[:, -1] == 3, -2]) == {0, 1, 2, 3, -99}
     assert dat[:, 54:62].sum() > 8 * dat[:, :54].sum() / 54                       # the slots of the events 27 .. 30 carry the weight
@@ -203,15 +141,10 @@ def test_cohort_at_n31_against_c_port(monkeypatch, top_cohort, pmin):
     event 30 alone in either tumour and in both), both kernel schedules, buffers NaN-poisoned; per-patient results against
     oracle/metmhn_ref.c at the bars of test_random_patients_against_c_oracle (lp 1e-9 / 1e-12, gradients 1e-8 / 1e-10).
     Row and column 31 of d_theta and the entries of events no row carries are compared like every other entry."""
-    from metmhn_amd import Engine
     lt, dp, dm, dat, ref = top_cohort
-    monkeypatch.setenv("MMHN_PSOLVE_MIN", pmin)
-    monkeypatch.setenv("MMHN_POISON", "1")
-    with Engine(N31) as e:
-        e.set_cohort(dat)
-        got = e.patient_grads(lt, dp, dm)
+    got = patient_grads(monkeypatch, N31, dat, (lt, dp, dm), MMHN_PSOLVE_MIN=pmin, MMHN_POISON="1")
     assert got[1].shape == (len(dat), 32, 32) and np.abs(ref[1][:, 31, :]).max() > 0 and np.abs(ref[1][:, :, 31]).max() > 0
-    _close_all(f"n = 31 cohort, MMHN_PSOLVE_MIN={pmin}", got, ref, (1e-9, 1e-12), (1e-8, 1e-10))
+    close_grads(f"n = 31 cohort, MMHN_PSOLVE_MIN={pmin}", got, ref, (1e-9, 1e-12), (1e-8, 1e-10))
 
 
 @pytest.mark.gpu
@@ -225,22 +158,13 @@ def test_cohort_at_n31_fp32_against_fp64(top_cohort):
         with Engine(N31, dtype=dt) as e:
             e.set_cohort(dat)
             res[dt] = D.combine_sums(e.cohort_sums(lt, dp, dm), N31 + 1, 0.5)
-    _close("n = 31 cohort fp32 score", res["f32"][0], res["f64"][0], 2e-5)
-    for x32, x64, nm in zip(res["f32"][1:], res["f64"][1:], ("d_theta", "d_dp", "d_dm")):
-        _close(f"n = 31 cohort fp32 {nm}", x32, x64, 2e-3, 2e-5)
+    close_grads("n = 31 cohort fp32", res["f32"], res["f64"], (2e-5, 0.0), FP32_BAR)
 
 
 def _k20_chain_top(kr, kc, rows_p, seed):
-    """tests/test_window_rows_gpu.py's _k20_chain at n = 31 with the events 28 .. 30 in every row: three rows of one shape
+    """tests/test_window_rows_gpu.py's k = 20 chains at n = 31 with the events 28 .. 30 in every row: three rows of one shape
     (kr row-class bits, kc column-class bits), orders 0 / 1 / 2; the row class carries 28 and 30, the column class 29 and 30"""
-    rng = np.random.default_rng(seed)
-    out = []
-    for order in range(3):
-        a = np.concatenate(([28, 30], rng.choice(28, size=kr - 2, replace=False)))
-        b = np.concatenate(([29, 30], rng.choice(28, size=kc - 2, replace=False)))
-        pt, mt = (a, b) if rows_p else (b, a)
-        out.append(_paired(N31, pt, mt, order))
-    return out
+    return shape_rows(N31, kr, kc, rows_p, 3, seed, fixed=((28, 30), (29, 30)))
 
 
 @pytest.mark.gpu
@@ -249,7 +173,7 @@ def test_window_route_at_n31(monkeypatch):
     tile kernels (0), poisoned, against oracle/metmhn_fast.c at the bars of
     test_full_size_patients_against_optimised_cpu_variant (lp 1e-10, gradients 1e-7 / 1e-10)."""
     from oracle import cref
-    from metmhn_amd import Engine, synthetic
+    from metmhn_amd import synthetic
     lt, dp, dm = synthetic.random_params(N31, seed=231)
     dat = np.array(_k20_chain_top(12, 7, True, 71) + _k20_chain_top(12, 7, False, 72), dtype=np.int8)
     assert (dat[:, :63].sum(1) == 20).all() and (dat[:, 56:62:2] | dat[:, 57:62:2]).all() and dat[:, [60, 61]].all()
@@ -257,18 +181,12 @@ def test_window_route_at_n31(monkeypatch):
     monkeypatch.setenv("MMHN_POISON", "1")
     monkeypatch.setenv("MMHN_TIME_KERNELS", "1")        # (6 * 2^20 states: launches are counted only when asked for)
     for ms in ("1", "0"):
-        monkeypatch.setenv("MMHN_WSOLVE", ms)
         # window route: its own minimum lowered, so that a row it turned away would show on the tile route; without it: the
         # per-patient kernel from one problem on, as in tests/test_window_rows_gpu.py
-        monkeypatch.delenv("MMHN_WSOLVE_MIN" if ms == "0" else "MMHN_PSOLVE_MIN", raising=False)
-        monkeypatch.setenv("MMHN_WSOLVE_MIN" if ms == "1" else "MMHN_PSOLVE_MIN", "1")
-        with Engine(N31) as e:
-            e.set_cohort(dat)
-            got = e.patient_grads(lt, dp, dm)
-            counters = e.counters()
+        got, counters = patient_grads(monkeypatch, N31, dat, (lt, dp, dm), counters=True, MMHN_WSOLVE=ms, **_ROUTE_MIN[ms])
         if ms == "1":
             _assert_window_route("n = 31 window chains", counters)
-        _close_all(f"n = 31 window chains, MMHN_WSOLVE={ms}", got, ref, (1e-10, 0.0), (1e-7, 1e-10))
+        close_grads(f"n = 31 window chains, MMHN_WSOLVE={ms}", got, ref, (1e-10, 0.0), (1e-7, 1e-10))
 
 
 # ---------------------------------------------------------------------------------------------------- GPU: the largest shapes
@@ -280,15 +198,8 @@ def _timed_reference(tag, lt, dp, dm, dat):
     return ref
 
 
-def _grads(monkeypatch, n, dat, dtype, lt, dp, dm, **env):
-    from metmhn_amd import Engine
-    for name, value in env.items():
-        monkeypatch.setenv(name, value)
-    with Engine(n, dtype=dtype) as e:
-        e.set_cohort(dat)
-        got = e.patient_grads(lt, dp, dm)
-        counters = e.counters()
-    return got, counters
+# the minimum of the route under test at 1 and the other one at its default, by MMHN_WSOLVE
+_ROUTE_MIN = {"1": {"MMHN_WSOLVE_MIN": "1", "MMHN_PSOLVE_MIN": None}, "0": {"MMHN_PSOLVE_MIN": "1", "MMHN_WSOLVE_MIN": None}}
 
 
 def _joint_launches(counters):
@@ -311,25 +222,24 @@ def _assert_window_route(tag, counters):
 def test_largest_fp64_window_shape(monkeypatch):
     """(kR, kC) = (15, 9), k = 25: WCfg<double>::KR and KC both at their maximum, one row per class orientation, orders 0
     and 2.  The window layout read in place (MMHN_WSOLVE=1) against the same solves converted to index order (2) as in
-    tests/test_wclass_external_rows.py's _check (1e-12 of the largest entry), and against oracle/metmhn_fast.c at the fp64
+    tests/test_wclass_external_rows.py's _check (WINDOW_TOL: 1e-12 of the largest entry), and against oracle/metmhn_fast.c at the fp64
     bars of test_window_layout_solves_match_cpu_port (lp 1e-10, gradients 1e-7 / 1e-10).  Measured: metmhn_fast.c takes
     1.5 s for the two rows on 16 threads (0.75 s per k = 25 row)."""
     from metmhn_amd import synthetic
     n = 25
     lt, dp, dm = synthetic.random_params(n)
-    dat = np.array([_paired(n, range(15), range(12, 21), 0), _paired(n, range(2, 11), range(8, 23), 2)], dtype=np.int8)
+    dat = np.array([paired(n, range(15), range(12, 21), 0), paired(n, range(2, 11), range(8, 23), 2)], dtype=np.int8)
     assert (dat[:, :2 * n + 1].sum(1) == 25).all()
     ref = _timed_reference("fp64 window corner, k = 25", lt, dp, dm, dat)
     monkeypatch.delenv("MMHN_PSOLVE_MIN", raising=False)
     monkeypatch.setenv("MMHN_WSOLVE_MIN", "1")          # (two window-shaped rows take the window route)
     monkeypatch.setenv("MMHN_POISON", "1")
-    win, cw = _grads(monkeypatch, n, dat, "f64", lt, dp, dm, MMHN_WSOLVE="1")
-    idx, ci = _grads(monkeypatch, n, dat, "f64", lt, dp, dm, MMHN_WSOLVE="2")
+    win, cw = patient_grads(monkeypatch, n, dat, (lt, dp, dm), counters=True, MMHN_WSOLVE="1")
+    idx, ci = patient_grads(monkeypatch, n, dat, (lt, dp, dm), counters=True, MMHN_WSOLVE="2")
     _assert_window_route("(15, 9) fp64, MMHN_WSOLVE=1", cw)      # (2 * 2^25 states: the batch is timed)
     _assert_window_route("(15, 9) fp64, MMHN_WSOLVE=2", ci)
-    for x, y, nm in zip(win, idx, ("lp", "d_theta", "d_dp", "d_dm")):
-        _close(f"(15, 9) fp64 window layout against index order, {nm}", x, y, 1e-12, 1e-12 * np.abs(y).max())
-    _close_all("(15, 9) fp64 window layout against metmhn_fast.c", win, ref, (1e-10, 0.0), (1e-7, 1e-10))
+    close_to_largest("(15, 9) fp64 window layout against index order,", win, idx, WINDOW_TOL["f64"])
+    close_grads("(15, 9) fp64 window layout against metmhn_fast.c", win, ref, (1e-10, 0.0), (1e-7, 1e-10))
 
 
 @pytest.mark.gpu
@@ -341,21 +251,17 @@ def test_largest_fp32_window_shapes(monkeypatch):
     from metmhn_amd import synthetic
     n = 27
     lt, dp, dm = synthetic.random_params(n)
-    dat = np.array([_paired(n, range(18), range(16, 24), 1), _paired(n, range(3, 15), range(10, 24), 0)], dtype=np.int8)
+    dat = np.array([paired(n, range(18), range(16, 24), 1), paired(n, range(3, 15), range(10, 24), 0)], dtype=np.int8)
     assert (dat[:, :2 * n + 1].sum(1) == 27).all()
     ref = _timed_reference("fp32 window corners, k = 27", lt, dp, dm, dat)
     monkeypatch.setenv("MMHN_POISON", "1")
     for ms in ("1", "0"):
         # (the window route's own minimum, so that a row it turned away would show on the tile route; MMHN_WSOLVE=0: the
         # per-patient kernel from one problem on)
-        monkeypatch.delenv("MMHN_WSOLVE_MIN" if ms == "0" else "MMHN_PSOLVE_MIN", raising=False)
-        got, counters = _grads(monkeypatch, n, dat, "f32", lt, dp, dm, MMHN_WSOLVE=ms,
-                               **{"MMHN_WSOLVE_MIN" if ms == "1" else "MMHN_PSOLVE_MIN": "1"})
+        got, counters = patient_grads(monkeypatch, n, dat, (lt, dp, dm), dtype="f32", counters=True, MMHN_WSOLVE=ms, **_ROUTE_MIN[ms])
         if ms == "1":
             _assert_window_route("k = 27 fp32, (18, 8) and (14, 12)", counters)      # (2 * 2^27 states: the batch is timed)
-        _close(f"k = 27 fp32 MMHN_WSOLVE={ms} lp", got[0], ref[0], 1e-4)
-        for x32, x64, nm in zip(got[1:], ref[1:], ("d_theta", "d_dp", "d_dm")):
-            _fp32_close(f"k = 27 fp32 MMHN_WSOLVE={ms} {nm}", x32, x64)
+        fp32_grads(f"k = 27 MMHN_WSOLVE={ms}", got, ref)
 
 
 @pytest.mark.gpu
@@ -375,29 +281,23 @@ def test_largest_tile_route_problem(monkeypatch):
     from metmhn_amd import synthetic
     n = 13
     lt, dp, dm = synthetic.random_params(n)
-    dat = np.array([_paired(n, range(13), range(12), 0)], dtype=np.int8)
+    dat = np.array([paired(n, range(13), range(12), 0)], dtype=np.int8)
     assert dat[0, :2 * n + 1].sum() == 26
     ref = _timed_reference("tile route, k = 26", lt, dp, dm, dat)
     monkeypatch.setenv("MMHN_POISON", "1")
     monkeypatch.delenv("MMHN_COOP", raising=False)
     for coop in (None, "0"):
-        got, counters = _grads(monkeypatch, n, dat, "f64", lt, dp, dm, **({} if coop is None else {"MMHN_COOP": coop}))
+        got, counters = patient_grads(monkeypatch, n, dat, (lt, dp, dm), counters=True, MMHN_COOP=coop)
         print(f"[limits] k = 26 tile route, MMHN_COOP={coop}: counters {counters}")
         levels = 1 if coop is None else 15
         assert counters["evals"] == 1, counters
         assert _joint_launches(counters) == (0, 0, levels, levels), (coop, counters)
         live = (8192 + 64) * 4096 * 8.0
         assert counters["csolve_fwd"]["alg_bytes"] == live and counters["csolve_adj"]["alg_bytes"] == live, (coop, counters)
-        _close_all(f"k = 26 tile route, MMHN_COOP={coop}", got, ref, (1e-10, 0.0), (1e-7, 1e-10))
+        close_grads(f"k = 26 tile route, MMHN_COOP={coop}", got, ref, (1e-10, 0.0), (1e-7, 1e-10))
 
 
 # ---------------------------------------------------------------------------------------------------- GPU: the order family
-def _order_bar():
-    """the bar every tests/test_order_*.py compares device and host at (tests/test_order_posteriors.py derives it)"""
-    from test_order_times import BAR
-    return BAR
-
-
 @pytest.fixture(scope="module")
 def order_cohort():
     """(model, dat) at n = 31: order_common.small_shapes_n8() with every event shifted up by 23 (events 23 .. 30, the seeding
@@ -425,7 +325,7 @@ def _host_run(mod, name, dat):
 
 def _bar(tag, **worst):
     """every figure against the order tests' bar, the worst ratio printed first"""
-    bar = _order_bar()
+    bar = BAR
     print(f"[limits] {tag}: " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()) + f"; worst error / bar = {max(worst.values()) / bar:.3g}")
     for name, v in worst.items():
         assert v <= bar, (tag, name, v)
@@ -456,7 +356,6 @@ def test_likeliest_orders_at_n31(order_cohort):
     """orders of width 63 with codes up to 62: the device's order and probability of every row against the host's (a tie:
     an order as likely as the host's), every order holds the row's slots once."""
     from order_common import Row
-    from test_orders_cohort import _same_or_tie
     mod, dat = order_cohort
     got = mod.likeliest_orders(dat)
     worst = 0.0
@@ -464,7 +363,7 @@ def test_likeliest_orders_at_n31(order_cohort):
         warnings.simplefilter("ignore", DeprecationWarning)
         for i, r in enumerate(dat):
             want = mod._row_order(dat, i)
-            _same_or_tie(mod, r, got[i], want, rel=_order_bar())
+            same_or_tie(mod, r, got[i], want, rel=BAR)
             worst = max(worst, abs(got[i][1] - want[1]) / want[1])
             assert set(got[i][0]) == Row(r, mod.n).slots and len(got[i][0]) == len(set(got[i][0])), i
     assert max(max(o, default=0) for o, _ in got) == 62
@@ -517,7 +416,6 @@ def test_order_positions_at_n31(order_cohort):
 
 @pytest.mark.gpu
 def test_order_times_at_n31(order_cohort):
-    from test_order_times import _diff, _orderings
     mod, dat = order_cohort
     dev, host = mod.order_times(dat), _host_run(mod, "order_times", dat)
     assert mod.times_fallback_rows == 0
@@ -526,19 +424,18 @@ def test_order_times_at_n31(order_cohort):
     np.testing.assert_array_equal(~np.isnan(dev.time), _carried(dat, mod.n))
     np.testing.assert_array_equal(~np.isnan(dev.obs), np.stack((np.ones(len(dat), dtype=bool), paired), axis=1))
     np.testing.assert_array_equal(~np.isnan(dev.pt_first), paired)
-    d = _diff(dev, host)
-    _bar("order_times at n = 31", evidence=d[0], times=d[1], pt_first=d[2], orderings=max(0.0, _orderings(dev.time, dev.obs, dat, mod.n)))
+    d = times_diff(dev, host)
+    _bar("order_times at n = 31", evidence=d[0], times=d[1], pt_first=d[2], orderings=max(0.0, times_orderings(dev.time, dev.obs, dat, mod.n)))
 
 
 @pytest.mark.gpu
 def test_order_snapshots_at_n31(order_cohort):
-    from test_order_snapshots import _diff, _patterns
     mod, dat = order_cohort
     dev, host = mod.order_snapshots(dat), _host_run(mod, "order_snapshots", dat)
     assert mod.snapshots_fallback_rows == 0
     assert dev.held.shape == (len(dat), 2, 63) and dev.late.shape == (len(dat), 2, 32) and dev.map_state.shape == (len(dat), 63)
-    _patterns(dev, dat, mod.n)                           # NaN / -1 wherever the row does not carry the code
-    d = _diff(dev, host)                                 # (map_state and map_first equal on every row)
+    snapshots_patterns(dev, dat, mod.n)                           # NaN / -1 wherever the row does not carry the code
+    d = snapshots_diff(dev, host)                        # (map_state and map_first equal on every row)
     _bar("order_snapshots at n = 31", evidence=d[0], held=d[1], late=d[2], map_prob=d[3])
 
 
@@ -548,7 +445,6 @@ def test_sample_orders_at_n31(order_cohort):
     MetMHN.sample_order's (a sample whose closest draw lies within 1e-9 of a boundary is set aside, as in
     tests/test_order_samples.py), log_prob to 1e-10."""
     from order_common import FIRST, KEY
-    from test_order_samples import MARGIN, MAX_EXCLUDED
     mod, dat = order_cohort
     M = 64
     dev = mod.sample_orders(dat, M, key=KEY, first=FIRST)

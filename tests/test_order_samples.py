@@ -26,14 +26,11 @@ import pytest
 from metmhn_amd import _philox
 from metmhn_amd.model import OrderSamples
 from metmhn_amd.state import MetState
-from order_common import (BIG_SAMPLES, ENTRIES, FIRST, KEY, all_orders, big_models, check_arguments_before_the_library,
+from order_common import (BIG_SAMPLES, ENTRIES, FIRST, KEY, MARGIN, MAX_EXCLUDED, all_orders, big_models, check_arguments_before_the_library,
                           check_big_samples, check_errors_name_the_row, check_too_large_rows_get_the_host_value, large_rows, luad, luad_selection, model,
                           random_paired_states, row, small_shapes_n8)
 
 ENTRY = ENTRIES["sample_orders"]
-
-MARGIN = 1e-9                     # a sample whose closest draw is nearer than this to a boundary is not compared
-MAX_EXCLUDED = 1e-3               # share of one test's samples that may be set aside
 
 
 def _bound(p, M):

@@ -29,9 +29,9 @@ import pytest
 from metmhn_amd import _lib
 from metmhn_amd.model import OrderSnapshot, OrderSnapshots
 from metmhn_amd.state import MetState
-from order_common import (Row, big_models, check_arguments_before_the_library, check_big_rows, check_errors_name_the_row,
+from order_common import (big_models, check_arguments_before_the_library, check_big_rows, check_errors_name_the_row,
                           check_too_large_rows_get_the_host_value, error_rows, host_only, large_rows, luad, luad_selection,
-                          model, random_paired_states, small_shapes_n8, too_large_cohort_k14)
+                          model, random_paired_states, small_shapes_n8, snapshots_diff, snapshots_patterns, too_large_cohort_k14, worst_entry)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY = SimpleNamespace(cohort="order_snapshots", single="order_snapshot", engine="order_snapshots",
@@ -41,24 +41,6 @@ ENTRY = SimpleNamespace(cohort="order_snapshots", single="order_snapshot", engin
                         workspace=1 << 20, luad=("fit", luad_selection))
 FIRST_OBS = ("PT", "Met", "unknown")
 BAR = 1e-12
-
-
-def _worst(d):
-    """Largest entry of d, the NaN ones (NaN in both operands, which the callers assert first) left out."""
-    d = np.asarray(d, dtype=float)
-    return float(np.max(np.where(np.isnan(d), 0.0, d), initial=0.0))
-
-
-def _diff(got, want):
-    """(relative difference of the evidence, worst absolute difference of held, of late, of map_prob); the NaN patterns,
-    map_first and map_state are asserted equal."""
-    for name in ("held", "late", "map_prob"):
-        np.testing.assert_array_equal(np.isnan(getattr(got, name)), np.isnan(getattr(want, name)), err_msg=name)
-    np.testing.assert_array_equal(got.map_first, want.map_first)
-    np.testing.assert_array_equal(got.map_state, want.map_state)
-    zg, zw = np.exp(got.log_evidence), np.exp(want.log_evidence)
-    return (float(np.max(np.abs(zg - zw) / zw)),) + tuple(
-        _worst(np.abs(np.asarray(getattr(got, name), dtype=float) - getattr(want, name))) for name in ("held", "late", "map_prob"))
 
 
 def _rows_of(run, idx):
@@ -91,7 +73,7 @@ def _mixture(pt, met, unk):
     late; map_prob against the larger of the two weighted ones)."""
     zp, zm, zu = (np.exp(r.log_evidence) for r in (pt, met, unk))
     p = zp / zu
-    d_held = max(_worst(np.abs(unk.held[0] - p * pt.held[0])), _worst(np.abs(unk.held[1] - (1.0 - p) * met.held[1])))
+    d_held = max(worst_entry(np.abs(unk.held[0] - p * pt.held[0])), worst_entry(np.abs(unk.held[1] - (1.0 - p) * met.held[1])))
     d_late = max(np.abs(unk.late[0] - p * pt.late[0]).max(), np.abs(unk.late[1] - (1.0 - p) * met.late[1]).max())
     return abs(zp + zm - zu) / zu, d_held, d_late, abs(unk.map_prob - max(p * pt.map_prob, (1.0 - p) * met.map_prob))
 
@@ -199,13 +181,13 @@ def test_paired_rows_against_enumeration(n, host_only):
         for first in FIRST_OBS:
             want = _paired_enumeration(mod, MetState(slots, size=2 * n + 1), first)
             results.append((got[first], want, (slots, first)))
-    worst = np.max([_diff(got, want) for got, want, _ in results], axis=0)
+    worst = np.max([snapshots_diff(got, want) for got, want, _ in results], axis=0)
     print(f"paired rows against enumeration, n = {n}: {len(results)} cases, events {seen}, worst evidence {worst[0]:.2e}, "
           f"held {worst[1]:.2e}, late {worst[2]:.2e}, map_prob {worst[3]:.2e}")
     for got, want, tag in results:
         assert got.held.shape == (2, 2 * n + 1) and got.late.shape == (2, n + 1) and got.map_state.shape == (2 * n + 1,), tag
         assert got.map_state.dtype == np.int8, tag
-        assert max(_diff(got, want)) <= BAR, (tag, _diff(got, want))
+        assert max(snapshots_diff(got, want)) <= BAR, (tag, snapshots_diff(got, want))
     assert len(results) == 2 * 8 * 3
     assert min(seen.values()) > 0
 
@@ -313,21 +295,6 @@ def _first_name(dat_row):
     return {0: "unknown", 1: "PT"}.get(int(dat_row[-2]), "Met")
 
 
-def _patterns(run, dat, n):
-    """The NaN / -1 patterns of a device result: codes carried, paired rows."""
-    paired = dat[:, -1] == 3
-    carried = np.zeros((len(dat), 2 * n + 1), dtype=bool)
-    for i, r in enumerate(dat):
-        if paired[i]:
-            carried[i, Row(r, n).codes] = True
-    np.testing.assert_array_equal(~np.isnan(run.held), np.repeat(carried[:, None], 2, axis=1))
-    np.testing.assert_array_equal(~np.isnan(run.late), np.broadcast_to(paired[:, None, None], run.late.shape))
-    np.testing.assert_array_equal(run.map_state >= 0, carried)
-    np.testing.assert_array_equal(run.map_first >= 0, paired)
-    np.testing.assert_array_equal(~np.isnan(run.map_prob), paired)
-    assert np.all(np.isfinite(run.log_evidence))
-
-
 def _paired_identities(run, dat, n):
     """Worst residuals of _identities over the paired rows of a cohort, the excluded regimes and the consistency of the
     chosen snapshot asserted row by row."""
@@ -355,12 +322,12 @@ def test_device_against_host_small_shapes():
     for name, shape in zip(ENTRY.fields, ((2, 2 * n + 1), (2, n + 1), (2 * n + 1,), (), ())):
         assert getattr(dev, name).shape == getattr(host, name).shape == (len(dat),) + shape, name
         assert getattr(dev, name).dtype == getattr(host, name).dtype, name
-    d = _diff(dev, host)
+    d = snapshots_diff(dev, host)
     ident = _paired_identities(dev, dat, n)
     print(f"device against host, small shapes: {len(dat)} rows, k in {sorted(set(k.tolist()))}, worst rel. evidence "
           f"{d[0]:.2e}, held {d[1]:.2e}, late {d[2]:.2e}, map_prob {d[3]:.2e}, identities {ident}")
     assert set(k.tolist()) >= {0, 1, 2, 3, 6, 7, 8, 9, 10, 11}
-    _patterns(dev, dat, n)
+    snapshots_patterns(dev, dat, n)
     assert (dat[:, -1] == 3).sum() == 52 and set(dev.map_first[dat[:, -1] == 3].tolist()) == {0, 1}
     assert max(d) <= BAR
     assert ident[:4].max() <= BAR and ident[4] == 0.0
@@ -391,14 +358,14 @@ def test_large_synthetic_rows():
         post = mod.order_posteriors(dat)
         times = mod.order_times(dat)
         assert mod.posteriors_fallback_rows == 0 and mod.times_fallback_rows == 0
-        _patterns(got, dat, n)
+        snapshots_patterns(got, dat, n)
         mix = [_mixture(_one(got, 3 * j + 1), _one(got, 3 * j + 2), _one(got, 3 * j)) for j in range(triples)]
         ident = _paired_identities(got, dat, n) if paired.any() else np.zeros(5)
         d_le = np.abs(np.expm1(got.log_evidence - post.log_evidence)).max()
-        d_pt = _worst(np.abs(got.held[:, 0, 2 * n] - times.pt_first))
+        d_pt = worst_entry(np.abs(got.held[:, 0, 2 * n] - times.pt_first))
         np.testing.assert_array_equal(np.isnan(got.held[:, 0, 2 * n]), np.isnan(times.pt_first))
         k14 = np.flatnonzero(k == 14)
-        d = _diff(_rows_of(got, k14), _host(mod, dat[k14]))
+        d = snapshots_diff(_rows_of(got, k14), _host(mod, dat[k14]))
         print(f"large rows, {tag}: {len(dat)} rows, k = {sorted(set(k.tolist()))}, mixture (evidence, held, late, map_prob) "
               f"{np.max(mix, axis=0) if mix else None}, identities {ident}, evidence against order_posteriors {d_le:.2e}, "
               f"held[0, seeding] against order_times' pt_first {d_pt:.2e}, {len(k14)} rows with k = 14 against the host {d}")
@@ -441,7 +408,7 @@ def test_luad_rows(golden):
     paired = dat[:, -1] == 3
     print(f"LUAD-28 fit: {len(dat)} rows ({paired.sum()} paired), k up to {k.max()}, evidence against order_posteriors "
           f"{d_le:.2e}, identities {ident}, map_prob in [{np.nanmin(run.map_prob):.3f}, {np.nanmax(run.map_prob):.3f}]")
-    _patterns(run, dat, n)
+    snapshots_patterns(run, dat, n)
     assert paired[k == 21].all()
     assert d_le <= BAR and ident[:4].max() <= BAR and ident[4] == 0.0
 
@@ -483,7 +450,7 @@ def test_too_large_rows_get_the_host_value(monkeypatch):
     mod, dat, ref, raw, host = check_too_large_rows_get_the_host_value(ENTRY, monkeypatch)
     for a in raw[:-1]:
         assert np.all(np.isnan(a[0])) if a.dtype == np.float64 else np.all(a[0] == -1)
-    d = _diff(_one(ref, 0), host)
+    d = snapshots_diff(_one(ref, 0), host)
     print(f"host fallback, k = 14: rel. evidence {d[0]:.2e}, held {d[1]:.2e}, late {d[2]:.2e}, map_prob {d[3]:.2e} "
           f"against the device")
     assert max(d) <= BAR

@@ -32,9 +32,9 @@ import pytest
 from metmhn_amd import _lib
 from metmhn_amd.model import OrderTimes
 from metmhn_amd.state import MetState
-from order_common import (Row, big_models, check_arguments_before_the_library, check_big_rows, check_errors_name_the_row,
+from order_common import (BAR, Row, big_models, check_arguments_before_the_library, check_big_rows, check_errors_name_the_row,
                           check_too_large_rows_get_the_host_value, error_rows, host_only, large_rows, luad, luad_selection,
-                          model, random_paired_states, small_shapes_n8, too_large_cohort_k14)
+                          last_observation, model, random_paired_states, small_shapes_n8, times_diff, times_orderings, too_large_cohort_k14)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY = SimpleNamespace(cohort="order_times", single="order_time", engine="order_times",
@@ -43,45 +43,6 @@ ENTRY = SimpleNamespace(cohort="order_times", single="order_time", engine="order
                         error_good=lambda n: error_rows(n)[0], too_large=too_large_cohort_k14,
                         workspace=1 << 20, luad=("fit", luad_selection))
 FIRST_OBS = ("PT", "Met", "unknown", "sync")
-BAR = 1e-12
-
-
-def _last(obs):
-    """The last observation time of rows of obs [..., 2]."""
-    return np.where(np.isnan(obs[..., 1]), obs[..., 0], obs[..., 1])
-
-
-def _diff(got, want):
-    """(relative difference of the evidence, worst difference of time and obs over the last observation time, absolute
-    difference of pt_first - 0 where both are NaN); the NaN patterns are asserted equal."""
-    np.testing.assert_array_equal(np.isnan(got.time), np.isnan(want.time))
-    np.testing.assert_array_equal(np.isnan(got.obs), np.isnan(want.obs))
-    np.testing.assert_array_equal(np.isnan(got.pt_first), np.isnan(want.pt_first))
-    zg, zw = np.exp(got.log_evidence), np.exp(want.log_evidence)
-    last = _last(np.asarray(want.obs))
-    worst = lambda d: float(np.max(np.where(np.isnan(d), 0.0, d), initial=0.0))          # (NaN: in both, checked above)
-    d_t = worst(np.abs(np.asarray(got.time) - want.time) / last[..., None])
-    d_o = worst(np.abs(np.asarray(got.obs) - want.obs) / last[..., None])
-    d_p = worst(np.abs(np.asarray(got.pt_first, dtype=float) - want.pt_first))
-    return float(np.max(np.abs(zg - zw) / zw)), max(d_t, d_o), d_p
-
-
-def _orderings(time, obs, dat, n):
-    """Worst violation, over the last observation time, of: seeding <= first observation <= second observation; a code of
-    one tumour alone >= the seeding (paired rows); every time <= the last observation."""
-    worst = 0.0
-    for i, r in enumerate(dat):
-        w = Row(r, n)
-        last = _last(obs[i])
-        gaps = [t - last for t in time[i, w.codes]]
-        if r[2 * n]:
-            gaps.append(time[i, 2 * n] - obs[i, 0])
-        if w.typ == 3:
-            gaps.append(obs[i, 0] - obs[i, 1])
-            both = set(w.lineages["pt"]) & set(c - 1 for c in w.lineages["mt"])
-            gaps += [time[i, 2 * n] - time[i, c] for c in w.codes if c != 2 * n and c - c % 2 not in both]
-        worst = max([worst] + [g / last for g in gaps])
-    return worst
 
 
 # ---------------------------------------------------------------------------------------------------- enumeration
@@ -226,14 +187,14 @@ def test_one_tumour_rows_against_enumeration(n, host_only):
             got = mod.order_time(state, status)
             want, Zl = _single_paths(mod, state, status)
             results.append((got, want, abs(np.exp(want.log_evidence) - Zl) / Zl, (sl, status)))
-    worst = np.max([_diff(got, want) + (dl,) for got, want, dl, _ in results], axis=0)
+    worst = np.max([times_diff(got, want) + (dl,) for got, want, dl, _ in results], axis=0)
     print(f"one-tumour rows against enumeration, n = {n}: {len(results)} cases, worst evidence {worst[0]:.2e}, times "
           f"{worst[1]:.2e}, enumerated evidence against the summed likelihood {worst[3]:.2e}")
     for got, want, dl, tag in results:
         assert got.time.shape == (2 * n + 1,) and got.obs.shape == (2,), tag
         assert np.isnan(got.obs[1]) and np.isnan(got.pt_first), tag
         assert dl <= BAR, tag
-        d = _diff(got, want)
+        d = times_diff(got, want)
         assert d[0] <= BAR and d[1] <= BAR, (tag, d)
     assert len(results) == 2 * 18
 
@@ -250,13 +211,13 @@ def test_paired_rows_against_enumeration(n, host_only):
             for first in FIRST_OBS:
                 want, dl = _paired_enumeration(mod, MetState(slots, size=2 * n + 1), first)
                 results.append((got[first], want, dl, (slots, first)))
-    worst = np.max([_diff(got, want) + (dl,) for got, want, dl, _ in results], axis=0)
+    worst = np.max([times_diff(got, want) + (dl,) for got, want, dl, _ in results], axis=0)
     print(f"paired rows against enumeration, n = {n}: {len(results)} cases, events {seen}, worst evidence {worst[0]:.2e}, "
           f"times {worst[1]:.2e}, pt_first {worst[2]:.2e}, an order's paths against its likelihood {worst[3]:.2e}")
     for got, want, dl, tag in results:
         assert got.time.shape == (2 * n + 1,) and got.obs.shape == (2,), tag
         assert dl <= BAR, tag
-        d = _diff(got, want)
+        d = times_diff(got, want)
         assert d[0] <= BAR and d[1] <= BAR and d[2] <= BAR, (tag, d)
     assert len(results) == 2 * 8 * 4
     assert min(seen.values()) > 0
@@ -267,7 +228,7 @@ def _mixture(pt, met, unk):
     pt_first, absolute; time and obs, over the last observation time)."""
     zp, zm, zu = (np.exp(r.log_evidence) for r in (pt, met, unk))
     p = zp / zu
-    last = _last(unk.obs)
+    last = last_observation(unk.obs)
     d_time = np.abs(p * pt.time + (1.0 - p) * met.time - unk.time)
     d = max(d_time[~np.isnan(d_time)].max(), np.abs(p * pt.obs + (1.0 - p) * met.obs - unk.obs).max()) / last
     return abs(zp + zm - zu) / zu, abs(unk.pt_first - p), d
@@ -296,7 +257,7 @@ def test_orderings(n, host_only):
         r[slots], r[-1] = 1, 3
         for first in FIRST_OBS:
             g = got[first]
-            worst = max(worst, _orderings(g.time[None], g.obs[None], r[None], n))
+            worst = max(worst, times_orderings(g.time[None], g.obs[None], r[None], n))
     print(f"orderings, n = {n}: {4 * len(cases)} cases, worst violation over the last observation time {worst:.2e}")
     assert worst <= BAR
 
@@ -355,9 +316,9 @@ def test_device_against_host_small_shapes():
     for i, r in enumerate(dat):
         carried[i, Row(r, n).codes] = True
     paired = dat[:, -1] == 3
-    d = _diff(dev, host)
+    d = times_diff(dev, host)
     print(f"device against host, small shapes: {len(dat)} rows, k in {sorted(ks)}, worst rel. evidence {d[0]:.2e}, times "
-          f"{d[1]:.2e}, pt_first {d[2]:.2e}, orderings {_orderings(dev.time, dev.obs, dat, n):.2e}")
+          f"{d[1]:.2e}, pt_first {d[2]:.2e}, orderings {times_orderings(dev.time, dev.obs, dat, n):.2e}")
     assert ks >= {0, 1, 2, 3, 6, 7, 8, 9, 10, 11}
     np.testing.assert_array_equal(~np.isnan(dev.time), carried)
     np.testing.assert_array_equal(~np.isnan(dev.obs), np.stack((np.ones(len(dat), dtype=bool), paired), axis=1))
@@ -365,7 +326,7 @@ def test_device_against_host_small_shapes():
     assert np.all(dev.pt_first[paired & (dat[:, -2] == 1)] == 1.0)
     assert np.all(dev.pt_first[paired & (dat[:, -2] != 0) & (dat[:, -2] != 1)] == 0.0)
     assert max(d) <= BAR
-    assert _orderings(dev.time, dev.obs, dat, n) <= BAR
+    assert times_orderings(dev.time, dev.obs, dat, n) <= BAR
 
 
 def _three_orders(dat):
@@ -394,10 +355,10 @@ def test_large_synthetic_rows():
                                         pt_first=got.pt_first[i])
         mix = [_mixture(row(3 * j + 1), row(3 * j + 2), row(3 * j)) for j in range(triples)]
         d_le = np.abs(np.expm1(got.log_evidence - post.log_evidence)).max()
-        order = _orderings(got.time, got.obs, dat, n)
+        order = times_orderings(got.time, got.obs, dat, n)
         k14 = np.flatnonzero(k == 14)
         host = _host(mod, dat[k14])
-        d = _diff(OrderTimes(got.log_evidence[k14], got.time[k14], got.obs[k14], got.pt_first[k14]), host)
+        d = times_diff(OrderTimes(got.log_evidence[k14], got.time[k14], got.obs[k14], got.pt_first[k14]), host)
         print(f"large rows, {tag}: {len(dat)} rows, k = {sorted(set(k.tolist()))}, mixture (evidence, pt_first, times) "
               f"{np.max(mix, axis=0) if mix else None}, orderings {order:.2e}, evidence against order_posteriors "
               f"{d_le:.2e}, {len(k14)} rows with k = 14 against the host {d}")
@@ -434,7 +395,7 @@ def test_luad_rows(golden):
     post = mod.order_posteriors(dat)
     assert mod.posteriors_fallback_rows == 0
     d_le = np.abs(np.expm1(le - post.log_evidence)).max()
-    order = _orderings(time, obs, dat, mod.n)
+    order = times_orderings(time, obs, dat, mod.n)
     paired = dat[:, -1] == 3
     print(f"LUAD-28 fit: {len(dat)} rows, k up to {k.max()}, evidence against order_posteriors {d_le:.2e}, orderings "
           f"{order:.2e}, pt_first in [{np.nanmin(pt_first):.3f}, {np.nanmax(pt_first):.3f}]")
@@ -485,7 +446,7 @@ def test_too_large_rows_get_the_host_value(monkeypatch):
     mod, dat, ref, raw, host = check_too_large_rows_get_the_host_value(ENTRY, monkeypatch)
     for a in raw[:-1]:
         assert np.all(np.isnan(a[0]))
-    d = _diff(OrderTimes(ref.log_evidence[0], ref.time[0], ref.obs[0], ref.pt_first[0]), host)
+    d = times_diff(OrderTimes(ref.log_evidence[0], ref.time[0], ref.obs[0], ref.pt_first[0]), host)
     print(f"host fallback, k = 14: rel. evidence {d[0]:.2e}, times {d[1]:.2e}, pt_first {d[2]:.2e} against the device")
     assert max(d) <= BAR
 

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from metmhn_amd.model import MetMHN
-from order_common import Row, all_orders, host_only, luad, mixed_cohort, model, row  # noqa: F401 (host_only: a fixture)
+from order_common import Row, all_orders, host_only, luad, mixed_cohort, model, row, same_or_tie  # noqa: F401 (host_only: a fixture)
 
 KINDS = ["isMetastasis", "PT", "Met", "unknown", "sync"]
 DIAG_ORDER = {"unknown": 0, "PT": 1, "Met": 2}
@@ -46,14 +46,6 @@ def test_host_backend_errors_carry_the_row(host_only):
 # ---------------------------------------------------------------------------------------------------- GPU
 def _host(mod, dat, i):
     return mod._row_order(dat, i)
-
-
-def _same_or_tie(mod, row, got, want, rel=1e-12):
-    (go, gp), (wo, wp) = got, want
-    assert abs(gp - wp) <= rel * wp, (row, gp, wp)
-    if go != wo:                                               # a tie: the device's order is as likely as the host's
-        _, status, first = Row(row, mod.n).call()
-        assert abs(mod.likelihood(go, status, first) - wp) <= rel * wp, (row, go, wo)
 
 
 @pytest.mark.gpu
@@ -91,7 +83,7 @@ def test_luad28_rows_match_the_host(golden, prefix):
     assert len(big) == 6
     got = mod.likeliest_orders(dat[sel])
     for j, i in enumerate(sel):
-        _same_or_tie(mod, dat[i], got[j], _host(mod, dat, i))
+        same_or_tie(mod, dat[i], got[j], _host(mod, dat, i))
 
 
 @pytest.mark.gpu
@@ -159,7 +151,7 @@ def test_front_overflow_falls_back_to_the_host(golden):
     assert mod.orders_fallback_rows == (s_1[k <= 14] == 1).sum() > 0
     ref = mod.likeliest_orders(sub)
     for r, a, b in zip(sub, got, ref):
-        _same_or_tie(mod, r, a, b)
+        same_or_tie(mod, r, a, b)
 
 
 @pytest.mark.gpu

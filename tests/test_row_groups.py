@@ -25,7 +25,7 @@ full-profile limit the device library is written to) and L alternatives in group
   * lambda_r: the addend w_g rho lp_g rounds twice and inherits D_g through lp_g:
         |d lambda_r| <= sum_g w_g rho_{g,r} (|lp_g| (eta_{g,r} + (M_r + 1) u) + D_g);
   * the reduction is the one of the row weights: recursive summation of P_cls addends of which each is a product rounded
-    once, against a reference that rounds each addend and the sum once (test_row_weights.WeightedReference with omega_r in the
+    once, against a reference that rounds each addend and the sum once (test_row_weights.py: WeightedReference with omega_r in the
     place of w_i):  (P_cls + 3) u S,  S = sum_r |omega_r v_r| (|lambda_r| for e = 0), plus sum_r |d omega_r| |v_r| (|d lambda_r|);
     the pre-combined buffer (P + 5) u (|w_pm| S_EM + S_NM) plus the same terms.
 A rho below the subnormal range is 0 on both sides (the reference rounds rho to float64); the cases keep away from the
@@ -42,9 +42,9 @@ import os
 import numpy as np
 import pytest
 
-from test_cohort_reduction import (MULTI_BATCH, MULTI_BATCH_WS, Reference, U, _cohort, _params, _within, raw_layout, red_per, stride,
-                                   wsums_layout)
-from test_row_weights import N4, PERC_MET, W_PM, WEIGHT_VALUES, _flat, _nm_class, _rows, _typed_cohort, _wsums
+import reduction_common as RC
+from eval_common import engine_pool
+from reduction_common import MULTI_BATCH, MULTI_BATCH_WS, N4, PERC_MET, W_PM, WEIGHT_VALUES, Reference, U, raw_layout, red_per, stride, wsums_layout
 from unknown_common import relabel, unknown_row
 
 LD = np.longdouble
@@ -118,7 +118,7 @@ class MixReference:
         sp[keep, 0] = d_la[keep]
         sp[keep, 1:] = d_om[keep, None] * np.abs(rows[keep, 1:]) + self.omega[keep, None] * spread[keep, 1:]
         self.counts = _group_counts(dat, ptr, idx, w)
-        self.r = Reference(R[keep], _nm_class(dat)[keep], self.counts[0], N, sp[keep])
+        self.r = Reference(R[keep], RC.nm_class(dat)[keep], self.counts[0], N, sp[keep])
 
     def raw(self):
         r = self.r
@@ -178,7 +178,7 @@ def _make_groups(dat, sizes, seed, hub=0, leave_out=0.1, singles=False):
 
 # ---- CPU: expand_missing against brute force ------------------------------------------------------------------------------------
 
-def _row(n, pt, mt, seeding, order, typ):
+def _entries_row(n, pt, mt, seeding, order, typ):
     r = np.zeros(2 * n + 3, dtype=np.int64)
     r[0:2 * n:2], r[1:2 * n:2] = pt, mt
     r[2 * n], r[2 * n + 1], r[2 * n + 2] = seeding, order, typ
@@ -187,14 +187,14 @@ def _row(n, pt, mt, seeding, order, typ):
 
 def _hand_missing_cohort():
     n, m = 4, MISSING
-    rows = [_row(n, [1, m, 0, m], [0, 0, 0, 0], 0, -99, 0),    # A: type 0, two missing
-            _row(n, [m, 1, 0, 0], [0, 0, m, 0], 1, -99, 1),    # B: type 1, a missing MT entry is ignored
-            _row(n, [m, 0, 0, 0], [1, m, m, 0], 1, -99, 2),    # C: type 2, a missing PT entry is ignored
-            _row(n, [1, m, 0, 0], [m, 1, m, 0], 1, 1, 3),      # D: paired, PT and MT missing independently
-            _row(n, [m, 1, 0, 0], [0, 0, 0, 0], 0, -99, 4),    # E: type 4
-            _row(n, [1, 1, 0, m], [0, 0, 0, 0], 0, -99, 0),    # F: shares its completions with A
-            _row(n, [1, 0, 0, 0], [0, 0, 0, 0], 0, -99, 0),    # G: nothing missing, a completion of A
-            _row(n, [1, 0, 0, 0], [0, 1, 0, 0], 1, 2, 3)]      # H: paired, nothing missing
+    rows = [_entries_row(n, [1, m, 0, m], [0, 0, 0, 0], 0, -99, 0),    # A: type 0, two missing
+            _entries_row(n, [m, 1, 0, 0], [0, 0, m, 0], 1, -99, 1),    # B: type 1, a missing MT entry is ignored
+            _entries_row(n, [m, 0, 0, 0], [1, m, m, 0], 1, -99, 2),    # C: type 2, a missing PT entry is ignored
+            _entries_row(n, [1, m, 0, 0], [m, 1, m, 0], 1, 1, 3),      # D: paired, PT and MT missing independently
+            _entries_row(n, [m, 1, 0, 0], [0, 0, 0, 0], 0, -99, 4),    # E: type 4
+            _entries_row(n, [1, 1, 0, m], [0, 0, 0, 0], 0, -99, 0),    # F: shares its completions with A
+            _entries_row(n, [1, 0, 0, 0], [0, 0, 0, 0], 0, -99, 0),    # G: nothing missing, a completion of A
+            _entries_row(n, [1, 0, 0, 0], [0, 1, 0, 0], 1, 2, 3)]      # H: paired, nothing missing
     return np.array(rows)
 
 
@@ -247,7 +247,7 @@ def test_expand_missing_against_brute_force():
     assert f < a and g7 < a and G.rows.shape[0] == 4 + 2 + 4 + 8 + 2 + 1       # F and G add no row of their own
     np.testing.assert_array_equal(G.rows[0], np.where(dat[0] == MISSING, 0, dat[0]))
     rng = np.random.default_rng(3)
-    big = _typed_cohort(N4, 60, 4).astype(np.int64)
+    big = RC.typed_cohort(N4, 60, 4).astype(np.int64)
     big[:, :2 * N4] = np.where(rng.random((60, 2 * N4)) < 0.2, MISSING, big[:, :2 * N4])
     _check_expansion(big, UF.expand_missing(big))
     other = np.where(dat == MISSING, 9, dat)                   # another marker
@@ -350,9 +350,9 @@ def test_mixture_is_the_marginal_of_the_dense_oracle():
     """logsumexp of the oracle's lp over the completions = log of the dense oracle's probability summed over the compatible
     states of the full space: two independent fp64 computations, 1e-12 relative as in the dense-oracle tests."""
     from metmhn_amd import Utilityfunctions as UF
-    lt, dp, dm = _params(N4)
+    lt, dp, dm = RC.params(N4)
     dat = _hand_missing_cohort()
-    dat = np.vstack((dat[[0, 1, 2, 5, 6]], _row(N4, [MISSING, 0, MISSING, 0], [0, 0, 0, 0], 0, -99, 0)[None, :]))   # (the empty genotype among the completions)
+    dat = np.vstack((dat[[0, 1, 2, 5, 6]], _entries_row(N4, [MISSING, 0, MISSING, 0], [0, 0, 0, 0], 0, -99, 0)[None, :]))   # (the empty genotype among the completions)
     G = UF.expand_missing(dat)
     for g in range(dat.shape[0]):
         _, lp_mix = _oracle_group_lp(lt, dp, dm, G, g)
@@ -362,7 +362,7 @@ def test_mixture_is_the_marginal_of_the_dense_oracle():
 
 def test_mixture_of_a_paired_row_is_the_marginal_of_the_dense_oracle():
     from metmhn_amd import Utilityfunctions as UF
-    lt, dp, dm = _params(N4)
+    lt, dp, dm = RC.params(N4)
     dat = _hand_missing_cohort()[[3]]
     G = UF.expand_missing(dat)
     assert G.ptr[-1] == 8
@@ -386,7 +386,7 @@ def _butterfly(lanes, op):
 def _mix_replay(lp, rows, kinds, ptr, idx, w, batches, order, N, mode, a, b, reverse=False, defect=False):
     """What the device writes, in float64 NumPy: k_group_lse (lane l takes the alternatives l, l + 64, ..., butterfly over the
     lanes), k_mix_weights (the memberships of a row in group order; reverse: in the opposite order), k_reduce_rows_mix in the
-    chunks and batch order of test_row_weights._replay_w.  defect: one row's rho is taken from the wrong group."""
+    chunks and batch order of test_row_weights.py: _replay_w.  defect: one row's rho is taken from the wrong group."""
     P, G, st = lp.shape[0], len(w), stride(N)
     lpg = np.zeros(G)
     for g in range(G):
@@ -449,8 +449,8 @@ def _replay_case(P, batches, sizes, seed, **how):
     order = [rng.permutation(nb) for nb in batches]
     ref = MixReference(lp, rows, dat, ptr, idx, w, N)
     c = ref.counts
-    r1 = _within(_mix_replay(lp, rows, kinds, ptr, idx, w, batches, order, N, 1, c[0], c[1], **how), *ref.raw(), "replayed raw")
-    r2 = _within(_mix_replay(lp, rows, kinds, ptr, idx, w, batches, order, N, 2, W_PM, 0.0, **how), *ref.wsums(W_PM), "replayed pre-combined")
+    r1 = RC.within(_mix_replay(lp, rows, kinds, ptr, idx, w, batches, order, N, 1, c[0], c[1], **how), *ref.raw(), "replayed raw")
+    r2 = RC.within(_mix_replay(lp, rows, kinds, ptr, idx, w, batches, order, N, 2, W_PM, 0.0, **how), *ref.wsums(W_PM), "replayed pre-combined")
     return max(r1, r2)
 
 
@@ -478,7 +478,7 @@ def test_rho_of_the_wrong_group_breaks_the_bound(P, batches, sizes):
 def test_group_counts_against_a_loop():
     import metmhn_amd.regularized_optimization as ro
     from metmhn_amd import Utilityfunctions as UF
-    dat = _typed_cohort(N4, 97, 3)
+    dat = RC.typed_cohort(N4, 97, 3)
     for seed in range(3):
         ptr, idx, w = _make_groups(dat, (1, 2, 5, 9), seed, hub=3, singles=seed == 1)
         assert ro._group_counts(dat, ptr, idx, w) == _group_counts(dat, ptr, idx, w)
@@ -496,36 +496,16 @@ def test_group_counts_against_a_loop():
 
 @pytest.fixture(scope="module")
 def make_engine():
-    """Engines kept for the module (at most four alive), created under MMHN_POISON=1; zerocopy=False: MMHN_ZEROCOPY=0."""
-    from metmhn_amd import Engine
-    live = {}
-
-    def get(n=N4, zerocopy=True, dtype="f64", workspace=None, tag=0):
-        key = (n, zerocopy, dtype, workspace, tag)
-        if key not in live:
-            while len(live) >= 4:
-                live.pop(next(iter(live))).close()
-            with pytest.MonkeyPatch.context() as mp:
-                mp.setenv("MMHN_POISON", "1")
-                if zerocopy:
-                    mp.delenv("MMHN_ZEROCOPY", raising=False)
-                else:
-                    mp.setenv("MMHN_ZEROCOPY", "0")
-                live[key] = Engine(n, dtype=dtype, workspace_bytes=workspace)
-        live[key] = live.pop(key)
-        return live[key]
-    yield get
-    for e in live.values():
-        e.close()
+    yield from engine_pool()
 
 
 def _all_outputs(e, lt, dp, dm):
-    return [e.cohort_sums(lt, dp, dm), e.cohort_sums(lt, dp, dm, with_grad=False), _wsums(e, lt, dp, dm, W_PM),
-            _wsums(e, lt, dp, dm, W_PM, with_grad=False), _flat(e.score_and_grad(lt, dp, dm, PERC_MET)), e.score(lt, dp, dm, PERC_MET)]
+    return [e.cohort_sums(lt, dp, dm), e.cohort_sums(lt, dp, dm, with_grad=False), RC.wsums(e, lt, dp, dm, W_PM),
+            RC.wsums(e, lt, dp, dm, W_PM, with_grad=False), RC.flat(e.score_and_grad(lt, dp, dm, PERC_MET)), e.score(lt, dp, dm, PERC_MET)]
 
 
 def _at_least_three_batches(dat, n):
-    """test_cohort_reduction.test_multi_batch_reduction's count of the least number of batches under MULTI_BATCH_WS."""
+    """test_cohort_reduction.py: test_multi_batch_reduction's count of the least number of batches under MULTI_BATCH_WS."""
     N = n + 1
     all_zero = (dat[:, -1] == 0) & (dat[:, 0:2 * n + 1:2].sum(axis=1) == 0)
     charged = dat.shape[0] * ((stride(N) + 1) * 8 + 2 * 8) + int((~all_zero).sum()) * ((N * N + 65) * 8 + 4 * 8)
@@ -537,14 +517,14 @@ def _at_least_three_batches(dat, n):
 def test_singleton_groups_of_weight_one_change_nothing(make_engine, how):
     """Every row its own group, weight 1: the same bits as without groups in both buffers and in mmhn_score_and_grad - and
     again after the groups are removed.  (lp_g = lp + log 1, rho = exp 0: every step is exact.)"""
-    lt, dp, dm = _params(N4)
+    lt, dp, dm = RC.params(N4)
     P = 4097
-    dat = _cohort(N4, P)
-    e = make_engine(zerocopy=how != "zerocopy0", workspace=MULTI_BATCH_WS if how == "multibatch" else None)
+    dat = RC.cohort(N4, P)
+    e = make_engine(N4, zerocopy=how != "zerocopy0", workspace=MULTI_BATCH_WS if how == "multibatch" else None)
     e.set_cohort(dat)
     assert e.row_groups is None
     plain = _all_outputs(e, lt, dp, dm)
-    rows_plain = _rows(e, lt, dp, dm)
+    rows_plain = RC.rows_of(e, lt, dp, dm)
     counts = e.row_weight_sums
     ptr, idx = np.arange(P + 1), np.arange(P)
     other = _make_groups(dat, BIG_SIZES, 5, hub=40)
@@ -561,7 +541,7 @@ def test_singleton_groups_of_weight_one_change_nothing(make_engine, how):
             assert not same and e.row_weight_sums != counts   # (the groups in between do reach the sums)
         else:
             assert same and e.row_weight_sums == counts
-        np.testing.assert_array_equal(_rows(e, lt, dp, dm), rows_plain)        # patient_grads stays per row and unmixed
+        np.testing.assert_array_equal(RC.rows_of(e, lt, dp, dm), rows_plain)        # patient_grads stays per row and unmixed
     e.set_row_groups(None, None)
     assert e.row_groups is None and e.row_weights is None
 
@@ -569,28 +549,28 @@ def test_singleton_groups_of_weight_one_change_nothing(make_engine, how):
 def _check_mixed(e, dat, groups, lt, dp, dm, tag, lp_fixture=None):
     """Both buffers of `e` (holding dat and the groups) with and without gradient against the reference of its own rows."""
     ptr, idx, w = groups
-    r1, r2 = _rows(e, lt, dp, dm), _rows(e, lt, dp, dm)
-    s1, s2 = _rows(e, lt, dp, dm, False), _rows(e, lt, dp, dm, False)
+    r1, r2 = RC.rows_of(e, lt, dp, dm), RC.rows_of(e, lt, dp, dm)
+    s1, s2 = RC.rows_of(e, lt, dp, dm, False), RC.rows_of(e, lt, dp, dm, False)
     with np.errstate(invalid="ignore"):
         dl = np.nan_to_num(np.maximum(np.maximum(np.abs(r1[:, 0] - r2[:, 0]), np.abs(s1[:, 0] - s2[:, 0])), np.abs(r1[:, 0] - s1[:, 0])), nan=0.0)
         sp, sp0 = np.nan_to_num(np.abs(r1 - r2), nan=0.0), np.nan_to_num(np.abs(s1 - s2), nan=0.0)
     ref = MixReference(r1[:, 0], r1, dat, ptr, idx, w, e.N, sp, dl)
     ref0 = MixReference(s1[:, 0], s1, dat, ptr, idx, w, e.N, sp0, dl)
     s = e.cohort_sums(lt, dp, dm)
-    a = _within(s, *ref.raw(), tag + " cohort_sums")
+    a = RC.within(s, *ref.raw(), tag + " cohort_sums")
     s0 = e.cohort_sums(lt, dp, dm, with_grad=False)
-    _within(s0, *ref0.raw(), tag + " cohort_sums(with_grad=False)")
+    RC.within(s0, *ref0.raw(), tag + " cohort_sums(with_grad=False)")
     assert not s0[4:].any(), f"{tag}: gradient entries of a score-only evaluation"
-    b = _within(_wsums(e, lt, dp, dm, W_PM), *ref.wsums(W_PM), tag + " cohort_wsums")
-    ws0 = _wsums(e, lt, dp, dm, W_PM, with_grad=False)
-    _within(ws0, *ref0.wsums(W_PM), tag + " cohort_wsums(with_grad=False)")
+    b = RC.within(RC.wsums(e, lt, dp, dm, W_PM), *ref.wsums(W_PM), tag + " cohort_wsums")
+    ws0 = RC.wsums(e, lt, dp, dm, W_PM, with_grad=False)
+    RC.within(ws0, *ref0.wsums(W_PM), tag + " cohort_wsums(with_grad=False)")
     assert not ws0[1:].any(), f"{tag}: gradient entries of a score-only pre-combined evaluation"
     assert (s[2], s[3]) == ref.counts[:2] and e.row_weight_sums == ref.counts, f"{tag}: counts {s[2:4]}, {e.row_weight_sums}"
     lpg, rho = e.group_posteriors(lt, dp, dm)
-    c = _within(lpg, ref0.lpg, ref0.lpg_bound, tag + " lp_group")
-    d = _within(rho, ref0.rho, ref0.rho_bound, tag + " rho")
+    c = RC.within(lpg, ref0.lpg, ref0.lpg_bound, tag + " lp_group")
+    d = RC.within(rho, ref0.rho, ref0.rho_bound, tag + " rho")
     tot = np.array([rho[ptr[g]:ptr[g + 1]].sum() for g in range(len(w))])
-    _within(tot, np.ones(len(w)), ref0.rho_sum_bound + U * np.diff(ptr), tag + " sum of rho")
+    RC.within(tot, np.ones(len(w)), ref0.rho_sum_bound + U * np.diff(ptr), tag + " sum of rho")
     print(f"{tag}: worst error / bound: raw {a:.3f}, pre-combined {b:.3f}, lp_group {c:.3f}, rho {d:.3f}; dropped rows {int((~ref.keep).sum())}")
     return s, ref
 
@@ -606,8 +586,8 @@ def test_mixed_sums_against_the_reference(make_engine, P, dtype, workspace):
     0, weights from WEIGHT_VALUES: both buffers, with and without gradient, lp_group and rho under the derived bound.  The
     MULTI_BATCH cohort under MULTI_BATCH_WS takes at least three batches, its groups span them: two sweeps with a gradient."""
     n = MULTI_BATCH[0] if workspace else N4
-    lt, dp, dm = _params(n)
-    dat = _typed_cohort(n, P, 11)
+    lt, dp, dm = RC.params(n)
+    dat = RC.typed_cohort(n, P, 11)
     if workspace:
         _at_least_three_batches(dat, n)
     big = P > 64
@@ -627,13 +607,13 @@ def test_mixed_sums_against_the_reference(make_engine, P, dtype, workspace):
 def test_an_alternative_of_probability_zero(make_engine):
     """theta_00 = exp(-800) is 0 in float64: every row with event 0 has probability 0, lp = -inf, more than 745 below its
     group's other alternative.  rho is exactly (1, 0), nothing becomes NaN, and the sums are those of the other rows."""
-    lt, dp, dm = _params(N4)
+    lt, dp, dm = RC.params(N4)
     lt = np.array(lt, copy=True)
     lt[0, 0] = -800.0
-    dat = np.array([_row(N4, [0, 1, 0, 0], [0, 0, 0, 0], 0, -99, 0), _row(N4, [1, 1, 0, 0], [0, 0, 0, 0], 0, -99, 0),
-                    _row(N4, [0, 0, 1, 0], [0, 0, 0, 0], 1, -99, 1), _row(N4, [1, 0, 1, 0], [0, 0, 0, 0], 1, -99, 1),
-                    _row(N4, [0, 0, 0, 1], [0, 0, 0, 0], 0, -99, 0)], dtype=np.int8)
-    e = make_engine(tag=4)
+    dat = np.array([_entries_row(N4, [0, 1, 0, 0], [0, 0, 0, 0], 0, -99, 0), _entries_row(N4, [1, 1, 0, 0], [0, 0, 0, 0], 0, -99, 0),
+                    _entries_row(N4, [0, 0, 1, 0], [0, 0, 0, 0], 1, -99, 1), _entries_row(N4, [1, 0, 1, 0], [0, 0, 0, 0], 1, -99, 1),
+                    _entries_row(N4, [0, 0, 0, 1], [0, 0, 0, 0], 0, -99, 0)], dtype=np.int8)
+    e = make_engine(N4, tag=4)
     e.set_cohort(dat)
     lp = e.patient_grads(lt, dp, dm, with_grad=False)
     assert np.isfinite(lp[[0, 2, 4]]).all() and (lp[[1, 3]] == -np.inf).all(), lp
@@ -643,7 +623,7 @@ def test_an_alternative_of_probability_zero(make_engine):
     np.testing.assert_array_equal(rho[:5], [1.0, 0.0, 1.0, 0.0, 1.0])
     np.testing.assert_array_equal(lpg[:3], lp[[0, 2, 4]])
     s, _ = _check_mixed(e, dat, groups, lt, dp, dm, "an alternative of probability 0")
-    assert np.isfinite(s).all() and np.isfinite(_flat(e.score_and_grad(lt, dp, dm, PERC_MET))).all()
+    assert np.isfinite(s).all() and np.isfinite(RC.flat(e.score_and_grad(lt, dp, dm, PERC_MET))).all()
 
 
 @pytest.mark.gpu
@@ -653,10 +633,10 @@ def test_posteriors_of_a_status_pair_are_p_seeded(make_engine):
     reproduces patient_status's p_seeded of the type-4 row.  Bound: r1 = 1 / (1 + exp(lp0 - lp1)) has |d r1 / d lp| <= 1 / 4; each
     lp is a logarithm, E ulps of its own size off, on either route: 0.25 * 2 * 2 E u (|lp0| + |lp1|), and 8 u for the
     handful of roundings of the two closed forms."""
-    lt, dp, dm = _params(N4)
+    lt, dp, dm = RC.params(N4)
     t4 = np.array([unknown_row(N4, ev) for ev in ([1], [0, 2], [0, 1, 2, 3])], dtype=np.int8)
     dat = np.vstack((t4, [relabel(r, 0) for r in t4], [relabel(r, 1) for r in t4]))
-    e = make_engine(tag=5)
+    e = make_engine(N4, tag=5)
     e.set_cohort(dat)
     _, p_seeded = e.patient_status(lt, dp, dm)
     with pytest.raises(RuntimeError, match=r"group 0 mixes the two blocks.*row 3.*row 6"):
@@ -667,7 +647,7 @@ def test_posteriors_of_a_status_pair_are_p_seeded(make_engine):
     lp0, lp1 = lpg[3:6], lpg[6:9]
     r1 = np.exp(lp1 - np.logaddexp(lp0, lp1))
     bound = 0.25 * 2 * 2 * E_ULPS * U * (np.abs(lp0) + np.abs(lp1)) + 8 * U
-    ratio = _within(r1, p_seeded[:3], bound, "rho of the status pair against p_seeded")
+    ratio = RC.within(r1, p_seeded[:3], bound, "rho of the status pair against p_seeded")
     print(f"status pair: worst error / bound {ratio:.3f}")
     np.testing.assert_allclose(lpg[:3], np.logaddexp(lp0, lp1), rtol=1e-14)
 
@@ -715,11 +695,11 @@ def _mixed_objective_reg(params, G, dat, perc_met, w_penal):
 def test_objective_with_missing_entries_by_definition():
     """score_and_grad_reg(..., groups=expand_missing(dat)) against oracle.cref's rows mixed in NumPy (1e-9 on the value, 1e-7 on the
     gradient), and the gradient as central differences of score_reg(..., groups=) along four random directions (step and
-    tolerance of test_gpu_parity.test_full_size_gradient_is_directional_difference_of_score)."""
+    tolerance of test_gpu_parity.py: test_full_size_gradient_is_directional_difference_of_score)."""
     import metmhn_amd.regularized_optimization as ro
     from metmhn_amd import Utilityfunctions as UF
     n = N4
-    lt, dp, dm = _params(n)
+    lt, dp, dm = RC.params(n)
     dat = _masked_cohort(n, 48, 31)
     G = UF.expand_missing(dat)
     assert G.ptr[-1] > 2 * 48 and G.rows.shape[0] < G.ptr[-1] and {0, 1, 2, 3} <= set(dat[:, -1].tolist())
@@ -753,7 +733,7 @@ def test_impute_missing_against_the_dense_oracle():
     (single-tumour rows and the paired row of the hand cohort; n = 4, 1e-12 relative).  An entry in an ignored column: NaN."""
     import metmhn_amd.regularized_optimization as ro
     from metmhn_amd import Utilityfunctions as UF
-    lt, dp, dm = _params(N4)
+    lt, dp, dm = RC.params(N4)
     dat = _hand_missing_cohort()[[0, 1, 2, 3, 5, 6]]
     G = UF.expand_missing(dat)
     try:
@@ -784,9 +764,9 @@ def test_refusals(make_engine):
     next evaluation is the one of the groups held."""
     from metmhn_amd import Engine, _lib
     from metmhn_amd.engine import unique_id
-    lt, dp, dm = _params(N4)
-    dat = _typed_cohort(N4, 33, 2)
-    e = make_engine(tag=3)
+    lt, dp, dm = RC.params(N4)
+    dat = RC.typed_cohort(N4, 33, 2)
+    e = make_engine(N4, tag=3)
     e.set_cohort(dat)
     good = _make_groups(dat, (1, 2, 5), 3, hub=3, singles=True)
     e.set_row_groups(*good)
@@ -874,7 +854,7 @@ def test_guard_rebuild_keeps_the_groups():
     them again - the second value is that of a fresh engine on the edited rows with the groups."""
     import metmhn_amd.regularized_optimization as ro
     from metmhn_amd import Utilityfunctions as UF
-    lt, dp, dm = _params(N4)
+    lt, dp, dm = RC.params(N4)
     G = UF.expand_missing(_masked_cohort(N4, 33, 8))
     try:
         before = ro.score(lt, dp, dm, G.rows, PERC_MET, groups=G)
@@ -911,7 +891,7 @@ def test_sharded_groups_are_refused(monkeypatch):
     import metmhn_amd.regularized_optimization as ro
     from metmhn_amd import Utilityfunctions as UF
     G = UF.expand_missing(_masked_cohort(N4, 33, 8))
-    lt, dp, dm = _params(N4)
+    lt, dp, dm = RC.params(N4)
     try:
         ro.score(lt, dp, dm, G.rows, PERC_MET)
         eng = ro._engine_for(G.rows, check=False)
@@ -925,7 +905,7 @@ def test_sharded_groups_are_refused(monkeypatch):
 @pytest.mark.gpu
 def test_learn_mhn_with_groups_matches_the_oracle_optimizer():
     """learn_mhn(..., groups=) under SciPy's L-BFGS-B reaches the objective the same optimizer reaches on the NumPy-mixed oracle
-    objective (test_gpu_parity.test_learn_mhn_matches_oracle_optimizer's settings and tolerance)."""
+    objective (test_gpu_parity.py: test_learn_mhn_matches_oracle_optimizer's settings and tolerance)."""
     import scipy.optimize as opt
     import metmhn_amd.regularized_optimization as ro
     from metmhn_amd import Utilityfunctions as UF
@@ -979,6 +959,6 @@ def test_luad28_with_a_three_gene_panel_mask(golden):
         rows[:, 0] = lp
         ref = MixReference(lp, rows, G.rows, G.ptr, G.idx, G.weights, 29, lp_spread=np.abs(lp - lp_own))
         s = e.cohort_sums(lt, a, b, with_grad=False)
-        ratio = _within(s, *ref.raw(), "LUAD-28, 3-gene mask: score-only sums")
+        ratio = RC.within(s, *ref.raw(), "LUAD-28, 3-gene mask: score-only sums")
         print(f"LUAD-28, 3-gene mask: {G.rows.shape[0]} distinct completed rows of {int(G.ptr[-1])}, {int((at >= 0).sum())} of them fixture rows; "
               f"worst error / bound {ratio:.3f}, largest |fit_lp - lp| {np.abs(lp - lp_own).max():.2e}")

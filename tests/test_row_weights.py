@@ -5,7 +5,7 @@ Definition (include/metmhn_amd.h): with weights w_i every cohort sum is sum_i w_
 counts are n_em = sum w_i [seeding = 1], n_pat = sum w_i, n_unknown = sum w_i [type 4]; for integer weights that is the objective
 of the cohort in which row i is written w_i times.  A row of weight 0 is absent.
 
-Reference of a weighted buffer: test_cohort_reduction.Reference over the engine's own per-row values (Engine.patient_grads, which
+Reference of a weighted buffer: reduction_common.Reference over the engine's own per-row values (Engine.patient_grads, which
 stays unweighted) times the weights, rows of weight 0 left out.  The float64 products w_i v_i are the addends, and the device may
 fuse the product into the addition, so every addend carries one rounding more than in the unweighted bound: (P_cls + 3) u S for
 the raw buffer, (P + 5) u (|w_pm| S_EM + S_NM) for the pre-combined one, S over |w_i v_i|, P_cls the rows of the class with
@@ -16,15 +16,10 @@ import os
 import numpy as np
 import pytest
 
-from test_cohort_reduction import (MULTI_BATCH, MULTI_BATCH_WS, Reference, U, _cohort, _params, _within, raw_layout, red_per, stride,
-                                   wsums_layout)
+import reduction_common as RC
+from eval_common import GOLDEN, close, close_grads, engine_pool
+from reduction_common import MULTI_BATCH, MULTI_BATCH_WS, N4, PERC_MET, W_PM, WEIGHT_VALUES, Reference, U, raw_layout, red_per, stride, wsums_layout
 from unknown_common import unknown_row
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-WEIGHT_VALUES = np.array([0.0, 0.5, 1.0, 2.0, 3.0, 7.25])
-W_PM = 0.37                                                   # EM / NM weight of the pre-combined buffer
-PERC_MET = 0.3
-N4 = 4
 
 
 def _weights(P, seed, zeros=True):
@@ -34,11 +29,6 @@ def _weights(P, seed, zeros=True):
     if P > 1:
         w[0], w[1] = 7.25, 0.5                                # (neighbours that differ: a shifted or permuted weight shows)
     return w
-
-
-def _nm_class(dat):
-    """Rows of the NM sums: type 0 and type 4 (unknown status, weight 1 of their own)."""
-    return (dat[:, -1] == 0) | (dat[:, -1] == 4)
 
 
 def _counts(dat, w):
@@ -53,7 +43,7 @@ def _counts(dat, w):
 
 class WeightedReference:
     """Exact weighted per-class sums of the rows [P, st] with the bound of the module docstring (weights None: all one, the
-    unweighted bound of test_cohort_reduction)."""
+    unweighted bound of tests/test_cohort_reduction.py)."""
 
     def __init__(self, rows, w, dat, N, spread=None):
         self.N = N
@@ -62,7 +52,7 @@ class WeightedReference:
         keep = w != 0
         self.counts = _counts(dat, w)
         sp = None if spread is None else spread[keep] * w[keep, None]
-        self.r = Reference(rows[keep] * w[keep, None], _nm_class(dat)[keep], self.counts[0], N, sp)
+        self.r = Reference(rows[keep] * w[keep, None], RC.nm_class(dat)[keep], self.counts[0], N, sp)
 
     def raw(self):
         r, x = self.r, self.extra
@@ -84,11 +74,6 @@ class WeightedReference:
         return self.wsums(w_pm)[1] / n_full, (w_pm, n_full)
 
 
-def _flat(res):
-    """(score, d_theta, d_dp, d_dm) as one vector in the order of the pre-combined buffer."""
-    return np.concatenate(([float(res[0])], np.ravel(res[1]), np.ravel(res[2]), np.ravel(res[3])))
-
-
 # ---- CPU: collapse_rows -------------------------------------------------------------------------------------------------------
 
 def _check_collapse(dat):
@@ -107,7 +92,7 @@ def _check_collapse(dat):
 
 def test_collapse_rows_hand_cohort():
     n = N4
-    base = _cohort(n, 33)
+    base = RC.cohort(n, 33)
     t4 = np.array([unknown_row(n, []), unknown_row(n, [1, 3]), unknown_row(n, [])], dtype=np.int8)
     dat = np.vstack((base[5:8], t4, base[:12], base[5:8], t4[1:], base[30:]))
     rows, counts, inverse = _check_collapse(dat)
@@ -166,8 +151,8 @@ def _replay_case(P, batches, seed, defect=False):
     w = _weights(P, seed + 1)
     order = [rng.permutation(nb) for nb in batches]
     ref = WeightedReference(rows, w, dat, N)
-    r1 = _within(_replay_w(rows, kinds, w, batches, order, N, 1, ref.counts[0], ref.counts[1], defect), *ref.raw(), "replayed raw")
-    r2 = _within(_replay_w(rows, kinds, w, batches, order, N, 2, W_PM, 0.0, defect), *ref.wsums(W_PM), "replayed pre-combined")
+    r1 = RC.within(_replay_w(rows, kinds, w, batches, order, N, 1, ref.counts[0], ref.counts[1], defect), *ref.raw(), "replayed raw")
+    r2 = RC.within(_replay_w(rows, kinds, w, batches, order, N, 2, W_PM, 0.0, defect), *ref.wsums(W_PM), "replayed pre-combined")
     return max(r1, r2)
 
 
@@ -191,19 +176,10 @@ def test_weights_in_row_order_break_the_bound(P, batches):
 
 # ---- CPU: the host code around the engine -----------------------------------------------------------------------------------
 
-def _typed_cohort(n, P, seed):
-    """_cohort with every seventh row replaced by a row of type 4 (the empty genotype among them)."""
-    dat = _cohort(n, P).copy()
-    rng = np.random.default_rng(seed)
-    for k, r in enumerate(range(3, P, 7)):
-        dat[r] = unknown_row(n, [] if k == 0 else rng.choice(n, size=int(rng.integers(1, n)), replace=False))
-    return dat
-
-
 def test_shard_weight_slices_cover_the_vector():
     import metmhn_amd.regularized_optimization as ro
     from metmhn_amd import distributed as D
-    dat = _typed_cohort(N4, 97, 3)
+    dat = RC.typed_cohort(N4, 97, 3)
     w = _weights(97, 5)
     w = w + np.arange(97) * 2.0 ** -20                        # (all different: a slice taken with other indices shows)
     for world in (1, 2, 3, 8):
@@ -218,7 +194,7 @@ def test_shard_weight_slices_cover_the_vector():
 
 def test_weighted_global_counts_against_a_loop():
     import metmhn_amd.regularized_optimization as ro
-    dat = _typed_cohort(N4, 97, 3)
+    dat = RC.typed_cohort(N4, 97, 3)
     assert ro._global_counts(dat) == _counts(dat, np.ones(97)) == (float(dat[:, -3].sum()), 97.0, float((dat[:, -1] == 4).sum()))
     for seed in range(4):
         w = _weights(97, seed)
@@ -251,70 +227,34 @@ def test_bootstrap_result_summaries():
 
 @pytest.fixture(scope="module")
 def make_engine():
-    """Engines kept for the module (at most four alive), created under MMHN_POISON=1; zerocopy=False: MMHN_ZEROCOPY=0."""
-    from metmhn_amd import Engine
-    live = {}
-
-    def get(n=N4, zerocopy=True, dtype="f64", workspace=None, tag=0):
-        key = (n, zerocopy, dtype, workspace, tag)
-        if key not in live:
-            while len(live) >= 4:
-                live.pop(next(iter(live))).close()
-            with pytest.MonkeyPatch.context() as mp:
-                mp.setenv("MMHN_POISON", "1")
-                if zerocopy:
-                    mp.delenv("MMHN_ZEROCOPY", raising=False)
-                else:
-                    mp.setenv("MMHN_ZEROCOPY", "0")
-                live[key] = Engine(n, dtype=dtype, workspace_bytes=workspace)
-        live[key] = live.pop(key)
-        return live[key]
-    yield get
-    for e in live.values():
-        e.close()
-
-
-def _rows(e, lt, dp, dm, with_grad=True):
-    """The engine's per-row values [P, st] = [lp, G, d_dp, d_dm] (with_grad=False: lp and zeros): never weighted."""
-    P, N = e.n_pat, e.N
-    rows = np.zeros((P, stride(N)))
-    if not with_grad:
-        rows[:, 0] = e.patient_grads(lt, dp, dm, with_grad=False)
-        return rows
-    lp, g, gp, gm = e.patient_grads(lt, dp, dm)
-    return np.concatenate((lp[:, None], g.reshape(P, N * N), gp, gm), axis=1)
+    yield from engine_pool()
 
 
 def _references(e, dat, w, lt, dp, dm, score_only=True):
     """(reference of a gradient evaluation, of a score-only one - None with score_only=False) of engine `e` holding `dat` with
     weights `w` (None: none), each with the spread of two downloads of the rows in its bound."""
     keep = slice(None) if w is None else np.asarray(w) != 0
-    r1, r2 = _rows(e, lt, dp, dm), _rows(e, lt, dp, dm)
+    r1, r2 = RC.rows_of(e, lt, dp, dm), RC.rows_of(e, lt, dp, dm)
     assert np.isfinite(r1[keep]).all()
     ref = WeightedReference(r1, w, dat, e.N, np.abs(r1 - r2))
     if not score_only:
         return ref, None
-    s1, s2 = _rows(e, lt, dp, dm, False), _rows(e, lt, dp, dm, False)
+    s1, s2 = RC.rows_of(e, lt, dp, dm, False), RC.rows_of(e, lt, dp, dm, False)
     assert np.isfinite(s1[keep]).all()
     return ref, WeightedReference(s1, w, dat, e.N, np.abs(s1 - s2))
-
-
-def _wsums(e, lt, dp, dm, w_pm, with_grad=True):
-    e.cohort_wsums_begin(lt, dp, dm, w_pm, with_grad=with_grad)
-    return e.cohort_wsums_end()
 
 
 def _check_weighted(e, dat, w, lt, dp, dm, tag):
     """Both buffers of `e` (holding dat and w) with and without gradients against its own rows; the raw sums."""
     ref, ref0 = _references(e, dat, w, lt, dp, dm)
     s = e.cohort_sums(lt, dp, dm)
-    a = _within(s, *ref.raw(), tag + " cohort_sums")
+    a = RC.within(s, *ref.raw(), tag + " cohort_sums")
     s0 = e.cohort_sums(lt, dp, dm, with_grad=False)
-    _within(s0, *ref0.raw(), tag + " cohort_sums(with_grad=False)")
+    RC.within(s0, *ref0.raw(), tag + " cohort_sums(with_grad=False)")
     assert not s0[4:].any(), f"{tag}: gradient entries of a score-only evaluation"
-    b = _within(_wsums(e, lt, dp, dm, W_PM), *ref.wsums(W_PM), tag + " cohort_wsums")
-    ws0 = _wsums(e, lt, dp, dm, W_PM, with_grad=False)
-    _within(ws0, *ref0.wsums(W_PM), tag + " cohort_wsums(with_grad=False)")
+    b = RC.within(RC.wsums(e, lt, dp, dm, W_PM), *ref.wsums(W_PM), tag + " cohort_wsums")
+    ws0 = RC.wsums(e, lt, dp, dm, W_PM, with_grad=False)
+    RC.within(ws0, *ref0.wsums(W_PM), tag + " cohort_wsums(with_grad=False)")
     assert not ws0[1:].any(), f"{tag}: gradient entries of a score-only weighted evaluation"
     assert (s[2], s[3]) == ref.counts[:2] and e.row_weight_sums == ref.counts, f"{tag}: counts {s[2:4]}, {e.row_weight_sums}"
     print(f"{tag}: worst error / bound: raw {a:.3f}, pre-combined {b:.3f}")
@@ -326,20 +266,20 @@ def _check_weighted(e, dat, w, lt, dp, dm, tag):
 def test_weights_of_one_change_nothing(make_engine, zerocopy):
     """w = 1 everywhere: the same bits as without weights in both buffers and in mmhn_score_and_grad - and again after the
     weights are removed."""
-    lt, dp, dm = _params(N4)
-    dat = _cohort(N4, 4097)
-    e = make_engine(zerocopy=zerocopy)
+    lt, dp, dm = RC.params(N4)
+    dat = RC.cohort(N4, 4097)
+    e = make_engine(N4, zerocopy=zerocopy)
     e.set_cohort(dat)
     assert e.row_weights is None
-    plain = [e.cohort_sums(lt, dp, dm), e.cohort_sums(lt, dp, dm, with_grad=False), _wsums(e, lt, dp, dm, W_PM),
-             _wsums(e, lt, dp, dm, W_PM, with_grad=False), _flat(e.score_and_grad(lt, dp, dm, PERC_MET)), e.score(lt, dp, dm, PERC_MET)]
+    plain = [e.cohort_sums(lt, dp, dm), e.cohort_sums(lt, dp, dm, with_grad=False), RC.wsums(e, lt, dp, dm, W_PM),
+             RC.wsums(e, lt, dp, dm, W_PM, with_grad=False), RC.flat(e.score_and_grad(lt, dp, dm, PERC_MET)), e.score(lt, dp, dm, PERC_MET)]
     counts = e.row_weight_sums
     assert counts == (float(dat[:, -3].sum()), 4097.0, 0.0)
     for w in (np.ones(4097), None, _weights(4097, 1), np.ones(4097)):
         e.set_row_weights(w)
         assert (e.row_weights is None) if w is None else np.array_equal(e.row_weights, w)
-        got = [e.cohort_sums(lt, dp, dm), e.cohort_sums(lt, dp, dm, with_grad=False), _wsums(e, lt, dp, dm, W_PM),
-               _wsums(e, lt, dp, dm, W_PM, with_grad=False), _flat(e.score_and_grad(lt, dp, dm, PERC_MET)), e.score(lt, dp, dm, PERC_MET)]
+        got = [e.cohort_sums(lt, dp, dm), e.cohort_sums(lt, dp, dm, with_grad=False), RC.wsums(e, lt, dp, dm, W_PM),
+               RC.wsums(e, lt, dp, dm, W_PM, with_grad=False), RC.flat(e.score_and_grad(lt, dp, dm, PERC_MET)), e.score(lt, dp, dm, PERC_MET)]
         same = all(np.array_equal(a, b) for a, b in zip(got, plain))
         if w is not None and not (w == 1).all():
             assert not same and e.row_weight_sums != counts   # (the weights in between do reach the sums)
@@ -357,11 +297,11 @@ WEIGHTED_SHAPES = [(1, "f64", None), (32, "f64", None), (33, "f64", None), (4097
 @pytest.mark.parametrize("P,dtype,workspace", WEIGHTED_SHAPES, ids=[f"P{P}-{d}-{'multibatch' if ws else 'onebatch'}" for P, d, ws in WEIGHTED_SHAPES])
 def test_weighted_sums_against_the_reference(make_engine, P, dtype, workspace):
     """Both buffers, with and without gradient, against the weighted reference under the bound; the MULTI_BATCH cohort under
-    MULTI_BATCH_WS is cut into at least three batches (test_cohort_reduction.test_multi_batch_reduction), where the order of
+    MULTI_BATCH_WS is cut into at least three batches (test_cohort_reduction.py: test_multi_batch_reduction), where the order of
     the patients of a batch and the order of the cohort's rows part."""
     n = MULTI_BATCH[0] if workspace else N4
-    lt, dp, dm = _params(n)
-    dat = _cohort(n, P)
+    lt, dp, dm = RC.params(n)
+    dat = RC.cohort(n, P)
     w = _weights(P, 10 + P)
     e = make_engine(n, dtype=dtype, workspace=workspace)
     e.set_cohort(dat)
@@ -380,7 +320,7 @@ def _definition_case(u, c, tag, with_collapse=True):
     import metmhn_amd.regularized_optimization as ro
     from metmhn_amd import Utilityfunctions as UF
     n = (u.shape[1] - 3) // 2
-    lt, dp, dm = _params(n)
+    lt, dp, dm = RC.params(n)
     full = np.repeat(u, c.astype(np.int64), axis=0)
     try:
         got_w = ro.score_and_grad(lt, dp, dm, u, PERC_MET, weights=c)
@@ -395,7 +335,7 @@ def _definition_case(u, c, tag, with_collapse=True):
         bw, (w_pm, n_full) = ref_w.objective_bound(PERC_MET)
         bf, (w_pm_f, n_full_f) = ref_f.objective_bound(PERC_MET)
         assert (w_pm, n_full) == (w_pm_f, n_full_f)
-        ratio = _within(_flat(got_w), _flat(got_f), bw + bf, tag + ": weighted against repeated rows")
+        ratio = RC.within(RC.flat(got_w), RC.flat(got_f), bw + bf, tag + ": weighted against repeated rows")
         print(f"{tag}: worst |weighted - repeated| / (sum of the bounds) {ratio:.3f}, w_pm {w_pm:.4f}, n_full {n_full}")
         if with_collapse:
             rows, counts, inverse = UF.collapse_rows(full)
@@ -403,7 +343,7 @@ def _definition_case(u, c, tag, with_collapse=True):
             np.testing.assert_array_equal(counts, c)
             got_c = ro.score_and_grad(lt, dp, dm, rows, PERC_MET, weights=counts)
             ref_c, _ = _references(ro._engine_for(rows, check=False), rows, counts, lt, dp, dm)
-            _within(_flat(got_c), _flat(got_f), ref_c.objective_bound(PERC_MET)[0] + bf, tag + ": collapse_rows fed back")
+            RC.within(RC.flat(got_c), RC.flat(got_f), ref_c.objective_bound(PERC_MET)[0] + bf, tag + ": collapse_rows fed back")
             ro.invalidate(rows)
     finally:
         ro.invalidate(u)
@@ -419,7 +359,7 @@ def _distinct(dat):
 def test_integer_weights_are_repeated_rows(U_rows):
     """The definition: integer weights c on distinct rows u give the objective of np.repeat(u, c), within the sum of the two
     sides' bounds over n_full; collapse_rows of the repeated array, fed back, gives it too."""
-    u = _distinct(_cohort(N4, 1500))[:U_rows]
+    u = _distinct(RC.cohort(N4, 1500))[:U_rows]
     assert u.shape[0] == U_rows
     rng = np.random.default_rng(U_rows)
     c = rng.choice([1.0, 2.0, 3.0, 7.0, 40.0], size=U_rows)
@@ -431,14 +371,14 @@ def test_weighted_rows_of_unknown_status():
     """Rows of type 4 with weights, among rows of types 0 - 3 and with the empty genotype: the weighted n_unknown of
     mmhn_get_row_weight_sums and the objective by the definition."""
     from metmhn_amd import Engine
-    u = _distinct(_typed_cohort(N4, 120, 9))
+    u = _distinct(RC.typed_cohort(N4, 120, 9))
     t4 = u[:, -1] == 4
     assert t4.sum() >= 5 and (t4 & (u[:, :2 * N4].sum(axis=1) == 0)).any() and set(np.unique(u[:, -1])) == {0, 1, 2, 3, 4}
     c = np.random.default_rng(4).choice([1.0, 2.0, 3.0, 5.0], size=u.shape[0])
     _definition_case(u, c, "with type-4 rows")
     w = _weights(u.shape[0], 8)
     w[np.flatnonzero(t4)[:3]] = (7.25, 0.0, 0.5)
-    lt, dp, dm = _params(N4)
+    lt, dp, dm = RC.params(N4)
     with Engine(N4) as e:
         e.set_cohort(u)
         assert e.n_unknown == int(t4.sum()) and e.row_weight_sums[2] == float(t4.sum())
@@ -448,7 +388,7 @@ def test_weighted_rows_of_unknown_status():
         # mmhn_score_and_grad weights with the real-valued n_unknown
         bound, (w_pm, n_full) = ref.objective_bound(PERC_MET)
         exact = ref.wsums(w_pm)[0] / n_full
-        _within(_flat(e.score_and_grad(lt, dp, dm, PERC_MET)), exact, bound + 2 * U * np.abs(exact), "mmhn_score_and_grad with type-4 weights")
+        RC.within(RC.flat(e.score_and_grad(lt, dp, dm, PERC_MET)), exact, bound + 2 * U * np.abs(exact), "mmhn_score_and_grad with type-4 weights")
 
 
 @pytest.mark.gpu
@@ -457,8 +397,8 @@ def test_weight_zero_is_absence(make_engine, zero):
     """A cohort with weights equals the cohort of its rows with w != 0 (with their weights): sums under the two bounds, counts
     equal.  every_em: no EM row is left, the objective takes the w = 1 branch of em_weight."""
     from metmhn_amd import distributed as D
-    lt, dp, dm = _params(N4)
-    dat = _typed_cohort(N4, 200, 2)
+    lt, dp, dm = RC.params(N4)
+    dat = RC.typed_cohort(N4, 200, 2)
     w = _weights(200, 21)
     if zero == "every_em":
         w[dat[:, -3] == 1] = 0.0
@@ -466,7 +406,7 @@ def test_weight_zero_is_absence(make_engine, zero):
         w[dat[:, -1] == 0] = 0.0
     keep = w != 0
     assert 0 < keep.sum() < 200 and (w == 0).sum() >= 20
-    a, b = make_engine(tag=1), make_engine(tag=2)
+    a, b = make_engine(N4, tag=1), make_engine(N4, tag=2)
     a.set_cohort(dat)
     a.set_row_weights(w)
     b.set_cohort(dat[keep])
@@ -474,14 +414,14 @@ def test_weight_zero_is_absence(make_engine, zero):
     sa, ref_a = _check_weighted(a, dat, w, lt, dp, dm, f"zero={zero} whole cohort")
     sb, ref_b = _check_weighted(b, dat[keep], w[keep], lt, dp, dm, f"zero={zero} rows with w != 0")
     assert a.row_weight_sums == b.row_weight_sums and tuple(sa[2:4]) == tuple(sb[2:4])
-    _within(sa, sb, ref_a.raw()[1] + ref_b.raw()[1], f"zero={zero}: raw sums of the two cohorts")
+    RC.within(sa, sb, ref_a.raw()[1] + ref_b.raw()[1], f"zero={zero}: raw sums of the two cohorts")
     bound_a, (w_pm, n_full) = ref_a.objective_bound(PERC_MET)
     bound_b, same = ref_b.objective_bound(PERC_MET)
     assert same == (w_pm, n_full)
     if zero != "some":
         assert w_pm == 1.0 and n_full == a.row_weight_sums[1]
-    got_a, got_b = _flat(a.score_and_grad(lt, dp, dm, PERC_MET)), _flat(b.score_and_grad(lt, dp, dm, PERC_MET))
-    _within(got_a, got_b, bound_a + bound_b, f"zero={zero}: objective of the two cohorts")
+    got_a, got_b = RC.flat(a.score_and_grad(lt, dp, dm, PERC_MET)), RC.flat(b.score_and_grad(lt, dp, dm, PERC_MET))
+    RC.within(got_a, got_b, bound_a + bound_b, f"zero={zero}: objective of the two cohorts")
     # weight 1 on the kept rows: the plain cohort of those rows, no weights at all
     ones = keep.astype(np.float64)
     a.set_row_weights(ones)
@@ -489,7 +429,7 @@ def test_weight_zero_is_absence(make_engine, zero):
     assert a.row_weight_sums == b.row_weight_sums == _counts(dat[keep], np.ones(int(keep.sum())))
     ra, _ = _references(a, dat, ones, lt, dp, dm)
     rb, _ = _references(b, dat[keep], None, lt, dp, dm)
-    _within(a.cohort_sums(lt, dp, dm), b.cohort_sums(lt, dp, dm), ra.raw()[1] + rb.raw()[1], f"zero={zero}: 0 / 1 weights against the sub-cohort")
+    RC.within(a.cohort_sums(lt, dp, dm), b.cohort_sums(lt, dp, dm), ra.raw()[1] + rb.raw()[1], f"zero={zero}: 0 / 1 weights against the sub-cohort")
     assert D.em_weight(*a.row_weight_sums[:2], PERC_MET, a.row_weight_sums[2]) == D.em_weight(*b.row_weight_sums[:2], PERC_MET, b.row_weight_sums[2])
 
 
@@ -498,9 +438,9 @@ def test_refusals(make_engine):
     """Every refused vector raises with a message that names the row and leaves the weights held before in place; a call
     between _begin and _end is refused and the pending evaluation delivers the old result; set_cohort clears the weights."""
     from metmhn_amd import Engine, _lib
-    lt, dp, dm = _params(N4)
-    dat = _cohort(N4, 33)
-    e = make_engine(tag=3)
+    lt, dp, dm = RC.params(N4)
+    dat = RC.cohort(N4, 33)
+    e = make_engine(N4, tag=3)
     e.set_cohort(dat)
     w = _weights(33, 3)
     e.set_row_weights(w)
@@ -556,8 +496,8 @@ def test_guard_rebuild_keeps_the_weights():
     """dat edited in place between two ro.score(..., weights=w): the guard's rebuild (set_cohort clears the weights) applies
     them again - the second value is that of a fresh engine on the edited array with w."""
     import metmhn_amd.regularized_optimization as ro
-    lt, dp, dm = _params(N4)
-    dat = _cohort(N4, 33).copy()
+    lt, dp, dm = RC.params(N4)
+    dat = RC.cohort(N4, 33).copy()
     w = _weights(33, 6)
     w[2] = 3.0
     try:
@@ -571,8 +511,8 @@ def test_guard_rebuild_keeps_the_weights():
         fresh = ro.score(lt, dp, dm, fresh_dat, PERC_MET, weights=w)
         assert ro._engine_for(fresh_dat, check=False) is not eng
         assert after == fresh and after != before
-        g_after = _flat(ro.score_and_grad(lt, dp, dm, dat, PERC_MET, weights=w))
-        np.testing.assert_array_equal(g_after, _flat(ro.score_and_grad(lt, dp, dm, fresh_dat, PERC_MET, weights=w)))
+        g_after = RC.flat(ro.score_and_grad(lt, dp, dm, dat, PERC_MET, weights=w))
+        np.testing.assert_array_equal(g_after, RC.flat(ro.score_and_grad(lt, dp, dm, fresh_dat, PERC_MET, weights=w)))
         # other weights on the cached cohort: no new engine, the counts follow; None removes them
         w2 = w[::-1].copy()
         s2 = ro.score(lt, dp, dm, dat, PERC_MET, weights=w2)
@@ -590,16 +530,16 @@ def test_guard_rebuild_keeps_the_weights():
 def test_one_rank_collective_path(monkeypatch):
     """MMHN_FORCE_ALLREDUCE=1: the weighted objective through the in-library all-reduce of one rank equals the plain path."""
     import metmhn_amd.regularized_optimization as ro
-    lt, dp, dm = _params(N4)
-    dat = _typed_cohort(N4, 200, 5)
+    lt, dp, dm = RC.params(N4)
+    dat = RC.typed_cohort(N4, 200, 5)
     w = _weights(200, 12)
     try:
-        plain = _flat(ro.score_and_grad(lt, dp, dm, dat, PERC_MET, weights=w))
+        plain = RC.flat(ro.score_and_grad(lt, dp, dm, dat, PERC_MET, weights=w))
         assert not ro._engine_for(dat, check=False)._sharded
         monkeypatch.setenv("MMHN_FORCE_ALLREDUCE", "1")
         monkeypatch.setenv("MMHN_STRICT_COMM", "1")
         other = dat.copy()
-        forced = _flat(ro.score_and_grad(lt, dp, dm, other, PERC_MET, weights=w))
+        forced = RC.flat(ro.score_and_grad(lt, dp, dm, other, PERC_MET, weights=w))
         eng = ro._engine_for(other, check=False)
         assert eng._sharded and eng._device_comm and np.array_equal(eng.row_weights, w)
         np.testing.assert_array_equal(forced, plain)
@@ -613,7 +553,7 @@ def test_bootstrap_fits():
     """60 rows, 3 replicates of 5 iterations: reproducible by key, the documented draw, every replicate the weighted fit."""
     import metmhn_amd.regularized_optimization as ro
     from metmhn_amd import Utilityfunctions as UF
-    dat = _typed_cohort(N4, 60, 1)
+    dat = RC.typed_cohort(N4, 60, 1)
     dat[40:50] = dat[10:20]                                   # duplicates: fewer distinct rows than rows
     pm, lam, N = PERC_MET, 1e-2, N4 + 1
     try:
@@ -652,7 +592,7 @@ def test_bootstrap_fits():
 @pytest.mark.gpu
 def test_luad28_collapsed(golden):
     """The 28-event LUAD cohort as its 3 297 distinct rows with their counts as weights, against the fixture of
-    test_gpu_parity.test_luad28_real_workload with its tolerances; with the 1 227 primaries of unknown status appended, the
+    test_gpu_parity.py: test_luad28_real_workload with its tolerances; with the 1 227 primaries of unknown status appended, the
     collapsed cohort against the uncollapsed one, each side under the bound of its own rows."""
     from metmhn_amd import Engine, Utilityfunctions as UF
     g = golden("luad28")
@@ -665,12 +605,9 @@ def test_luad28_collapsed(golden):
         assert e.row_weight_sums == (float(g["dat"][:, -3].sum()), 4852.0, 0.0)
         for pt in ("indep", "fit"):
             lt, a, b = g[pt + "_theta"], g[pt + "_dp"], g[pt + "_dm"]
-            s, G, ga, gb = e.score_and_grad(lt, a, b, pm)
-            np.testing.assert_allclose(s, g[pt + "_score"], rtol=1e-9, err_msg=pt)
-            np.testing.assert_allclose(G, g[pt + "_d_th"], rtol=1e-7, atol=1e-10, err_msg=pt)
-            np.testing.assert_allclose(ga, g[pt + "_d_dp"], rtol=1e-7, atol=1e-10, err_msg=pt)
-            np.testing.assert_allclose(gb, g[pt + "_d_dm"], rtol=1e-7, atol=1e-10, err_msg=pt)
-            np.testing.assert_allclose(float(e.score(lt, a, b, pm)), g[pt + "_score"], rtol=1e-9)
+            close_grads(f"collapsed LUAD-28 {pt}", e.score_and_grad(lt, a, b, pm), [g[pt + s] for s in ("_score", "_d_th", "_d_dp", "_d_dm")],
+                        (1e-9, 0.0), (1e-7, 1e-10))
+            close(f"collapsed LUAD-28 {pt} score", float(e.score(lt, a, b, pm)), g[pt + "_score"], 1e-9)
     unknown = np.load(os.path.join(GOLDEN, "luad28_unknown_rows.npy"))
     dat = np.vstack((g["dat"], unknown))
     rows, counts, _ = UF.collapse_rows(dat)
@@ -684,12 +621,12 @@ def test_luad28_collapsed(golden):
         ref_c, _ = _references(e, rows, counts, lt, a, b, score_only=False)
         ref_f, _ = _references(full, dat, None, lt, a, b, score_only=False)
         sc, sf = e.cohort_sums(lt, a, b), full.cohort_sums(lt, a, b)
-        r1 = _within(sc, *ref_c.raw(), "LUAD-28 + unknown, collapsed, against its own rows")
-        r2 = _within(sc, sf, ref_c.raw()[1] + ref_f.raw()[1], "LUAD-28 + unknown: collapsed against uncollapsed sums")
+        r1 = RC.within(sc, *ref_c.raw(), "LUAD-28 + unknown, collapsed, against its own rows")
+        r2 = RC.within(sc, sf, ref_c.raw()[1] + ref_f.raw()[1], "LUAD-28 + unknown: collapsed against uncollapsed sums")
         bc, (w_pm, n_full) = ref_c.objective_bound(pm)
         bf, same = ref_f.objective_bound(pm)
         assert same == (w_pm, n_full)
-        r3 = _within(_flat(e.score_and_grad(lt, a, b, pm)), _flat(full.score_and_grad(lt, a, b, pm)), bc + bf,
+        r3 = RC.within(RC.flat(e.score_and_grad(lt, a, b, pm)), RC.flat(full.score_and_grad(lt, a, b, pm)), bc + bf,
                      "LUAD-28 + unknown: collapsed against uncollapsed objective")
         print(f"LUAD-28 + unknown rows, {rows.shape[0]} distinct of {dat.shape[0]}: worst error / bound {r1:.3f} (own rows), "
               f"{r2:.3f} (sums), {r3:.3f} (objective)")

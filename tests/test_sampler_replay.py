@@ -20,8 +20,7 @@ import pytest
 
 from metmhn_amd import synthetic
 from oracle import sampler_replay as R
-from test_montecarlo import N_SIM, _cases, sim  # noqa: F401  (sim: the module's parameters and NumPy samples)
-from test_simulate_summary import host_counts
+from sampler_common import N_SIM, cases, host_counts, sim  # noqa: F401  (sim: the module's parameters and NumPy samples)
 
 MARGIN = 1e-11            # a trajectory whose closest draw is nearer than this to a boundary is not compared
 MAX_EXCLUDED = 1e-3       # share of one test's trajectories that may be set aside
@@ -92,10 +91,10 @@ def replayed(sim):  # noqa: F811
 
 
 def test_replay_matches_analytic_probabilities(sim, replayed):  # noqa: F811
-    """The nine rows of test_montecarlo._cases: replayed frequency against the oracle's probability, 4.5 sigma."""
+    """The nine rows of sampler_common.cases: replayed frequency against the oracle's probability, 4.5 sigma."""
     from oracle import metmhn_oracle as O
     lt, dp, dm, _ = sim
-    for name, row, count in _cases(replayed.dat):
+    for name, row, count in cases(replayed.dat):
         p = float(np.exp(O.score(lt, dp, dm, np.array([row], dtype=np.int8), 0)))
         sigma = np.sqrt(p * (1 - p) / N_SIM)
         assert count >= 25, f"{name}: too few samples ({count})"

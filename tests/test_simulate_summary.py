@@ -12,18 +12,7 @@ import pytest
 from metmhn_amd import Engine, synthetic
 from metmhn_amd import Utilityfunctions as U
 from metmhn_amd import simulations as S
-
-
-def host_counts(d, od, n_mut):
-    """The counts of include/metmhn_amd.h, from simulate_dat rows d and simulate_orders rows od."""
-    N = n_mut + 1
-    seeded = d[:, -2] == 1
-    ptb, mtb = d[:, 0:2 * n_mut:2].astype(np.int64), d[:, 1:2 * n_mut:2].astype(np.int64)
-    bsc, _ = S.extract_bse(od, N, N - 1)
-    head = [len(d), seeded.sum(), (d[:, -1] == 1).sum(), (d[:, -1] == 2).sum()]
-    rows = [bsc[:, :-1].sum(axis=0), ptb[seeded].sum(axis=0), mtb[seeded].sum(axis=0), (ptb & mtb)[seeded].sum(axis=0),
-            ptb[~seeded].sum(axis=0)]
-    return np.concatenate([np.array(head, dtype=np.int64)] + [r.astype(np.int64) for r in rows])
+from sampler_common import host_counts
 
 
 def typed_cohort(d):

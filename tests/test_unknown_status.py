@@ -7,9 +7,10 @@ import os
 import numpy as np
 import pytest
 
+import reduction_common as RC
 import unknown_common as UC
+from eval_common import GOLDEN
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 PERC_MET = 0.3
 
 
@@ -127,11 +128,6 @@ def _engine(monkeypatch, n, dtype="f64", env=None, workspace=None):
     return Engine(n, dtype=dtype, workspace_bytes=workspace)
 
 
-def _rows(e, lt, dp, dm):
-    import test_cohort_reduction as CR
-    return CR._rows_of(e, lt, dp, dm)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("env", ({}, {"MMHN_SMALL": "0"}, {"MMHN_POISON": "1"}), ids=("default", "staged", "poison"))
 @pytest.mark.parametrize("dtype", ("f64", "f32"))
@@ -172,9 +168,8 @@ def test_shapes_against_the_engines_own_rows(monkeypatch, dtype):
 
 
 def _mixed(n=6, P=60, n_unknown=20, seed=11):
-    """test_cohort_reduction's mixed cohort (every type and order code) with type-4 rows of 0 .. n events dealt between its rows."""
-    import test_cohort_reduction as CR
-    known = CR._cohort(n, P)
+    """reduction_common.cohort's mixed cohort (every type and order code) with type-4 rows of 0 .. n events dealt between its rows."""
+    known = RC.cohort(n, P)
     rng = np.random.default_rng(seed)
     unknown = np.array([UC.unknown_row(n, rng.choice(n, size=i % (n + 1), replace=False)) for i in range(n_unknown)], dtype=np.int8)
     at = np.sort(rng.choice(P + 1, size=n_unknown, replace=True))
@@ -188,7 +183,6 @@ def test_mixed_cohort_sums_and_objective(monkeypatch):
     """cohort_sums = the per-patient rows added per class (type-4 rows in the weight-1 class), within the recursive-summation
     bound of tests/test_cohort_reduction.py; score_and_grad = the definition built from the rows and the counts; score = its
     first output; the objective layer (regularized_optimization) gives the same numbers."""
-    import test_cohort_reduction as CR
     from metmhn_amd import distributed as D, regularized_optimization as ro
     n = 6
     lt, dp, dm = UC.params(n)
@@ -196,12 +190,12 @@ def test_mixed_cohort_sums_and_objective(monkeypatch):
     with _engine(monkeypatch, n) as e:
         e.set_cohort(dat)
         assert e.n_unknown == 20
-        r1, r2 = _rows(e, lt, dp, dm), _rows(e, lt, dp, dm)
+        r1, r2 = RC.rows_of(e, lt, dp, dm), RC.rows_of(e, lt, dp, dm)
         assert np.array_equal(r1, r2) and np.isfinite(r1).all()
         cls1 = np.isin(dat[:, -1], (0, 4))
-        ref = CR.Reference(r1, cls1, float(dat[:, -3].sum()), n + 1)
+        ref = RC.Reference(r1, cls1, float(dat[:, -3].sum()), n + 1)
         sums = e.cohort_sums(lt, dp, dm)
-        print(f"cohort_sums: worst error / bound {CR.check_raw(sums, ref, 'cohort_sums with type-4 rows'):.3f}")
+        print(f"cohort_sums: worst error / bound {RC.check_raw(sums, ref, 'cohort_sums with type-4 rows'):.3f}")
         s, g, a, b = e.score_and_grad(lt, dp, dm, PERC_MET)
         s_only = e.score(lt, dp, dm, PERC_MET)
     want = UC.objective(r1, dat, PERC_MET)
@@ -210,11 +204,11 @@ def test_mixed_cohort_sums_and_objective(monkeypatch):
     # bound, as for the pre-combined buffer of tests/test_cohort_reduction.py: the class sums are within (P_cls + 2) u S of the
     # exact ones, the weighting and the division add four roundings: (P + 8) u (w S_EM + S_NM) / n_full per element
     flat = lambda t: np.concatenate(([t[0]], np.ravel(t[1]), t[2], t[3]))
-    bound = (dat.shape[0] + 8) * CR.U * (w * ref.abs_em + ref.abs_nm) / n_full
+    bound = (dat.shape[0] + 8) * RC.U * (w * ref.abs_em + ref.abs_nm) / n_full
     want_v = flat(want)
     for name, got_v in (("Engine.score_and_grad", flat((s, g, a, b))), ("distributed.combine_sums", flat(D.combine_sums(sums, n + 1, PERC_MET, 20))),
                         ("regularized_optimization.score_and_grad", flat(ro.score_and_grad(lt, dp, dm, dat, PERC_MET)))):
-        print(f"{name} against the definition: worst error / bound {CR._within(got_v, want_v, bound, name):.3f}")
+        print(f"{name} against the definition: worst error / bound {RC.within(got_v, want_v, bound, name):.3f}")
     assert abs(s_only - s) <= bound[0] and abs(ro.score(lt, dp, dm, dat, PERC_MET) - s) <= bound[0], "score and score_and_grad disagree"
     ro.invalidate()
 
@@ -228,10 +222,10 @@ def test_known_rows_do_not_move(monkeypatch):
     keep = dat[:, -1] != 4
     with _engine(monkeypatch, n) as e:
         e.set_cohort(dat)
-        with_unknown = _rows(e, lt, dp, dm)
+        with_unknown = RC.rows_of(e, lt, dp, dm)
         e.set_cohort(dat[keep])
         assert e.n_unknown == 0
-        without = _rows(e, lt, dp, dm)
+        without = RC.rows_of(e, lt, dp, dm)
         _, ps = e.patient_status(lt, dp, dm)
     assert np.isnan(ps).all()
     assert np.array_equal(with_unknown[keep], without)
@@ -242,10 +236,9 @@ def test_known_rows_do_not_move_across_batches(monkeypatch):
     """The same for a cohort in several batches (workspace limit 1 MiB), a type-4 row after every third row: type-4 rows on both
     sides of every batch edge, the batches of the two cohorts cut at different rows.  The type-4 rows themselves against a
     one-batch engine, ==."""
-    import test_cohort_reduction as CR
     n, P = 6, 1500
     lt, dp, dm = UC.params(n)
-    known = CR._cohort(n, P)
+    known = RC.cohort(n, P)
     rng = np.random.default_rng(5)
     pool = np.array([UC.unknown_row(n, rng.choice(n, size=i % (n + 1), replace=False)) for i in range(P // 3)], dtype=np.int8)
     dat = np.insert(known, np.arange(3, P + 1, 3)[:len(pool)], pool, axis=0)
@@ -253,16 +246,16 @@ def test_known_rows_do_not_move_across_batches(monkeypatch):
     # (plan.h: footprint() charges every row (stride + 1) doubles and two T, and every problem N^2 + 65 T and four vectors: at
     # least three batches under 1 MiB)
     some = dat[:, 0:2 * n + 1:2].sum(axis=1) + (dat[:, -1] != 0) > 0
-    assert dat.shape[0] * ((CR.stride(n + 1) + 1) * 8 + 16) + int(some.sum()) * (((n + 1) ** 2 + 65) * 8 + 32) >= 2.5 * (1 << 20)
+    assert dat.shape[0] * ((RC.stride(n + 1) + 1) * 8 + 16) + int(some.sum()) * (((n + 1) ** 2 + 65) * 8 + 32) >= 2.5 * (1 << 20)
     with _engine(monkeypatch, n, workspace=1 << 20) as e:
         e.set_cohort(dat)
-        cut = _rows(e, lt, dp, dm)
+        cut = RC.rows_of(e, lt, dp, dm)
         _, ps_cut = e.patient_status(lt, dp, dm)
         e.set_cohort(dat[keep])
-        cut_known = _rows(e, lt, dp, dm)
+        cut_known = RC.rows_of(e, lt, dp, dm)
     with _engine(monkeypatch, n) as e:
         e.set_cohort(dat)
-        one = _rows(e, lt, dp, dm)
+        one = RC.rows_of(e, lt, dp, dm)
         _, ps_one = e.patient_status(lt, dp, dm)
     assert np.isfinite(cut).all()
     assert np.array_equal(cut[keep], cut_known)
@@ -273,7 +266,7 @@ def test_known_rows_do_not_move_across_batches(monkeypatch):
 @pytest.mark.gpu
 def test_objective_gradient_against_central_differences(monkeypatch):
     """The mixed cohort: the gradient of the regularised objective against central differences of score_reg along four random
-    directions (h = 1e-5, rtol 2e-6, atol 1e-9: the step and bar of test_gpu_parity's finite-difference test)."""
+    directions (h = 1e-5, rtol 2e-6, atol 1e-9: the step and bar of test_gpu_parity.py's finite-difference test)."""
     from metmhn_amd import regularized_optimization as ro
     n = 6
     lt, dp, dm = UC.params(n)
@@ -386,7 +379,7 @@ def test_luad28_with_unknown_primaries(monkeypatch, golden):
     """The 28-event LUAD cohort with its 1 227 primaries of unknown status (tests/golden/luad28_unknown_rows.npy, made by
     tests/tools/make_golden_luad_unknown.py) at the reference's published fit: lp and p_seeded of a fixed sample of 100 of these
     rows and of the 10 widest against the oracle's mixture; the whole cohort of 6 079 rows evaluated in the three dispatches of
-    test_gpu_parity's LUAD test, finite throughout."""
+    test_gpu_parity.py's LUAD test, finite throughout."""
     from metmhn_amd import Engine
     g = golden("luad28")
     unknown = np.load(os.path.join(GOLDEN, "luad28_unknown_rows.npy"))

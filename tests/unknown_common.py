@@ -4,8 +4,8 @@ NumPy reference and the bars.
 Reference of a type-4 row with PT genotype x: oracle.metmhn_oracle.patient_lp / patient_grad on the row relabelled as type 0
 (lp0) and as type 1 with seeding = 1 (lp1), combined here:
     lp = logaddexp(lp0, lp1),  r1 = exp(lp1 - lp) = P(seeded | x),  grad = (1 - r1) grad0 + r1 grad1,  d_dm = 0.
-Bars: the per-patient bars of tests/test_gpu_parity.py (fp64: lp rtol 1e-9 atol 1e-12, gradients rtol 1e-8 atol 1e-10; fp32: lp
-rtol 1e-4, gradients 2e-3 |ref| + 2e-5).  For p_seeded, r1 = 1 / (1 + exp(lp0 - lp1)) has |dr1 / d(lp0 - lp1)| = r1 (1 - r1) <= 1 / 4,
+Bars: the per-patient bars of tests/test_gpu_parity.py and tests/test_parity_fp32.py (fp64: lp rtol 1e-9 atol 1e-12, gradients
+rtol 1e-8 atol 1e-10; fp32: lp rtol 1e-4, gradients 2e-3 |ref| + 2e-5).  For p_seeded, r1 = 1 / (1 + exp(lp0 - lp1)) has |dr1 / d(lp0 - lp1)| = r1 (1 - r1) <= 1 / 4,
 so with each of lp0, lp1 inside the lp bar: |dr1| <= 0.25 (rtol (|lp0| + |lp1|) + 2 atol)."""
 import functools
 
