@@ -12,7 +12,10 @@
 //   * a thread works on one BLOCK of NC = 2^RB columns per step and keeps the last H = 2^HB blocks - a WINDOW of
 //     H * NC columns - in registers: moves along the RB + HB lowest column bits are register arithmetic;
 //   * everything above (the other column bits, then the row bits beyond the tenth: the EXTERNAL index Sigma) is
-//     the thread's own earlier output, re-read from global memory: (K - 15) / 2 reads per state instead of 3.5;
+//     the thread's own earlier output.  External bit 0 toggles from one window pass to the next, so the block a move
+//     along it needs is the one the thread formed a pass ago: it is still in slot beta of the window and is taken from
+//     there.  The nX - 1 bits above it are re-read from global memory: (nX - 1) / 2 reads per state (k = 20, fp64:
+//     2; k = 25, fp32: 4) instead of the 3.5 of a tile;
 //   * moves along the lane bits read the NEIGHBOUR LANE'S WINDOW REGISTERS directly (DPP / swizzle / bpermute, no
 //     LDS storage): a lane of lane-level m (popcount of l) runs m whole windows behind, so the block it needs is
 //     exactly what slot beta of the lower lane's window still holds from that lane's previous window pass;
@@ -225,7 +228,6 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
     const Desc& d0 = descs[w0.prob];
     const int k = sgpr(d0.k), kR = sgpr(w0.kR), kC = sgpr(w0.kC), nXc = sgpr(w0.nXc), nXr = sgpr(w0.nXr);
     const int nX = NXT >= 0 ? NXT : nXc + nXr;
-    constexpr bool EV2 = TR && NXT == 5;
     constexpr bool DEEP = NXT >= 7;                            // (at five external bits - k = 20 - measured slower: 13.4 against 13.1 ms)
     // table offsets: constants with the full tables, per shape with the factored ones
     const WOff wo = L::offsets(kR, kC);
@@ -399,7 +401,11 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
     // set-up and spilled)
     enter(0);
     reskew();
-    VecT Wd[H];                                                // the window
+    // The window.  INVARIANT: from the end of a step to the end of the same step of the lane's next pass, slot beta holds the
+    // block (Sigma, beta) the lane formed in that pass - exactly the bits it stored.  A step writes Wd[beta] only at its very
+    // end, and nothing between two passes (enter, leave, deskew, reskew, begin_pass) may write Wd: the lane moves read the
+    // neighbour lane's slot, and the move along external bit 0 reads the lane's own (step: own_take).
+    VecT Wd[H];
 #pragma unroll
     for (int b = 0; b < H; ++b)
 #pragma unroll
@@ -494,14 +500,27 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
           for (int c = 0; c < NC; ++c) acc[c] = fma_m(r, nv[c], acc[c]);
         }
       };
-      // request slot -> external bit.  REV (fp64): the far bits are requested first, the nearest - the most recently written
-      // window, the likeliest cache hit - takes the slot at the end of the step that is requested and waited for in one go
-      // (forward 13.5 -> 13.1 ms per 5 000 patients; no gain in fp32 at k = 25, whose slots are all requested a phase ahead)
-      auto sb = [&](int sl) -> int { return C::REV ? nX - 1 - sl : sl; };
+      // External bit 0 is never requested: its source (Sigma ^ 1, beta) is the block this thread formed at the same beta one
+      // pass ago for the same patient (Sigma toggles bit 0 from pass to pass, and the move exists only on the odd passes of
+      // a patient), and that block is still in Wd[beta] (see the invariant at Wd).  A lane outside the pipeline or a move
+      // that does not exist contributes exactly zero: by a select, the slot's stale content is not zero.
+      auto own_take = [&]() {
+        const bool has = (TR ? !(Sgo & 1u) : (Sgo & 1u) != 0u) && soff != OOB;
+        VecT nv;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) nv[c] = has ? Wd[beta][c] : T(0);
+        ext_take(0, nv);
+      };
+      // request slot -> external bit, over the nR = nX - 1 bits above bit 0.  REV (fp64): the far bits are requested first
+      // (forward 13.5 -> 13.1 ms per 5 000 patients; no gain in fp32 at k = 25, whose slots are all requested a phase ahead).
+      // The terms keep the order of the bits they had when bit 0 was a request of its own - REV: bit 0 last of the external
+      // terms, otherwise first - so at k = 20 the sums associate as before.
+      const int nR = nX - 1;
+      auto sb = [&](int sl) -> int { return C::REV ? nX - 1 - sl : sl + 1; };
       auto ld_ext = [&](int j) -> VecT { return ld_row(ext_off(j), boff); };
       VecT ev0, ev1;
-      if (nX > 0) ev0 = ld_ext(sb(0));
-      if (nX > 1) ev1 = ld_ext(sb(1));
+      if (nR > 0) ev0 = ld_ext(sb(0));
+      if (nR > 1) ev1 = ld_ext(sb(1));
       __builtin_amdgcn_sched_barrier(0);
       // lane moves: the neighbour lane's window slot (its previous window pass = this lane's pass)
       {
@@ -518,16 +537,13 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
       }
       __builtin_amdgcn_sched_barrier(0);
       STAMP(0);
-      if (nX > 0) ext_take(sb(0), ev0);
-      if (nX > 1) ext_take(sb(1), ev1);
-      if (nX > 2) {
+      if (!C::REV && nX > 0) own_take();
+      if (nR > 0) ext_take(sb(0), ev0);
+      if (nR > 1) ext_take(sb(1), ev1);
+      if (nR > 2) {
         ev0 = ld_ext(sb(2));
-        if (nX > 3) ev1 = ld_ext(sb(3));
+        if (nR > 3) ev1 = ld_ext(sb(3));
       }
-      // EV2 (transposed, five external bits - every k = 20 cohort): the fifth request goes out with the second pair into a
-      // register set of its own instead of request-and-wait at the end (adjoint 14.1 -> 13.2 ms; forward 13.1 -> 13.6: off there)
-      VecT ev2;
-      if constexpr (EV2) ev2 = ld_ext(sb(4));
       __builtin_amdgcn_sched_barrier(0);
       STAMP(1);
       // wave moves: the block the neighbour wave published one step ago
@@ -548,14 +564,14 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
           }
         }
       }
-      // DEEP (seven or more external bits, known at compile time - k = 25: 9): the pairs of external blocks are requested one
-      // phase ahead of their use all the way down the step, instead of request-and-wait pairs at its end
+      // DEEP (seven or more external bits, known at compile time - k = 25: 9, eight requests): the pairs of external blocks are
+      // requested one phase ahead of their use all the way down the step, instead of request-and-wait pairs at its end
       if constexpr (DEEP) {
         __builtin_amdgcn_sched_barrier(0);
         ext_take(sb(2), ev0);
         ext_take(sb(3), ev1);
         ev0 = ld_ext(sb(4));
-        if (nX > 5) ev1 = ld_ext(sb(5));
+        ev1 = ld_ext(sb(5));
       }
       __builtin_amdgcn_sched_barrier(0);
       STAMP(2);
@@ -583,20 +599,21 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
       if constexpr (DEEP) {
         __builtin_amdgcn_sched_barrier(0);
         ext_take(sb(4), ev0);
-        if (nX > 5) ext_take(sb(5), ev1);
-        if (nX > 6) ev0 = ld_ext(sb(6));
-        if (nX > 7) ev1 = ld_ext(sb(7));
-      } else if (nX > 2) {
-        ext_take(sb(2), ev0);
-        if (nX > 3) ext_take(sb(3), ev1);
-        if constexpr (EV2) ext_take(sb(4), ev2);
-        else
-        for (int j0 = 4; j0 < nX; j0 += 2) {                   // (spaces of more than 20 bits)
-          ev0 = ld_ext(sb(j0));
-          if (j0 + 1 < nX) ev1 = ld_ext(sb(j0 + 1));
-          ext_take(sb(j0), ev0);
-          if (j0 + 1 < nX) ext_take(sb(j0 + 1), ev1);
+        ext_take(sb(5), ev1);
+        if (nR > 6) ev0 = ld_ext(sb(6));
+        if (nR > 7) ev1 = ld_ext(sb(7));
+      } else {
+        if (nR > 2) {
+          ext_take(sb(2), ev0);
+          if (nR > 3) ext_take(sb(3), ev1);
+          for (int j0 = 4; j0 < nR; j0 += 2) {                 // (spaces of more than 20 bits)
+            ev0 = ld_ext(sb(j0));
+            if (j0 + 1 < nR) ev1 = ld_ext(sb(j0 + 1));
+            ext_take(sb(j0), ev0);
+            if (j0 + 1 < nR) ext_take(sb(j0 + 1), ev1);
+          }
         }
+        if (C::REV && nX > 0) own_take();
       }
       __builtin_amdgcn_sched_barrier(0);
       STAMP(3);
@@ -625,14 +642,15 @@ __global__ __launch_bounds__(WROWS) void k_wsolve(const Desc* __restrict__ descs
       }
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (DEEP) {
-        if (nX > 6) ext_take(sb(6), ev0);
-        if (nX > 7) ext_take(sb(7), ev1);
-        for (int j0 = 8; j0 < nX; j0 += 2) {
+        if (nR > 6) ext_take(sb(6), ev0);
+        if (nR > 7) ext_take(sb(7), ev1);
+        for (int j0 = 8; j0 < nR; j0 += 2) {
           ev0 = ld_ext(sb(j0));
-          if (j0 + 1 < nX) ev1 = ld_ext(sb(j0 + 1));
+          if (j0 + 1 < nR) ev1 = ld_ext(sb(j0 + 1));
           ext_take(sb(j0), ev0);
-          if (j0 + 1 < nX) ext_take(sb(j0 + 1), ev1);
+          if (j0 + 1 < nR) ext_take(sb(j0 + 1), ev1);
         }
+        if (C::REV) own_take();
         __builtin_amdgcn_sched_barrier(0);
       }
       // the block itself: moves along the RB lowest column bits (only the rates in use are fetched), diagonal
