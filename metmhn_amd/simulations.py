@@ -12,6 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from .engine import Engine
+from .results import _residuals
 
 _engines: dict = {}
 
@@ -245,17 +246,8 @@ class PairSummary:
         if dat.ndim != 2 or dat.shape[1] != 2 * self.n_mut + 3:
             raise ValueError(f"dat must have shape (n_pat, {2 * self.n_mut + 3}), got {dat.shape}")
         n_type, obs = pair_counts(dat)
-        out = {}
-        for t, stratum in enumerate(STRATA):
-            if n_type[t] == 0:
-                continue
-            p = self.frequencies(stratum)
-            n = np.float64(n_type[t])
-            with np.errstate(divide="ignore", invalid="ignore"):
-                r = (obs[t] - n * p) / np.sqrt(n * p * (1.0 - p))
-            r[~((p > 0.0) & (p < 1.0))] = np.nan
-            out[stratum] = r
-        return out
+        return {stratum: _residuals(obs[t], np.float64(n_type[t]), self.frequencies(stratum))
+                for t, stratum in enumerate(STRATA) if n_type[t]}
 
 
 def simulate_pairs(log_theta, pt_d_ef, mt_d_ef, n_sim: int, original_key=0, first: int = 0) -> PairSummary:
