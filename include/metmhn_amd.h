@@ -635,6 +635,38 @@ int mmhn_partner_distributions(mmhn_handle h, const double* log_theta, const dou
                                const int8_t* genotypes, const int8_t* targets, int64_t n_rows, double* values,
                                int32_t* status, double* summaries, double* full);
 
+/* ---- exact PT x MT co-occurrence and joint burden tables --------------------------------------
+ * mmhn_cross_table: the second moments of the (PT x MT) table of which mmhn_partner_distributions gives one row or column:
+ * P(the primary tumour holds mutation i, the metastasis holds mutation j, seeded) for every i, j and P(|PT| = k, |MT| = l,
+ * seeded) for every k, l, exactly.  After the seeding the two tumours are independent chains, each stopped by its own clock,
+ * so every bilinear statistic of the pair factorises through the founder z:
+ *   E[phi(PT) psi(MT); seeded] = sum_z Z(z) a_phi(z) b_psi(z),    Z = sigma G0 of mmhn_metastasis_distribution,
+ *   a_phi(z) = (kappa1(z) phi(z) + sum over j not in z of lambda_j(z) a_phi(z + j)) / den1(z)      from the full genotype down,
+ *   b_psi(z) the same with mu_j, kappam, denm
+ * (the notation of mmhn_partner_distributions).  The features of a chain are the n_mut gene indicators [mutation i held] and
+ * the n_mut + 1 burden indicators [|x| = k]: 2 ceil((2 n_mut + 1) / 4) backward sweeps of four planes over all 2^n_mut
+ * genotypes when every plane fits, one forward plane for Z, and a fold per pair of blocks (metmhn_amd/csrc/cross.h).
+ * Everything is a JOINT probability with "seeded"; the conditionals are the outputs over `mass`.  fp64 engines only;
+ * independent of the loaded cohort.
+ *   with_burden                                 0: only the n_mut gene features are swept, the burden outputs are NaN and
+ *                                               the gene outputs have the bytes they have with the burden
+ *   out [1 + 2 n + n n + (n + 1)(n + 1) + 2 n (n + 1)], n = n_mut, in this order:
+ *     mass                                      sum Z = P(seeded)
+ *     pt [n], mt [n]                            sum Z a_i = P(PT holds i, seeded), sum Z b_j = P(MT holds j, seeded)
+ *     cross [n][n]                              sum Z a_i b_j
+ *     burden [n + 1][n + 1]                     [k][l] = P(|PT| = k, |MT| = l, seeded)
+ *     gene_burden [2][n][n + 1]                 [0][i][l] = P(PT holds i, |MT| = l, seeded), [1][j][k] = P(MT holds j, |PT| = k, seeded)
+ * The planes are planned against the workspace limit: Z, one block of the metastasis and as many blocks of the primary tumour
+ * as fit are resident, 1 + 4 + 4 ceil((2 n + 1) / 4) planes of 8 B x 2^n_mut at the most; blocks that do not fit are swept again
+ * per block of the metastasis.  The call fails (return 1, the last error names the bytes needed) when the minimum - 72 B x
+ * 2^n_mut, the two sets of rate tables, the tile list and the tiles' partial sums - exceeds the workspace limit: there is no
+ * partial table and nothing is launched.  A mutation of rate 0 gives exact zeros in its pt entry and its rows of cross and
+ * gene_burden[0].  Every shape depends on n_mut alone and there are no atomics: no byte of the output depends on the
+ * workspace limit, on how many blocks were held or swept again, or on an earlier call.
+ */
+int mmhn_cross_table(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, int with_burden,
+                     double* out);
+
 /* ---- measurement -------------------------------------------------------------------
  * mmhn_bench_kronvec: `batch` resident copies of a 2^k vector, `iters` back-to-back
  * launches of mmhn_kronvec_batched's launch (diag = 0: y = Q_off p into a NaN-filled y, every tile of every vector,
@@ -665,7 +697,7 @@ typedef struct {
   int32_t comm_rank;  /* this engine's rank in it (ncclCommUserRank), -1: none */
 } mmhn_counters;
 /* ABI version of this header: bumped whenever an exported signature or structure changes (4: mmhn_bench_kronvec has its
- * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions, mmhn_order_samples, mmhn_simulate_pairs, mmhn_order_times, mmhn_order_snapshots, mmhn_seeding_forecasts, mmhn_seeding_landscape, mmhn_genotype_distribution, mmhn_metastasis_distribution and mmhn_partner_distributions were added within version 8, purely additive changes).  A client built against another header must refuse to run:
+ * `tiles` argument, mmhn_debug_lane_moves exists; 5: mmhn_counters has six kernel classes and the communicator's size / rank; 6: mmhn_likeliest_orders exists; 7: mmhn_simulate_summary exists; 8: mmhn_order_posteriors exists; mmhn_order_precedences, mmhn_order_positions, mmhn_order_samples, mmhn_simulate_pairs, mmhn_order_times, mmhn_order_snapshots, mmhn_seeding_forecasts, mmhn_seeding_landscape, mmhn_genotype_distribution, mmhn_metastasis_distribution, mmhn_partner_distributions and mmhn_cross_table were added within version 8, purely additive changes).  A client built against another header must refuse to run:
  * mmhn_abi_version() != MMHN_ABI_VERSION (metmhn_amd/_lib.py checks it on load). */
 #define MMHN_ABI_VERSION 8
 int mmhn_abi_version(void);

@@ -97,6 +97,7 @@ SIGNATURES = {
     "mmhn_genotype_distribution": [C.c_void_p, f64p, f64p, i8p, C.c_int64, f64p, i32p, f64p, f64p],
     "mmhn_metastasis_distribution": [C.c_void_p, f64p, f64p, f64p, i8p, C.c_int64, f64p, i32p, f64p, f64p],
     "mmhn_partner_distributions": [C.c_void_p, f64p, f64p, f64p, C.c_int, i8p, i8p, C.c_int64, f64p, i32p, f64p, f64p],
+    "mmhn_cross_table": [C.c_void_p, f64p, f64p, f64p, C.c_int, f64p],
 }
 OTHER_SYMBOLS = ("mmhn_destroy", "mmhn_last_error", "mmhn_abi_version")
 ABI_VERSION = 8          # MMHN_ABI_VERSION of include/metmhn_amd.h these prototypes were written against

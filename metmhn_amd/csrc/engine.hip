@@ -5,7 +5,7 @@
 // batches, routes, work lists, offsets), host.h (errors, device arrays, lanes, MMHN_* knob readers), comm.h (RCCL),
 // rowmix_host.h (row weights and row groups: their checks, device copies and the launches of the group kernels),
 // prims.h / orders_host.h / orderpost_host.h (the batching of the order-posterior entry points, opr_rows) /
-// orderprec_host.h / orderpos_host.h / ordertime_host.h / ordersnap_host.h / ordersample_host.h / forecast_host.h / lattice_host.h / landscape_host.h / genodist_host.h / metdist_host.h / partner_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
+// orderprec_host.h / orderpos_host.h / ordertime_host.h / ordersnap_host.h / ordersample_host.h / forecast_host.h / lattice_host.h / landscape_host.h / genodist_host.h / metdist_host.h / partner_host.h / cross_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
 //
 // Pipeline of one evaluation (reference call graph: regularized_optimization.py:163-267 ->
 // likelihood.py:_g_coupled_*, _grad_prim_obs, _grad_met_obs), run batch by batch with every
@@ -1124,6 +1124,7 @@ struct Engine : EngineBase {
 #include "genodist_host.h"
 #include "metdist_host.h"
 #include "partner_host.h"
+#include "cross_host.h"
 #include "sampler_host.h"
 #include "bench.h"
 
@@ -1789,6 +1790,17 @@ int mmhn_partner_distributions(mmhn_handle h, const double* log_theta, const dou
   REQUIRE(h->dtype == MMHN_F64, "the partner distribution needs an fp64 engine (MMHN_F64)");
   partner_distributions(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, given, genotypes, targets, n_rows,
                         values, status, summaries, full);
+  API_END
+}
+
+// ---- exact PT x MT co-occurrence and joint burden tables: the second moments of the (PT x MT) table through the founder
+int mmhn_cross_table(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, int with_burden,
+                     double* out) {
+  API_BEGIN
+  GUARD(h);
+  REQUIRE(log_theta && obs1 && obs2 && out, "null pointer");
+  REQUIRE(h->dtype == MMHN_F64, "the cross table needs an fp64 engine (MMHN_F64)");
+  cross_table(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, with_burden != 0, out);
   API_END
 }
 

@@ -730,6 +730,25 @@ class Engine:
                     np.ascontiguousarray(sums[:, :, 1 + n * n:]))
         return values, status, sums, whole
 
+    # ---- cross table
+    def cross_table(self, log_theta, obs1, obs2, burden=True):
+        """The exact second moments of the (PT x MT) table (mmhn_cross_table; one forward plane for the founder, a backward
+        sweep of four planes per block of four features of either chain, a fold per pair of blocks), all joint with
+        "seeded": float64 mass, pt [n], mt [n], cross [n, n] = P(PT holds i, MT holds j, seeded), burden [n+1, n+1] =
+        P(|PT| = k, |MT| = l, seeded), gene_burden [2, n, n+1] (PT gene i against |MT| = l, MT gene j against |PT| = k).
+        burden=False sweeps the n gene features only: burden and gene_burden are NaN, the rest has the same bytes.  An fp64
+        engine only.  Raises when 72 B x 2^n, the tables, the tile list and the tiles' partial sums exceed the workspace
+        limit; above that the planes that fit are held and the others swept again, with the same bytes."""
+        if getattr(self, "dtype", "f64") != "f64":
+            raise ValueError("the cross table needs an fp64 engine (dtype='f64')")
+        lt, ltp = self._theta(log_theta); a, ap = self._rates(obs1, "obs1"); b, bp = self._rates(obs2, "obs2")
+        n = self.n
+        out = np.empty(1 + 2 * n + n * n + (n + 1) * (n + 1) + 2 * n * (n + 1))      # (the library fills it with NaN first)
+        _lib.check(self.lib.mmhn_cross_table(self.h, ltp, ap, bp, 1 if burden else 0, out.ctypes.data_as(f64p)))
+        at = np.cumsum([0, 1, n, n, n * n, (n + 1) * (n + 1), 2 * n * (n + 1)])
+        mass, pt, mt, cross, bur, gb = (out[at[k]:at[k + 1]].copy() for k in range(6))
+        return float(mass[0]), pt, mt, cross.reshape(n, n), bur.reshape(n + 1, n + 1), gb.reshape(2, n, n + 1)
+
     # ---- measurement
     def bench_kronvec(self, log_theta, state, batch, iters, transpose=False, jacobi=False, tiles=False):
         """ms per launch of mmhn_kronvec_batched's launch (or the fused Jacobi step); tiles=True also returns

@@ -1,5 +1,5 @@
-"""Host definitions of the seeding forecast and of the four sweeps over all 2^n genotypes: what the device kernels of
-csrc/forecast.h, landscape.h, genodist.h, metdist.h and partner.h are tested against and what their comments send the
+"""Host definitions of the seeding forecast and of the five sweeps over all 2^n genotypes: what the device kernels of
+csrc/forecast.h, landscape.h, genodist.h, metdist.h, partner.h and cross.h are tested against and what their comments send the
 reader to.  NumPy, level by level over the popcount of the genotype code, the moves of a level in the order of their
 bit - the order the kernels are checked against, so nothing here is reordered or fused.
 
@@ -7,8 +7,9 @@ What it holds, top to bottom.  _level_moves, the ascending level sweep that the 
 sweeps of _partner_host share.  Then class _LatticeHost, which model.MetMHN inherits: the rates (_lattice_host_rates:
 lambda and sigma; _lattice_host_chains: with them the metastasis' rates, the three clocks and the three denominators),
 _forecast_next and _forecast_host (seeding_forecast behind its checks), _landscape_host (the one descending sweep, four
-numerators per move: it shares the rates only), _genodist_host, _metdist_host, _partner_rates and _partner_host, and the
-three summaries by their definition (_genodist_summary_host, _metdist_summary_host, _partner_summary_host).
+numerators per move: it shares the rates only), _genodist_host, _metdist_host, _partner_rates and _partner_host, the
+three summaries by their definition (_genodist_summary_host, _metdist_summary_host, _partner_summary_host), and _cross_host
+(the founder plane by _metdist_host's lines, a descending sweep per chain over all features, the fold).
 
 Who calls it.  MetMHN's forecast and lattice entry points (model.py) for backend="host": seeding_forecast always, the
 others through _lattice_whole / _lattice_at, which choose between these and the HIP library.
@@ -242,3 +243,44 @@ class _LatticeHost:
         """The PartnerSummary of the planes P [2, 2^n], by its definition."""
         s = _LatticeHost._genodist_summary_host(P)
         return PartnerSummary(s.mass, s.pairs, s.burden)
+
+    # ------------------------------------------------------------------ second moments of the (PT x MT) table
+    def _cross_host(self, planes: bool = False):
+        """The definition of the cross table: mass, pt [n], mt [n], cross [n, n], burden [n+1, n+1], gene_burden
+        [2, n, n+1], all joint with "seeded".  After the seeding the two tumours are independent chains, so a bilinear
+        statistic of the pair factorises through the founder z: E[phi(PT) psi(MT); seeded] = sum_z Z(z) a_phi(z) b_psi(z)
+        with Z = sigma G0 (_metdist_host's founder plane, the same lines) and the value functions
+            a_phi(z) = (kappa1(z) phi(z) + sum_{j not in z} lambda_j(z) a_phi(z + j)) / den1(z)
+        of the primary tumour's chain, b_psi the same with mu, kappam, denm - level by level over the popcount, descending,
+        the moves of a state in ascending bit.  The 2 n + 1 features of a chain: the n gene indicators, then the n + 1
+        burden indicators.  With `planes` also Z [2^n] and the value functions A, B [2 n + 1, 2^n]."""
+        n, size = self.n, 1 << self.n
+        R = self._lattice_host_chains()
+        F0, G0 = np.zeros(size), np.zeros(size)
+        F0[0] = 1.0
+        levels = (R.idx[R.level == lev] for lev in range(n + 1))
+        for _, ys in _level_moves(levels, n, ((F0, G0, R.lam),)):
+            G0[ys] = F0[ys] / R.den0[ys]
+        Z = R.sig * G0
+        phi = np.stack([(R.idx >> i & 1).astype(np.float64) for i in range(n)] +
+                       [(R.level == k).astype(np.float64) for k in range(n + 1)])
+        values = []
+        for rate, kap, den in ((R.lam, R.kap1, R.den1), (R.mu, R.kapm, R.denm)):
+            a = np.zeros((2 * n + 1, size))
+            for lev in range(n, -1, -1):
+                xs = R.idx[R.level == lev]
+                num = np.zeros((2 * n + 1, len(xs)))
+                for j in range(n):
+                    m = (xs >> j & 1) == 0
+                    x = xs[m]
+                    num[:, m] += rate[j][x] * a[:, x | 1 << j]
+                a[:, xs] = (kap[xs] * phi[:, xs] + num) / den[xs]
+            values.append(a)
+        A, B = values
+        M = np.stack([((Z * a) * B).sum(axis=1) for a in A])      # [f, g] = sum_z (Z a_f) b_g, NumPy's pairwise sums
+        out = SimpleNamespace(mass=float(Z.sum()), pt=(Z * A[:n]).sum(axis=1), mt=(Z * B[:n]).sum(axis=1),
+                              cross=np.ascontiguousarray(M[:n, :n]), burden=np.ascontiguousarray(M[n:, n:]),
+                              gene_burden=np.stack((M[:n, n:], M[n:, :n].T)))
+        if planes:
+            out.Z, out.A, out.B = Z, A, B
+        return out

@@ -759,3 +759,46 @@ class MetMHN(_OrderHost, _LatticeHost):
             mass, fat, at = (np.ascontiguousarray(values[:, k]) for k in range(3))
             summaries = [PartnerSummary(sums[0][i], sums[1][i], sums[2][i]) for i in range(R)]
         return SimpleNamespace(mass=mass, at_target=at, founder_at_target=fat, codes=codes, summaries=summaries, given=given)
+
+    # ------------------------------------------------------------------ second moments of the (PT x MT) table
+    def cross_distribution(self, backend: str = "device", burden: bool = True) -> "CrossSummary":
+        """The exact PT x MT co-occurrence and joint burden tables of a seeded pair - the second moments of the table of which
+        partner_distribution gives one row or column: cross[i, j] = P(PT holds i, MT holds j, seeded), burden[k, l] =
+        P(|PT| = k, |MT| = l, seeded), with the marginals pt, mt, the mixed gene_burden and mass = P(seeded) (CrossSummary;
+        everything joint with "seeded").  After the seeding the two tumours are independent chains, so every bilinear
+        statistic of the pair factorises through the founder z.  With partner_distribution's symbols and Z = sigma G0,
+        metastasis_distribution's founder:
+            a_phi(z) = (kappa1(z) phi(z) + sum_{j not in z} lambda_j(z) a_phi(z + j)) / den1(z)     from the full genotype down
+            b_psi(z) the same with mu, kappam, denm;        E[phi(PT) psi(MT); seeded] = sum_z Z(z) a_phi(z) b_psi(z)
+        phi = [mutation i held] gives `cross`, phi = [|x| = k] gives `burden`.  The full (PT x MT) table has no such form: it
+        needs the 2^(2n+1) joint space; its second moments do not.
+
+        backend="device": one call of the HIP library (mmhn_cross_table): 2 ceil((2n+1)/4) backward sweeps of four planes
+        when 8 B x 2^n x (5 + 4 ceil((2n+1)/4)) fit the workspace limit, more sweeps and the same bytes when only fewer
+        planes fit (72 B x 2^n at the least); nothing of size 2^n comes back.  burden=False sweeps the n gene features only:
+        burden and gene_burden are NaN, the rest has the same bytes.  backend="host": the definition in NumPy
+        (lattice_host.py: _cross_host), n <= 24, always with the burden.  (CrossSummary and PairedSummary live in
+        metmhn_amd.results; this module's public names are pinned.)"""
+        from .results import CrossSummary
+        _check_backend(backend)
+        n = self.n
+        if backend == "host":
+            c = self._cross_host()
+            got = (c.mass, c.pt, c.mt, c.cross, c.burden, c.gene_burden)
+            if not burden:
+                got = got[:4] + (np.full((n + 1, n + 1), np.nan), np.full((2, n, n + 1), np.nan))
+        else:
+            from .jx import engine
+            got = engine(n).cross_table(self.log_theta, self.obs1, self.obs2, burden=bool(burden))
+        return CrossSummary(*got)
+
+    def paired_summary(self, backend: str = "device") -> "PairedSummary":
+        """The exact pairwise frequencies of a seeded pair over the columns [PT_0, MT_0, PT_1, MT_1, ...] - the exact form of
+        simulate_pairs(...).frequencies("paired") and, through compare(dat), of the posterior-predictive check of a cohort's
+        paired rows: cross_distribution for the PT x MT block and the two one-tumour sweeps for the others
+        (genotype_distribution_at's and metastasis_distribution_at's summaries; no plane comes back)."""
+        from .results import PairedSummary
+        _check_backend(backend)
+        none = np.zeros((0, self.n), dtype=np.int8)
+        return PairedSummary(self.genotype_distribution_at(none, backend).summary,
+                             self.metastasis_distribution_at(none, backend).summary, self.cross_distribution(backend))

@@ -581,6 +581,38 @@ def partner_forecast(log_theta, log_d_p, log_d_m, dat, backend: str = "device"):
     return out
 
 
+def paired_fit(log_theta, log_d_p, log_d_m, dat, backend: str = "device"):
+    """How well the model's exact second moments of a seeded pair fit the paired rows (type 3) of `dat` - the counterpart
+    of genotype_fit and metastasis_fit for what the two tumours of a patient share, from MetMHN.paired_summary with
+    obs1 = log_d_p, obs2 = log_d_m.  A namespace of
+    rows: the number of paired rows;
+    residuals: summary.compare(dat), {"paired": [2n, 2n]} - the exact form of simulate_pairs(...).compare(dat)["paired"];
+    shared, pt_private, mt_private: (observed [n], expected [n]) - how many paired rows hold mutation i in both tumours, in
+        the primary tumour only, in the metastasis only, against rows x the model's probability (shared(), pt / mass -
+        shared(), mt / mass - shared() of the CrossSummary);
+    burden: {"pt", "mt", "shared": (observed mean, expected mean)} - the mean mutation counts of the paired rows against the
+        marginals of burden_pmf() and expected_shared() (observed NaN without paired rows);
+    summary: the results.PairedSummary."""
+    from types import SimpleNamespace
+    from .model import MetMHN
+    arr = np.ascontiguousarray(np.asarray(dat).astype(np.int8))
+    n = (arr.shape[1] - 3) // 2
+    summary = MetMHN(log_theta, log_d_p, log_d_m).paired_summary(backend)
+    cross = summary.cross
+    rows = arr[arr[:, -1] == 3]
+    pt, mt = rows[:, 0:2 * n:2].astype(np.int64), rows[:, 1:2 * n:2].astype(np.int64)
+    R = rows.shape[0]
+    both = cross.shared()
+    only_pt, only_mt = cross.pt / cross.mass - both, cross.mt / cross.mass - both
+    pmf, k = cross.burden_pmf(), np.arange(n + 1)
+    mean = lambda v: float(v.mean()) if R else float("nan")
+    burden = {"pt": (mean(pt.sum(axis=1)), float(k @ pmf.sum(axis=1))), "mt": (mean(mt.sum(axis=1)), float(k @ pmf.sum(axis=0))),
+              "shared": (mean((pt & mt).sum(axis=1)), cross.expected_shared())}
+    return SimpleNamespace(rows=R, residuals=summary.compare(arr), shared=((pt & mt).sum(axis=0), R * both),
+                           pt_private=((pt & ~mt & 1).sum(axis=0), R * only_pt),
+                           mt_private=((mt & ~pt & 1).sum(axis=0), R * only_mt), burden=burden, summary=summary)
+
+
 def _unpack(params, n_total):
     params = np.asarray(params, dtype=np.float64)
     return (params[0:n_total ** 2].reshape((n_total, n_total)), params[n_total ** 2:n_total * (n_total + 1)],

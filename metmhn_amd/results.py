@@ -1,7 +1,7 @@
 """What MetMHN's entry points return: the result containers of the order family (OrderPosterior(s) ... OrderSamples), of
 the forecast and the landscape (SeedingForecast(s), SeedingLandscape) and of the three genotype distributions with their
-exact summaries (GenotypeSummary, MetastasisSummary, PartnerSummary and the strata tuples), and the cohort statistics
-computed from them.  NumPy only: nothing here touches the model or the device.  model.py fills the containers (from the
+exact summaries (GenotypeSummary, MetastasisSummary, PartnerSummary and the strata tuples), of the exact second moments
+of the paired table (CrossSummary, PairedSummary), and the cohort statistics computed from them.  NumPy only: nothing here touches the model or the device.  model.py fills the containers (from the
 HIP library or from order_host.py / lattice_host.py) and re-exports every name; simulations.PairSummary.compare shares
 _residuals, and _entry_times serves OrderSamples' two sample means."""
 from __future__ import annotations
@@ -512,3 +512,123 @@ class PartnerDistribution(SimpleNamespace):
         """founder / mass: the distribution of the founder's genotype given the observed tumour (NaN if mass is 0)."""
         with np.errstate(divide="ignore", invalid="ignore"):
             return self.founder / np.float64(self.mass)
+
+
+def _log_odds(f, row, col) -> np.ndarray:
+    """Log odds ratio of the 2x2 tables with joint frequency f [a, b] and marginal ones row [a], col [b]:
+    log(p11 p00 / (p10 p01)); NaN where a cell is not positive (PairSummary's rule)."""
+    p10, p01 = row[:, None] - f, col[None, :] - f
+    p00 = 1.0 - row[:, None] - col[None, :] + f
+    cells = np.stack((f, p10, p01, p00))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lo = np.log(f) + np.log(p00) - np.log(p10) - np.log(p01)
+    lo[~(cells > 0).all(axis=0)] = np.nan
+    return lo
+
+
+class CrossSummary:
+    """The exact second moments of the (PT x MT) table of a seeded pair, all JOINT with "seeded" (the callers divide by
+    `mass`): mass = P(seeded), pt [n] = P(PT holds i, seeded), mt [n] = P(MT holds j, seeded), cross [n, n] = P(PT holds i,
+    MT holds j, seeded), burden [n+1, n+1] = P(|PT| = k, |MT| = l, seeded), gene_burden [2, n, n+1]: [0, i, l] = P(PT holds
+    i, |MT| = l, seeded), [1, j, k] = P(MT holds j, |PT| = k, seeded).  What simulate_pairs estimates from samples in the
+    PT x MT block of its "paired" stratum, without the sampling error.  MetMHN.cross_distribution fills it; with
+    burden=False the last two are NaN."""
+
+    def __init__(self, mass, pt, mt, cross, burden, gene_burden):
+        self.mass = float(mass)
+        self.pt = np.asarray(pt, dtype=np.float64).reshape(-1)
+        self.n_mut = n = self.pt.shape[0]
+        self.mt = np.asarray(mt, dtype=np.float64).reshape(n)
+        self.cross = np.asarray(cross, dtype=np.float64).reshape(n, n)
+        self.burden = np.asarray(burden, dtype=np.float64).reshape(n + 1, n + 1)
+        self.gene_burden = np.asarray(gene_burden, dtype=np.float64).reshape(2, n, n + 1)
+
+    def __repr__(self):
+        return f"CrossSummary(n_mut={self.n_mut}, mass={self.mass})"
+
+    def shared(self) -> np.ndarray:
+        """[n]: the probability that both tumours of a seeded pair hold mutation i, diag(cross) / mass."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.diag(self.cross) / np.float64(self.mass)
+
+    def in_primary_given_metastasis(self) -> np.ndarray:
+        """[n]: P(PT holds i | MT holds i, seeded) = diag(cross) / mt (NaN where mt is 0)."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.diag(self.cross) / self.mt
+
+    def in_metastasis_given_primary(self) -> np.ndarray:
+        """[n]: P(MT holds i | PT holds i, seeded) = diag(cross) / pt (NaN where pt is 0)."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.diag(self.cross) / self.pt
+
+    def expected_shared(self) -> float:
+        """The expected number of mutations both tumours of a seeded pair hold, trace(cross) / mass."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return float(np.trace(self.cross) / np.float64(self.mass))
+
+    def frequencies(self) -> np.ndarray:
+        """cross / mass [n, n]: [i, j] the probability that the PT of a seeded pair holds i and its MT holds j."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.cross / np.float64(self.mass)
+
+    def burden_pmf(self) -> np.ndarray:
+        """burden / mass [n+1, n+1]: the joint distribution of the two tumours' mutation counts of a seeded pair."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.burden / np.float64(self.mass)
+
+    def log_odds(self) -> np.ndarray:
+        """[n, n]: log odds ratio of (i in PT, j in MT) of a seeded pair from its 2x2 table, log(p11 p00 / (p10 p01)) with
+        p11 = cross / mass and the other cells from pt / mass and mt / mass; NaN where a cell is not positive."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return _log_odds(self.frequencies(), self.pt / np.float64(self.mass), self.mt / np.float64(self.mass))
+
+
+PAIRED_STRATA = ("paired",)                     # the one stratum of a PairedSummary: cohort rows of type 3
+
+
+class PairedSummary:
+    """The exact pairwise frequencies of a seeded pair over the 2 n columns [PT_0, MT_0, PT_1, MT_1, ...] of
+    simulations.PairSummary - the exact form of simulate_pairs(...).frequencies("paired"): the PT x PT block from
+    `primary` (GenotypeSummary, plane 1 over its mass), MT x MT from `metastasis` (MetastasisSummary, plane 1 over its
+    mass), PT x MT from `cross` (CrossSummary, over its mass); [2i, 2i+1] = mutation i in both tumours.
+    MetMHN.paired_summary fills it."""
+
+    def __init__(self, primary, metastasis, cross):
+        self.primary, self.metastasis, self.cross = primary, metastasis, cross
+        self.n_mut = n = cross.n_mut
+        self.mass = cross.mass
+        f = np.empty((2 * n, 2 * n))
+        f[0::2, 0::2] = primary.frequencies("EM-PT")
+        f[1::2, 1::2] = metastasis.frequencies("MT")
+        f[0::2, 1::2] = cross.frequencies()
+        f[1::2, 0::2] = cross.frequencies().T
+        self._frequencies = f
+
+    def __repr__(self):
+        return f"PairedSummary(n_mut={self.n_mut}, mass={self.mass})"
+
+    def _stratum(self, stratum):
+        if stratum not in PAIRED_STRATA:
+            raise ValueError(f"stratum must be one of {PAIRED_STRATA}, got {stratum!r}")
+
+    def frequencies(self, stratum="paired") -> np.ndarray:
+        """[2n, 2n]: joint frequencies of two columns of a seeded pair, marginal ones on the diagonal."""
+        self._stratum(stratum)
+        return self._frequencies.copy()
+
+    def log_odds(self, stratum="paired") -> np.ndarray:
+        """Log odds ratio of every two columns from their 2x2 table; NaN where a cell is not positive (the diagonal
+        included)."""
+        f = self.frequencies(stratum)
+        return _log_odds(f, np.diag(f), np.diag(f))
+
+    def compare(self, dat) -> dict:
+        """The exact form of simulate_pairs(...).compare(dat)["paired"]: {"paired": residuals [2n, 2n]} - the standardised
+        residuals (obs - rows p) / sqrt(rows p (1 - p)) of the type-3 rows' Utilityfunctions.pair_counts against
+        p = frequencies("paired"), NaN where p is not inside (0, 1); {} for a cohort without paired rows."""
+        from .Utilityfunctions import pair_counts
+        dat = np.asarray(dat)
+        if dat.ndim != 2 or dat.shape[1] != 2 * self.n_mut + 3:
+            raise ValueError(f"dat must have shape (n_pat, {2 * self.n_mut + 3}), got {dat.shape}")
+        n_type, obs = pair_counts(dat)
+        return {"paired": _residuals(obs[3], np.float64(n_type[3]), self.frequencies("paired"))} if n_type[3] else {}
