@@ -1,8 +1,32 @@
-"""What the tests of the sweeps over all 2^n genotypes share (test_seeding_landscape.py, test_genotype_distribution.py,
-test_metastasis_distribution.py): the tile size read from the header, the error measures, the device's reduction and
-the brute-force summary it is held against, the models with a dead mutation, the cohort of the fit tests and the body
-of the three test_same_bytes_whatever_the_queries.  Imported by name (`from lattice_common import ...`); tests/ is on
-sys.path.  The bars are derived in the three files' docstrings: each keeps its own eps_of, bound and summary_bound."""
+"""What the tests of the seeding forecasts and of the sweeps over all 2^n genotypes share (test_seeding_forecasts.py,
+test_seeding_landscape.py, test_genotype_distribution.py, test_metastasis_distribution.py, test_partner_distribution.py,
+test_cross_table.py): the tile size read from the header, the error measures, the bars of the device against the host,
+the device's reduction and the brute-force summary it is held against, the models with a dead mutation, the cohort of the
+fit tests, the host results computed once, the library kept out of reach and the body of the three
+test_same_bytes_whatever_the_queries.  Imported by name (`from lattice_common import ...`); tests/ is on sys.path.
+
+The bars of the device against the host definition, derived once.  Both sides are fp64 evaluations of non-negative
+sum-products, so relative errors add along a path and a sum takes the worst of its terms plus its additions; u = 2^-53.
+  The rates.  The primary tumour's (pt_eps): A = max_j (|theta_jj| + sum_i |theta_ji|) (the seeding included), B = sum
+|obs1_i| - with the entry n where the clock exp(obs1_n) is a factor of a value (the distributions), without it where it is
+not (the forecasts and the landscape) -: an exponential of a sum of at most n + 2 terms, and the device's product of three
+of them, is within eps = 2 (n + 2) u max(A, B) + 4 u of the exact rate.  The pair's (pair_eps): A = max_j (|theta_jj| +
+|theta_jn| + sum_i |theta_ji|), B = max(sum |obs1_i|, sum |obs2_i|) (the n-th entries included): a rate or a clock is an
+exponential of a sum of at most n + 3 terms and on the device a product of FOUR exponentials (the tile's factor, the two
+tables, exp(theta_jn) or exp(obs_n)), within eps = 2 (n + 3) u max(A, B) + 5 u.
+  The chain (chain_bound).  One step of a chain takes its rates from both sides, once in the numerator and once in den
+(4 eps), and `per_step` roundings: the products, the additions of the numerator and of den and the division, on both
+sides.  A value sits behind at most `steps` steps: steps (4 eps + per_step u).  Where a value leaves as a clock or a rate
+times G (`out`): 2 eps + 8 u for both sides.  Where it is summed over the genotypes (`summed`): RED(n) = 52 +
+ceil(2^(n - c) / 256) additions on the device (genodist.h: 8 + 4 + 32 in the fold of a tile, ceil(tiles / 256) + 8 across the
+tiles), at most n + 19 for NumPy's pairwise sum of 2^n contiguous entries on the host (blocks of 128 on 8 accumulators,
+16 + 3 additions, and a tree above them): (RED(n) + n + 19) u.  Each file states its own `steps` and `per_step` and what it
+measured; the counts that more than one file needs stand here once (forecast_bound, landscape_bound, genodist_bound,
+genodist_summary_bound); every bar is asserted to stay below 1e-9.
+  Two host evaluations of one quantity (identity_bar, the CPU identities of the partner distribution and the cross table)
+share their fp64 rates: a step costs a product, at most n + 1 additions of the numerator, n + 2 of den and the division,
+2 n + 5 u; a path has at most 2 n + 4 steps and 3 u on the way out; two paths and the additions of the sums."""
+import functools
 import os
 import re
 
@@ -16,6 +40,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -53
 C = int(re.search(r"constexpr int LS_TILE_BITS = (\d+);",
                   open(os.path.join(ROOT, "metmhn_amd", "csrc", "lattice.h")).read()).group(1))
+S_FORECAST = 655                   # forecast.h: the longest chain of additions behind an output of the forward kernel
 WORST = {}                         # test -> worst error / bound seen (printed)
 
 
@@ -40,6 +65,11 @@ def rel(got, ref, nan=False):
     return float(np.max(np.abs(got[live] - ref[live]) / np.abs(ref[live]), initial=0.0))
 
 
+def rel_nan(got, ref):
+    """rel where NaN must sit where NaN sits."""
+    return rel(got, ref, nan=True)
+
+
 def ld_rel(got, ref):
     """Worst relative difference of fp64 `got` against long double `ref`; exact zeros exact."""
     got, ref = np.asarray(got), np.asarray(ref)
@@ -57,6 +87,63 @@ def note(tag, worst):
 def red(n):
     """Longest chain of additions of the device's reduction."""
     return 52 + -(-(1 << max(n - C, 0)) // 256)
+
+
+def pt_eps(mod, clock=True):
+    """The rate error of the primary tumour's chain (module docstring); clock: obs1 with its entry n."""
+    th, n = mod._pt_log_theta, mod.n
+    A = max(abs(th[j, j]) + np.abs(np.delete(th[j, :n], j) if j < n else th[j, :n]).sum() for j in range(n + 1))
+    B = np.abs(mod.obs1 if clock else mod.obs1[:n]).sum()
+    return 2 * (n + 2) * U * max(A, B) + 4 * U
+
+
+def pair_eps(mod):
+    """The rate error of the pair's chains (module docstring)."""
+    th, n = mod.log_theta, mod.n
+    A = max(np.abs(th[j, :n]).sum() + (abs(th[j, n]) if j < n else abs(th[n, n])) for j in range(n + 1))
+    B = max(np.abs(mod.obs1).sum(), np.abs(mod.obs2).sum())
+    return 2 * (n + 3) * U * max(A, B) + 5 * U
+
+
+def chain_bound(eps, steps, per_step, out=False, summed=None):
+    """steps (4 eps + per_step u) [+ 2 eps + 8 u with `out`] [+ (RED(n) + n + 19) u with summed = n] (module docstring)."""
+    b = steps * (4 * eps + per_step * U)
+    if out:
+        b = b + 2 * eps + 8 * U
+    if summed is not None:
+        b = b + (red(summed) + summed + 19) * U
+    assert b < 1e-9, (steps, per_step, summed, b)
+    return b
+
+
+def forecast_bound(mod, f):
+    """A row of f free mutations of the forward kernel against its host definition (tests/test_seeding_forecasts.py): f + 1
+    levels of 2 f + 6 roundings and the final sums."""
+    b = chain_bound(pt_eps(mod, clock=False), f + 1, 2 * f + 6) + S_FORECAST * U
+    assert b < 1e-9, (f, b)
+    return b
+
+
+def landscape_bound(mod, clock=False):
+    """The device landscape against its host definition (tests/test_seeding_landscape.py): n + 1 states of 2 n + 8 roundings;
+    clock: with the eps of the distributions that are held against it."""
+    return chain_bound(pt_eps(mod, clock), mod.n + 1, 2 * mod.n + 8)
+
+
+def genodist_bound(mod):
+    """Either plane of the primary tumour's distribution on the device against its host definition
+    (tests/test_genotype_distribution.py): n + 2 steps of 4 n + 14 roundings and the way out."""
+    return chain_bound(pt_eps(mod), mod.n + 2, 4 * mod.n + 14, out=True)
+
+
+def genodist_summary_bound(mod):
+    """genodist_bound with the reductions of a summary entry."""
+    return chain_bound(pt_eps(mod), mod.n + 2, 4 * mod.n + 14, out=True, summed=mod.n)
+
+
+def identity_bar(n, additions):
+    """Two host evaluations of one quantity, in u (module docstring): two paths and the additions of the sum."""
+    return 2 * ((2 * n + 4) * (2 * n + 5) + 3) + additions
 
 
 def summary_rel(got, ref):
@@ -101,6 +188,40 @@ def fit_cohort(n=5):
     import unknown_common as UC
     extra = [UC.unknown_row(n, e) for e in ([0, 3], [], [1, 2, 4], [0, 3])]
     return np.vstack((mixed_cohort(n), mixed_cohort(n)[:3], extra)).astype(np.int8)
+
+
+def genotype(n, held):
+    """The int8 genotype [n] that holds the mutations `held`."""
+    g = np.zeros(n, dtype=np.int8)
+    g[list(held)] = 1
+    return g
+
+
+def frozen(got):
+    """`got` - an array, or a tuple or an object of arrays - with every array read-only: what a cached host(...) returns."""
+    parts = got if isinstance(got, tuple) else (got,) if isinstance(got, np.ndarray) else vars(got).values()
+    for a in parts:
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return got
+
+
+def host_once(compute):
+    """Decorator of a host(*key) that returns the host definition's result: computed once per key, never written to."""
+    @functools.lru_cache(maxsize=None)
+    @functools.wraps(compute)
+    def cached(*key):
+        return frozen(compute(*key))
+    return cached
+
+
+def no_library(monkeypatch):
+    """From here on the test fails if it reaches the library."""
+    import metmhn_amd.jx as jx
+
+    def no_engine(*a, **k):
+        raise AssertionError("the library was reached")
+    monkeypatch.setattr(jx, "engine", no_engine)
 
 
 def check_same_bytes(call, planes, n, at=None):

@@ -9,24 +9,22 @@ GPU: the device against the host definition, against the device's one-tumour swe
 share no backward code with the new kernels), against simulate_pairs, the same bytes under a workspace limit that forces
 blocks to be swept again and with or without the burden, a mutation of rate 0, paired_fit.
 
-The bound of the device against the host.  tests/test_partner_distribution.py's scheme with its eps_of: both sides are fp64
-evaluations of non-negative sum-products, so relative errors add along a path and a sum takes the worst of its terms plus
-its additions.  A rate or a clock is within eps of the exact one; one step of a chain costs, both sides together,
-4 eps + (4 n + 16) u (a rate, a product, at most n + 1 additions of the numerator, a rate and at most n + 2 additions of
-den, the division, on either side).  The path behind a term Z(z) a(z) b(z): G0's chain to z (|z| + 1 steps), the two value
-functions from z to the full genotype (n - |z| + 1 steps each), the product (one step): 2 n - |z| + 4 <= 2 n + 4 steps; on
-the way the clock times the feature, 2 eps + 8 u.  Every term agrees within relative
+The bound of the device against the host: lattice_common's chain_bound with the pair's eps (pair_eps).  One step of a
+chain costs, both sides together, 4 n + 16 roundings (a product, at most n + 1 additions of the numerator, at most n + 2
+additions of den, the division, on either side).  The path behind a term Z(z) a(z) b(z): G0's chain to z (|z| + 1 steps),
+the two value functions from z to the full genotype (n - |z| + 1 steps each), the product (one step): 2 n - |z| + 4 <=
+2 n + 4 steps; on the way the clock times the feature.  Every term agrees within relative
     bound(n) = (2 n + 4) (4 eps + (4 n + 16) u) + 2 eps + 8 u
-and the tables add the reductions - RED(n) on the device (4 states a thread, 8 levels of the block sum, ceil(tiles / 256)
-+ 8 across the tiles: below lattice_common.red), at most n + 19 for NumPy's pairwise sum on the host -:
-    table_bound(n) = bound(n) + (RED(n) + n + 19) u,
-below 1e-9 for every shape used here (asserted).  The device's one-tumour summaries against their host definitions stay
-within (n + 2) (4 eps + (4 n + 16) u) + 2 eps + 8 u + (RED(n) + n + 19) u (their files); the device's partner summaries
-within test_partner_distribution.summary_bound, which is table_bound's expression.
+and the tables add the reductions - on the device 4 states a thread, 8 levels of the block sum, ceil(tiles / 256) + 8 across
+the tiles: below lattice_common.red -:
+    table_bound(n) = bound(n) + (RED(n) + n + 19) u.
+The device's one-tumour summaries against their host definitions stay within test_metastasis_distribution.py's n + 2 steps
+of 4 n + 16 with the reductions (sweep_summary_bound); the device's partner summaries within table_bound, which is
+test_partner_distribution.py's expression for them.
 
-The bars of the CPU identities: test_partner_distribution.identity_bar, two host evaluations of one quantity: two paths of
-at most 2 n + 4 steps of 2 n + 5 u, and the additions of the sums - 11 u for a NumPy sum of at most 64 terms, so 11 u for a
-table entry, 22 u for the double sum over the queries and the partners of the partner distributions.
+The bars of the CPU identities: lattice_common.identity_bar, two host evaluations of one quantity, and the additions of
+the sums - 11 u for a NumPy sum of at most 64 terms, so 11 u for a table entry, 22 u for the double sum over the queries and
+the partners of the partner distributions.
 
 Measured, CPU: host against the dense oracle 3.1e-15 relative at the worst (n = 1 .. 4); against the sums of the host
 partner distributions 0.017 of the bar at the worst (n = 1); the identities 0.011 of the bar at the worst (3.8 u of 572 u at
@@ -39,7 +37,6 @@ device's partner distributions 1.8e-4; Monte Carlo 2.53 standard errors at the w
 The siblings' reduction-alone test (the device's tables against long-double sums over planes copied out) is not built: the
 ABI call has no output of the planes, which a slot's next block overwrites.
 """
-import functools
 import re
 
 import numpy as np
@@ -47,40 +44,28 @@ import pytest
 
 from metmhn_amd import regularized_optimization as ro
 from metmhn_amd.results import CrossSummary, GenotypeSummary, MetastasisSummary, PairedSummary
-from lattice_common import C, U, bits, fit_cohort, ld_rel, note, red, rel, without
+from lattice_common import (C, U, bits, chain_bound, fit_cohort, host_once, identity_bar, ld_rel, no_library, note, pair_eps, rel,
+                            without)
 from order_common import model, paired
-from test_partner_distribution import eps_of, identity_bar
 
 FIELDS = ("mass", "pt", "mt", "cross", "burden", "gene_burden")
 GENES = ("mass", "pt", "mt", "cross")
 
 
-def bound(mod):
-    """A term Z a b of the device against the host definition (module docstring)."""
-    n, eps = mod.n, eps_of(mod)
-    return (2 * n + 4) * (4 * eps + (4 * n + 16) * U) + 2 * eps + 8 * U
-
-
 def table_bound(mod):
-    b = bound(mod) + (red(mod.n) + mod.n + 19) * U
-    assert b < 1e-9, (mod.n, b)
-    return b
+    """An entry of the device's tables against the host definition (module docstring)."""
+    return chain_bound(pair_eps(mod), 2 * mod.n + 4, 4 * mod.n + 16, out=True, summed=mod.n)
 
 
 def sweep_summary_bound(mod):
-    """A summary entry of a one-tumour sweep on the device against its host definition, with this file's eps."""
-    n, eps = mod.n, eps_of(mod)
-    return (n + 2) * (4 * eps + (4 * n + 16) * U) + 2 * eps + 8 * U + (red(n) + n + 19) * U
+    """A summary entry of a one-tumour sweep on the device against its host definition, with the pair's eps."""
+    return chain_bound(pair_eps(mod), mod.n + 2, 4 * mod.n + 16, out=True, summed=mod.n)
 
 
-@functools.lru_cache(maxsize=None)
+@host_once
 def host(n, seed):
-    """_cross_host of order_common.model(n, seed) with its planes, computed once and never written to."""
-    got = model(n, seed=seed)._cross_host(planes=True)
-    for a in vars(got).values():
-        if isinstance(a, np.ndarray):
-            a.setflags(write=False)
-    return got
+    """_cross_host of order_common.model(n, seed) with its planes."""
+    return model(n, seed=seed)._cross_host(planes=True)
 
 
 def worst_rel(got, ref, names=FIELDS):
@@ -282,12 +267,9 @@ def test_python_layer_on_a_mixed_cohort():
 
 
 def test_refusals(monkeypatch):
-    import metmhn_amd.jx as jx
     from metmhn_amd.engine import Engine
 
-    def no_engine(*a, **k):
-        raise AssertionError("the library was reached")
-    monkeypatch.setattr(jx, "engine", no_engine)
+    no_library(monkeypatch)
     mod = model(5, seed=36)
     for call in (mod.cross_distribution, mod.paired_summary):
         with pytest.raises(ValueError, match="backend must be 'device' or 'host'"):

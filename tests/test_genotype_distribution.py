@@ -10,22 +10,15 @@ double, rates of 0, compare / genotype_fit against their formulas, the refusals.
 GPU: the device against the host definition, against the engine's own cohort rows, against the backward sweep
 (landscape.h, whose recursion shares no line with the forward one), the reduction alone, the bytes whatever the queries.
 
-The bound of the device against the host.  Both sides are fp64 evaluations of non-negative sum-products, so relative
-errors add along a path and a sum takes the worst of its terms plus its additions.  With u = 2^-53,
-A = max_j (|theta_jj| + sum_i |theta_ji|) (the seeding included), B = sum |obs1_i| (obs1_n included): an exponential of a
-sum of at most n + 2 terms, and the device's product of three of them, is within eps = 2 (n + 2) u max(A, B) + 4 u of the
-exact rate.  One step of the chain, on one side: the numerator takes a rate (eps), a product and at most n + 1 additions
-(the n pulls and, for the seeded plane, G0 sigma); the den takes a rate (eps), at most n + 2 additions and, for kappa1 =
-kappa0 exp(obs1_n), one product and the exponential's own 2 u; the division: 2 eps + (2 n + 7) u.  Both sides: 4 eps +
-(4 n + 14) u.  The chain behind a value is at most n + 1 states deep and n + 2 steps through the seeding (G0 sigma of the
-same state is one more step).  On the way out kappa times G: 2 eps + 8 u for both sides.  Every value of both planes
-agrees within relative
+The bound of the device against the host (lattice_common.genodist_bound): chain_bound with the primary tumour's eps (pt_eps, obs1 with
+the clock's entry).  One step of the chain, on one side: the numerator takes a product and at most n + 1 additions (the n
+pulls and, for the seeded plane, G0 sigma); the den takes at most n + 2 additions and, for kappa1 = kappa0 exp(obs1_n),
+one product and the exponential's own 2 u; the division: (2 n + 7) u, both sides 4 n + 14 a step.  The chain behind a value
+is at most n + 1 states deep and n + 2 steps through the seeding (G0 sigma of the same state is one more step); on the way
+out kappa times G.  Every value of both planes agrees within relative
     bound(n) = (n + 2) (4 eps + (4 n + 14) u) + 2 eps + 8 u,
-below 1e-9 for every shape used here (asserted).  The summary adds its reductions.  Device (genodist.h): 8 + 4 + 32
-additions in the fold of a tile, ceil(tiles / 256) + 8 across the tiles: RED(n) = 52 + ceil(2^(n - c) / 256).  Host: NumPy's
-pairwise sum of a contiguous vector of 2^n entries, blocks of 128 on 8 accumulators (16 + 3 additions) and a tree above
-them: at most n + 19.  Summary bound: bound(n) + (RED(n) + n + 19) u.  The device's summary against the long-double sums of
-the device's own `full` output has the reduction's term alone: RED(n) u (1 % on top for the long-double side).
+the summary within bound(n) + (RED(n) + n + 19) u.  The device's summary against the long-double sums of the device's own
+`full` output has the reduction's term alone: RED(n) u (1 % on top for the long-double side).
 
 Measured on an MI355X, worst error / bound per test: device against host 3.1e-3 for the planes (n = 1; 1.5e-3 at
 n = c + 3) and 2.7e-3 for the summary; exp(lp) of the engine's own rows 5.4e-6 and p_seeded 1.1e-6 of the 1e-9 bar; mass[1]
@@ -33,7 +26,6 @@ against the device landscape 0 (n = c + 6) and 7.3e-6 (n = 22); the reduction al
 CPU: the host definition against the dense oracle 2.0e-15 relative at the worst, p_seeded against the oracle's mixture
 1.1e-7 of its bar, the recursion's residual 3.6 u against 26 u, the host summary 0.14 of (n + 19) u.
 """
-import functools
 import re
 
 import numpy as np
@@ -42,38 +34,17 @@ import pytest
 import metmhn_amd.model as model_mod
 from metmhn_amd import regularized_optimization as ro
 from metmhn_amd.model import GenotypeDistribution, GenotypeSummary, MetMHN
-from lattice_common import C, U, bits, brute_summary, check_same_bytes, fit_cohort, ld_rel, note, red, rel, summary_rel, without
+from lattice_common import (C, U, bits, brute_summary, check_same_bytes, fit_cohort, host_once, landscape_bound, ld_rel, no_library,
+                            note, red, rel, summary_rel, without)
+from lattice_common import genodist_bound as bound, genodist_summary_bound as summary_bound
 from order_common import model
 
 
-def eps_of(mod):
-    th, n = mod._pt_log_theta, mod.n
-    A = max(abs(th[j, j]) + np.abs(np.delete(th[j, :n], j) if j < n else th[j, :n]).sum() for j in range(n + 1))
-    B = np.abs(mod.obs1).sum()
-    return 2 * (n + 2) * U * max(A, B) + 4 * U
-
-
-def bound(mod):
-    """Either plane of the device against the host definition (module docstring)."""
-    n, eps = mod.n, eps_of(mod)
-    b = (n + 2) * (4 * eps + (4 * n + 14) * U) + 2 * eps + 8 * U
-    assert b < 1e-9, (n, b)
-    return b
-
-
-def summary_bound(mod):
-    b = bound(mod) + (red(mod.n) + mod.n + 19) * U
-    assert b < 1e-9, (mod.n, b)
-    return b
-
-
-@functools.lru_cache(maxsize=None)
+@host_once
 def host(n, seed):
-    """(planes [2, 2^n], GenotypeSummary) of order_common.model(n, seed) by the host definition: computed once, never
-    written to."""
+    """(planes [2, 2^n], GenotypeSummary) of order_common.model(n, seed) by the host definition."""
     mod = model(n, seed=seed)
     whole = mod._genodist_host()
-    whole.setflags(write=False)
     return whole, mod._genodist_summary_host(whole)
 
 
@@ -273,11 +244,7 @@ def test_compare_and_genotype_fit_on_a_mixed_cohort():
 
 
 def test_refusals(monkeypatch):
-    import metmhn_amd.jx as jx
-
-    def no_engine(*a, **k):
-        raise AssertionError("the library was reached")
-    monkeypatch.setattr(jx, "engine", no_engine)
+    no_library(monkeypatch)
     n = 5
     mod = model(n, seed=36)
     G = bits(n, [1, 10, 0])
@@ -380,10 +347,8 @@ def test_seeded_mass_against_the_backward_sweep(n):
     _, _, sums, _ = engine(n).genotype_distribution(mod.log_theta, mod.obs1, np.zeros((0, n), dtype=np.int8))
     back, status, _ = engine(n).seeding_landscape(mod.log_theta, mod.obs1, np.zeros((1, n), dtype=np.int8), "observation")
     assert status.tolist() == [0]
-    landscape_bound = (n + 1) * (4 * eps_of(mod) + (2 * n + 8) * U)
-    assert landscape_bound < 1e-9
     note(f"mass[1] against the landscape's p_seed of the empty genotype, n = {n}",
-         rel(sums[0][1], back[0, 0]) / (summary_bound(mod) + landscape_bound))
+         rel(sums[0][1], back[0, 0]) / (summary_bound(mod) + landscape_bound(mod, clock=True)))
     assert abs(sums[0].sum() - 1.0) <= summary_bound(mod)
 
 

@@ -12,21 +12,16 @@ GPU: the device against the host definition, against the engine's own type-2 row
 (which share no code with the sweep), against the device's genotype distribution and landscape, the reduction alone, the
 bytes whatever the queries, Monte Carlo.
 
-The bound of the device against the host.  tests/test_genotype_distribution.py's derivation with the metastasis' terms.
-Both sides are fp64 evaluations of non-negative sum-products, so relative errors add along a path and a sum takes the
-worst of its terms plus its additions.  With u = 2^-53, A = max_j (|theta_jj| + |theta_jn| + sum_i |theta_ji|) (the
-seeding included), B = max(sum |obs1_i|, sum |obs2_i|) (the n-th entries included): a rate is now an exponential of a sum
-of at most n + 3 terms, and on the device a product of FOUR exponentials (the tile's factor, the two tables,
-exp(theta_jn)), within eps = 2 (n + 3) u max(A, B) + 5 u of the exact rate.  One step of the chain, on one side: the
-numerator takes a rate (eps), a product and at most n + 1 additions (the n pulls and G0 sigma), and for FC one more product
-(G0 sigma times |y|); the den takes a rate (eps) and at most n + 2 additions; the division: 2 eps + (2 n + 8) u.  Both
-sides: 4 eps + (4 n + 16) u.  The chain behind a value is n + 1 states and the seeding step: n + 2 steps.  On the way out
-sigma or kappam times G: 2 eps + 8 u for both sides.  Every value of the three planes agrees within relative
+The bound of the device against the host: lattice_common's chain_bound with the pair's eps (pair_eps).  One step of the
+chain, on one side: the numerator takes a product and at most n + 1 additions (the n pulls and G0 sigma), and for FC one
+more product (G0 sigma times |y|); the den takes at most n + 2 additions; the division: (2 n + 8) u, both sides 4 n + 16 a
+step.  The chain behind a value is n + 1 states and the seeding step: n + 2 steps; on the way out sigma or kappam times G.
+Every value of the three planes agrees within relative
     bound(n) = (n + 2) (4 eps + (4 n + 16) u) + 2 eps + 8 u,
-below 1e-9 for every shape used here (asserted).  The summary adds its reductions, which are genodist.h's: RED(n) = 52 +
-ceil(2^(n - c) / 256) on the device, at most n + 19 for NumPy's pairwise sum.  Summary bound: bound(n) + (RED(n) + n + 19) u;
-the device's summary against the long-double sums of its own `full` planes: RED(n) u (1 % on top for the long-double side).
-founder_events = C / M is a quotient of two such values: 2 bound(n) + u.
+the summary, whose reductions are genodist.h's, within bound(n) + (RED(n) + n + 19) u; the device's summary against the
+long-double sums of its own `full` planes: RED(n) u (1 % on top for the long-double side).  founder_events = C / M is a
+quotient of two such values: 2 bound(n) + u.  Against the primary tumour's sweeps the bar adds their files' bounds
+(lattice_common's genodist_bound, genodist_summary_bound and landscape_bound).
 
 Measured on an MI355X, worst error / bound per test: device against host 3.2e-3 for the planes (n = 1; 1.7e-3 at
 n = c + 3) and 2.9e-3 for the summary; exp(lp) of the engine's own type-2 rows 9.5e-6 of the 1e-9 bar; founder_events
@@ -38,61 +33,34 @@ CPU: the host definition against the dense oracle 2.9e-15 relative at the worst,
 posteriors 1.3e-15 absolute, coinciding chains 6.8e-16 relative, the recursion's residual 3.8 u against 27 u, the host summary
 0.17 of (n + 19) u.
 """
-import functools
-
 import numpy as np
 import pytest
 
 import metmhn_amd.model as model_mod
 from metmhn_amd import regularized_optimization as ro
 from metmhn_amd.model import GenotypeSummary, MetastasisDistribution, MetastasisSummary, MetMHN
-from lattice_common import C, U, bits, brute_summary, check_same_bytes, ld_rel, note, red, rel, summary_rel, without
+from lattice_common import (C, U, bits, brute_summary, chain_bound, check_same_bytes, genodist_bound, genodist_summary_bound,
+                            host_once, landscape_bound, ld_rel, no_library, note, pair_eps, red, rel, summary_rel, without)
 from lattice_common import fit_cohort as pt_fit_cohort
 from order_common import mixed_cohort, model
 
 PLANES = ("founder", "metastasis", "founder_weighted")
 
 
-def eps_of(mod):
-    th, n = mod.log_theta, mod.n
-    A = max(np.abs(th[j, :n]).sum() + (abs(th[j, n]) if j < n else abs(th[n, n])) for j in range(n + 1))
-    B = max(np.abs(mod.obs1).sum(), np.abs(mod.obs2).sum())
-    return 2 * (n + 3) * U * max(A, B) + 5 * U
-
-
 def bound(mod):
     """Any plane of the device against the host definition (module docstring)."""
-    n, eps = mod.n, eps_of(mod)
-    b = (n + 2) * (4 * eps + (4 * n + 16) * U) + 2 * eps + 8 * U
-    assert b < 1e-9, (n, b)
-    return b
+    return chain_bound(pair_eps(mod), mod.n + 2, 4 * mod.n + 16, out=True)
 
 
 def summary_bound(mod):
-    b = bound(mod) + (red(mod.n) + mod.n + 19) * U
-    assert b < 1e-9, (mod.n, b)
-    return b
+    return chain_bound(pair_eps(mod), mod.n + 2, 4 * mod.n + 16, out=True, summed=mod.n)
 
 
-def genodist_bounds(mod):
-    """(eps, bound, summary bound) of the primary tumour's sweep as tests/test_genotype_distribution.py derives them, for the
-    checks of this sweep against that one."""
-    th, n = mod._pt_log_theta, mod.n
-    A = max(abs(th[j, j]) + np.abs(np.delete(th[j, :n], j) if j < n else th[j, :n]).sum() for j in range(n + 1))
-    eps = 2 * (n + 2) * U * max(A, np.abs(mod.obs1).sum()) + 4 * U
-    b = (n + 2) * (4 * eps + (4 * n + 14) * U) + 2 * eps + 8 * U
-    sb = b + (red(n) + n + 19) * U
-    assert sb < 1e-9, (n, sb)
-    return eps, b, sb
-
-
-@functools.lru_cache(maxsize=None)
+@host_once
 def host(n, seed):
-    """(planes [3, 2^n], MetastasisSummary) of order_common.model(n, seed) by the host definition: computed once, never
-    written to."""
+    """(planes [3, 2^n], MetastasisSummary) of order_common.model(n, seed) by the host definition."""
     mod = model(n, seed=seed)
     whole = mod._metdist_host()
-    whole.setflags(write=False)
     return whole, mod._metdist_summary_host(whole)
 
 
@@ -343,11 +311,7 @@ def test_summary_methods_and_metastasis_fit_on_a_mixed_cohort():
 
 
 def test_refusals(monkeypatch):
-    import metmhn_amd.jx as jx
-
-    def no_engine(*a, **k):
-        raise AssertionError("the library was reached")
-    monkeypatch.setattr(jx, "engine", no_engine)
+    no_library(monkeypatch)
     n = 5
     mod = model(n, seed=36)
     G = bits(n, [1, 10, 0])
@@ -470,7 +434,7 @@ def test_coinciding_chains_against_the_device_seeded_plane():
     got = mod.metastasis_distribution()
     seeded = mod.genotype_distribution().seeded
     note(f"M against the device's seeded plane with coinciding chains, n = {n}",
-         rel(got.metastasis, seeded) / (bound(mod) + genodist_bounds(mod)[1]))
+         rel(got.metastasis, seeded) / (bound(mod) + genodist_bound(mod)))
 
 
 @pytest.mark.gpu
@@ -484,13 +448,11 @@ def test_masses_against_the_other_sweeps(n):
     _, _, gsums, _ = engine(n).genotype_distribution(mod.log_theta, mod.obs1, np.zeros((0, n), dtype=np.int8))
     back, status, _ = engine(n).seeding_landscape(mod.log_theta, mod.obs1, np.zeros((1, n), dtype=np.int8), "observation")
     assert status.tolist() == [0]
-    landscape_bound = (n + 1) * (4 * genodist_bounds(mod)[0] + (2 * n + 8) * U)
-    assert landscape_bound < 1e-9
     for what, v in (("sum Z", whole[0].sum()), ("sum M", whole[1].sum()), ("mass[0]", sums[0][0]), ("mass[1]", sums[0][1])):
         note(f"{what} against genotype_distribution's mass[1], n = {n}",
-             rel(v, gsums[0][1]) / (summary_bound(mod) + genodist_bounds(mod)[2]))
+             rel(v, gsums[0][1]) / (summary_bound(mod) + genodist_summary_bound(mod)))
         note(f"{what} against the landscape's p_seed of the empty genotype, n = {n}",
-             rel(v, back[0, 0]) / (summary_bound(mod) + landscape_bound))
+             rel(v, back[0, 0]) / (summary_bound(mod) + landscape_bound(mod, clock=True)))
     want = (popcounts(n) * whole[0]).sum()
     note(f"sum C against sum |y| Z, n = {n}", rel(whole[2].sum(), want) / (2 * summary_bound(mod)))
 

@@ -10,31 +10,25 @@ its identities, the recursion in long double, a mutation of rate 0, the Python l
 GPU: the device against the host definition, against the engine's own paired rows (which share no code with the sweep),
 against the device's one-tumour sweeps, the reduction alone, the bytes whatever the other rows, a mutation of rate 0.
 
-The bound of the device against the host.  tests/test_metastasis_distribution.py's scheme: both sides are fp64 evaluations
-of non-negative sum-products, so relative errors add along a path and a sum takes the worst of its terms plus its
-additions.  u = 2^-53, A = max_j (|theta_jj| + |theta_jn| + sum_i |theta_ji|), B = max(sum |obs1_i|, sum |obs2_i|): a rate or
-a clock is an exponential of a sum of at most n + 3 terms and on the device a product of four exponentials (the tile's
-factor, the two tables, exp(theta_jn) or exp(obs_n)), within eps = 2 (n + 3) u max(A, B) + 5 u of the exact one.  One step of
-a chain, on one side: the numerator takes a rate (eps), a product and at most n + 1 additions (n pulls and the source), the
-den a rate and at most n + 2 additions, the division: 2 eps + (2 n + 8) u; both sides 4 eps + (4 n + 16) u.  The path behind
-J_q(y) through a founder z: G0's chain to z (|z| + 1 states), B's chain from z to q (|q| - |z| + 1 states), the product
-sigma G0 B (one step: a rate and two products), the partner's chain from z to y (|y| - |z| + 1 states): |q| + |y| - |z| + 4
-steps, at most 2 n + 4 (z empty, q and y full; the issue's 3 n + 4 counts |z| three times instead of taking it off twice).
-On the way out the clock times G: 2 eps + 8 u.  Every value of both planes agrees within relative
+The bound of the device against the host: lattice_common's chain_bound with the pair's eps (pair_eps).  One step of a
+chain, on one side: the numerator takes a product and at most n + 1 additions (n pulls and the source), the den at most
+n + 2 additions, the division: (2 n + 8) u, both sides 4 n + 16 a step.  The path behind J_q(y) through a founder z: G0's
+chain to z (|z| + 1 states), B's chain from z to q (|q| - |z| + 1 states), the product sigma G0 B (one step: a rate and two
+products), the partner's chain from z to y (|y| - |z| + 1 states): |q| + |y| - |z| + 4 steps, at most 2 n + 4 (z empty, q and y
+full; the issue's 3 n + 4 counts |z| three times instead of taking it off twice); on the way out the clock times G.  Every
+value of both planes agrees within relative
     bound(n) = (2 n + 4) (4 eps + (4 n + 16) u) + 2 eps + 8 u,
-below 1e-9 for every shape used here (asserted).  The summary and `mass` add the reductions: RED(n) on the device, at most
-n + 19 for NumPy's pairwise sum: bound(n) + (RED(n) + n + 19) u; the device's summary against long-double sums of its own
+the summary and `mass` within bound(n) + (RED(n) + n + 19) u; the device's summary against long-double sums of its own
 `full` planes: RED(n) u (1 % on top for the long-double side).  The one-tumour sweeps against their host definitions stay
-within their files' bounds, which (n + 2) (4 eps + (4 n + 16) u) + 2 eps + 8 u with this file's (larger) eps covers.
+within their files' bounds, which test_metastasis_distribution.py's n + 2 steps of 4 n + 16 with the pair's (larger) eps
+cover (sweep_bound).
 
-The bars of the CPU identities.  Both sides are host evaluations with the same fp64 rates, so a step of a chain costs a
-product, at most n + 1 additions of the numerator, at most n + 2 of den and the division: 2 n + 5 u; the path behind a value
-has at most 2 n + 4 steps (above), the way out adds at most 3 u (the clock times G; sigma G0 B is counted as a step):
-P(n) = (2 n + 4) (2 n + 5) + 3 u, 275 u at n = 6.  A sum of at most 64 non-negative terms in NumPy's pairwise order (eight
-accumulators, then a tree) adds at most 7 + 3 + 1 = 11 u and is as accurate as its worst term otherwise.  A sum against a
-single value of a one-tumour sweep (whose own path, n + 2 steps, is shorter) or against another such sum: 2 P(n) + 11 u, 561 u
-at n = 6 and 101 u at n = 1; J_PT=x(y) against J_MT=y(x), two paths and no sum: 2 P(n) u.  These are worst cases over paths of
-full length; "a few dozen u" is what is measured (printed per n).
+The bars of the CPU identities (lattice_common.identity_bar).  Both sides are host evaluations with the same fp64 rates:
+P(n) = (2 n + 4) (2 n + 5) + 3 u a path, 275 u at n = 6.  A sum of at most 64 non-negative terms in NumPy's pairwise order
+(eight accumulators, then a tree) adds at most 7 + 3 + 1 = 11 u and is as accurate as its worst term otherwise.  A sum
+against a single value of a one-tumour sweep (whose own path, n + 2 steps, is shorter) or against another such sum:
+2 P(n) + 11 u, 561 u at n = 6 and 101 u at n = 1; J_PT=x(y) against J_MT=y(x), two paths and no sum: 2 P(n) u.  These are
+worst cases over paths of full length; "a few dozen u" is what is measured (printed per n).
 
 Measured, CPU: the host definition against the dense oracle 3.1e-15 relative at the worst (n = 1 .. 5); the identities
 1.1e-15 relative at the worst (9.8 u of 550 u at n = 6; 0.047 of its bar at the worst, n = 1); the recursion's residual in long double 4.3 u against the derived 2 n + 6 = 22 u
@@ -52,37 +46,26 @@ import pytest
 import metmhn_amd.model as model_mod
 from metmhn_amd import regularized_optimization as ro
 from metmhn_amd.model import GenotypeSummary, MetMHN, PartnerDistribution, PartnerSummary
-from lattice_common import C, U, bits, brute_summary, fit_cohort, ld_rel, note, red, rel, summary_rel, without
+from lattice_common import (C, U, bits, brute_summary, chain_bound, fit_cohort, host_once, identity_bar, ld_rel, no_library, note,
+                            pair_eps, red, rel, summary_rel, without)
 from order_common import model, paired
 
 GIVEN = ("PT", "MT")
 
 
-def eps_of(mod):
-    th, n = mod.log_theta, mod.n
-    A = max(np.abs(th[j, :n]).sum() + (abs(th[j, n]) if j < n else abs(th[n, n])) for j in range(n + 1))
-    B = max(np.abs(mod.obs1).sum(), np.abs(mod.obs2).sum())
-    return 2 * (n + 3) * U * max(A, B) + 5 * U
-
-
 def bound(mod):
     """Either plane of the device against the host definition (module docstring)."""
-    n, eps = mod.n, eps_of(mod)
-    b = (2 * n + 4) * (4 * eps + (4 * n + 16) * U) + 2 * eps + 8 * U
-    assert b < 1e-9, (n, b)
-    return b
+    return chain_bound(pair_eps(mod), 2 * mod.n + 4, 4 * mod.n + 16, out=True)
 
 
 def summary_bound(mod):
-    b = bound(mod) + (red(mod.n) + mod.n + 19) * U
-    assert b < 1e-9, (mod.n, b)
-    return b
+    """A summary entry or `mass`: bound with the reductions."""
+    return chain_bound(pair_eps(mod), 2 * mod.n + 4, 4 * mod.n + 16, out=True, summed=mod.n)
 
 
 def sweep_bound(mod):
-    """A one-tumour sweep's value on the device against its host definition, with this file's eps (module docstring)."""
-    n, eps = mod.n, eps_of(mod)
-    return (n + 2) * (4 * eps + (4 * n + 16) * U) + 2 * eps + 8 * U
+    """A one-tumour sweep's value on the device against its host definition, with the pair's eps (module docstring)."""
+    return chain_bound(pair_eps(mod), mod.n + 2, 4 * mod.n + 16, out=True)
 
 
 def popcount(x):
@@ -96,12 +79,7 @@ def host(n, seed, given):
     mod = model(n, seed=seed)
     rates = mod._partner_rates()
 
-    @functools.lru_cache(maxsize=None)
-    def of(q):
-        whole = mod._partner_host(q, given, rates)
-        whole.setflags(write=False)
-        return whole
-    return of
+    return host_once(lambda q: mod._partner_host(q, given, rates))
 
 
 def queries(n):
@@ -144,11 +122,6 @@ def test_host_definition_against_the_dense_oracle():
             worst = max(worst, rel(host(n, n, "PT")(x)[1, y], ref), rel(host(n, n, "MT")(y)[1, x], ref))
     print(f"host J against exp(dense.patient_lp) of the paired rows of unknown order, n = 1 .. 5: worst relative {worst:.2e}")
     assert worst <= 1e-12
-
-
-def identity_bar(n, additions):
-    """Two host evaluations of one quantity, in u (module docstring): two paths and the additions of the sum."""
-    return 2 * ((2 * n + 4) * (2 * n + 5) + 3) + additions
 
 
 def test_identities():
@@ -332,11 +305,7 @@ def test_python_layer_on_a_mixed_cohort():
 
 
 def test_refusals(monkeypatch):
-    import metmhn_amd.jx as jx
-
-    def no_engine(*a, **k):
-        raise AssertionError("the library was reached")
-    monkeypatch.setattr(jx, "engine", no_engine)
+    no_library(monkeypatch)
     n = 5
     mod = model(n, seed=36)
     g = bits(n, [10])[0]

@@ -5,13 +5,11 @@ CPU: the host definition against a dense absorbing-chain solve built entry by en
 by state (1e-12 relative, the bar against the dense oracle elsewhere), its identities, the link to the likelihood side
 (1 - the summed type-0 likelihoods of every PT genotype), zero rates and refusals, the cohort wrapper.
 
-GPU: the device against the host definition under a bound computed from the row.  Both are fp64 evaluations of
-non-negative sum-products, so with u = 2^-53, A = max_j (|theta_jj| + sum_i |theta_ji|) (the seeding included), B = sum
-|obs1_i|: an exponential of a sum of at most n + 2 terms, and the device's product of three of them, is within
-eps = 2 (n + 2) u max(A, B) + 4 u; a state's den and pull add at most 2 f + 6 roundings, f + 1 levels deep; the final sums
-add S u, S the longest chain of additions of either side - 655 for the device's reduction (forecast.h), NumPy's pairwise
-sums are shorter.  Every output agrees within relative (f + 1) (4 eps + (2 f + 6) u) + S u, which stays below 1e-9 for
-every row used here (asserted).
+GPU: the device against the host definition under a bound computed from the row (lattice_common.forecast_bound): chain_bound with the
+primary tumour's eps (pt_eps, obs1 without the clock's entry).  A state's den and pull add at most 2 f + 6 roundings, f + 1
+levels deep; the final sums add S u, S the longest chain of additions of either side - S_FORECAST = 655 for the device's
+reduction (forecast.h), NumPy's pairwise sums are shorter.  Every output agrees within relative
+(f + 1) (4 eps + (2 f + 6) u) + S u.
 
 Measured on an MI355X, worst error / bound per test: shapes 5.1e-3 (n_mut = 31, until the observation), mixed widths 6.9e-3,
 LUAD-28's 20 fullest genotypes (f = 13 .. 18) 1.6e-3; until the seeding every figure is below 1.1e-3.  The host definition
@@ -24,19 +22,12 @@ import pytest
 
 from metmhn_amd import regularized_optimization as ro
 from metmhn_amd.model import MetMHN, SeedingForecasts
+from lattice_common import forecast_bound, frozen, genotype, note
+from lattice_common import rel_nan as rel
 from order_common import model
 
-U = 2.0 ** -53
-S_DEVICE = 655                     # forecast.h: the longest chain of additions behind an output of the device
 UNTIL = ("seeding", "observation")
 FIELDS = ("p_seed", "time", "before", "with_seed", "n_before")
-WORST = {}                         # test -> worst error / bound seen (printed)
-
-
-def genotype(n, held):
-    g = np.zeros(n, dtype=np.int8)
-    g[list(held)] = 1
-    return g
 
 
 def rates(mod, held_set, until):
@@ -121,18 +112,6 @@ def recursion(mod, g, until):
         F = ld(1) if idx == 0 else sum(G[idx ^ 1 << b] * lam(free[b], state(idx ^ 1 << b), ld) for b in range(f) if idx >> b & 1)
         G[idx] = F / (sum(lam(j, y, ld) for j in free if j not in y) + sig(y, ld) + kap(y, ld))
     return outputs(mod, g, G, until, ld)
-
-
-def rel(got, ref):
-    """Worst |got - ref| / |ref| over the entries; NaN must sit where NaN sits, an exact 0 must be met exactly."""
-    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    assert (np.isnan(got) == np.isnan(ref)).all(), "NaN pattern"
-    ok = ~np.isnan(ref)
-    zero = ok & (ref == 0)
-    assert (got[zero] == 0).all(), "an exact zero of the reference is not met"
-    live = ok & ~zero
-    return float(np.max(np.abs(got[live] - ref[live]) / np.abs(ref[live]), initial=0.0))
 
 
 # ------------------------------------------------------------------------------------------------------------------ CPU
@@ -299,23 +278,9 @@ def test_cohort_wrapper(monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU
-def bound(mod, f):
-    th, n = mod._pt_log_theta, mod.n
-    A = max(abs(th[j, j]) + np.abs(np.delete(th[j, :n], j) if j < n else th[j, :n]).sum() for j in range(n + 1))
-    B = np.abs(mod.obs1[:n]).sum()
-    eps = 2 * (n + 2) * U * max(A, B) + 4 * U
-    b = (f + 1) * (4 * eps + (2 * f + 6) * U) + S_DEVICE * U
-    assert b < 1e-9, (f, b)
-    return b
-
-
 @functools.lru_cache(maxsize=None)
 def _host(n, seed, key, until):
-    mod = model(n, seed=seed)
-    r = mod.seeding_forecast(np.frombuffer(key, dtype=np.int8), until)
-    for name in ("before", "with_seed", "n_before", "next"):
-        getattr(r, name).setflags(write=False)
-    return r
+    return frozen(model(n, seed=seed).seeding_forecast(np.frombuffer(key, dtype=np.int8), until))
 
 
 def host(n, seed, g, until):
@@ -329,12 +294,10 @@ def against_host(tag, n, seed, G, until, dev, mod=None, ref=None):
     for i, g in enumerate(G):
         f = int((g == 0).sum())
         r = ref[i] if ref is not None else host(n, seed, g, until)
-        b = bound(mod, f)
+        b = forecast_bound(mod, f)
         for name, a in zip(FIELDS, dev):
             worst = max(worst, rel(a[i], getattr(r, name)) / b)
-    WORST[tag] = max(WORST.get(tag, 0.0), worst)
-    print(f"{tag}, until {until}: worst error / bound {worst:.3e} over {len(G)} rows")
-    assert worst <= 1.0, (tag, worst)
+    note(f"{tag}, until {until}, {len(G)} rows", worst)
 
 
 def shape_rows():
@@ -465,7 +428,7 @@ def test_output_layout_statuses_and_identities():
         for i, fi in enumerate(f):
             assert (n_before[good][i, fi + 1:] == 0.0).all()
         # each side of an identity is one output within its bound of the exact value (twice for a sum of f of them)
-        check_identities(mod, G[good], until, r, np.array([4 * bound(mod, int(fi)) for fi in f]))
+        check_identities(mod, G[good], until, r, np.array([4 * forecast_bound(mod, int(fi)) for fi in f]))
     with pytest.raises(ValueError, match=r"^row 4: "):
         mod.seeding_forecasts(G)
     th = mod.log_theta.copy()

@@ -7,20 +7,17 @@ oracle elsewhere; exact zeros exact), its identities, the four recursions re-eva
 0, the refusals and the cohort wrapper.
 
 GPU: the device landscape against the host definition and against the forward kernel (mmhn_seeding_forecasts, which
-shares no code with the backward one) under a bound computed from the model.  Both sides are fp64 evaluations of
-non-negative sum-products, so with u = 2^-53, A = max_j (|theta_jj| + sum_i |theta_ji|) (the seeding included),
-B = sum |obs1_i|: an exponential of a sum of at most n + 2 terms, and the device's product of three of them, is within
-eps = 2 (n + 2) u max(A, B) + 4 u; a state's numerator and den take their rates from both sides (4 eps) and add at most
-2 n + 8 roundings; the chain behind a value is at most n + 1 states deep; no value is a sum over tiles, so there is no
-reduction term.  Every value agrees within relative bound(n) = (n + 1) (4 eps + (2 n + 8) u), which stays below 1e-9 for
-every shape used here (asserted).  Against the forward kernel the bar is bound(n) + the forecast bound of the row
-(tests/test_seeding_forecasts.py: (f + 1) (4 eps + (2 f + 6) u) + 655 u).
+shares no code with the backward one) under a bound computed from the model: lattice_common's chain_bound with the
+primary tumour's eps (pt_eps, obs1 without the clock's entry).  A state's numerator and den add at most 2 n + 8 roundings,
+both sides together; the chain behind a value is at most n + 1 states deep; no value is a sum over tiles, so there is no
+reduction term.  Every value agrees within relative bound(n) = (n + 1) (4 eps + (2 n + 8) u).  Against the forward kernel
+the bar is bound(n) + the forecast bound of the row (tests/test_seeding_forecasts.py: f + 1 steps of 2 f + 6, and
+S_FORECAST u for the final sums).
 
 Measured on an MI355X, worst error / bound per test: device against host 1.7e-2 (n = 1, until the seeding; 2.4e-3 at
 n = c + 3), against the forward kernel 5.4e-4 (n = c + 6) and 2.1e-4 (n = 22), statuses 2.5e-3, seeding_risk against
 seeding_forecast 1.4e-3.  The host definition against seeding_forecast of every genotype (CPU): 3.6e-15 relative at the worst.
 """
-import functools
 import re
 
 import numpy as np
@@ -29,54 +26,19 @@ import pytest
 import metmhn_amd.model as model_mod
 from metmhn_amd import regularized_optimization as ro
 from metmhn_amd.model import MetMHN, SeedingLandscape
-from lattice_common import C, U, bits, check_same_bytes, note
-from lattice_common import rel as lattice_rel
+from lattice_common import C, U, bits, check_same_bytes, forecast_bound, genotype, host_once, note
+from lattice_common import landscape_bound as bound
+from lattice_common import rel_nan as rel
 from order_common import mixed_cohort, model
 
 UNTIL = ("seeding", "observation")
 FIELDS = SeedingLandscape.FIELDS
-S_FORECAST = 655                   # forecast.h: the longest chain of additions behind an output of the forward kernel
 
 
-def genotype(n, held):
-    g = np.zeros(n, dtype=np.int8)
-    g[list(held)] = 1
-    return g
-
-
-def rel(got, ref):
-    """lattice_common.rel where NaN must sit where NaN sits."""
-    return lattice_rel(got, ref, nan=True)
-
-
-def eps_of(mod):
-    th, n = mod._pt_log_theta, mod.n
-    A = max(abs(th[j, j]) + np.abs(np.delete(th[j, :n], j) if j < n else th[j, :n]).sum() for j in range(n + 1))
-    B = np.abs(mod.obs1[:n]).sum()
-    return 2 * (n + 2) * U * max(A, B) + 4 * U
-
-
-def bound(mod):
-    """The device landscape against the host definition (module docstring)."""
-    n = mod.n
-    b = (n + 1) * (4 * eps_of(mod) + (2 * n + 8) * U)
-    assert b < 1e-9, (n, b)
-    return b
-
-
-def forecast_bound(mod, f):
-    """The forward kernel against its host definition, as tests/test_seeding_forecasts.py derives it."""
-    b = (f + 1) * (4 * eps_of(mod) + (2 * f + 6) * U) + S_FORECAST * U
-    assert b < 1e-9, (f, b)
-    return b
-
-
-@functools.lru_cache(maxsize=None)
+@host_once
 def host(n, seed, until):
-    """The host landscape [4, 2^n] of order_common.model(n, seed): computed once, never written to."""
-    whole = model(n, seed=seed)._landscape_host(until)
-    whole.setflags(write=False)
-    return whole
+    """The host landscape [4, 2^n] of order_common.model(n, seed)."""
+    return model(n, seed=seed)._landscape_host(until)
 
 
 def forecast_scalars(r):
