@@ -1,8 +1,9 @@
-// Host side of the metMHN engine: the engine's state, its kernel launches, the cohort evaluation and the
-// C ABI of include/metmhn_amd.h.  One engine = one GPU; one main lane (host.h: Lane - a HIP stream with its cooperative flag
+// Host side of the metMHN engine: the engine's state, its kernel launches and the cohort evaluation.
+// One engine = one GPU; one main lane (host.h: Lane - a HIP stream with its cooperative flag
 // set and its fork / join events) and three side lanes that an evaluation forks off it.
 // The rest of the host side lives in headers of this one translation unit: plan.h (the cohort planner, host-only:
-// batches, routes, work lists, offsets), host.h (errors, device arrays, lanes, MMHN_* knob readers), comm.h (RCCL),
+// batches, routes, work lists, offsets), host.h (errors, device arrays, lanes, the kernel timer, MMHN_* knob readers), comm.h (RCCL),
+// tsolve_host.h (the book-keeping of the cooperative launches), capi.h (the C ABI of include/metmhn_amd.h, included last),
 // rowmix_host.h (row weights and row groups: their checks, device copies and the launches of the group kernels),
 // prims.h / orders_host.h / orderpost_host.h (the batching of the order-posterior entry points, opr_rows) /
 // orderprec_host.h / orderpos_host.h / ordertime_host.h / ordersnap_host.h / ordersample_host.h / forecast_host.h / lattice_host.h / landscape_host.h / genodist_host.h / metdist_host.h / partner_host.h / cross_host.h / sampler_host.h / bench.h (what is not the cohort evaluation).
@@ -34,6 +35,7 @@
 #include "host.h"
 #include "comm.h"
 #include "plan.h"
+#include "tsolve_host.h"
 #include "sampler.h"
 #include "rowmix.h"
 
@@ -102,12 +104,66 @@ struct Config {
   }
 };
 
+// what of an engine does not depend on its dtype: the ABI reads it without a dispatch (capi.h)
 struct EngineBase {
   virtual ~EngineBase() = default;
   int dtype = 0;
   int device = 0;
   hipStream_t stream = nullptr;       // the main lane's (Engine::main.s): set when the engine is created, never reassigned
   Config cfg;
+  int n = 0, N = 0;
+  // ---- cohort: its shape
+  long long n_pat = 0;
+  int n_cols = 0;
+  long long n_unknown = 0;            // rows of dat type 4
+  // the three counts of the objective: sum of w [seeding = 1], sum of w, sum of w [type 4], taken on the host in row order -
+  // plain: w = 1 (the integer counts), weighted: the row weights, grouped: the weights of the row groups
+  struct Counts { double em = 0, pat = 0, unknown = 0; } plain, weighted, grouped;
+  // ---- row weights (mmhn_set_row_weights, rowmix_host.h): by cohort row, empty = none
+  std::vector<double> row_w;
+  // ---- row groups (mmhn_set_row_groups, rowmix.h, rowmix_host.h): the group lists and weights as given (grp_ptr empty = none)
+  std::vector<long long> grp_ptr;
+  std::vector<int> grp_rows;
+  std::vector<double> grp_w;
+  double reduce_flag = 0.0, reduce_flag_sum = 0.0;            // mmhn_set_reduce_flag / mmhn_get_reduce_flag
+  // ---- communicator: patient shards on several GPUs, one communicator per engine, the all-reduce runs on the engine's stream
+  ncclComm_t comm = nullptr;
+  int comm_rank = 0, comm_size = 1;
+  mmhn_counters cnt{};                // mmhn_get_counters
+
+  int stride() const { return 1 + N * N + 2 * N; }
+  int full_len() const { return 4 + 2 * N * N + 3 * N; }     // doubles of mmhn_cohort_sums
+  bool mixing() const { return !grp_ptr.empty(); }
+  // the counts of the objective that hold for the next evaluation (with row groups: the group-weighted ones)
+  const Counts& counts() const { return mixing() ? grouped : row_w.empty() ? plain : weighted; }
+  void row_weight_sums(double* out3) const { out3[0] = counts().em; out3[1] = counts().pat; out3[2] = counts().unknown; }
+  void reset_counters() {                              // (what RCCL said about the communicator stays)
+    const int r = cnt.comm_ranks, k = cnt.comm_rank;
+    cnt = mmhn_counters{};
+    cnt.comm_ranks = r; cnt.comm_rank = k;
+  }
+  void comm_init(const ncclUniqueId& id, int rank, int nranks) {
+    REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks, "comm_init: rank / n_ranks out of range");
+    REQUIRE(nranks == 1 || !mixing(), "comm_init: the engine holds row groups, which need a one-rank engine (remove them first)");
+    comm_destroy();
+    RCCLCHECK(rccl().CommInitRank(&comm, nranks, id, rank));
+    comm_rank = rank; comm_size = nranks;
+    // what RCCL itself says about the communicator (mmhn_get_counters: the bench line's proof that it spans the ranks)
+    int cnt_ = 0, rk_ = -1;
+    RCCLCHECK(rccl().CommCount(comm, &cnt_));
+    RCCLCHECK(rccl().CommUserRank(comm, &rk_));
+    if (cnt_ != nranks || rk_ != rank) {
+      comm_destroy();
+      throw Fail{"comm_init: RCCL reports " + std::to_string(cnt_) + " ranks / rank " + std::to_string(rk_) + ", asked for " +
+                 std::to_string(nranks) + " / " + std::to_string(rank)};
+    }
+    cnt.comm_ranks = cnt_; cnt.comm_rank = rk_;
+  }
+  void comm_destroy() {
+    if (comm) { (void)rccl().CommDestroy(comm); comm = nullptr; }
+    comm_rank = 0; comm_size = 1;
+    cnt.comm_ranks = 0; cnt.comm_rank = -1;
+  }
 };
 
 template <typename T> struct Engine;
@@ -135,7 +191,6 @@ static void raise_lds(size_t bytes, K... kernels) {
 template <typename T>
 struct Engine : EngineBase {
   using PList = mmhn::PList<T>;
-  int n = 0, N = 0;
   // ---- parameters
   DevArr<Params<T>> d_par;
   Params<T>* h_par = nullptr;         // pinned: the per-evaluation upload is a true async copy
@@ -145,11 +200,6 @@ struct Engine : EngineBase {
   DevArr<int> d_lvl;
   // ---- cohort: the rows, their plan (plan.h) and its device copy, one entry per batch
   std::vector<int8_t> dat;
-  long long n_pat = 0;
-  int n_cols = 0;
-  // the three counts of the objective: sum of w [seeding = 1], sum of w, sum of w [type 4], taken on the host in row order -
-  // plain: w = 1 (the integer counts), weighted: the row weights, grouped: the weights of the row groups
-  struct Counts { double em = 0, pat = 0, unknown = 0; } plain, weighted, grouped;
   std::vector<Batch> batches;
   std::vector<BatchDev> dev;
   // ---- workspace (sized for the largest batch)
@@ -162,17 +212,11 @@ struct Engine : EngineBase {
   DevArr<T> zarena;
   struct View { T* p = nullptr; } GJ, DJ, Abuf;
   int pi_owner = -1, qJ_owner = -1;   // batch whose (pruned) layout the zero-initialised buffers hold
-  DevArr<double> lp, out, sums, abi_sums, redbuf;
+  DevArr<double> lp, out, sums, redbuf;
   DevArr<double> resp;                // [n_pat] by cohort row: P(seeded | genotype) of the rows of unknown status (dat type 4), written
                                       // where their score is formed; NaN everywhere else (filled once, when the cohort is set)
-  long long n_unknown = 0;            // rows of dat type 4
-  // ---- row weights (mmhn_set_row_weights, rowmix_host.h): by cohort row, empty = none
-  std::vector<double> row_w;
-  // ---- row groups (mmhn_set_row_groups, rowmix.h, rowmix_host.h): the group lists and weights as given (grp_ptr empty =
-  // none), the transposed lists and the per-evaluation arrays on the device
-  std::vector<long long> grp_ptr;
-  std::vector<int> grp_rows;
-  std::vector<double> grp_w;
+  // ---- row groups on the device (the lists and weights as given: EngineBase): the group lists, the transposed lists and the
+  // per-evaluation arrays
   struct GroupsDev {
     DevArr<long long> gptr, mptr;
     DevArr<int> grows, mgrp;
@@ -180,51 +224,35 @@ struct Engine : EngineBase {
   } gd;
   bool want_rho = false;              // mmhn_group_posteriors: k_group_lse also writes rho
   DevArr<JLink<T>> links;
-  double* h_abi = nullptr;            // pinned landing buffer of the result download
-  double* h_abi_dev = nullptr;        // device view of it
   // ---- lanes (host.h): main carries the joint path; side[0], side[1] the small-space launches (small_classes), side[2] the
   // staged own-problem patients, whose cooperative launches use the second flag set
   Lane main, side[3];
-  // ---- cooperative launches (tsolve.h): queue heads + abort word, the flags of the tiles (value = epoch of the launch that
-  // finished the tile), the pinned host copy of the abort word
-  DevArr<CoopCtl> coop_ctl;
-  DevArr<unsigned> coop_flags[2];   // one set per lane that issues such launches (Lane::flags): two may be in flight together
-  unsigned coop_epoch = 0;
-  int coop_slot = 0;
-  unsigned* h_abort = nullptr;
-  unsigned* h_abort_dev = nullptr;
-  bool coop_used = false;           // an evaluation issued a cooperative launch since the last check_abort
+  // ---- cooperative launches (tsolve_host.h)
+  CoopState coop;
   bool coop_alone = false;          // set per batch: no side stream carries whole-CU work next to the joint solves (tsolve.h: WPE)
+  // ---- set by cohort_sums_begin around evaluate(): the last batch's reduction also packs (k_reduce_parts_pack; done: it did)
+  struct Pack { int mode = 0; double a = 0, b = 0; double* dst = nullptr; bool done = false; } pack;
   // ---- pending evaluation (cohort_sums_begin ... cohort_sums_end)
-  bool sums_pending = false;
-  std::chrono::steady_clock::time_point sums_t0, sums_issued;
-  int sums_len = 0;                                           // doubles of the pending result
-  // set by cohort_sums_begin around evaluate(): the last batch's reduction also packs (k_reduce_parts_pack)
-  int pack_mode = 0;
-  double pack_a = 0, pack_b = 0;
-  double* pack_dst = nullptr;
-  bool packed_in_eval = false;
-  double reduce_flag = 0.0, reduce_flag_sum = 0.0;            // mmhn_set_reduce_flag / mmhn_get_reduce_flag
-  bool flag_pending = false;
-  // ---- communicator: patient shards on several GPUs, one communicator per engine, the all-reduce runs on the engine's stream
-  ncclComm_t comm = nullptr;
-  int comm_rank = 0, comm_size = 1;
-  // ---- counters (mmhn_get_counters).  HIP events around the dominant kernels: an event record costs ~5 us of host time,
-  // which a short evaluation cannot afford (it is bound by the host's issue rate) - only batches of at least 2^26 states
-  // are timed (set per batch; MMHN_TIME_KERNELS=1: every batch)
-  bool time_kernels = true;
-  mmhn_counters cnt{};
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
-  size_t ev_used = 0;
-  std::vector<double> ev_bytes;
-  std::vector<int> ev_slot;           // MMHN_K_* class of the timed launch
+  struct Pending {
+    bool on = false;
+    std::chrono::steady_clock::time_point t0, issued;
+    int len = 0;                        // doubles of the pending result
+    bool flag = false;                  // the reduce flag rides behind them
+    DevArr<double> abi_sums;            // the buffer that is all-reduced
+    double* h_abi = nullptr;            // pinned landing buffer of the result download
+    double* h_abi_dev = nullptr;        // device view of it
+  } pending;
+  // ---- timed launches (host.h), set per batch
+  KernelTimer timer;
 
   static long long zarena_elems(long long nJ, long long asize, int N) { return up4(3 * nJ * N * N) + up4(3 * nJ * N) + up4(asize); }
   // elements of a batch's zarena that the memset clears
   static long long zclear_elems(const Batch& b, int N) { return zarena_elems((long long)b.dJ.size(), b.aclr, N); }
 
-  Engine(int dev_id, int n_mut) : n(n_mut), N(n_mut + 1) {
+  Engine(int dev_id, int n_mut) {
+    dtype = std::is_same<T, double>::value ? MMHN_F64 : MMHN_F32;
     device = dev_id;
+    n = n_mut; N = n_mut + 1;
     cnt.comm_rank = -1;
     REQUIRE(n_mut >= 1 && n_mut < MAXN, "n_mut must be in [1, 31]");
     DevGuard guard(device);
@@ -271,11 +299,7 @@ struct Engine : EngineBase {
               &k_sweep<T, false>, &k_sweep<T, true>, &k_diag<T>, &k_diag<T, 1024>,
               &k_prep<T, false>, &k_prep<T, true>, &k_prep<T, false, 1024>, &k_grad_rows<T, 1>, &k_grad_rows<T>,
               &k_pclass<T, false>, &k_pclass<T, true>, &k_class_marg<T>);
-    coop_ctl.alloc(1);
-    HIPCHECK(hipMemset(coop_ctl.p, 0, sizeof(CoopCtl)));
-    HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&h_abort), 64, hipHostMallocDefault));
-    HIPCHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h_abort_dev), h_abort, 0));
-    *h_abort = 0u;
+    coop.init();
     for (Lane& l : side) {
       HIPCHECK(hipStreamCreateWithFlags(&l.s, hipStreamNonBlocking));
       HIPCHECK(hipEventCreateWithFlags(&l.ev_fork, hipEventDisableTiming));
@@ -283,29 +307,31 @@ struct Engine : EngineBase {
     }
     side[2].flags = 1;
   }
-  ~Engine() override {                       // runs under the DevGuard of mmhn_destroy
+  // runs under the DevGuard of mmhn_destroy.  The order of the releases is written out here (communicator, timing events,
+  // side lanes, pinned buffers, main stream); device arrays go with their DevArr afterwards.
+  ~Engine() override {
     comm_destroy();
-    for (auto& e : ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    timer.release();
     for (Lane& l : side) {
       if (l.ev_join) (void)hipEventDestroy(l.ev_join);
       if (l.ev_fork) (void)hipEventDestroy(l.ev_fork);
       if (l.s) (void)hipStreamDestroy(l.s);
     }
     if (h_par) (void)hipHostFree(h_par);
-    if (h_abi) (void)hipHostFree(h_abi);
-    if (h_abort) (void)hipHostFree(h_abort);
+    if (pending.h_abi) (void)hipHostFree(pending.h_abi);
+    coop.release();
     if (stream) (void)hipStreamDestroy(stream);
     stream = nullptr;
   }
-  int stride() const { return 1 + N * N + 2 * N; }
 
   // ---------------------------------------------------------------- parameters
+  // lt == nullptr: a zero log-theta (exp(0.0) is exactly 1.0)
   void build_params(const double* lt, const double* ldp, const double* ldm, bool upload = true) {
-    REQUIRE(!sums_pending, "an evaluation begun with mmhn_cohort_sums_begin has not been collected (its parameter upload may still be in flight)");
+    REQUIRE(!pending.on, "an evaluation begun with mmhn_cohort_sums_begin has not been collected (its parameter upload may still be in flight)");
     // exp(theta_ij - d_j) = exp(theta_ij) * exp(-d_j): N^2 + 2N exponentials per evaluation instead of 3 N^2 (this runs
     // on the host before the first launch of every evaluation - 26 us of a 400 us LUAD evaluation as three full passes)
     std::vector<double> eth((size_t)N * N), enp(N, 1.0), enm(N, 1.0);
-    for (int e = 0; e < N * N; ++e) eth[e] = std::exp(lt[e]);
+    for (int e = 0; e < N * N; ++e) eth[e] = lt ? std::exp(lt[e]) : 1.0;
     if (ldp) for (int j = 0; j < N; ++j) enp[j] = std::exp(-ldp[j]);
     if (ldm) for (int j = 0; j < N; ++j) enm[j] = std::exp(-ldm[j]);
     for (int s = 0; s < NPSET; ++s) {
@@ -363,7 +389,7 @@ struct Engine : EngineBase {
                            lidg, rhs, rhs_mode, scal, std::max(maxk, 1), tab);
       }, tr);
     };
-    if (alg_bytes > 0) { timed(L, MMHN_K_OTHER_SOLVE, alg_bytes, launch); return; }   // (a launch without algorithmic bytes is never timed)
+    if (alg_bytes > 0) { timer.timed(L, MMHN_K_OTHER_SOLVE, alg_bytes, launch); return; }   // (a launch without algorithmic bytes is never timed)
     launch();
     HIPCHECK(hipGetLastError());
   }
@@ -377,19 +403,6 @@ struct Engine : EngineBase {
       hipLaunchKernelGGL((k_kv<T, tr_(), 1, jac()>), dim3(ntiles), dim3(KSB), lds, L.s, descs, map, ntiles, p, y, tab, hxt, maxk, zmap, lidg, rhs);
     }, tr, lidg != nullptr);
     HIPCHECK(hipGetLastError());
-  }
-  void collect_events() {
-    for (size_t i = 0; i < ev_used; ++i) {
-      float ms = 0;
-      HIPCHECK(hipEventElapsedTime(&ms, ev_pool[i].first, ev_pool[i].second));
-      mmhn_kernel_counter& c = cnt.kernel[ev_slot[i]];
-      c.ms += ms;
-      c.launches += 1;
-      c.alg_bytes += ev_bytes[i];
-    }
-    ev_used = 0;
-    ev_bytes.clear();
-    ev_slot.clear();
   }
 
   void launch_diag(const Lane& L, const Desc* descs, const int2* map, int ntiles, const T* p, T* outp, const T* dvec, int what,
@@ -433,30 +446,6 @@ struct Engine : EngineBase {
   void poison_fill(const Lane& L, T* p, long long count) {
     if (cfg.poison && count > 0) HIPCHECK(hipMemsetAsync(p, 0xFF, (size_t)count * sizeof(T), L.s));
   }
-  // timed launch helper shared by the two solvers: the events are recorded on the lane of the launch (they are not
-  // created with hipEventDisableTiming - evaluate() keeps a timed batch on the main lane)
-  template <typename F>
-  void timed(const Lane& L, int slot, double alg_bytes, F&& launch) {
-    if (!time_kernels) {
-      launch();
-      HIPCHECK(hipGetLastError());
-      return;
-    }
-    if (ev_used == ev_pool.size()) {
-      hipEvent_t a, b;
-      HIPCHECK(hipEventCreate(&a));
-      HIPCHECK(hipEventCreate(&b));
-      ev_pool.push_back({a, b});
-    }
-    hipEvent_t e0 = ev_pool[ev_used].first, e1 = ev_pool[ev_used].second;
-    ++ev_used;
-    ev_bytes.push_back(alg_bytes);
-    ev_slot.push_back(slot);
-    HIPCHECK(hipEventRecord(e0, L.s));
-    launch();
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipEventRecord(e1, L.s));
-  }
 
   // k_psolve2 (one workgroup per patient, all-seeded-tile launches)
   size_t psolve2_lds(int maxk) const {
@@ -473,17 +462,16 @@ struct Engine : EngineBase {
       double bytes = 0;
       for (const WDesc& w : b.wd) bytes += 0.5 * (double)(1ll << b.dJ[w.prob].k) * sizeof(T);
       T* yw = b.wdirect ? y : (tr ? qM.p : piM.p);
-      timed(L, tr ? MMHN_K_PSOLVE_ADJ : MMHN_K_PSOLVE_FWD, bytes, [&]() {
+      timer.timed(L, tr ? MMHN_K_PSOLVE_ADJ : MMHN_K_PSOLVE_FWD, bytes, [&]() {
         const int nch = (int)b.wchains.size();
         const dim3 g((unsigned)std::min(nch, cfg.plan.wsolve_wgs > 0 ? cfg.plan.wsolve_wgs : cfg.plan.n_cu)), bk(WROWS);
         const size_t lds = wsolve_lds<T>();
-#define WS_ARGS g, bk, lds, L.s, db.dJ.p, db.wd.p, db.wchains.p, nch, yw, tabJ.p, links.p, qS.p
+        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, g, bk, lds, L.s, db.dJ.p, db.wd.p, db.wchains.p, nch, yw, tabJ.p, links.p, qS.p); };
         // (a batch whose chains all have the same number of external bits - every k = 20 cohort: 5, k = 25: 9 - runs the instantiation
         // that knows it at compile time)
-        if (b.wnx == WCfg<T>::NXT) { if (tr) hipLaunchKernelGGL((k_wsolve<T, true, WCfg<T>::NXT>), WS_ARGS); else hipLaunchKernelGGL((k_wsolve<T, false, WCfg<T>::NXT>), WS_ARGS); }
-        else if (tr) hipLaunchKernelGGL((k_wsolve<T, true>), WS_ARGS);
-        else hipLaunchKernelGGL((k_wsolve<T, false>), WS_ARGS);
-#undef WS_ARGS
+        if (b.wnx == WCfg<T>::NXT) { if (tr) go(&k_wsolve<T, true, WCfg<T>::NXT>); else go(&k_wsolve<T, false, WCfg<T>::NXT>); }
+        else if (tr) go(&k_wsolve<T, true>);
+        else go(&k_wsolve<T, false>);
       });
       if (!b.wdirect) {
         hipLaunchKernelGGL((k_wconvert<T>), dim3(nW, 32), dim3(WROWS), 0, L.s, db.dJ.p, db.wd.p, yw, y);
@@ -499,7 +487,7 @@ struct Engine : EngineBase {
       const double bytes = (double)b.ptiles.size() * (double)(1 << TB) * sizeof(T);
       const bool dlok = b.max_dl <= dl_cap;       // every patient's dP / dM tile slices fit the dl area: branch-free instantiation
       const int nold = (int)b.olist.size();
-      timed(L, tr ? MMHN_K_PSOLVE_ADJ : MMHN_K_PSOLVE_FWD, bytes, [&]() {
+      timer.timed(L, tr ? MMHN_K_PSOLVE_ADJ : MMHN_K_PSOLVE_FWD, bytes, [&]() {
         with_flags([&](auto tr_, auto dl) {
           hipLaunchKernelGGL((k_psolve2<T, tr_(), dl()>), dim3(nold), dim3(TSB), lds, L.s, db.dJ.p, db.ptoff.p, db.ptiles.p, d_par.p, y, rhs_mode,
                              d_perm.p, mk, tabJ.p, links.p, qS.p, dl_cap, db.olist.p);
@@ -538,31 +526,19 @@ struct Engine : EngineBase {
       const int nitems = (int)cl.items.size();
       REQUIRE(nitems == P.ntiles, "cooperative solve: work list and tile list differ");
       REQUIRE(L.flags >= 0, "cooperative solve: issued on a lane without a flag set");
-      DevArr<unsigned>& flags = coop_flags[L.flags];
-      if (flags.n < (size_t)nitems) {
-        HIPCHECK(hipStreamSynchronize(L.s));                // (a launch of this lane may still poll the old array)
-        flags.alloc((size_t)nitems + 1024);
-        HIPCHECK(hipMemsetAsync(flags.p, 0, flags.n * sizeof(unsigned), L.s));
-      }
-      if (++coop_epoch == 0u) {                                // (wrapped: no stale flag may equal a future epoch)
-        HIPCHECK(hipDeviceSynchronize());
-        for (auto& f : coop_flags) if (f.p) HIPCHECK(hipMemset(f.p, 0, f.n * sizeof(unsigned)));
-        coop_epoch = 1u;
-      }
-      coop_slot = (coop_slot + 1) & 3;
-      const int slot = L.flags * 4 + coop_slot;
-      coop_used = true;
-      timed(L, P.kslot, per_tile * nitems, [&]() {
+      const CoopState::Launch cl_ = coop.begin_launch(L, nitems);
+      timer.timed(L, P.kslot, per_tile * nitems, [&]() {
         const dim3 g((unsigned)std::min(nitems, cfg.coop_wgs > 0 ? cfg.coop_wgs : cfg.plan.n_cu)), bk(TSB);
-#define CS_ARGS g, bk, lds, L.s, P.d, dcl.items.p, dcl.deps.p, nitems, flags.p, coop_epoch, coop_ctl.p, slot, h_abort_dev, cfg.coop_fault ? 1 : 0, \
-                y, lidg, rhs, rhs_mode, scal, d_perm.p, mk, P.tab, links.p, qS.p
+        auto go = [&](auto kern) {
+          hipLaunchKernelGGL(kern, g, bk, lds, L.s, P.d, dcl.items.p, dcl.deps.p, nitems, cl_.flags, cl_.epoch, coop.ctl.p, cl_.slot, coop.h_abort_dev,
+                             cfg.coop_fault ? 1 : 0, y, lidg, rhs, rhs_mode, scal, d_perm.p, mk, P.tab, links.p, qS.p);
+        };
         // (three of the four (lidg, coop_alone) variants exist: a list with a lidg vector never runs the 4-wave one)
         with_flags([&](auto tr_) {
-          if (lidg) hipLaunchKernelGGL((k_csolve<T, tr_(), true>), CS_ARGS);
-          else if (coop_alone) hipLaunchKernelGGL((k_csolve<T, tr_(), false, 4>), CS_ARGS);   // (nothing runs beside the joint solves of this batch: 93 registers)
-          else hipLaunchKernelGGL((k_csolve<T, tr_(), false>), CS_ARGS);
+          if (lidg) go(&k_csolve<T, tr_(), true>);
+          else if (coop_alone) go(&k_csolve<T, tr_(), false, 4>);   // (nothing runs beside the joint solves of this batch: 93 registers)
+          else go(&k_csolve<T, tr_(), false>);
         }, tr);
-#undef CS_ARGS
       });
       return;
     }
@@ -570,23 +546,13 @@ struct Engine : EngineBase {
       const int lev = tr ? nlev - 1 - s : s;
       const int beg = (*P.lof)[lev], cntl = (*P.lof)[lev + 1] - beg;
       if (cntl == 0) continue;
-      timed(L, P.kslot, per_tile * cntl, [&]() {
+      timer.timed(L, P.kslot, per_tile * cntl, [&]() {
         with_flags([&](auto tr_, auto jac) {
           hipLaunchKernelGGL((k_tsolve<T, tr_(), jac()>), dim3(cntl), dim3(TSB), lds, L.s, P.d, P.lmap + beg, d_par.p, y, lidg, rhs, rhs_mode, scal,
                              d_perm.p, d_lvl.p, mk, P.tab, links.p, qS.p);
         }, tr, lidg != nullptr);
       });
     }
-  }
-  // a spin of a cooperative launch timed out (tsolve.h): the results of the evaluation are garbage - fail the call, and put
-  // the words back so that the engine stays usable.  Call after the stream has been synchronised.
-  void check_abort() {
-    if (!coop_used) return;
-    coop_used = false;
-    if (*h_abort == 0u) return;
-    *h_abort = 0u;
-    (void)hipMemset(coop_ctl.p, 0, sizeof(CoopCtl));
-    throw Fail{"cooperative tile solve: a wait for another workgroup's tile timed out (results discarded)"};
   }
 
   // ---------------------------------------------------------------- cohort
@@ -615,7 +581,7 @@ struct Engine : EngineBase {
   void set_cohort(const int8_t* d_, long long np, int nc) {
     REQUIRE(nc == 2 * n + 3, "dat must have 2*n_mut+3 columns");
     REQUIRE(np >= 0, "negative patient count");
-    REQUIRE(!sums_pending, "mmhn_set_cohort: an evaluation begun with mmhn_cohort_sums_begin has not been collected");
+    REQUIRE(!pending.on, "mmhn_set_cohort: an evaluation begun with mmhn_cohort_sums_begin has not been collected");
     dat.assign(d_, d_ + np * nc);
     n_pat = np;
     n_cols = nc;
@@ -639,10 +605,6 @@ struct Engine : EngineBase {
       throw;
     }
   }
-  bool mixing() const { return !grp_ptr.empty(); }
-  // the counts of the objective that hold for the next evaluation (with row groups: the group-weighted ones)
-  const Counts& counts() const { return mixing() ? grouped : row_w.empty() ? plain : weighted; }
-  void row_weight_sums(double* out3) const { out3[0] = counts().em; out3[1] = counts().pat; out3[2] = counts().unknown; }
   // device copies of the plan and the workspace
   void place_cohort() {
     dev.resize(batches.size());
@@ -745,7 +707,7 @@ struct Engine : EngineBase {
   void batch_prepare(const Batch& b, bool grad, bool cleared) {
     const int nJ = (int)b.dJ.size();
     coop_alone = b.stg[0].empty();                          // (no second cooperative launch on a side stream next to the joint solves)
-    time_kernels = cfg.force_timing || b.vecJ + b.vecS >= (1ll << 26);
+    timer.on = cfg.force_timing || b.vecJ + b.vecS >= (1ll << 26);
     GJ.p = zarena.p;
     DJ.p = GJ.p + up4(3ll * nJ * N * N);
     Abuf.p = DJ.p + up4(3ll * nJ * N);
@@ -848,7 +810,7 @@ struct Engine : EngineBase {
     if (!cfg.plan.use_jacobi) {
       // algorithmic bytes: the seeded halves of pi and q_J read once
       const double mbytes = (double)b.vecJ * sizeof(T);
-      timed(main, MMHN_K_PCLASS, mbytes, [&]() {
+      timer.timed(main, MMHN_K_PCLASS, mbytes, [&]() {
         if (b.wdirect) {                                                  // window-layout problems: both classes, two reads
           const int nW = (int)b.wd.size();
           hipLaunchKernelGGL((k_wclass<T>), dim3((unsigned)std::min(nW, cfg.plan.n_cu)), dim3(WROWS), wclass_lds<T>(), main.s, db.dJ.p, db.wd.p, nW, pi.p, qJ.p, Abuf.p);
@@ -905,10 +867,10 @@ struct Engine : EngineBase {
       hipLaunchKernelGGL(k_reduce_rows_w, dim3(cols.x, nchunk), dim3(BLOCK), 0, main.s, db.pats.p, npat, per, out.p, st, nelem,
                          db.wrow.p, redbuf.p);
     HIPCHECK(hipGetLastError());
-    if (pack_mode && &b == &batches.back()) {
+    if (pack.mode && &b == &batches.back()) {
       hipLaunchKernelGGL(k_reduce_parts_pack, dim3((st + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, main.s, redbuf.p, st, nelem, nchunk,
-                         sums.p, pack_mode, N, pack_a, pack_b, pack_dst);
-      packed_in_eval = true;
+                         sums.p, pack.mode, N, pack.a, pack.b, pack.dst);
+      pack.done = true;
     } else {
       hipLaunchKernelGGL(k_reduce_parts, dim3(cols.x, 2), dim3(BLOCK), 0, main.s, redbuf.p, st, nelem, nchunk, sums.p);
     }
@@ -920,7 +882,7 @@ struct Engine : EngineBase {
     std::vector<double> tmp((size_t)npat * st);
     HIPCHECK(hipMemcpyAsync(tmp.data(), out.p, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, main.s));
     HIPCHECK(hipStreamSynchronize(main.s));
-    check_abort();
+    coop.check_abort();
     for (int i = 0; i < npat; ++i)
       std::memcpy(host_out + (size_t)b.pats[i].row * st, tmp.data() + (size_t)i * st, st * sizeof(double));
   }
@@ -928,7 +890,7 @@ struct Engine : EngineBase {
     std::vector<double> hs(2 * stride());
     HIPCHECK(hipMemcpyAsync(hs.data(), sums.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost, main.s));
     HIPCHECK(hipStreamSynchronize(main.s));
-    check_abort();
+    coop.check_abort();
     std::memcpy(host_sums, hs.data(), hs.size() * sizeof(double));
   }
 
@@ -939,7 +901,7 @@ struct Engine : EngineBase {
   // the sweep with gradient.
   void evaluate(const double* lt, const double* ldp, const double* ldm, bool want_grad, double* host_sums,
                 double* host_out) {
-    REQUIRE(!sums_pending, "an evaluation begun with mmhn_cohort_sums_begin has not been collected");
+    REQUIRE(!pending.on, "an evaluation begun with mmhn_cohort_sums_begin has not been collected");
     const bool mix = mixing();
     const int nsweep = mix && want_grad && batches.size() > 1 ? 2 : 1;
     const bool reduce_behind = mix && !want_grad && batches.size() > 1;
@@ -957,7 +919,7 @@ struct Engine : EngineBase {
         prep(main, db.dJ.p, nJ, tabJ.p, true, b.maxkcJ);              // (first: the head of the critical chain)
         // staged patients that are their own problem: a side lane of their own from here to the assembly, with its own
         // flag set for their cooperative launches (a timed batch keeps them on the main lane, where its events are recorded)
-        Lane& own = time_kernels ? main : side[2];
+        Lane& own = timer.on ? main : side[2];
         const bool own_apart = &own != &main && !b.stg[0].empty();
         if (own_apart) {
           own.begin(main);
@@ -993,7 +955,7 @@ struct Engine : EngineBase {
       launch_mix(*this, main);
       for (const Batch& b : batches) reduce_batch(b, 1);
     }
-    time_kernels = true;
+    timer.on = true;
     if (host_sums) {
       download_sums(host_sums);
       finish_eval(t0);
@@ -1007,13 +969,8 @@ struct Engine : EngineBase {
     for (long long i = 0; i < n_pat; ++i) lp_out[i] = rows[(size_t)i * st];
     if (n_pat > 0) HIPCHECK(hipMemcpy(p_seeded, resp.p, (size_t)n_pat * sizeof(double), hipMemcpyDeviceToHost));
   }
-  void reset_counters() {                              // (what RCCL said about the communicator stays)
-    const int r = cnt.comm_ranks, k = cnt.comm_rank;
-    cnt = mmhn_counters{};
-    cnt.comm_ranks = r; cnt.comm_rank = k;
-  }
   void finish_eval(std::chrono::steady_clock::time_point t0) {
-    collect_events();
+    timer.collect(cnt);
     cnt.eval_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     cnt.evals += 1;
   }
@@ -1027,84 +984,59 @@ struct Engine : EngineBase {
   // w_combined (optional): pack w * EM + NM on the device (k_pack_wsums) - 1 + N^2 + 2N doubles travel instead of
   // 4 + 2 N^2 + 3 N
   void cohort_sums_begin(const double* lt, const double* ldp, const double* ldm, bool grad, const double* w_combined = nullptr) {
-    REQUIRE(!sums_pending, "mmhn_cohort_sums_begin: the previous evaluation has not been collected");
-    sums_t0 = std::chrono::steady_clock::now();
-    const int full = 4 + 2 * N * N + 3 * N;
-    const int total = w_combined ? stride() : full;
-    abi_sums.alloc(full);
-    if (!h_abi) {
-      HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&h_abi), (size_t)full * sizeof(double), hipHostMallocDefault));
-      HIPCHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h_abi_dev), h_abi, 0));
+    Pending& pd = pending;
+    REQUIRE(!pd.on, "mmhn_cohort_sums_begin: the previous evaluation has not been collected");
+    pd.t0 = std::chrono::steady_clock::now();
+    const int total = w_combined ? stride() : full_len();
+    pd.abi_sums.alloc(full_len());
+    if (!pd.h_abi) {
+      HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&pd.h_abi), (size_t)full_len() * sizeof(double), hipHostMallocDefault));
+      HIPCHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&pd.h_abi_dev), pd.h_abi, 0));
     }
     // without a communicator the packing kernel writes the result straight into the pinned buffer; with one the
     // all-reduce works on device memory and the copy engine brings its result down
-    double* packed = (cfg.zero_copy && !comm) ? h_abi_dev : abi_sums.p;
+    double* packed = (cfg.zero_copy && !comm) ? pd.h_abi_dev : pd.abi_sums.p;
     // the reduce flag belongs to the weighted evaluation alone: a plain one in between leaves it for the next weighted one.
     // Taken out of the member before anything is issued, so that an evaluation that throws cannot leave it to a later one.
     double flag = 0.0;
     if (w_combined) { flag = reduce_flag; reduce_flag = 0.0; }
-    pack_mode = w_combined ? 2 : 1;
-    pack_a = w_combined ? *w_combined : counts().em; pack_b = w_combined ? flag : counts().pat; pack_dst = packed;
-    packed_in_eval = false;
-    struct Unset { int& m; ~Unset() { m = 0; } } unset{pack_mode};
+    pack = Pack{w_combined ? 2 : 1, w_combined ? *w_combined : counts().em, w_combined ? flag : counts().pat, packed, false};
+    struct Unset { int& m; ~Unset() { m = 0; } } unset{pack.mode};
     evaluate(lt, ldp, ldm, grad, nullptr, nullptr);
-    if (!packed_in_eval) {                                 // (no batch: an empty cohort)
+    if (!pack.done) {                                      // (no batch: an empty cohort)
       if (w_combined) hipLaunchKernelGGL(k_pack_wsums, dim3(2), dim3(256), 0, stream, sums.p, N, *w_combined, packed, flag);
       else hipLaunchKernelGGL(k_pack_sums, dim3(2), dim3(256), 0, stream, sums.p, N, counts().em, counts().pat, packed);
       HIPCHECK(hipGetLastError());
     }
     const int moved = total + (w_combined ? 1 : 0);            // (the reduce flag rides behind the pre-combined buffer)
-    if (comm) RCCLCHECK(rccl().AllReduce(abi_sums.p, abi_sums.p, (size_t)moved, ncclFloat64, ncclSum, comm, stream));
-    if (packed == abi_sums.p) HIPCHECK(hipMemcpyAsync(h_abi, abi_sums.p, moved * sizeof(double), hipMemcpyDeviceToHost, stream));
-    flag_pending = w_combined != nullptr;
-    sums_issued = std::chrono::steady_clock::now();
-    sums_pending = true;
-    sums_len = total;
+    if (comm) RCCLCHECK(rccl().AllReduce(pd.abi_sums.p, pd.abi_sums.p, (size_t)moved, ncclFloat64, ncclSum, comm, stream));
+    if (packed == pd.abi_sums.p) HIPCHECK(hipMemcpyAsync(pd.h_abi, pd.abi_sums.p, moved * sizeof(double), hipMemcpyDeviceToHost, stream));
+    pd.flag = w_combined != nullptr;
+    pd.issued = std::chrono::steady_clock::now();
+    pd.on = true;
+    pd.len = total;
   }
   void cohort_sums_end(double* o, int expect_len) {
-    REQUIRE(sums_pending, "mmhn_cohort_sums_end without mmhn_cohort_sums_begin");
-    REQUIRE(expect_len == sums_len, "mmhn_cohort_sums_end / mmhn_cohort_wsums_end does not match the _begin call");
-    sums_pending = false;
+    Pending& pd = pending;
+    REQUIRE(pd.on, "mmhn_cohort_sums_end without mmhn_cohort_sums_begin");
+    REQUIRE(expect_len == pd.len, "mmhn_cohort_sums_end / mmhn_cohort_wsums_end does not match the _begin call");
+    pd.on = false;
     HIPCHECK(hipStreamSynchronize(stream));
-    check_abort();
-    std::memcpy(o, h_abi, (size_t)sums_len * sizeof(double));
-    reduce_flag_sum = flag_pending ? h_abi[sums_len] : 0.0;
+    coop.check_abort();
+    std::memcpy(o, pd.h_abi, (size_t)pd.len * sizeof(double));
+    reduce_flag_sum = pd.flag ? pd.h_abi[pd.len] : 0.0;
     if (cfg.trace_host)
       std::fprintf(stderr, "[mmhn] evaluation issued after %.1f us, complete after %.1f us\n",
-                   std::chrono::duration<double, std::micro>(sums_issued - sums_t0).count(),
-                   std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - sums_t0).count());
-    finish_eval(sums_t0);
+                   std::chrono::duration<double, std::micro>(pd.issued - pd.t0).count(),
+                   std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - pd.t0).count());
+    finish_eval(pd.t0);
   }
   // (A hipGraph replay of the evaluation was measured on the LUAD-reduced cohort, ROCm 7.0.2: the host is free after
   // 75 us instead of 535 us, but the graph takes 660 us to execute against 550 us for the eager launches - dropped.)
   void cohort_sums(const double* lt, const double* ldp, const double* ldm, bool grad, double* o) {
     cohort_sums_begin(lt, ldp, ldm, grad);
-    cohort_sums_end(o, 4 + 2 * N * N + 3 * N);
+    cohort_sums_end(o, full_len());
   }
-
-  void comm_init(const ncclUniqueId& id, int rank, int nranks) {
-    REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks, "comm_init: rank / n_ranks out of range");
-    REQUIRE(nranks == 1 || !mixing(), "comm_init: the engine holds row groups, which need a one-rank engine (remove them first)");
-    comm_destroy();
-    RCCLCHECK(rccl().CommInitRank(&comm, nranks, id, rank));
-    comm_rank = rank; comm_size = nranks;
-    // what RCCL itself says about the communicator (mmhn_get_counters: the bench line's proof that it spans the ranks)
-    int cnt_ = 0, rk_ = -1;
-    RCCLCHECK(rccl().CommCount(comm, &cnt_));
-    RCCLCHECK(rccl().CommUserRank(comm, &rk_));
-    if (cnt_ != nranks || rk_ != rank) {
-      comm_destroy();
-      throw Fail{"comm_init: RCCL reports " + std::to_string(cnt_) + " ranks / rank " + std::to_string(rk_) + ", asked for " +
-                 std::to_string(nranks) + " / " + std::to_string(rank)};
-    }
-    cnt.comm_ranks = cnt_; cnt.comm_rank = rk_;
-  }
-  void comm_destroy() {
-    if (comm) { (void)rccl().CommDestroy(comm); comm = nullptr; }
-    comm_rank = 0; comm_size = 1;
-    cnt.comm_ranks = 0; cnt.comm_rank = -1;
-  }
-
 };
 
 }  // namespace mmhn
@@ -1127,791 +1059,4 @@ struct Engine : EngineBase {
 #include "cross_host.h"
 #include "sampler_host.h"
 #include "bench.h"
-
-// ======================================================================================
-// C ABI
-// ======================================================================================
-using namespace mmhn;
-
-struct mmhn_engine {
-  int dtype;
-  int n;
-  EngineBase* impl;
-};
-
-#define API_BEGIN try {
-#define API_END                                   \
-  return 0;                                       \
-  }                                               \
-  catch (const Fail& f) { g_err = f.msg; return 1; } \
-  catch (const std::exception& e) { g_err = e.what(); return 2; }
-
-// engine's device current for the rest of the entry point
-#define GUARD(h)                            \
-  REQUIRE(h && h->impl, "null handle");     \
-  DevGuard dev_guard_(h->impl->device)
-
-#define DISPATCH(h, call)                                             \
-  do {                                                                \
-    REQUIRE(h && h->impl, "null handle");                             \
-    if (h->dtype == MMHN_F64) static_cast<Engine<double>*>(h->impl)->call; \
-    else static_cast<Engine<float>*>(h->impl)->call;                  \
-  } while (0)
-// ... and a free function template over the engine (prims.h, orders_host.h, bench.h)
-#define DISPATCH_FN(h, fn, ...)                                                            \
-  do {                                                                                     \
-    REQUIRE(h && h->impl, "null handle");                                                  \
-    if (h->dtype == MMHN_F64) fn(*static_cast<Engine<double>*>(h->impl), __VA_ARGS__);     \
-    else fn(*static_cast<Engine<float>*>(h->impl), __VA_ARGS__);                           \
-  } while (0)
-
-extern "C" {
-
-const char* mmhn_last_error(void) { return g_err.c_str(); }
-
-int mmhn_create(int device_id, int n_mut, int dtype, mmhn_handle* out) {
-  API_BEGIN
-  REQUIRE(out, "null out pointer");
-  REQUIRE(dtype == MMHN_F64 || dtype == MMHN_F32, "dtype must be MMHN_F64 or MMHN_F32");
-  int ndev = 0;
-  HIPCHECK(hipGetDeviceCount(&ndev));
-  REQUIRE(ndev > 0, "no HIP device visible: metmhn_amd needs a GPU (no CPU fallback)");
-  REQUIRE(device_id >= 0 && device_id < ndev, "device_id out of range");
-  auto* h = new mmhn_engine{dtype, n_mut, nullptr};
-  try {
-    if (dtype == MMHN_F64) h->impl = new Engine<double>(device_id, n_mut);
-    else h->impl = new Engine<float>(device_id, n_mut);
-  } catch (...) { delete h; throw; }
-  h->impl->dtype = dtype;
-  *out = h;
-  API_END
-}
-
-void mmhn_destroy(mmhn_handle h) {
-  if (!h) return;
-  try {
-    if (h->impl) {
-      DevGuard guard(h->impl->device);     // device memory, stream and communicator are released on their GPU
-      delete h->impl;
-    }
-  } catch (...) {
-  }
-  delete h;
-}
-
-int mmhn_set_workspace_limit(mmhn_handle h, size_t bytes) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(bytes >= (size_t)1 << 20, "workspace limit below 1 MiB");
-  h->impl->cfg.plan.ws_limit = bytes;
-  API_END
-}
-
-int mmhn_set_cohort(mmhn_handle h, const int8_t* dat, int64_t n_pat, int n_cols) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(dat || n_pat == 0, "null dat");
-  DISPATCH(h, set_cohort(dat, n_pat, n_cols));
-  API_END
-}
-
-// n_unknown: rows of dat type 4 - weight 1, outside the EM / NM balance (they ride in the NM sums)
-static void weights(double n_em, double n_pat, double n_unknown, double perc_met, double* w, double* n_full) {
-  const double n_nm = n_pat - n_em - n_unknown;           // regularized_optimization.py:121-128
-  *w = (n_em * n_nm != 0) ? perc_met * n_nm / ((1 - perc_met) * n_em) : 1.0;
-  *n_full = *w * n_em + n_nm + n_unknown;
-}
-static long long unknown_rows(mmhn_handle h) {
-  return h->dtype == MMHN_F64 ? static_cast<Engine<double>*>(h->impl)->n_unknown : static_cast<Engine<float>*>(h->impl)->n_unknown;
-}
-
-int mmhn_set_row_weights(mmhn_handle h, const double* w, int64_t n) {
-  API_BEGIN
-  GUARD(h);
-  DISPATCH_FN(h, set_row_weights, w, n);
-  API_END
-}
-
-int mmhn_get_row_weight_sums(mmhn_handle h, double* out3) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(out3, "null pointer");
-  DISPATCH(h, row_weight_sums(out3));
-  API_END
-}
-
-int mmhn_set_row_groups(mmhn_handle h, const int64_t* ptr, int64_t n_groups, const int64_t* rows, const double* w) {
-  API_BEGIN
-  GUARD(h);
-  DISPATCH_FN(h, set_row_groups, ptr, n_groups, rows, w);
-  API_END
-}
-
-int mmhn_group_posteriors(mmhn_handle h, const double* lt, const double* ldp, const double* ldm, double* lp_group, double* rho) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && ldp && ldm && lp_group && rho, "null pointer");
-  DISPATCH_FN(h, group_posteriors, lt, ldp, ldm, lp_group, rho);
-  API_END
-}
-
-int mmhn_cohort_sums(mmhn_handle h, const double* lt, const double* ldp, const double* ldm, int with_grad,
-                     double* sums) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && ldp && ldm && sums, "null pointer");
-  DISPATCH(h, cohort_sums(lt, ldp, ldm, with_grad != 0, sums));
-  API_END
-}
-
-int mmhn_cohort_sums_begin(mmhn_handle h, const double* lt, const double* ldp, const double* ldm, int with_grad) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && ldp && ldm, "null pointer");
-  DISPATCH(h, cohort_sums_begin(lt, ldp, ldm, with_grad != 0));
-  API_END
-}
-
-int mmhn_cohort_sums_end(mmhn_handle h, double* sums) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(sums, "null pointer");
-  DISPATCH(h, cohort_sums_end(sums, 4 + 2 * (h->n + 1) * (h->n + 1) + 3 * (h->n + 1)));
-  API_END
-}
-
-int mmhn_cohort_wsums_begin(mmhn_handle h, const double* lt, const double* ldp, const double* ldm, int with_grad, double w) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && ldp && ldm, "null pointer");
-  REQUIRE(std::isfinite(w), "w must be finite");
-  DISPATCH(h, cohort_sums_begin(lt, ldp, ldm, with_grad != 0, &w));
-  API_END
-}
-
-int mmhn_set_reduce_flag(mmhn_handle h, double value) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(std::isfinite(value), "the flag must be finite");
-  DISPATCH(h, reduce_flag = value);
-  API_END
-}
-int mmhn_get_reduce_flag(mmhn_handle h, double* summed) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(summed, "null pointer");
-  if (h->dtype == MMHN_F64) *summed = static_cast<Engine<double>*>(h->impl)->reduce_flag_sum;
-  else *summed = static_cast<Engine<float>*>(h->impl)->reduce_flag_sum;
-  API_END
-}
-
-int mmhn_cohort_wsums_end(mmhn_handle h, double* wsums) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(wsums, "null pointer");
-  DISPATCH(h, cohort_sums_end(wsums, 1 + (h->n + 1) * (h->n + 1) + 2 * (h->n + 1)));
-  API_END
-}
-
-int mmhn_score_and_grad(mmhn_handle h, const double* lt, const double* ldp, const double* ldm, double perc_met,
-                        double* score, double* d_theta, double* d_dp, double* d_dm) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && ldp && ldm && score, "null pointer");
-  const int N = h->n + 1;
-  const bool grad = d_theta && d_dp && d_dm;
-  std::vector<double> s(4 + 2 * N * N + 3 * N);
-  DISPATCH(h, cohort_sums(lt, ldp, ldm, grad, s.data()));
-  double w, nf;
-  double c3[3];
-  DISPATCH(h, row_weight_sums(c3));
-  weights(s[2], s[3], c3[2], perc_met, &w, &nf);
-  *score = (w * s[0] + s[1]) / nf;
-  if (grad) {
-    const double* gem = s.data() + 4;
-    const double* gnm = gem + N * N;
-    const double* pem = gnm + N * N;
-    const double* pnm = pem + N;
-    const double* mem_ = pnm + N;
-    for (int e = 0; e < N * N; ++e) d_theta[e] = (w * gem[e] + gnm[e]) / nf;
-    for (int i = 0; i < N; ++i) { d_dp[i] = (w * pem[i] + pnm[i]) / nf; d_dm[i] = w * mem_[i] / nf; }
-  }
-  API_END
-}
-
-int mmhn_score(mmhn_handle h, const double* lt, const double* ldp, const double* ldm, double perc_met,
-               double* score) {
-  return mmhn_score_and_grad(h, lt, ldp, ldm, perc_met, score, nullptr, nullptr, nullptr);
-}
-
-int mmhn_patient_grads(mmhn_handle h, const double* lt, const double* ldp, const double* ldm, double* lp,
-                       double* d_theta, double* d_dp, double* d_dm) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && ldp && ldm && lp, "null pointer");
-  const int N = h->n + 1, st = 1 + N * N + 2 * N;
-  long long np = 0;
-  if (h->dtype == MMHN_F64) np = static_cast<Engine<double>*>(h->impl)->n_pat;
-  else np = static_cast<Engine<float>*>(h->impl)->n_pat;
-  std::vector<double> rows((size_t)np * st), s(2 * st);
-  const bool grad = d_theta != nullptr;
-  DISPATCH(h, evaluate(lt, ldp, ldm, grad, s.data(), rows.data()));
-  for (long long i = 0; i < np; ++i) {
-    const double* r = rows.data() + (size_t)i * st;
-    lp[i] = r[0];
-    if (grad) {
-      std::memcpy(d_theta + (size_t)i * N * N, r + 1, N * N * sizeof(double));
-      if (d_dp) std::memcpy(d_dp + (size_t)i * N, r + 1 + N * N, N * sizeof(double));
-      if (d_dm) std::memcpy(d_dm + (size_t)i * N, r + 1 + N * N + N, N * sizeof(double));
-    }
-  }
-  API_END
-}
-
-int mmhn_patient_status(mmhn_handle h, const double* lt, const double* ldp, const double* ldm, double* lp, double* p_seeded) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && ldp && ldm && lp && p_seeded, "null pointer");
-  DISPATCH(h, patient_status(lt, ldp, ldm, lp, p_seeded));
-  API_END
-}
-
-int mmhn_get_unknown_rows(mmhn_handle h, int64_t* n_unknown) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(n_unknown, "null pointer");
-  *n_unknown = unknown_rows(h);
-  API_END
-}
-
-// ---- joint primitives
-#define JOINT_DESC(state) make_joint(state, h->n)
-
-int mmhn_kronvec(mmhn_handle h, const double* lt, const int8_t* state, const double* p, double* y, int diag,
-                 int transpose) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && state && p && y, "null pointer");
-  const Desc d = JOINT_DESC(state);
-  DISPATCH(h, build_params(lt, nullptr, nullptr));
-  DISPATCH_FN(h, api_kronvec, d, p, y, diag != 0, transpose != 0);
-  API_END
-}
-int mmhn_kronvec_batched(mmhn_handle h, const double* lt, const int8_t* state, int64_t batch, const double* p,
-                         double* y, int diag, int transpose) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && state && p && y, "null pointer");
-  REQUIRE(batch >= 1, "batch must be positive");
-  const Desc d = JOINT_DESC(state);
-  DISPATCH(h, build_params(lt, nullptr, nullptr));
-  DISPATCH_FN(h, api_kronvec_batched, d, batch, p, y, diag != 0, transpose != 0);
-  API_END
-}
-int mmhn_jacobi_step_batched(mmhn_handle h, const double* lt, const double* ldp, const double* ldm, const int8_t* state,
-                             int64_t batch, const double* p, const double* rhs, double* y, int transpose) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && ldp && ldm && state && p && rhs && y, "null pointer");
-  REQUIRE(batch >= 1, "batch must be positive");
-  const Desc d = JOINT_DESC(state);
-  DISPATCH(h, build_params(lt, ldp, ldm));
-  DISPATCH_FN(h, api_jacobi_step_batched, d, batch, p, rhs, y, transpose != 0);
-  API_END
-}
-int mmhn_kron_diag(mmhn_handle h, const double* lt, const int8_t* state, double* out) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && state && out, "null pointer");
-  const Desc d = JOINT_DESC(state);
-  DISPATCH(h, build_params(lt, nullptr, nullptr));
-  DISPATCH_FN(h, api_diag, d, nullptr, out, KD_DQ);
-  API_END
-}
-int mmhn_diag_scal(mmhn_handle h, const double* log_d, const int8_t* state, const double* p, double* y, int which) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(log_d && state && p && y, "null pointer");
-  REQUIRE(which == 0 || which == 1, "which must be 0 (d_p) or 1 (d_m)");
-  const Desc d = JOINT_DESC(state);
-  REQUIRE(d.seedbit >= 0, "diag_scal needs an active seeding slot");
-  const int N = h->n + 1;
-  std::vector<double> lt((size_t)N * N, 0.0);
-  DISPATCH(h, build_params(lt.data(), which == 0 ? log_d : nullptr, which == 1 ? log_d : nullptr));
-  DISPATCH_FN(h, api_diag, d, p, y, which == 0 ? KD_DP : KD_DM);
-  API_END
-}
-int mmhn_obs_states(mmhn_handle h, const int8_t* state, int pt_first, int64_t* idx, int64_t* count) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(h && state && idx && count, "null pointer");
-  obs_indices(JOINT_DESC(state), pt_first != 0, idx, count);
-  API_END
-}
-int mmhn_resolvent(mmhn_handle h, const double* lt, const double* ldp, const double* ldm, const int8_t* state,
-                   const double* x, double* y, int transpose) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && ldp && ldm && state && x && y, "null pointer");
-  const Desc d = JOINT_DESC(state);
-  DISPATCH(h, build_params(lt, ldp, ldm));
-  DISPATCH_FN(h, api_resolvent, d, nullptr, x, y, transpose != 0);
-  API_END
-}
-int mmhn_x_partial_Q_y(mmhn_handle h, const double* lt, const int8_t* state, const double* x, const double* y,
-                       double* G) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && state && x && y && G, "null pointer");
-  const Desc d = JOINT_DESC(state);
-  DISPATCH(h, build_params(lt, nullptr, nullptr));
-  DISPATCH_FN(h, api_xQy_joint, d, x, y, G);
-  API_END
-}
-int mmhn_x_partial_D_y(mmhn_handle h, const double* ldp, const double* ldm, const int8_t* state, const double* x,
-                       const double* y, double* d_dp, double* d_dm) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(ldp && ldm && state && x && y && d_dp && d_dm, "null pointer");
-  const Desc d = JOINT_DESC(state);
-  const int N = h->n + 1;
-  std::vector<double> lt((size_t)N * N, 0.0);
-  DISPATCH(h, build_params(lt.data(), ldp, ldm));
-  DISPATCH_FN(h, api_xDy_joint, d, x, y, d_dp, d_dm);
-  API_END
-}
-
-int mmhn_partial_diag_scal(mmhn_handle h, const double* log_d, const int8_t* state, const double* p, int i, int which,
-                           double* y) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(log_d && state && p && y, "null pointer");
-  REQUIRE(which == 0 || which == 1, "which must be 0 (d_p) or 1 (d_m)");
-  const int n = h->n, N = n + 1;
-  REQUIRE(i >= 0 && i <= n, "event index out of range");
-  const Desc d = JOINT_DESC(state);
-  REQUIRE(d.seedbit >= 0, "partial_diag_scal needs an active seeding slot");
-  // kronvec.py:632-644, :704-710: zero when the tumour's slot of event i is inactive; i == n: the seeding bit
-  const int bit = i == n ? d.seedbit : (which == 0 ? d.bitP[i] : d.bitM[i]);
-  std::vector<double> lt((size_t)N * N, 0.0);
-  DISPATCH(h, build_params(lt.data(), which == 0 ? log_d : nullptr, which == 1 ? log_d : nullptr));
-  if (bit < 0) {
-    std::memset(y, 0, sizeof(double) << d.k);
-  } else {
-    DISPATCH_FN(h, api_diag, d, p, y, which == 0 ? KD_DP : KD_DM, bit);
-  }
-  API_END
-}
-
-// ---- single-tumour primitives
-int mmhn_v_kronvec(mmhn_handle h, const double* lt, const int8_t* state, const double* p, double* y, int diag,
-                   int transpose) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && state && p && y, "null pointer");
-  const Desc d = make_single(state, h->n, PS_THETA, OBS_ONE);
-  DISPATCH(h, build_params(lt, nullptr, nullptr));
-  DISPATCH_FN(h, api_kronvec, d, p, y, diag != 0, transpose != 0);
-  API_END
-}
-int mmhn_v_resolvent(mmhn_handle h, const double* lt, const int8_t* state, const double* d_rates, const double* x,
-                     double* y, int transpose) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && state && x && y, "null pointer");
-  const Desc d = make_single(state, h->n, PS_THETA, OBS_ONE);
-  DISPATCH(h, build_params(lt, nullptr, nullptr));
-  DISPATCH_FN(h, api_resolvent, d, d_rates, x, y, transpose != 0);
-  API_END
-}
-int mmhn_v_x_partial_Q_y(mmhn_handle h, const double* lt, const int8_t* state, const double* x, const double* y,
-                         double* G, double* d_diag) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && state && x && y && G, "null pointer");
-  const Desc d = make_single(state, h->n, PS_THETA, OBS_ONE);
-  DISPATCH(h, build_params(lt, nullptr, nullptr));
-  DISPATCH_FN(h, api_xQy_single, d, x, y, G, d_diag);
-  API_END
-}
-
-int mmhn_v_kron_diag(mmhn_handle h, const double* lt, const int8_t* state, const double* diag, double* out) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && state && out, "null pointer");
-  const Desc d = make_single(state, h->n, PS_THETA, OBS_ONE);
-  DISPATCH(h, build_params(lt, nullptr, nullptr));
-  DISPATCH_FN(h, api_diag, d, diag, out, diag ? KD_QP : KD_DQ);
-  API_END
-}
-int mmhn_v_scal_d_pt(mmhn_handle h, const double* ldp, const double* ldm, const int8_t* state, const double* vec,
-                     double* out_p, double* out_m) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(ldp && ldm && state && vec && out_p && out_m, "null pointer");
-  REQUIRE(state[h->n] == 1, "scal_d_pt needs the seeding event in the state (vanilla.py:142)");
-  const Desc d = make_single(state, h->n, PS_THETA, OBS_MET);
-  const int N = h->n + 1;
-  std::vector<double> lt((size_t)N * N, 0.0);
-  DISPATCH(h, build_params(lt.data(), ldp, ldm));
-  DISPATCH_FN(h, api_diag, d, vec, out_p, KD_SDP);
-  DISPATCH_FN(h, api_diag, d, vec, out_m, KD_DM);
-  API_END
-}
-int mmhn_v_d_scal_d_pt(mmhn_handle h, const double* ldp, const double* ldm, const int8_t* state, const double* vec,
-                       int i, double* out_p, double* out_m) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(ldp && ldm && state && vec && out_p && out_m, "null pointer");
-  const int n = h->n, N = n + 1;
-  REQUIRE(i >= 0 && i <= n, "event index out of range");
-  REQUIRE(state[n] == 1, "d_scal_d_pt needs the seeding event in the state");
-  const Desc d = make_single(state, n, PS_THETA, OBS_MET);
-  std::vector<double> lt((size_t)N * N, 0.0);
-  DISPATCH(h, build_params(lt.data(), ldp, ldm));
-  // vanilla.py:182-187: inactive event -> zeros; i == n -> (0, d_m part); otherwise both parts restricted to "i happened"
-  if (d.bitP[i] < 0 || i == n) std::memset(out_p, 0, sizeof(double) << d.k);
-  else DISPATCH_FN(h, api_diag, d, vec, out_p, KD_SDP, d.bitP[i]);
-  if (d.bitP[i] < 0) std::memset(out_m, 0, sizeof(double) << d.k);
-  else DISPATCH_FN(h, api_diag, d, vec, out_m, KD_DM, i == n ? -1 : d.bitP[i]);
-  API_END
-}
-int mmhn_v_x_partial_D_y(mmhn_handle h, const double* ldp, const double* ldm, const int8_t* state, const double* x,
-                         const double* y, double* d_dp, double* d_dm) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(ldp && ldm && state && x && y && d_dp && d_dm, "null pointer");
-  REQUIRE(state[h->n] == 1, "x_partial_D_y needs the seeding event in the state");
-  const Desc d = make_single(state, h->n, PS_THETA, OBS_MET);
-  const int N = h->n + 1;
-  std::vector<double> lt((size_t)N * N, 0.0);
-  DISPATCH(h, build_params(lt.data(), ldp, ldm));
-  DISPATCH_FN(h, api_xDy_single, d, x, y, d_dp, d_dm);
-  API_END
-}
-
-// ---- patient shards on several GPUs: one RCCL communicator per engine
-int mmhn_comm_unique_id(void* id128) {
-  API_BEGIN
-  REQUIRE(id128, "null pointer");
-  static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is 128 bytes");
-  ncclUniqueId id;
-  RCCLCHECK(rccl().GetUniqueId(&id));
-  std::memcpy(id128, &id, sizeof(id));
-  API_END
-}
-int mmhn_comm_init(mmhn_handle h, const void* id128, int rank, int n_ranks) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(id128, "null pointer");
-  ncclUniqueId id;
-  std::memcpy(&id, id128, sizeof(id));
-  DISPATCH(h, comm_init(id, rank, n_ranks));
-  API_END
-}
-int mmhn_comm_destroy(mmhn_handle h) {
-  API_BEGIN
-  GUARD(h);
-  DISPATCH(h, comm_destroy());
-  API_END
-}
-
-// ---- likeliest event orders of a cohort
-int mmhn_likeliest_orders(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, const int8_t* dat,
-                          int64_t n_pat, int n_cols, int front_cap, int8_t* orders, double* prob, int32_t* status) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(log_theta && obs1 && obs2 && orders && prob && status, "null pointer");
-  REQUIRE(dat || n_pat == 0, "null dat");
-  REQUIRE(n_pat >= 0 && n_pat < ((int64_t)1 << 31), "n_pat out of range");
-  REQUIRE(h->dtype == MMHN_F64, "likeliest orders need an fp64 engine (MMHN_F64)");
-  likeliest_orders(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, front_cap, orders, prob,
-                                                         status);
-  API_END
-}
-
-// ---- pre-seeding posteriors of a cohort: the sum over the orders mmhn_likeliest_orders maximises over
-int mmhn_order_posteriors(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, const int8_t* dat,
-                          int64_t n_pat, int n_cols, double* log_evidence, double* pre, double* seed_pos, int32_t* status) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(log_theta && obs1 && obs2 && log_evidence && pre && seed_pos && status, "null pointer");
-  REQUIRE(dat || n_pat == 0, "null dat");
-  REQUIRE(n_pat >= 0 && n_pat < ((int64_t)1 << 31), "n_pat out of range");
-  REQUIRE(h->dtype == MMHN_F64, "order posteriors need an fp64 engine (MMHN_F64)");
-  order_posteriors(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, log_evidence, pre,
-                   seed_pos, status);
-  API_END
-}
-
-// ---- pairwise precedence posteriors of a cohort: which of two events came first, over the same orders
-int mmhn_order_precedences(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, const int8_t* dat,
-                           int64_t n_pat, int n_cols, double* log_evidence, double* prec, int32_t* status) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(log_theta && obs1 && obs2 && log_evidence && prec && status, "null pointer");
-  REQUIRE(dat || n_pat == 0, "null dat");
-  REQUIRE(n_pat >= 0 && n_pat < ((int64_t)1 << 31), "n_pat out of range");
-  REQUIRE(h->dtype == MMHN_F64, "order precedences need an fp64 engine (MMHN_F64)");
-  order_precedences(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, log_evidence, prec,
-                    status);
-  API_END
-}
-
-// ---- posterior event positions of a cohort: where in its lineage every event happened, over the same orders
-int mmhn_order_positions(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, const int8_t* dat,
-                         int64_t n_pat, int n_cols, double* log_evidence, double* pos_pt, double* pos_mt, int32_t* status) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(log_theta && obs1 && obs2 && log_evidence && pos_pt && pos_mt && status, "null pointer");
-  REQUIRE(dat || n_pat == 0, "null dat");
-  REQUIRE(n_pat >= 0 && n_pat < ((int64_t)1 << 31), "n_pat out of range");
-  REQUIRE(h->dtype == MMHN_F64, "order positions need an fp64 engine (MMHN_F64)");
-  order_positions(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, log_evidence, pos_pt,
-                  pos_mt, status);
-  API_END
-}
-
-// ---- posterior event and observation times of a cohort: when every event and observation happened, over the same orders
-int mmhn_order_times(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, const int8_t* dat,
-                     int64_t n_pat, int n_cols, double* log_evidence, double* time, double* obs, double* pt_first,
-                     int32_t* status) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(log_theta && obs1 && obs2 && log_evidence && time && obs && pt_first && status, "null pointer");
-  REQUIRE(dat || n_pat == 0, "null dat");
-  REQUIRE(n_pat >= 0 && n_pat < ((int64_t)1 << 31), "n_pat out of range");
-  REQUIRE(h->dtype == MMHN_F64, "order times need an fp64 engine (MMHN_F64)");
-  order_times(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, log_evidence, time, obs,
-              pt_first, status);
-  API_END
-}
-
-// ---- posterior genotypes at the first observation of a cohort's paired rows: what the two tumours held then, over the same orders
-int mmhn_order_snapshots(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, const int8_t* dat,
-                         int64_t n_pat, int n_cols, double* log_evidence, double* held, double* late, int8_t* map_state,
-                         int32_t* map_first, double* map_prob, int32_t* status) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(log_theta && obs1 && obs2 && log_evidence && held && late && map_state && map_first && map_prob && status,
-          "null pointer");
-  REQUIRE(dat || n_pat == 0, "null dat");
-  REQUIRE(n_pat >= 0 && n_pat < ((int64_t)1 << 31), "n_pat out of range");
-  REQUIRE(h->dtype == MMHN_F64, "order snapshots need an fp64 engine (MMHN_F64)");
-  order_snapshots(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, log_evidence, held, late,
-                  map_state, map_first, map_prob, status);
-  API_END
-}
-
-// ---- posterior samples of the event orders of a cohort: orders drawn with their exact probability given the row
-int mmhn_order_samples(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, const int8_t* dat,
-                       int64_t n_pat, int n_cols, int64_t first, int64_t n_samples, uint64_t seed, double* log_evidence,
-                       int8_t* orders, double* log_prob, int32_t* status) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(log_theta && obs1 && obs2 && log_evidence && status, "null pointer");
-  REQUIRE(dat || n_pat == 0, "null dat");
-  REQUIRE(n_pat >= 0 && n_pat < ((int64_t)1 << 31), "n_pat out of range");
-  REQUIRE(first >= 0, "first must be non-negative");
-  REQUIRE(n_samples >= 0 && n_samples < ((int64_t)1 << 31), "n_samples out of range");
-  REQUIRE(n_samples <= INT64_MAX - first, "first + n_samples overflows 64 bits");
-  REQUIRE((orders && log_prob) || n_samples == 0, "null pointer");
-  REQUIRE(h->dtype == MMHN_F64, "order samples need an fp64 engine (MMHN_F64)");
-  order_samples(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, dat, n_pat, n_cols, first, n_samples, seed,
-                log_evidence, orders, log_prob, status);
-  API_END
-}
-
-// ---- seeding forecasts from a tumour's genotype: what comes before the seeding, how likely it is before the next look
-int mmhn_seeding_forecasts(mmhn_handle h, const double* log_theta, const double* obs1, const int8_t* genotypes, int64_t n_rows,
-                           int until, double* p_seed, double* time, double* before, double* with_seed, double* n_before,
-                           int32_t* status) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(n_rows >= 0 && n_rows < ((int64_t)1 << 31), "n_rows out of range");
-  REQUIRE(log_theta && obs1, "null pointer");
-  REQUIRE((genotypes && p_seed && time && before && with_seed && n_before && status) || n_rows == 0, "null pointer");
-  REQUIRE(h->dtype == MMHN_F64, "seeding forecasts need an fp64 engine (MMHN_F64)");
-  seeding_forecasts(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, genotypes, n_rows, until, p_seed, time, before,
-                    with_seed, n_before, status);
-  API_END
-}
-
-// ---- seeding landscape: the forecast scalars of every genotype of the model from one backward sweep
-int mmhn_seeding_landscape(mmhn_handle h, const double* log_theta, const double* obs1, int until, const int8_t* genotypes,
-                           int64_t n_rows, double* values, int32_t* status, double* full) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(n_rows >= 0 && n_rows < ((int64_t)1 << 31), "n_rows out of range");
-  REQUIRE(log_theta && obs1, "null pointer");
-  REQUIRE((genotypes && values && status) || n_rows == 0, "null pointer");
-  REQUIRE(h->dtype == MMHN_F64, "the seeding landscape needs an fp64 engine (MMHN_F64)");
-  seeding_landscape(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, until, genotypes, n_rows, values, status, full);
-  API_END
-}
-
-// ---- genotype distribution of the primary tumour: every genotype's probability, unseeded and seeded, from one forward sweep
-int mmhn_genotype_distribution(mmhn_handle h, const double* log_theta, const double* obs1, const int8_t* genotypes,
-                               int64_t n_rows, double* values, int32_t* status, double* summary, double* full) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(n_rows >= 0 && n_rows < ((int64_t)1 << 31), "n_rows out of range");
-  REQUIRE(log_theta && obs1, "null pointer");
-  REQUIRE((genotypes && values && status) || n_rows == 0, "null pointer");
-  REQUIRE(h->dtype == MMHN_F64, "the genotype distribution needs an fp64 engine (MMHN_F64)");
-  genotype_distribution(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, genotypes, n_rows, values, status, summary, full);
-  API_END
-}
-
-// ---- genotype distribution of the metastasis and its founder: every genotype's Z, M, C from one forward sweep
-int mmhn_metastasis_distribution(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2,
-                                 const int8_t* genotypes, int64_t n_rows, double* values, int32_t* status, double* summary,
-                                 double* full) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(n_rows >= 0 && n_rows < ((int64_t)1 << 31), "n_rows out of range");
-  REQUIRE(log_theta && obs1 && obs2, "null pointer");
-  REQUIRE((genotypes && values && status) || n_rows == 0, "null pointer");
-  REQUIRE(h->dtype == MMHN_F64, "the metastasis distribution needs an fp64 engine (MMHN_F64)");
-  metastasis_distribution(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, genotypes, n_rows, values, status,
-                          summary, full);
-  API_END
-}
-
-// ---- genotype distribution of one tumour given the other: a row or column of the (PT x MT) table per query genotype
-int mmhn_partner_distributions(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, int given,
-                               const int8_t* genotypes, const int8_t* targets, int64_t n_rows, double* values,
-                               int32_t* status, double* summaries, double* full) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(n_rows >= 0 && n_rows < ((int64_t)1 << 31), "n_rows out of range");
-  REQUIRE(log_theta && obs1 && obs2, "null pointer");
-  REQUIRE((genotypes && values && status) || n_rows == 0, "null pointer");
-  REQUIRE(h->dtype == MMHN_F64, "the partner distribution needs an fp64 engine (MMHN_F64)");
-  partner_distributions(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, given, genotypes, targets, n_rows,
-                        values, status, summaries, full);
-  API_END
-}
-
-// ---- exact PT x MT co-occurrence and joint burden tables: the second moments of the (PT x MT) table through the founder
-int mmhn_cross_table(mmhn_handle h, const double* log_theta, const double* obs1, const double* obs2, int with_burden,
-                     double* out) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(log_theta && obs1 && obs2 && out, "null pointer");
-  REQUIRE(h->dtype == MMHN_F64, "the cross table needs an fp64 engine (MMHN_F64)");
-  cross_table(*static_cast<Engine<double>*>(h->impl), log_theta, obs1, obs2, with_burden != 0, out);
-  API_END
-}
-
-// ---- Gillespie sampler
-int mmhn_simulate(mmhn_handle h, const double* lt, const double* pt_d_ef, const double* mt_d_ef, int64_t n_sim,
-                  uint64_t seed, int8_t* dat_out, int8_t* orders_out) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(h && lt && pt_d_ef && mt_d_ef && dat_out, "null pointer");
-  REQUIRE(n_sim >= 0, "n_sim must be non-negative");
-  const int N = h->n + 1;
-  REQUIRE(N < SIM_MAXN, "too many events for the sampler (n_mut <= 30: event and diagnosis flags share one 32-bit set)");
-  simulate(h->impl->stream, lt, pt_d_ef, mt_d_ef, h->n, n_sim, seed, dat_out, orders_out);
-  API_END
-}
-
-int mmhn_simulate_summary(mmhn_handle h, const double* lt, const double* pt_d_ef, const double* mt_d_ef, int64_t first,
-                          int64_t n_sim, uint64_t seed, int64_t* counts) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(h && lt && pt_d_ef && mt_d_ef && counts, "null pointer");
-  REQUIRE(first >= 0, "first must be non-negative");
-  REQUIRE(n_sim >= 0, "n_sim must be non-negative");
-  REQUIRE(n_sim <= INT64_MAX - first, "first + n_sim overflows 64 bits");
-  const int N = h->n + 1;
-  REQUIRE(N < SIM_MAXN, "too many events for the sampler (n_mut <= 30: event and diagnosis flags share one 32-bit set)");
-  simulate_summary(h->impl->stream, h->impl->device, h->impl->cfg.sim_chunk, lt, pt_d_ef, mt_d_ef, h->n, first, n_sim, seed, counts);
-  API_END
-}
-
-int mmhn_simulate_pairs(mmhn_handle h, const double* lt, const double* pt_d_ef, const double* mt_d_ef, int64_t first,
-                        int64_t n_sim, uint64_t seed, int64_t* n_class, int64_t* pairs, int64_t* burden) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(h && lt && pt_d_ef && mt_d_ef && n_class && pairs && burden, "null pointer");
-  REQUIRE(first >= 0, "first must be non-negative");
-  REQUIRE(n_sim >= 0, "n_sim must be non-negative");
-  REQUIRE(n_sim <= INT64_MAX - first, "first + n_sim overflows 64 bits");
-  const int N = h->n + 1;
-  REQUIRE(N < SIM_MAXN, "too many events for the sampler (n_mut <= 30: event and diagnosis flags share one 32-bit set)");
-  simulate_pairs(h->impl->stream, h->impl->device, h->impl->cfg.sim_chunk, lt, pt_d_ef, mt_d_ef, h->n, first, n_sim, seed, n_class,
-                 pairs, burden);
-  API_END
-}
-
-// ---- measurement
-int mmhn_bench_kronvec(mmhn_handle h, const double* lt, const int8_t* state, int64_t batch, int iters,
-                       int transpose, int jacobi, double* ms_per_launch, int64_t* tiles) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(lt && state && ms_per_launch, "null pointer");
-  const Desc d = JOINT_DESC(state);
-  DISPATCH(h, build_params(lt, nullptr, nullptr));
-  long long tl[2] = {0, 0};
-  if (h->dtype == MMHN_F64)
-    *ms_per_launch = bench_kronvec(*static_cast<Engine<double>*>(h->impl), d, batch, iters, transpose != 0, jacobi != 0, tl);
-  else
-    *ms_per_launch = bench_kronvec(*static_cast<Engine<float>*>(h->impl), d, batch, iters, transpose != 0, jacobi != 0, tl);
-  if (tiles) { tiles[0] = tl[0]; tiles[1] = tl[1]; }
-  API_END
-}
-int mmhn_bench_stream(mmhn_handle h, size_t bytes, int iters, int kind, double* gbps) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(gbps, "null pointer");
-  if (h->dtype == MMHN_F64) *gbps = bench_stream(*static_cast<Engine<double>*>(h->impl), bytes, iters, kind);
-  else *gbps = bench_stream(*static_cast<Engine<float>*>(h->impl), bytes, iters, kind);
-  API_END
-}
-#ifdef MMHN_STAMPS
-// diagnostic builds only: shader cycles wave 0 of every k_psolve workgroup spent per phase ([0..7] forward, [8..15] adjoint)
-int mmhn_debug_stamps(mmhn_handle h, double* out16, int reset) {
-  API_BEGIN
-  GUARD(h);
-  unsigned long long v[16];
-  HIPCHECK(hipDeviceSynchronize());
-  HIPCHECK(hipMemcpyFromSymbol(v, HIP_SYMBOL(g_stamps), sizeof(v)));
-  for (int i = 0; i < 16; ++i) out16[i] = (double)v[i];
-  if (reset) { std::memset(v, 0, sizeof(v)); HIPCHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), v, sizeof(v))); }
-  API_END
-}
-#endif
-int mmhn_get_counters(mmhn_handle h, mmhn_counters* out) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(h && h->impl && out, "null pointer");
-  if (h->dtype == MMHN_F64) *out = static_cast<Engine<double>*>(h->impl)->cnt;
-  else *out = static_cast<Engine<float>*>(h->impl)->cnt;
-  API_END
-}
-int mmhn_debug_lane_moves(mmhn_handle h, int transposed, int* out) {
-  API_BEGIN
-  GUARD(h);
-  REQUIRE(out, "null pointer");
-  DevArr<int> d;
-  d.alloc(6 * 64);
-  if (transposed) hipLaunchKernelGGL((k_lane_moves<true>), dim3(1), dim3(64), 0, h->impl->stream, d.p);
-  else hipLaunchKernelGGL((k_lane_moves<false>), dim3(1), dim3(64), 0, h->impl->stream, d.p);
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipMemcpyAsync(out, d.p, 6 * 64 * sizeof(int), hipMemcpyDeviceToHost, h->impl->stream));
-  HIPCHECK(hipStreamSynchronize(h->impl->stream));
-  API_END
-}
-
-int mmhn_abi_version(void) { return MMHN_ABI_VERSION; }
-
-int mmhn_reset_counters(mmhn_handle h) {
-  API_BEGIN
-  GUARD(h);
-  DISPATCH(h, reset_counters());
-  API_END
-}
-
-}  // extern "C"
+#include "capi.h"

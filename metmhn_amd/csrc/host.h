@@ -1,5 +1,5 @@
 // Host-side plumbing shared by the engine and its helpers: error type and checks, owning device arrays, the device
-// guard of the ABI entry points and the readers of the MMHN_* environment knobs.
+// guard of the ABI entry points, the lanes, the kernel timer and the readers of the MMHN_* environment knobs.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +7,10 @@
 #include <cstring>
 #include <string>
 #include <type_traits>
+#include <utility>
+#include <vector>
+
+#include "../../include/metmhn_amd.h"
 
 namespace mmhn {
 
@@ -68,7 +72,7 @@ struct DevGuard {
 
 // A stream of the engine with what belongs to it.  Every launch helper takes the lane it issues on, so the stream, the flag
 // set of a cooperative launch and the events a stage waits for cannot come apart.
-// flags: index of the engine's coop_flags[] set its cooperative launches use, which also picks their CoopCtl slots
+// flags: index of the CoopState::flags[] set (tsolve_host.h) its cooperative launches use, which also picks their CoopCtl slots
 // (flags * 4 + ...); -1: the lane carries none.  Launches of two lanes may be in flight together, so two lanes that both
 // issue cooperative launches never share a set.
 // fork / join: a side lane waits for a point of the main lane (begin), and the main lane later for the side lane's last
@@ -99,6 +103,60 @@ struct Lane {
   // (an evaluation that threw between a fork and its join must not leave its flags to the next one: the side stream
   // would wait for the previous evaluation's event and start before this one's parameters are up)
   void reset() { forked = fork_recorded = false; }
+};
+
+// The times of the dominant kernels for the counters (mmhn_get_counters): HIP events around a launch, read when the
+// evaluation is complete.  An event record costs ~5 us of host time, which a short evaluation cannot afford (it is bound by
+// the host's issue rate): the engine turns the timer on per batch, for batches of at least 2^26 states
+// (MMHN_TIME_KERNELS=1: every batch).  Off, a timed launch is the launch and its error check.
+struct KernelTimer {
+  bool on = true;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
+  size_t used = 0;
+  std::vector<double> bytes;
+  std::vector<int> slot;              // MMHN_K_* class of the timed launch
+  // the events are recorded on the lane of the launch (they are not created with hipEventDisableTiming - evaluate() keeps
+  // a timed batch on the main lane)
+  template <typename F>
+  void timed(const Lane& L, int slot_, double alg_bytes, F&& launch) {
+    if (!on) {
+      launch();
+      HIPCHECK(hipGetLastError());
+      return;
+    }
+    if (used == pool.size()) {
+      hipEvent_t a, b;
+      HIPCHECK(hipEventCreate(&a));
+      HIPCHECK(hipEventCreate(&b));
+      pool.push_back({a, b});
+    }
+    hipEvent_t e0 = pool[used].first, e1 = pool[used].second;
+    ++used;
+    bytes.push_back(alg_bytes);
+    slot.push_back(slot_);
+    HIPCHECK(hipEventRecord(e0, L.s));
+    launch();
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(e1, L.s));
+  }
+  // after the lanes have been synchronised
+  void collect(mmhn_counters& cnt) {
+    for (size_t i = 0; i < used; ++i) {
+      float ms = 0;
+      HIPCHECK(hipEventElapsedTime(&ms, pool[i].first, pool[i].second));
+      mmhn_kernel_counter& c = cnt.kernel[slot[i]];
+      c.ms += ms;
+      c.launches += 1;
+      c.alg_bytes += bytes[i];
+    }
+    used = 0;
+    bytes.clear();
+    slot.clear();
+  }
+  void release() {
+    for (auto& e : pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    pool.clear();
+  }
 };
 
 // Run-time booleans as compile-time arguments of a generic lambda, to pick a template instantiation:

@@ -1,4 +1,4 @@
-// Single-problem primitives of the C ABI (mmhn_kronvec, mmhn_resolvent, mmhn_x_partial_Q_y, ... and the mmhn_v_* ones):
+// Single-problem primitives of the C ABI (capi.h: mmhn_kronvec, mmhn_resolvent, mmhn_x_partial_Q_y, ... and the mmhn_v_* ones):
 // one restricted space per call, set up from scratch, run through the engine's launch helpers and copied back.  These are
 // the paths of the API and the tests; the cohort evaluation (engine.hip) does not come through here.
 #pragma once

@@ -27,7 +27,7 @@ struct WeightCheck {
 template <typename T>
 void set_row_weights(Engine<T>& E, const double* w, long long nw) {
   const std::string fn = "mmhn_set_row_weights: ";
-  REQUIRE(!E.sums_pending, fn + "an evaluation begun with mmhn_cohort_sums_begin has not been collected");
+  REQUIRE(!E.pending.on, fn + "an evaluation begun with mmhn_cohort_sums_begin has not been collected");
   if (!w) {
     E.row_w.clear();
     for (BatchDev& d : E.dev) d.wrow.release();
@@ -75,7 +75,7 @@ void clear_row_groups(Engine<T>& E) {
 template <typename T>
 void set_row_groups(Engine<T>& E, const int64_t* ptr, long long ng, const int64_t* rows, const double* w) {
   const std::string fn = "mmhn_set_row_groups: ";
-  REQUIRE(!E.sums_pending, fn + "an evaluation begun with mmhn_cohort_sums_begin has not been collected");
+  REQUIRE(!E.pending.on, fn + "an evaluation begun with mmhn_cohort_sums_begin has not been collected");
   if (ng == 0 || !ptr || !rows || !w) {
     REQUIRE(ng == 0 || (!ptr && !rows && !w), fn + "null pointer next to " + std::to_string(ng) + " groups (group 0)");
     clear_row_groups(E);
